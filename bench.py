@@ -17,9 +17,15 @@ batches per 1 000 env steps) is drawn from the rings and all-gathered.  The per-
 records (`full-u16`, `full`) are timed beside it as secondary legs with their link bound.
 Prints ONE JSON line on rank 0 - whatever happens after the headline leg: every secondary leg runs
 under a deadline and an error guard (LineGuard), and the line is printed with what has been measured
-when one of them fails.  At N = 1 the line also carries the other single-GPU configurations of
-BASELINE.json (`configs`), the scan on the other tracks (`tracks`), the first steps after a reset
-(`fresh_reset`) and the CPU baseline.
+when one of them fails.
+
+A plain run measures the headline alone: set-up, settling, warm-up, the `--steps` timed steps (with the
+scan's launch timers, from which `roofline` is derived) and the line.  `--full` adds every secondary leg:
+at N = 1 the other single-GPU configurations of BASELINE.json (`configs`), the scan on the other tracks
+(`tracks`), the first steps after a reset (`fresh_reset`), the long steady-state windows, the per-kernel
+pass, action_repeat 4, follow-the-gap and the CPU baseline; at N > 1 the payload self-checks, the other
+gather modes and configs[4]'s track mix.  `--dump-outputs DIR` writes what the last timed step returned
+(see `dump_outputs`).
 """
 from __future__ import annotations
 
@@ -114,7 +120,49 @@ def parse_args():
     ap.add_argument("--raycast-variant", type=int, default=None)
     ap.add_argument("--debug-knob", action="append", default=[], metavar="NAME=VALUE",
                     help="experiment knob passed to rc_debug_set (ray_threads, ray_split, ray_wg_per_cu, band_log2)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every secondary leg after the headline (CPU baseline, other configurations and tracks, steady-state "
+                         "windows, per-kernel pass, action_repeat 4, follow-the-gap; N > 1: payload self-checks and the other "
+                         "gather modes).  Off: the run measures the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's env outputs) as DIR/<field>.npy "
+                         "in float32 / float64; see dump_outputs")
     return ap.parse_args()
+
+
+DUMP_BUDGET_BYTES = 48 << 20         # the files of --dump-outputs together stay below this
+DUMP_SAMPLE_SEED = 20240229
+
+
+def dump_outputs(views, out_dir):
+    """Write the env outputs of the last step (`views`: name -> [num_envs, cars_per_env, ...] device tensors) as
+    out_dir/<name>.npy: float32 fields and uint8 flags as float32, int32 counters as float64 (exact).  The per-car scalars and
+    short vectors (pose, reward, done, ...) are written for every car; the wide rows (lidar, lidar_occupancy) for a fixed, seeded
+    sample of cars sized to DUMP_BUDGET_BYTES, whose flat car indices are in sampled_cars.npy.  `action_in` is an input slot, not
+    an output, and is left out."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    fields = {n: t for n, t in views.items() if n != "action_in"}
+    first = next(iter(fields.values()))
+    n_cars = first.shape[0] * first.shape[1]
+    width = {n: t[0, 0].numel() for n, t in fields.items()}
+    out_type = {n: (np.float64 if t.dtype == torch.int32 else np.float32) for n, t in fields.items()}
+    wide = [n for n in fields if width[n] > 64]
+    narrow = [n for n in fields if n not in wide]
+    narrow_bytes = sum(n_cars * width[n] * np.dtype(out_type[n]).itemsize for n in narrow)
+    row_bytes = sum(width[n] * np.dtype(out_type[n]).itemsize for n in wide)
+    k = min(n_cars, max(1, (DUMP_BUDGET_BYTES - narrow_bytes) // max(row_bytes, 1)))
+    rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_cars, size=k, replace=False))
+    rows_dev = torch.from_numpy(rows).to(first.device)
+    for n, t in fields.items():
+        if n in wide:
+            a = t.reshape(n_cars, *t.shape[2:]).index_select(0, rows_dev).cpu().numpy()
+        else:
+            a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, f"{n}.npy"), a.astype(out_type[n]))
+    if wide:
+        np.save(os.path.join(out_dir, "sampled_cars.npy"), rows.astype(np.float64))
 
 
 def cpu_baseline(track, cars, obs_type, repeat, n_envs):
@@ -664,7 +712,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
         env = make_env()
     # the first steps after a reset, timed on their own (N = 1): what `--settle 0` would put into the timed window
     fresh = None
-    if not distributed and not args.no_configs:
+    if args.full and not distributed and not args.no_configs:
         n_fresh = 20
         for k in range(150):                 # the chip at its working clocks first: what is measured is the poses, not the ramp
             env.step_random(seed=3, step=1000 + k)
@@ -917,8 +965,10 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
         scan_symbol = env.scan_kernel_name()
     # a long steady-state figure of the SAME env and loop right behind the driver's window (a 20-step window is
     # 3.7 ms, too short for an outside observer; this one is >= 2 000 steps, ~0.4 s, and contains its share of order re-sorts)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env.views, args.dump_outputs)
     steady = steady_long = None
-    if not distributed and not args.no_configs:
+    if args.full and not distributed and not args.no_configs:
         def window(n):
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
@@ -947,17 +997,18 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
             steady_long["note"] = (f"the same loop for about {args.observable_seconds:.0f} s of wall time without a pause (no timers, no host "
                                    f"synchronisation inside): long enough for a sampler that polls the GPU every 5 s to see it busy twice")
     # the other kernels of the step: a short untimed pass with all timers on
-    env.reset_kernel_times()
-    env.set_profiling(True, kernels=[L.K_PATCH, L.K_DYNAMICS])
-    n_pass = min(args.steps, 50)
-    for k in range(n_pass):
-        gather.step(step_no + k)
-    step_no += n_pass
-    finish(gather)
-    env.set_profiling(False)
-    for name, v in env.kernel_times().items():
-        if name != "rc_raycast_kernel":
-            ktimes[name] = v
+    if args.full:
+        env.reset_kernel_times()
+        env.set_profiling(True, kernels=[L.K_PATCH, L.K_DYNAMICS])
+        n_pass = min(args.steps, 50)
+        for k in range(n_pass):
+            gather.step(step_no + k)
+        step_no += n_pass
+        finish(gather)
+        env.set_profiling(False)
+        for name, v in env.kernel_times().items():
+            if name != "rc_raycast_kernel":
+                ktimes[name] = v
 
     value = total_envs * args.steps * args.repeat / dt
     n_cars = shard.num_envs * args.cars
@@ -1000,7 +1051,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
         # all-reduce; ncclCommCount of the C-ABI's communicator when that transport is used)
         "rccl_ranks": comm_ranks if (distributed and args.backend == "nccl") else None,
         "comm_backend": args.backend if distributed else None, "comm_ranks": comm_ranks, "abi_comm_ranks": abi_ranks,
-        "time_budget_s": args.time_budget,
+        "time_budget_s": args.time_budget, "full": bool(args.full),
     })
     out.update({
         "roofline": {
@@ -1041,7 +1092,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
             "is `configs4_track_mix`.")
     if fresh is not None:
         out["fresh_reset"] = fresh
-    if distributed:
+    if distributed and args.full:
         # cpu_baseline is timed on rank 0 of the N = 1 run only (the driver's contract): the N > 1 line points at it
         cb = None
         cbp = os.path.join(ROOT, "profiles", "cpu_baseline_n1.json")
@@ -1074,7 +1125,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
 
     # the headline payload's self-check: the only thing after the timed region that can fail the run
     checks = {}
-    if distributed and gather_mode != "none" and not args.no_gather_check:
+    if args.full and distributed and gather_mode != "none" and not args.no_gather_check:
         with guard.leg("headline_check"):        # (an exception or a hang in the check itself ends the run with the line; a MISMATCH fails it)
             checks[gather_mode] = gather.check(step_no, dist)
             step_no += 8
@@ -1096,7 +1147,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
     # line can least do without: N = 1 - the CPU baseline (the contract names it), then the other configurations; N > 1 - BASELINE
     # configs[4] itself, the steady state of the headline payload, the whole-record concat at the reference's cadence, the
     # per-sub-step payloads, and the simulation alone last.
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         with guard.leg("cpu_baseline"):
             from oracle import cpu_baseline as cb
             out["cpu_baseline"] = cpu_baseline(track, args.cars, args.obs_type, args.repeat, args.cpu_envs)
@@ -1108,7 +1159,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
     # the headline's payload (the sharded store) over the mix.  Each rank builds a SECOND env on its track of the mix (the
     # headline's env stays as it is); ranks on different tracks run steps of different length, so the closing barrier waits for
     # the slowest track - which is the point of the configuration.
-    if distributed and not args.mixed_tracks and not args.no_gather_modes and guard.go("configs4_track_mix", 40):
+    if args.full and distributed and not args.mixed_tracks and not args.no_gather_modes and guard.go("configs4_track_mix", 40):
         with guard.leg("configs4_track_mix"):
             mix = ["columbia", "austria", "barcelona"]
             mine = mix[rank % 3]
@@ -1149,7 +1200,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
         return float(max(per_step, 1 << 20)) * n_steps
 
     n_long = max(10 * args.steps, 200)
-    if distributed and gather_mode != "none" and guard.go("steady_state", 15, kind="gather", weight=leg_weight(gather_mode, n_long + args.settle)):
+    if args.full and distributed and gather_mode != "none" and guard.go("steady_state", 15, kind="gather", weight=leg_weight(gather_mode, n_long + args.settle)):
         with guard.leg("steady_state", kind="gather", weight=leg_weight(gather_mode, n_long + args.settle)):
             g = make_collector(gather_mode)
             if gather_mode == "sharded":
@@ -1167,7 +1218,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
     # (dreamer/wrappers.py:107-116 ActionRepeat inside, :213-219 Collect outside), the reference runs action_repeat 4
     # (dreamer/dream.py:55) - so one record crosses the links per 4 sub-steps, the scan runs once per record, and the link
     # bound is set against a step of four dynamics kernels + one scan.  (The legs below gather a record per sub-step.)
-    if distributed and not args.no_gather_modes:
+    if args.full and distributed and not args.no_gather_modes:
         out["gather_modes_repeat_4"] = {} if rank == 0 else None
         for m in ("full-u16", "full"):
             n_leg = max(args.steps // 4, 5)
@@ -1202,7 +1253,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
     # (xGMI full mesh, 7 links x 76.8 GB/s inbound per GPU).  Each leg sets the env up for its own payload only
     # (`includes` says what its step carried); `none` is the pure simulation rate; `batch` = sharded without the per-step
     # summary.  Cheapest and most informative first: a leg that fails ends the run with the legs before it in the line.
-    if distributed and not args.no_gather_modes:
+    if args.full and distributed and not args.no_gather_modes:
         order = [m for m in ("none", "batch", "sharded", "summary", "full-u16", "full") if m != gather_mode]
         for m in order:
             wgt = leg_weight(m, max(args.steps // 4, 5 if m not in ("batch", "sharded") else 2 * BATCH_EVERY) + args.settle + 4)
@@ -1238,7 +1289,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
             p2p_close()
 
     # the reference's own setting, action_repeat 4 with the scan once per agent step (dreamer/dream.py:55)
-    if guard.go("action_repeat_4", 8):
+    if args.full and guard.go("action_repeat_4", 8):
         with guard.leg("action_repeat_4"):
             r4_steps = max(args.steps // 4, 5)
             g = make_collector("none")
@@ -1252,7 +1303,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
 
     # secondary figure: cars driven along the track at speed by the reference's follow-the-gap law (its other prefill
     # policy, dreamer/dream.py:211-216) instead of crawling under random actions: single-GPU runs only
-    if world == 1 and not args.no_cpu_baseline_ftg and guard.go("follow_the_gap", 10):
+    if args.full and world == 1 and not args.no_cpu_baseline_ftg and guard.go("follow_the_gap", 10):
         with guard.leg("follow_the_gap"):
             mean_range_random = float(env.views["lidar"].float().mean().item())
             env.reset(mode="random", seed=0)
@@ -1284,7 +1335,7 @@ def run(args, guard, rank, local_rank, world, distributed, t0_run):
                         "(ros_agent/agents/follow_the_gap/src/agent.py:128-234) as a device agent - after 150 settling steps "
                         "(cars at 4 m/s instead of crawling under random actions); includes the agent's kernel"}
     env.close()
-    if rank == 0 and world == 1 and not args.no_configs:
+    if args.full and rank == 0 and world == 1 and not args.no_configs:
         # BASELINE.json configs[1..3], each a few ms of GPU time (configs[0] is the CPU plumbing case, configs[4]
         # the 8-GPU run: `--gpus 8 --mixed-tracks`)
         cfgs = [("configs[1]: 4 096 envs, columbia, 1080-beam lidar", "columbia", 4096, 1, "lidar", 400, 40, "random"),

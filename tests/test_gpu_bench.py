@@ -34,7 +34,7 @@ def _json_line(stdout):
 
 def test_bench_single_gpu_contract():
     r = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "2", "--envs", "4096", "--track",
-                        "columbia", "--cpu-envs", "4096", "--numpy-envs", "256", "--observable-seconds", "2"], cwd=ROOT, capture_output=True,
+                        "columbia", "--cpu-envs", "4096", "--numpy-envs", "256", "--observable-seconds", "2", "--full"], cwd=ROOT, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, _errtext(r.stderr)
     d = _json_line(r.stdout)
@@ -78,11 +78,37 @@ def test_bench_single_gpu_contract():
     assert 1.5 < sl["seconds"] < 6.0 and sl["steps"] > d["steady"]["steps"] and sl["env_steps_per_s"] > 0.5 * d["steady"]["env_steps_per_s"]
 
 
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own; --steps sets the timed steps (one
+    scan launch each); --dump-outputs writes the last timed step's outputs, identical from run to run with the same arguments."""
+    import numpy as np
+    lines = []
+    for name in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--steps", "7", "--warmup", "2", "--envs", "4096", "--track", "columbia",
+                            "--dump-outputs", str(tmp_path / name)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, _errtext(r.stderr)
+        lines.append(_json_line(r.stdout))
+    d = lines[0]
+    assert REQUIRED <= set(d) and d["steps"] == 7 and d["roofline"]["launches"] == 7 and d["value"] > 1e6
+    assert d["ms_per_step"] == pytest.approx(4096 / d["value"] * 1e3, rel=1e-9) and d["config"]["full"] is False
+    assert not {"cpu_baseline", "configs", "tracks", "fresh_reset", "steady", "steady_long", "action_repeat_4", "follow_the_gap",
+                "exact_render", "leg_errors", "aborted"} & set(d)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) and {"lidar.npy", "pose.npy", "reward.npy", "done.npy", "sampled_cars.npy"} <= set(files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y, equal_nan=True), f
+    assert np.load(tmp_path / "a" / "pose.npy").shape == (4096, 1, 6)
+    lidar, rows = np.load(tmp_path / "a" / "lidar.npy"), np.load(tmp_path / "a" / "sampled_cars.npy")
+    assert lidar.shape == (len(rows), 1080) and 0 < len(rows) <= 4096 and np.all(np.diff(rows) > 0) and lidar.max() > 0
+
+
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2 ...` with NO launcher around it (the way the driver starts the N = 1 line): the process
     starts its two ranks itself, rank 0's single JSON line comes through, and the communicator's own rank count is in it."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "6", "--warmup", "2",
-                        "--envs", "2048"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--envs", "2048", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, _errtext(r.stderr)
     d = _json_line(r.stdout)
     assert d["n_gpus"] == 2 and d["config"]["total_envs"] == 4096 and d["config"]["comm_ranks"] == 2
@@ -101,7 +127,7 @@ def test_bench_sees_one_flipped_bit_in_a_gathered_record():
     the line says so and the run fails (each rank exits 4; the launcher reports the failure)."""
     import os
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1",
-                        "--envs", "1024", "--no-gather-modes"], cwd=ROOT, capture_output=True, text=True, timeout=900,
+                        "--envs", "1024", "--no-gather-modes", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900,
                        env=dict(os.environ, RC_BENCH_CORRUPT_GATHER="1"))
     assert r.returncode != 0, _errtext(r.stderr)
     d = _json_line(r.stdout)
@@ -114,7 +140,7 @@ def test_a_secondary_leg_that_raises_or_hangs_does_not_cost_the_headline():
     are then inside a collective it never joins), or hanging, ends the run with the ONE line: the headline, the legs
     measured before it, and `aborted` naming the leg - and exit code 5 (a leg was lost; VERDICT r5 #1b: not 0)."""
     import os
-    base = [sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1", "--envs", "1024"]
+    base = [sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1", "--envs", "1024", "--full"]
     r = subprocess.run(base, cwd=ROOT, capture_output=True, text=True, timeout=900, env=dict(os.environ, RC_BENCH_FAIL_LEG="summary:1"))
     assert r.returncode == 5, _errtext(r.stderr)
     d = _json_line(r.stdout)
@@ -153,7 +179,7 @@ def test_legs_are_budgeted_from_the_time_left():
     in `legs_skipped`, every rank taking the same branch) instead of running into the launcher's time-out; that is not an
     error: exit 0, headline and self-check present."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--steps", "4", "--warmup", "1", "--envs", "1024",
-                        "--time-budget", "30"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--time-budget", "30", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, _errtext(r.stderr)
     d = _json_line(r.stdout)
     assert d["value"] > 0 and d["gather_check"]["payloads"]["sharded"]["ok"] is True and "aborted" not in d
@@ -164,7 +190,7 @@ def test_legs_are_budgeted_from_the_time_left():
 def test_bench_two_ranks_peer_copy_transport():
     """The same two ranks with the gather as direct peer copies (hipIpc works between processes on one device)."""
     r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--backend", "gloo", "--gather-via", "p2p", "--steps", "6",
-                        "--warmup", "2", "--envs", "2048"], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--warmup", "2", "--envs", "2048", "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, _errtext(r.stderr)
     d = _json_line(r.stdout)
     # (the headline stays the sharded store over torch.distributed; the per-step record gathers go over the peer copies)
@@ -179,7 +205,7 @@ def test_bench_two_ranks_peer_copy_transport():
 def test_bench_two_ranks_functional():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--steps", "6", "--warmup",
-           "2", "--envs", "2048", "--backend", "gloo", "--no-cpu-baseline"]
+           "2", "--envs", "2048", "--backend", "gloo", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, _errtext(r.stderr)
     d = _json_line(r.stdout)

@@ -7,7 +7,8 @@ import pytest
 from racing_dreamer_amd import track_assets as ta
 from racing_dreamer_amd import track_compiler as tc
 
-REF_MAPS = "/root/reference/docs/maps/maps"
+# the reference's map images (docs/maps/maps) that the tests below compile: yaml as shipped, images stored as lossless PNG
+REF_MAPS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "maps")
 
 
 BASELINE_TRACKS = ("columbia", "austria", "barcelona", "treitlstrasse_v2", "gbr")
@@ -47,7 +48,6 @@ def test_assets_present_and_sane():
             assert gaps.max() < 0.5                                            # a closed loop, evenly spaced
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MAPS), reason="reference maps only exist in the build container")
 def test_maps_npz_export_has_the_generators_keys_and_values(tmp_path):
     """generate-costmap.py:410-425: key names, value conventions and frame of the racecar_gym-style maps.npz."""
     out = tmp_path / "maps.npz"
@@ -127,7 +127,6 @@ def test_bfs_matches_naive_dilation_restatement():
     assert np.array_equal(np.where(steps < 0, 0, steps), dist.astype(int) * (mask | fl))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MAPS), reason="reference maps only exist in the build container")
 def test_committed_assets_reproduce_from_the_reference_maps():
     t = tc.compile_track("treitlstrasse_v2", REF_MAPS)
     a = ta.load_track("treitlstrasse_v2")
@@ -160,10 +159,7 @@ def test_scene_export_is_what_the_plotting_code_loads(tmp_path):
     from racing_dreamer_amd.compat.racecar_gym.envs.scenarios import World
     from racing_dreamer_amd.track_assets import load_track
     from racing_dreamer_amd.track_compiler import export_scene
-    maps_dir = "/root/reference/docs/maps/maps"
-    if not os.path.isdir(maps_dir):
-        import pytest
-        pytest.skip("needs the reference's map images (build container only)")
+    maps_dir = REF_MAPS
     track = "columbia_slam"
     config_file = export_scene(track, maps_dir, str(tmp_path))
     assert config_file.endswith(f"{track}/{track}.yml")

@@ -3,7 +3,7 @@
 # the env of stage 1 kept (RC_EXP_KEEP_ENV=1: its stream is older than the communicator's).  profiles/r06_i_ab_stream_order_one_rank.txt
 run() {  # name, env...
   name=$1; shift
-  env "$@" python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py \
+  env "$@" python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full \
       --gpus 1 --force-gather --steps 20 --warmup 5 --no-gather-modes 2>gpurun_out/abso_$name.err > gpurun_out/abso_$name.json || { tail -3 gpurun_out/abso_$name.err; }
   python - <<PY
 import json

@@ -2,7 +2,7 @@
 # The plain `--gpus N` line's new legs (whole-record gathers at action_repeat 4, configs[4]'s track mix) with ONE rank over
 # the real RCCL backend (GPU box): bash tools/bench_one_rank_rccl.sh
 mkdir -p gpurun_out
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513 bench.py \
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29513 bench.py --full \
     --gpus 1 --force-gather --steps 20 --warmup 5 2>gpurun_out/one_rank_r5.err > gpurun_out/one_rank_r5.json || { tail -5 gpurun_out/one_rank_r5.err; exit 1; }
 python - <<'PY'
 import json
@@ -18,7 +18,7 @@ print("gather_check", d["gather_check"]["ok"], sorted(d["gather_check"]["payload
 PY
 # ... and the per-step record gathers through the two other transports (the headline stays the sharded store over torch.distributed)
 for via in abi p2p; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29514 bench.py \
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29514 bench.py --full \
       --gpus 1 --force-gather --steps 20 --warmup 5 --gather-via $via 2>gpurun_out/one_rank_$via.err > gpurun_out/one_rank_$via.json || { tail -5 gpurun_out/one_rank_$via.err; exit 1; }
   python - <<PY
 import json
