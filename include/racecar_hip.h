@@ -215,6 +215,50 @@ int rc_step_random(rc_env *env, uint64_t seed, uint32_t step, int32_t repeat);
 int rc_step_group(rc_env **envs, int32_t n, const float *actions_dev, int32_t repeat);
 int rc_step_random_group(rc_env **envs, int32_t n, uint64_t seed, uint32_t step, int32_t repeat);
 
+/* ---- Domain randomization (per episode), both features opt-in and off by default; with both off every output is what it is
+ * without them (the production kernels run).  Each handle has its own settings; rc_step_group honours every handle's.
+ *
+ * Vehicle parameters: five binary32 values per car, columns of a float32 [n_cars][5] array in this order (nominal values =
+ * the spec's constants, bit for bit):
+ *   0 wheel_max  [rad]              front-wheel angle at full steering command     0.19   (steering gain = -wheel_max)
+ *   1 accel_max  [m/s^2]            longitudinal acceleration at full motor        4.0
+ *   2 drag       [1/s]              velocity-proportional deceleration             0.8
+ *   3 max_vel    [m/s]              the velocity clamp                             5.0
+ *   4 steer_step [rad per sub-step] the steering slew per dt = 0.01 s              0.032
+ * The integrator does the same operations in the same order with the car's value as the operand.  The agent-side kernels
+ * (rc_follow_the_gap, rc_follow_the_gap_reference) keep mapping a wheel angle to a command with the NOMINAL 0.19 rad: an
+ * agent does not know its car.  The parameters are state, not record: rc_arena_bytes, the trajectory slab and the compact
+ * slab do not change.
+ *
+ * rc_set_vehicle_randomization: random mode.  At every reset of an env (rc_reset and the auto-reset inside rc_step) each of
+ * its cars draws value_i = lo[i] + u * (hi[i] - lo[i]), u = (w >> 8) * 2^-24, one binary32 rounding per operator (lo == hi
+ * gives lo exactly).  Word j = 5 a + i (car slot a, parameter i) is word j % 4 (x, y, z, w) of Philox4x32-10 keyed by `seed`
+ * with counter (global env id, episode value the spawn draw of that reset uses, j / 4, 2) - the spawn uses counter word 3 = 0
+ * and the random actions their own counters, so starts and actions do not change, and sharding does not change the draw.
+ * Takes effect at each env's next reset.  lo or hi NULL = off (every car back to the nominal values).
+ * rc_set_vehicle_params: fixed mode.  Copies float32 [n_cars][5] from DEVICE memory (stream-ordered); the values persist
+ * across resets and nothing is drawn.  NULL = off.
+ * rc_vehicle_params: the handle's device array of the current values, float32 [n_cars][5] (*bytes = n_cars * 20).
+ *
+ * LiDAR noise (obs lidar only; the occupancy renders do not change): for every beam of every car, after the inter-car minimum
+ * and before the lidar_transform scaling,
+ *     if r < 15: r = clamp(r + n, 0, 15)       n = (k0 + k1 + k2 + k3 - 8190) * s,  s = fl(sigma * 4.2286398820579052e-4f)
+ *     if d < D:  r = 15  (no return)           D = floor(p_drop * 65536 + 0.5)
+ * k0..k3 are bits 0-11 and 12-23 of two words w0, w1, d = (w0 >> 24) << 8 | (w1 >> 24): Irwin-Hall(4) of 12-bit uniforms,
+ * standardised (zero mean, unit variance: 4.2286398820579052e-4 = sqrt(3 / (4096^2 - 1)) in binary32), z bounded by
+ * +- 3.46 sigma; dropout probability D / 65536.  The words come from lowbias32 (two multiply / xor-shift rounds:
+ * x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16):
+ *     key = h(seed_lo ^ h(global car id ^ h(episode ^ h(sub-steps ^ seed_hi))))   (the env's counters as they stand when
+ *                                                                                   the scan runs)
+ *     w_j = h(key + (2 * beam + j) * 0x9E3779B9), j = 0, 1                        (all arithmetic mod 2^32)
+ * so the noise does not depend on which wave or round computes a beam, nor on the sharding.  The uint16 compact copy
+ * quantises the noisy value.  sigma = p_drop = 0 = off.  Runs in its own scan instantiations (rc_scan_kernel_name:
+ * "rc_raycast_car_noise_kernel<...>"); a lab variant, the bounded validation build and the instrumented build refuse it. */
+int rc_set_vehicle_randomization(rc_env *env, const float *lo, const float *hi, uint64_t seed);
+int rc_set_vehicle_params(rc_env *env, const float *params_dev);
+int rc_vehicle_params(rc_env *env, void **dev_ptr, size_t *bytes);
+int rc_set_lidar_noise(rc_env *env, float sigma, float p_drop, uint64_t seed);
+
 /* Batched follow-the-gap agent on the device (the prefill / baseline agent of dreamer/dream.py:211-216, whose
  * host form is agents.gap_follower.GapFollower): from the current LiDAR scan of every car, clip to 6 m,
  * 5-beam smoothing over the forward 202.5 deg, safety bubble of +-60 beams around the closest return, point the wheels at

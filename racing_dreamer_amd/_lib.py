@@ -66,6 +66,10 @@ SYMBOLS = {
     "rc_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "rc_step_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "rc_set_pose": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rc_set_vehicle_randomization": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "rc_set_vehicle_params": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rc_vehicle_params": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
+    "rc_set_lidar_noise": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_uint64]),
     "rc_follow_the_gap": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     "rc_follow_the_gap_reference": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
     "rc_fill_random_actions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),

@@ -19,6 +19,7 @@ from typing import Dict, Optional, Union
 
 import numpy as np
 import torch
+import torch.utils.dlpack
 
 from . import _lib as L
 from . import spec
@@ -59,6 +60,44 @@ TASKS = {"maximize_progress": spec.TASK_MAX_PROGRESS, "max_progress": spec.TASK_
          "max_speed": spec.TASK_MAX_SPEED, "n_step_progress": spec.TASK_N_STEP_PROGRESS}
 
 
+class _DLDevice(C.Structure):
+    _fields_ = [("device_type", C.c_int32), ("device_id", C.c_int32)]
+
+
+class _DLDataType(C.Structure):
+    _fields_ = [("code", C.c_uint8), ("bits", C.c_uint8), ("lanes", C.c_uint16)]
+
+
+class _DLTensor(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("device", _DLDevice), ("ndim", C.c_int32), ("dtype", _DLDataType),
+                ("shape", C.POINTER(C.c_int64)), ("strides", C.POINTER(C.c_int64)), ("byte_offset", C.c_uint64)]
+
+
+class _DLManagedTensor(C.Structure):
+    _fields_ = [("dl_tensor", _DLTensor), ("manager_ctx", C.c_void_p), ("deleter", C.c_void_p)]
+
+
+class _BorrowedDeviceArray:
+    """A float32 array in device memory that the library owns, handed to torch through DLPack without a copy (no deleter: the
+    memory stays the library's).  Valid while the handle lives."""
+
+    def __init__(self, ptr: int, shape, device: torch.device, kind: int = 10):      # 10 = kDLROCM (1 = kDLCPU)
+        self._shape = (C.c_int64 * len(shape))(*shape)
+        self._managed = _DLManagedTensor()
+        t = self._managed.dl_tensor
+        t.data, t.device, t.ndim = ptr, _DLDevice(kind, device.index or 0), len(shape)
+        t.dtype, t.shape, t.strides, t.byte_offset = _DLDataType(2, 32, 1), self._shape, None, 0     # float32, row-major
+        self._kind, self._index = kind, device.index or 0
+
+    def __dlpack_device__(self):
+        return (self._kind, self._index)
+
+    def __dlpack__(self, stream=None, **_kw):
+        new = C.pythonapi.PyCapsule_New
+        new.restype, new.argtypes = C.py_object, [C.c_void_p, C.c_char_p, C.c_void_p]
+        return new(C.addressof(self._managed), b"dltensor", None)
+
+
 def _ensure_lab() -> None:
     """Build the lab library (scan variants 0-6, the stamps build) if the one on disk does not belong to the sources - the
     request that `libracecar_lab.so` exists for.  libracecar_hip.so loads it itself, on the first launch of a lab kernel."""
@@ -76,12 +115,14 @@ class BatchedRaceEnv:
                  time_limit_steps: int = 0, auto_reset: bool = False, profiling: bool = False,
                  lidar_transform: str = "metres", car_tasks=None, n_steps: int = 10,
                  shared_arena: Optional[torch.Tensor] = None, arena_total_cars: int = 0, arena_first_car: int = 0,
-                 stream: Optional[torch.cuda.Stream] = None):
+                 stream: Optional[torch.cuda.Stream] = None, vehicle_randomization=None, lidar_noise=None):
         """car_tasks: optional task name per car slot (agents A, B, ... of a scenario yml; None entries = `task`), e.g.
         ["maximize_progress", "n_step_progress", ...] for baselines/scenarios/max_progress/columbia.yml; n_steps: the
         window of `n_step_progress` in sub-steps.  shared_arena / arena_total_cars / arena_first_car / stream: this env
         fills cars [arena_first_car, ...) of an arena laid out for arena_total_cars cars and runs on the given stream -
-        how `MixedTrackEnv` puts one handle per track behind one set of output tensors."""
+        how `MixedTrackEnv` puts one handle per track behind one set of output tensors.  vehicle_randomization = (lo, hi, seed)
+        and lidar_noise = (sigma, p_drop, seed): the same as calling `set_vehicle_randomization` / `set_lidar_noise` right
+        after construction."""
         if obs_type not in OBS_TYPES:
             raise ValueError(f"obs_type must be one of {sorted(OBS_TYPES)}, got {obs_type!r}")
         if task not in TASKS:
@@ -161,6 +202,14 @@ class BatchedRaceEnv:
             L.check(self._lib.rc_get(self._h, L.F_TIME, C.byref(p1), C.byref(n1)))
             self.summary_slab = self._arena_view[p0.value - base:p1.value - base + n1.value]
         self._own_views = self.views
+        ptr, nb = C.c_void_p(), C.c_size_t()
+        L.check(self._lib.rc_vehicle_params(self._h, C.byref(ptr), C.byref(nb)))
+        self._vp_array = _BorrowedDeviceArray(ptr.value, (self.n_cars, len(spec.VEHICLE_PARAMS)), self.device)
+        self._vehicle_params = torch.utils.dlpack.from_dlpack(self._vp_array)
+        if vehicle_randomization is not None:
+            self.set_vehicle_randomization(*vehicle_randomization)
+        if lidar_noise is not None:
+            self.set_lidar_noise(*lidar_noise)
         if profiling:
             self.set_profiling(True)
 
@@ -257,6 +306,43 @@ class BatchedRaceEnv:
         L.check(self._lib.rc_set_pose(self._h, a.ctypes.data))
         self._exit()
         return self.views
+
+    # ------------------------------------------------------------------ domain randomization (include/racecar_hip.h)
+    def set_vehicle_randomization(self, lo=None, hi=None, seed: int = 0) -> None:
+        """Random mode of the five per-car vehicle parameters (`spec.VEHICLE_PARAMS`: wheel_max, accel_max, drag, max_vel,
+        steer_step): at every reset of an env, rc_reset or auto-reset, each car draws value = lo + u (hi - lo) from Philox keyed
+        by `seed` and (global env id, episode, call, 2).  Takes effect at each env's next reset.  lo = hi = None: off (the
+        spec's constants).  E.g. `env.set_vehicle_randomization(**spec.DR_DEPLOYMENT_LOCK, seed=1)`."""
+        if lo is None or hi is None:
+            L.check(self._lib.rc_set_vehicle_randomization(self._h, None, None, C.c_uint64(0)))
+            return
+        lo_a = np.ascontiguousarray(np.asarray(lo, np.float32).reshape(len(spec.VEHICLE_PARAMS)))
+        hi_a = np.ascontiguousarray(np.asarray(hi, np.float32).reshape(len(spec.VEHICLE_PARAMS)))
+        L.check(self._lib.rc_set_vehicle_randomization(self._h, lo_a.ctypes.data, hi_a.ctypes.data, C.c_uint64(int(seed))))
+
+    def set_vehicle_params(self, params: Optional[torch.Tensor]) -> None:
+        """Fixed mode: float32 [n_cars, 5] (or [num_envs, cars_per_env, 5]) vehicle parameters that persist across resets and
+        are never drawn (evaluation sweeps).  None: off."""
+        if params is None:
+            L.check(self._lib.rc_set_vehicle_params(self._h, None))
+            return
+        t = torch.as_tensor(params, dtype=torch.float32).to(self.device).reshape(self.n_cars, len(spec.VEHICLE_PARAMS)).contiguous()
+        self._enter()
+        L.check(self._lib.rc_set_vehicle_params(self._h, t.data_ptr()))
+        self._exit()
+        self._vp_source = t                  # (the copy is stream-ordered: keep the source alive until the next call)
+
+    @property
+    def vehicle_params(self) -> torch.Tensor:
+        """Device view float32 [n_cars, 5] of every car's current vehicle parameters (nominal values while randomization is
+        off) - state, not record: it changes at resets, so clone what must be kept."""
+        return self._vehicle_params
+
+    def set_lidar_noise(self, sigma: float = 0.0, p_drop: float = 0.0, seed: int = 0) -> None:
+        """Gaussian-like range noise (standardised Irwin-Hall(4), `sigma` metres) and dropout (a beam reads 15 m, "no return",
+        with probability `p_drop`) on the `lidar` scan, counter-based per (seed, global car, episode, sub-step, beam).
+        sigma = p_drop = 0: off."""
+        L.check(self._lib.rc_set_lidar_noise(self._h, float(sigma), float(p_drop), C.c_uint64(int(seed))))
 
     def set_raycast_variant(self, variant: int) -> None:
         """0 = plain traversal, 1 = free-rectangle skipping, 2 = tuned skipping, 3 = tuned + packed block table
@@ -714,6 +800,30 @@ class MixedTrackEnv:
         if len(self.parts) > 8:
             return self._fork_join(lambda p, blk: p._lib.rc_step_random(p._h, C.c_uint64(seed), C.c_uint32(step), rep))
         return self._ordered(lambda: self._lib.rc_step_random_group(self._handles(), len(self.parts), C.c_uint64(seed), C.c_uint32(step), rep))
+
+    # domain randomization: the same settings on every block (each block's handle keys its draws by its global env ids)
+    def set_vehicle_randomization(self, lo=None, hi=None, seed: int = 0) -> None:
+        for p in self.parts:
+            p.set_vehicle_randomization(lo, hi, seed)
+
+    def set_vehicle_params(self, params: Optional[torch.Tensor]) -> None:
+        """float32 [n_cars, 5] in arena order (or None: off)."""
+        if params is None:
+            for p in self.parts:
+                p.set_vehicle_params(None)
+            return
+        t = torch.as_tensor(params, dtype=torch.float32).to(self.device).reshape(self.n_cars, len(spec.VEHICLE_PARAMS))
+        for p, (a, b) in zip(self.parts, self.blocks):
+            p.set_vehicle_params(t[a * self.cars_per_env:b * self.cars_per_env])
+
+    @property
+    def vehicle_params(self) -> torch.Tensor:
+        """float32 [n_cars, 5] in arena order: a COPY gathered from the blocks (each handle holds its own)."""
+        return torch.cat([p.vehicle_params for p in self.parts])
+
+    def set_lidar_noise(self, sigma: float = 0.0, p_drop: float = 0.0, seed: int = 0) -> None:
+        for p in self.parts:
+            p.set_lidar_noise(sigma, p_drop, seed)
 
     def follow_the_gap_reference(self, dt: Optional[float] = None):
         self._fork_join(lambda p, blk: p._lib.rc_follow_the_gap_reference(p._h, 0.01 * p.action_repeat if dt is None else float(dt), None))

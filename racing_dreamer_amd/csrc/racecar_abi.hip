@@ -227,6 +227,7 @@ struct rc_env {
     int exact_chunk = 0;
     void *exact_mem = nullptr;
     float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
+    float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)
     void *order_mem = nullptr;         // RcStateDev::order + the sort's bucket counters (batches of RC_ORDER_MIN_CARS cars and more)
     uint32_t order_age = 0;            // observations since the cars were last sorted by track position
     const float *last_scan_rows = nullptr;   // the LiDAR rows the last scan of this handle wrote (the small batches' cost keys)
@@ -446,6 +447,9 @@ int render_reference_patches(rc_env *env) {
 }
 
 int observe(rc_env *env) {
+    if (env->params.noise_on && (env->launch.raycast_variant != 7 || env->launch.scan_guarded || env->launch.scan_stamps))
+        return fail(RC_ERR_INVALID, "LiDAR noise (rc_set_lidar_noise) is applied by the default scan (variant 7) only, not by a lab variant, "
+                                  "the bounded validation build or the instrumented build");
     int rc_sort = sort_cars_if_due(env);
     if (rc_sort) return rc_sort;
     TIMED(env, RC_K_RAYCAST, rck_launch_raycast(env->params, env->launch, env->stream));
@@ -713,6 +717,20 @@ int rc_field_layout(const rc_config *cfg, int32_t field, size_t *section_offset,
     return RC_OK;
 }
 
+namespace {
+// The spec's values of the five per-car vehicle parameters, in RC_VP_* order (the bit patterns of racecar_spec.h's constants).
+const float kNominalVehicle[RC_VP_COUNT] = {RCS_WHEEL_MAX, RCS_ACCEL_MAX, RCS_DRAG, RCS_MAX_VEL, RCS_STEER_STEP};
+
+// every car's vehicle parameters back to the nominal values (randomization off), stream-ordered
+int fill_nominal_vehicle(rc_env *env) {
+    std::vector<float> rows((size_t)env->n_cars * RC_VP_COUNT);
+    for (size_t i = 0; i < rows.size(); ++i) rows[i] = kNominalVehicle[i % RC_VP_COUNT];
+    HIP_TRY(hipMemcpyAsync(env->vp_mem, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));          // (the host rows go out of scope)
+    return RC_OK;
+}
+}  // namespace
+
 int rc_create(const rc_config *cfg, rc_env **out) {
     if (!out) return fail(RC_ERR_INVALID, "out is NULL");
     *out = nullptr;
@@ -812,6 +830,10 @@ int rc_create(const rc_config *cfg, rc_env **out) {
     p.act_lo1 = cfg->action_low[1];
     p.act_hi0 = cfg->action_high[0];
     p.act_hi1 = cfg->action_high[1];
+    HIP_TRY_FREE(hipMalloc((void **)&env->vp_mem, (size_t)n * RC_VP_COUNT * sizeof(float)));
+    p.vparams = env->vp_mem;
+    p.vp_mode = RC_VP_OFF;
+    if (fill_nominal_vehicle(env)) FAIL_FREE(RC_ERR_HIP);
     hipDeviceProp_t prop;
     HIP_TRY_FREE(hipGetDeviceProperties(&prop, cfg->device));
     env->launch.n_cu = prop.multiProcessorCount;
@@ -836,6 +858,7 @@ void rc_destroy(rc_env *env) {
     if (env->own_arena && env->arena) (void)hipFree(env->arena);
     if (env->state_mem) (void)hipFree(env->state_mem);
     if (env->ftg_prev) (void)hipFree(env->ftg_prev);
+    if (env->vp_mem) (void)hipFree(env->vp_mem);
     if (env->exact_mem) (void)hipFree(env->exact_mem);
     if (env->order_mem) (void)hipFree(env->order_mem);
     if (env->group_dev) (void)hipFree(env->group_dev);
@@ -1241,7 +1264,12 @@ static int group_step(rc_env **envs, int32_t n, const float *actions_dev, int32_
         cars += envs[b]->n_cars;
     }
     g.wave_start[n] = waves;
-    TIMED(lead, RC_K_DYNAMICS, rck_launch_dynamics_group(g, lead->cfg.cars_per_env, repeat, ra, lead->stream));
+    bool dr = false, noise = false;       // a block with the feature off runs the same code with its nominal values / no noise
+    for (int b = 0; b < n; ++b) {
+        dr |= envs[b]->params.vp_mode != RC_VP_OFF;
+        noise |= envs[b]->params.noise_on != 0;
+    }
+    TIMED(lead, RC_K_DYNAMICS, rck_launch_dynamics_group(g, lead->cfg.cars_per_env, repeat, ra, lead->stream, dr));
     // scan: a wave = one car (or 1 / split of one); the split follows the group's total, as one handle of that size would
     int split = lead->dbg[RC_DBG_RAY_SPLIT];
     if (split < 1 || split > 17) split = scan_split(cars, lead->launch.n_cu);
@@ -1251,7 +1279,7 @@ static int group_step(rc_env **envs, int32_t n, const float *actions_dev, int32_
         waves += envs[b]->n_cars * split;
     }
     g.wave_start[n] = waves;
-    TIMED(lead, RC_K_RAYCAST, rck_launch_raycast_group(g, lead->cfg.cars_per_env, split, lead->stream));
+    TIMED(lead, RC_K_RAYCAST, rck_launch_raycast_group(g, lead->cfg.cars_per_env, split, lead->stream, noise));
     for (int b = 0; b < n; ++b) envs[b]->last_scan_rows = envs[b]->params.out.lidar;
     for (int b = 0; b < n; ++b) {
         if (envs[b]->params.render_patch)
@@ -1272,6 +1300,57 @@ int rc_step_group(rc_env **envs, int32_t n, const float *actions_dev, int32_t re
 int rc_step_random_group(rc_env **envs, int32_t n, uint64_t seed, uint32_t step, int32_t repeat) {
     const RcRandomActions ra{1, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), step};
     return group_step(envs, n, nullptr, repeat, ra, "rc_step_random_group");
+}
+
+// ---- domain randomization ------------------------------------------------------------------------------------------------
+int rc_set_vehicle_randomization(rc_env *env, const float *lo, const float *hi, uint64_t seed) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    if (!lo || !hi) {                                     // off: the constants again, in the kernels and in the view
+        env->params.vp_mode = RC_VP_OFF;
+        return fill_nominal_vehicle(env);
+    }
+    for (int i = 0; i < RC_VP_COUNT; ++i)
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || lo[i] > hi[i])
+            return fail(RC_ERR_INVALID, "vehicle randomization: parameter %d needs finite lo <= hi (got %g, %g)", i, (double)lo[i], (double)hi[i]);
+    for (int i = 0; i < RC_VP_COUNT; ++i) { env->params.vp_lo[i] = lo[i]; env->params.vp_hi[i] = hi[i]; }
+    env->params.vp_seed_lo = (uint32_t)(seed & 0xffffffffu);
+    env->params.vp_seed_hi = (uint32_t)(seed >> 32);
+    env->params.vp_mode = RC_VP_RANDOM;
+    return RC_OK;
+}
+
+int rc_set_vehicle_params(rc_env *env, const float *params_dev) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    if (!params_dev) {
+        env->params.vp_mode = RC_VP_OFF;
+        return fill_nominal_vehicle(env);
+    }
+    HIP_TRY(hipMemcpyAsync(env->vp_mem, params_dev, (size_t)env->n_cars * RC_VP_COUNT * sizeof(float), hipMemcpyDeviceToDevice, env->stream));
+    env->params.vp_mode = RC_VP_FIXED;
+    return RC_OK;
+}
+
+int rc_vehicle_params(rc_env *env, void **dev_ptr, size_t *bytes) {
+    if (!env || !dev_ptr) return fail(RC_ERR_INVALID, "NULL argument");
+    *dev_ptr = env->vp_mem;
+    if (bytes) *bytes = (size_t)env->n_cars * RC_VP_COUNT * sizeof(float);
+    return RC_OK;
+}
+
+int rc_set_lidar_noise(rc_env *env, float sigma, float p_drop, uint64_t seed) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!(sigma >= 0.0f) || !std::isfinite(sigma)) return fail(RC_ERR_INVALID, "LiDAR noise: sigma must be finite and >= 0 (got %g)", (double)sigma);
+    if (!(p_drop >= 0.0f && p_drop <= 1.0f)) return fail(RC_ERR_INVALID, "LiDAR noise: p_drop must lie in [0, 1] (got %g)", (double)p_drop);
+    RcParams &p = env->params;
+    p.noise_on = (sigma > 0.0f || p_drop > 0.0f) ? 1 : 0;
+    const float z_scale = RC_NOISE_Z_SCALE;
+    p.noise_scale = sigma * z_scale;                                     // one binary32 rounding
+    p.noise_drop = (uint32_t)std::floor((double)p_drop * 65536.0 + 0.5);   // 0 .. 65536
+    p.noise_seed_lo = (uint32_t)(seed & 0xffffffffu);
+    p.noise_seed_hi = (uint32_t)(seed >> 32);
+    return RC_OK;
 }
 
 int rc_step_host(rc_env *env, const float *actions_host, int32_t repeat) {
@@ -1954,6 +2033,7 @@ int rc_scan_kernel_name(rc_env *env, char *out, size_t bytes) {
     if (li.raycast_variant != 7) snprintf(out, bytes, "rc_raycast_kernel<%d, %d>", a, li.raycast_variant);
     else if (li.scan_stamps != nullptr && a == 1) snprintf(out, bytes, "rc_raycast_car_stamps_kernel");
     else if (li.scan_guarded) snprintf(out, bytes, "rc_raycast_car_kernel<%d, false, true>", a);
+    else if (env->params.noise_on) snprintf(out, bytes, "rc_raycast_car_noise_kernel<%d, %s>", a, li.car_split > 1 ? "true" : "false");
     else snprintf(out, bytes, "rc_raycast_car_kernel<%d, %s, false>", a, li.car_split > 1 ? "true" : "false");
     return RC_OK;
 }

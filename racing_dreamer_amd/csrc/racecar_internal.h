@@ -72,6 +72,14 @@ struct RcOutDev {                // output arena sections (see rc_field)
     uint16_t *lidar_u16;         // optional [n][1080] uint16 copy of the LiDAR row (rc_set_compact_slab), else null
 };
 
+// Per-car vehicle parameters of the integrator (include/racecar_hip.h, rc_set_vehicle_randomization): the columns of vparams.
+enum { RC_VP_WHEEL_MAX = 0, RC_VP_ACCEL_MAX = 1, RC_VP_DRAG = 2, RC_VP_MAX_VEL = 3, RC_VP_STEER_STEP = 4, RC_VP_COUNT = 5 };
+enum { RC_VP_OFF = 0, RC_VP_RANDOM = 1, RC_VP_FIXED = 2 };
+#define RC_VP_TAG 2u                            // Philox counter word 3 of the vehicle draw (the spawn draw uses 0)
+// LiDAR noise: z = (k0 + k1 + k2 + k3 - 8190) * RC_NOISE_Z_SCALE, k_i four 12-bit uniforms: zero mean, unit variance
+// (RC_NOISE_Z_SCALE = sqrt(3 / (4096^2 - 1)) rounded to binary32; oracle side: tests/dr_oracle.py)
+#define RC_NOISE_Z_SCALE 4.2286398820579052e-4f
+
 struct RcParams {
     RcTrackDev trk;
     RcStateDev st;
@@ -87,6 +95,16 @@ struct RcParams {
     int32_t car_task[4];         // task per car slot (resolved: never -1)
     int32_t n_steps;             // window of RC_TASK_N_STEP_PROGRESS [sub-steps]
     uint32_t *scan_overrun;      // device counter: waves of the BOUNDED scan build that used up a round's trip budget
+    // ---- domain randomization (rc_set_vehicle_randomization / rc_set_vehicle_params / rc_set_lidar_noise).  Appended, so that
+    // the kernel-argument offsets of everything above stay where the production instantiations read them.
+    float *vparams;              // [n_cars][RC_VP_COUNT] the car's vehicle parameters (nominal values while vp_mode is off)
+    int32_t vp_mode;             // RC_VP_OFF | RC_VP_RANDOM | RC_VP_FIXED
+    float vp_lo[RC_VP_COUNT], vp_hi[RC_VP_COUNT];   // random: value = lo + u (hi - lo) at every reset
+    uint32_t vp_seed_lo, vp_seed_hi;
+    int32_t noise_on;            // the scan adds range noise and dropout (rc_raycast_*_noise_kernel)
+    float noise_scale;           // sigma * RC_NOISE_Z_SCALE, rounded once (host)
+    uint32_t noise_drop;         // dropout threshold on 16 bits: floor(p_drop * 65536 + 0.5)
+    uint32_t noise_seed_lo, noise_seed_hi;
 };
 
 #define RC_PATCH_SKIP 0x7fffffff
@@ -145,8 +163,8 @@ hipError_t rck_sample_windows(const RcSampleWindows &a, hipStream_t s);
 hipError_t rck_cost_keys(const float *lidar_dev, int n_cars, float *key_dev, hipStream_t s);
 hipError_t rck_sort_cars(const float *progress_dev, int n_cars, uint32_t *counts_dev, int32_t *order_dev, hipStream_t s);
 struct RcRandomActions;
-hipError_t rck_launch_dynamics_group(const RcGroup &g, int cars_per_env, int repeat, const RcRandomActions &ra, hipStream_t s);
-hipError_t rck_launch_raycast_group(const RcGroup &g, int cars_per_env, int split, hipStream_t s);
+hipError_t rck_launch_dynamics_group(const RcGroup &g, int cars_per_env, int repeat, const RcRandomActions &ra, hipStream_t s, bool dr);   // dr: some block's vp_mode is on
+hipError_t rck_launch_raycast_group(const RcGroup &g, int cars_per_env, int split, hipStream_t s, bool noise);   // noise: some block's noise_on
 struct RcBatchRows {             // rc_sample_batch: what turns the row gather into the gather of a whole training batch
     uint32_t obs_mask, reset_mask;                   // by position in the gather's field table
     uint32_t reset_word[RC_GATHER_MAX_FIELDS];

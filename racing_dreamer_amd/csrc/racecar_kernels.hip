@@ -311,6 +311,36 @@ __device__ __forceinline__ void apply_reset(const RcParams &p, int e, Car (&car)
     agent_steps = 0;
 }
 
+// Vehicle randomization (rc_set_vehicle_randomization): the parameters of the cars of env e for the episode that a reset with
+// episode value ep starts.  Word j = 5 a + i (car a, parameter i) is word j % 4 of Philox(global env id, ep, j / 4, RC_VP_TAG);
+// value = lo + u (hi - lo), u = (w >> 8) 2^-24, one rounding per operator (lo == hi gives lo exactly).
+template <int A>
+__device__ __forceinline__ void draw_vehicle(const RcParams &p, int e, uint32_t ep, float (&vp)[A][RC_VP_COUNT]) {
+    const uint32_t g = p.first_env + (uint32_t)e;
+    constexpr int kCalls = (RC_VP_COUNT * A + 3) / 4;
+    uint32_t w[4 * kCalls];
+#pragma unroll
+    for (int k = 0; k < kCalls; ++k) {
+        const rcd::u32x4 r = rcd::philox4x32(g, ep, (uint32_t)k, RC_VP_TAG, p.vp_seed_lo, p.vp_seed_hi);
+        w[4 * k] = r.x; w[4 * k + 1] = r.y; w[4 * k + 2] = r.z; w[4 * k + 3] = r.w;
+    }
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+#pragma unroll
+        for (int i = 0; i < RC_VP_COUNT; ++i) {
+            const float u = (float)(w[RC_VP_COUNT * a + i] >> 8) * 5.9604644775390625e-8f;
+            vp[a][i] = p.vp_lo[i] + u * (p.vp_hi[i] - p.vp_lo[i]);
+        }
+}
+
+template <int A>
+__device__ __forceinline__ void store_vehicle(const RcParams &p, int e, const float (&vp)[A][RC_VP_COUNT]) {
+#pragma unroll
+    for (int a = 0; a < A; ++a)
+#pragma unroll
+        for (int i = 0; i < RC_VP_COUNT; ++i) p.vparams[(size_t)(e * A + a) * RC_VP_COUNT + i] = vp[a][i];
+}
+
 template <int A>
 __device__ __forceinline__ void load_cars(const RcParams &p, int e, Car (&car)[A]) {
 #pragma unroll
@@ -377,10 +407,12 @@ __device__ __forceinline__ void store_step_results(const RcParams &p, int e, con
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int A>
+template <int A, bool DR = false>
 // rand_on != 0: the actions are not read but drawn here, U(-1, 1)^2 from Philox keyed by (seed, step, global car id) -
 // the same numbers rc_random_actions_kernel writes (synthetic random-action rollouts without a launch of their own);
 // they are stored to `actions` as well, so the buffer shows what was applied.
+// DR: the five vehicle parameters of the integrator come from the car (RcParams::vparams) instead of the spec's constants - the
+// same operations in the same order, only the operand differs - and a reset in random mode draws them anew (draw_vehicle).
 __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restrict__ actions, const int repeat, const int rand_on,
                                              const uint32_t rand_lo, const uint32_t rand_hi, const uint32_t rand_step, const int e) {
     const RcTrackDev &t = p.trk;
@@ -391,6 +423,13 @@ __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restric
     int steps = p.st.steps[e], agent_steps = p.st.agent_steps[e];
     Spawn spawn[A];
     if (p.auto_reset) prepare_reset<A>(p, e, episode, spawn);      // ahead of the step: see prepare_reset
+    float vp[A][RC_VP_COUNT];
+    if (DR) {
+#pragma unroll
+        for (int a = 0; a < A; ++a)
+#pragma unroll
+            for (int i = 0; i < RC_VP_COUNT; ++i) vp[a][i] = p.vparams[(size_t)(e * A + a) * RC_VP_COUNT + i];
+    }
     float motor[A], steer[A];
     bool any_done = false;
 #pragma unroll
@@ -426,10 +465,13 @@ __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restric
             for (int a = 0; a < A; ++a) {
                 Car &c = car[a];
                 const float m = motor[a];
-                const float force = fabsf(m) * RCS_ACCEL_MAX;
-                const float acc = (m >= 0.0f ? force : -force) - RCS_DRAG * c.v;
-                c.v = clampf(c.v + acc * RCS_DT, 0.0f, RCS_MAX_VEL);
-                const float dd = clampf(steer[a] * RCS_STEER_GAIN - c.dl, -RCS_STEER_STEP, RCS_STEER_STEP);
+                const float accel_max = DR ? vp[a][RC_VP_ACCEL_MAX] : RCS_ACCEL_MAX, drag = DR ? vp[a][RC_VP_DRAG] : RCS_DRAG;
+                const float max_vel = DR ? vp[a][RC_VP_MAX_VEL] : RCS_MAX_VEL, steer_step = DR ? vp[a][RC_VP_STEER_STEP] : RCS_STEER_STEP;
+                const float steer_gain = DR ? -vp[a][RC_VP_WHEEL_MAX] : RCS_STEER_GAIN;
+                const float force = fabsf(m) * accel_max;
+                const float acc = (m >= 0.0f ? force : -force) - drag * c.v;
+                c.v = clampf(c.v + acc * RCS_DT, 0.0f, max_vel);
+                const float dd = clampf(steer[a] * steer_gain - c.dl, -steer_step, steer_step);
                 c.dl = c.dl + dd;
                 float sd, cd;
                 sincos32(c.dl, sd, cd);
@@ -516,7 +558,13 @@ __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restric
         bool fin = false;
 #pragma unroll
         for (int a = 0; a < A; ++a) fin |= car[a].done != 0;
-        if (fin) apply_reset<A>(p, e, car, spawn, episode, steps, agent_steps);
+        if (fin) {
+            apply_reset<A>(p, e, car, spawn, episode, steps, agent_steps);
+            if (DR && p.vp_mode == RC_VP_RANDOM) {
+                draw_vehicle<A>(p, e, episode, vp);
+                store_vehicle<A>(p, e, vp);
+            }
+        }
     }
     store_state_and_obs<A>(p, e, car, steps, agent_steps);
 }
@@ -527,6 +575,16 @@ __global__ __launch_bounds__(256) void rc_dynamics_kernel(RcParams p, float *__r
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.num_envs) return;
     dynamics_env<A>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+}
+
+// The same with the vehicle parameters per car (rc_set_vehicle_randomization / rc_set_vehicle_params): launched only while a
+// handle's vp_mode is not off, so the kernel above stays what it was.
+template <int A>
+__global__ __launch_bounds__(256) void rc_dynamics_dr_kernel(RcParams p, float *__restrict__ actions, int repeat,
+                                                             int rand_on, uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.num_envs) return;
+    dynamics_env<A, true>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
 }
 
 // Where the car of rank r (position along the track) stands in RcStateDev::order - see rc_order_place_kernel.
@@ -561,6 +619,19 @@ __global__ __launch_bounds__(256) void rc_dynamics_group_kernel(const RcParams *
     dynamics_env<A>(p, g.actions[b], repeat, rand_on, rand_lo, rand_hi, rand_step, e);
 }
 
+// (a group in which some handle's vehicle parameters are per car; a block whose handle has them off reads its nominal values)
+template <int A>
+__global__ __launch_bounds__(256) void rc_dynamics_dr_group_kernel(const RcParams *__restrict__ params, RcGroup g, int repeat, int rand_on,
+                                                                   uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
+    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    if (wave >= g.wave_start[g.n]) return;
+    const int b = group_block(g, wave);
+    const RcParams p = params[b];
+    const int e = (wave - g.wave_start[b]) * 64 + (int)(threadIdx.x & 63u);
+    if (e >= p.num_envs) return;
+    dynamics_env<A, true>(p, g.actions[b], repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+}
+
 template <int A>
 __global__ __launch_bounds__(256) void rc_reset_kernel(RcParams p, const uint8_t *__restrict__ mask) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -585,6 +656,18 @@ __global__ __launch_bounds__(256) void rc_reset_kernel(RcParams p, const uint8_t
     }
     store_step_results<A>(p, e, car, steps);
     store_state_and_obs<A>(p, e, car, steps, agent_steps);
+}
+
+// rc_reset with vehicle randomization in random mode: the reset above, then the new episode's vehicle parameters
+template <int A>
+__global__ __launch_bounds__(256) void rc_reset_dr_kernel(RcParams p, const uint8_t *__restrict__ mask) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.num_envs) return;
+    if (mask != nullptr && mask[e] == 0) return;
+    const uint32_t episode = p.st.episode[e];
+    float vp[A][RC_VP_COUNT];
+    draw_vehicle<A>(p, e, episode, vp);
+    store_vehicle<A>(p, e, vp);
 }
 
 // Device self-test of that property (rc_selftest_reciprocal): every fp32 with biased exponent in [exp_lo, exp_hi],
@@ -775,6 +858,39 @@ __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *_
     // (this launch hands every XCD a STRETCH of the slots, not every eighth: it takes the cars by rank)
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[order_slot_of_rank(slot, (uint32_t)p.n_cars)] : slot;
     scan_car<A, false, OVERLAP, false>(p, car, part, split, threadIdx.x & 63u, lds_row);
+}
+
+// The scan with LiDAR noise and dropout (rc_set_lidar_noise; scan_car's NOISE, lidar_noise in racecar_scan.h): new
+// instantiations, launched only while a handle's noise is on, so the production kernels above stay what they were.
+template <int A, bool OVERLAP>
+__global__ __launch_bounds__(256) void rc_raycast_car_noise_kernel(RcParams p, int split) {
+    extern __shared__ uint32_t lds_words[];
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
+    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned slot = wave / (unsigned)split, part = wave - slot * (unsigned)split;
+    if (slot >= (unsigned)p.n_cars) return;
+    const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[slot] : slot;
+    scan_car<A, false, OVERLAP, false, true>(p, car, part, split, lane, lds_row);
+}
+
+template <int A, bool OVERLAP>
+__global__ __launch_bounds__(256) void rc_raycast_group_noise_kernel(const RcParams *__restrict__ params, RcGroup g, int split) {
+    extern __shared__ uint32_t lds_words[];
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
+    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const int launched = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    const int per_xcd = (g.wave_start[g.n] + 7) >> 3;
+    const int wave = (launched & 7) * per_xcd + (launched >> 3);
+    if ((launched >> 3) >= per_xcd || wave >= g.wave_start[g.n]) return;
+    const int b = group_block(g, wave);
+    const RcParams p = params[b];
+    const unsigned local = (unsigned)(wave - g.wave_start[b]);
+    const unsigned slot = local / (unsigned)split, part = local - slot * (unsigned)split;
+    if (slot >= (unsigned)p.n_cars) return;
+    const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[order_slot_of_rank(slot, (uint32_t)p.n_cars)] : slot;
+    scan_car<A, false, OVERLAP, false, true>(p, car, part, split, threadIdx.x & 63u, lds_row);
 }
 
 // lidar_occupancy (H11, dreamer/wrappers.py:390-408): ego-aligned 64x64 patch of the drivable area,
@@ -1911,7 +2027,11 @@ hipError_t rck_set_lds_limits(size_t lds_bytes) {
                           reinterpret_cast<const void *>(rc_raycast_car_kernel<1, true, false>), reinterpret_cast<const void *>(rc_raycast_car_kernel<2, true, false>),
                           reinterpret_cast<const void *>(rc_raycast_car_kernel<3, true, false>), reinterpret_cast<const void *>(rc_raycast_car_kernel<4, true, false>),
                           reinterpret_cast<const void *>(rc_raycast_car_kernel<1, false, true>), reinterpret_cast<const void *>(rc_raycast_car_kernel<2, false, true>),
-                          reinterpret_cast<const void *>(rc_raycast_car_kernel<3, false, true>), reinterpret_cast<const void *>(rc_raycast_car_kernel<4, false, true>)}) {
+                          reinterpret_cast<const void *>(rc_raycast_car_kernel<3, false, true>), reinterpret_cast<const void *>(rc_raycast_car_kernel<4, false, true>),
+                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<1, false>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<2, false>),
+                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<3, false>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<4, false>),
+                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<1, true>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<2, true>),
+                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<3, true>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<4, true>)}) {
         e = hipFuncGetAttributes(&fa, k);
         if (e != hipSuccess) return e;
         if (fa.sharedSizeBytes != 0) return hipErrorInvalidValue;
@@ -1934,18 +2054,34 @@ hipError_t rck_set_lds_limits(size_t lds_bytes) {
 
 hipError_t rck_launch_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s) {
     const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
+    if (p.vp_mode != RC_VP_OFF) {
+        DISPATCH_A(p.cars_per_env, launch((rc_dynamics_dr_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
+        return hipGetLastError();
+    }
     DISPATCH_A(p.cars_per_env, launch((rc_dynamics_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
     return hipGetLastError();
 }
 
-hipError_t rck_launch_dynamics_group(const RcGroup &g, int cars_per_env, int repeat, const RcRandomActions &ra, hipStream_t s) {
+hipError_t rck_launch_dynamics_group(const RcGroup &g, int cars_per_env, int repeat, const RcRandomActions &ra, hipStream_t s, bool dr) {
     const int waves = g.wave_start[g.n], blocks = (waves + 3) / 4;
+    if (dr) {
+        DISPATCH_A(cars_per_env, launch((rc_dynamics_dr_group_kernel<kA>), dim3(blocks), dim3(256), 0, s, g.params, g, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
+        return hipGetLastError();
+    }
     DISPATCH_A(cars_per_env, launch((rc_dynamics_group_kernel<kA>), dim3(blocks), dim3(256), 0, s, g.params, g, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
     return hipGetLastError();
 }
 
-hipError_t rck_launch_raycast_group(const RcGroup &g, int cars_per_env, int split, hipStream_t s) {
+hipError_t rck_launch_raycast_group(const RcGroup &g, int cars_per_env, int split, hipStream_t s, bool noise) {
     const int waves = ((g.wave_start[g.n] + 7) / 8) * 8;     // one wave per workgroup, as the single-handle scan; whole turns of the 8 XCDs
+    if (noise) {
+        if (split > 1) {
+            DISPATCH_A(cars_per_env, launch((rc_raycast_group_noise_kernel<kA, true>), dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s, g.params, g, split));
+        } else {
+            DISPATCH_A(cars_per_env, launch((rc_raycast_group_noise_kernel<kA, false>), dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s, g.params, g, split));
+        }
+        return hipGetLastError();
+    }
     if (split > 1) {
         DISPATCH_A(cars_per_env, launch((rc_raycast_group_kernel<kA, true>), dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s, g.params, g, split));
     } else {
@@ -1956,6 +2092,8 @@ hipError_t rck_launch_raycast_group(const RcGroup &g, int cars_per_env, int spli
 
 hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s) {
     const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
+    if (p.vp_mode == RC_VP_RANDOM)        // the new episode's vehicle parameters first: the draw reads the episode value the reset increments
+        DISPATCH_A(p.cars_per_env, hipLaunchKernelGGL((rc_reset_dr_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
     DISPATCH_A(p.cars_per_env, launch((rc_reset_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
     return hipGetLastError();
 }
@@ -1972,6 +2110,14 @@ hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, hipStre
     }
     const int threads = li.car_threads, per = threads / 64;                     // waves per workgroup
     const long long waves = (long long)p.n_cars * li.car_split;
+    if (p.noise_on) {                 // LiDAR noise: its own instantiations (the ABI refuses it with the bounded build)
+        if (li.car_split > 1) {
+            DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_noise_kernel<kA, true>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
+        } else {
+            DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_noise_kernel<kA, false>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
+        }
+        return hipGetLastError();
+    }
     if (li.scan_guarded) {            // a validation band is in force: the build whose trip loop counts its trips
         DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_kernel<kA, false, true>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
     } else if (li.car_split > 1) {    // small batch, few waves per SIMD: prepare the next round under the first request

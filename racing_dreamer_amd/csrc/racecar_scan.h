@@ -450,10 +450,45 @@ constexpr unsigned kCarLdsBytes = kCarRowBytes + 2 * RC_FIRST_PLANES;  // ... an
 // took the exact path, 25 / 26 trips per round (a nibble each), 24 HW_ID, 5 XCC_ID.
 // OVERLAP: the next round is prepared under the first request of the current one (ray_traverse's `between`) instead of
 // ahead of the traversal.
-template <int A, bool STAMPS = false, bool OVERLAP = false, bool GUARD = true>
+// LiDAR noise (rc_set_lidar_noise; oracle side: tests/dr_oracle.py).  lowbias32 (C. Wellons' 32-bit integer hash: two
+// multiply / xor-shift rounds) keys a car by (noise seed, global car id, its env's episode and sub-step counters) and, from
+// that key, a beam by its index: words w0, w1 = hash(key + (2 beam + j) 0x9E3779B9), j = 0, 1.  z = (k0 + k1 + k2 + k3 - 8190)
+// * RC_NOISE_Z_SCALE with k0, k1 = bits 0-11, 12-23 of w0 and k2, k3 those of w1 (Irwin-Hall(4) of 12-bit uniforms: zero
+// mean, unit variance); the beam drops out when (w0 >> 24) << 8 | (w1 >> 24) < noise_drop.  Everything but the last
+// multiply and add is integer, so nothing depends on which wave or round computes a beam.
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ uint32_t noise_car_key(const RcParams &p, uint32_t global_car, uint32_t episode, uint32_t steps) {
+    return lowbias32(p.noise_seed_lo ^ lowbias32(global_car ^ lowbias32(episode ^ lowbias32(steps ^ p.noise_seed_hi))));
+}
+// range r [m] of beam `beam` after the inter-car minimum, before the transform
+__device__ __forceinline__ float lidar_noise(const RcParams &p, uint32_t key, uint32_t beam, float r) {
+    const uint32_t x0 = key + beam * (2u * 0x9E3779B9u);
+    const uint32_t w0 = lowbias32(x0), w1 = lowbias32(x0 + 0x9E3779B9u);
+    const int k = (int)((w0 & 0xfffu) + ((w0 >> 12) & 0xfffu) + (w1 & 0xfffu) + ((w1 >> 12) & 0xfffu));
+    const float n = (float)(k - 8190) * p.noise_scale;                  // exact integer, one rounding
+    r = r < RCS_MAX_RANGE ? rcd::clampf(r + n, 0.0f, RCS_MAX_RANGE) : r;
+    const uint32_t d = ((w0 >> 16) & 0xff00u) | (w1 >> 24);
+    return d < p.noise_drop ? RCS_MAX_RANGE : r;
+}
+
+// NOISE: range noise and dropout (lidar_noise) after the inter-car minimum - rc_raycast_*_noise_kernel; a block of a group
+// launch whose handle has the noise off (noise_on = 0) skips it.
+template <int A, bool STAMPS = false, bool OVERLAP = false, bool GUARD = true, bool NOISE = false>
 __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, const unsigned part, const int split,
                                          const unsigned lane, const uint32_t lds_row, unsigned long long *stamps = nullptr) {
     const RcTrackDev &t = p.trk;
+    uint32_t noise_key = 0u;
+    if (NOISE && p.noise_on) {       // the counters as they stand when the scan runs (after the step, after an auto-reset)
+        const unsigned env = car / (unsigned)A;
+        noise_key = noise_car_key(p, p.first_env * (uint32_t)A + car, p.st.episode[env], (uint32_t)p.st.steps[env]);
+    }
     auto stamp = [&](int slot) {
         if (STAMPS && stamps != nullptr) {
             const unsigned long long now = __builtin_amdgcn_s_memtime();
@@ -586,6 +621,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
                 }
             }
         }
+        if (NOISE && p.noise_on) rng = lidar_noise(p, noise_key, (unsigned)round * 64u + lane, rng);
         if (p.lidar_transform == 1) rng = rng / RCS_MAX_RANGE - 0.5f;                 // dreamer/tools.py:274
         else if (p.lidar_transform == 2) rng = rng * (1.0f / RCS_MAX_RANGE);          // single_agent.py:92-99
         if (STAMPS) asm volatile("" :: "v"(rng));

@@ -44,6 +44,16 @@ STEER_RATE = 3.2              # rad/s steering slew limit                       
 X_REAR, X_FRONT, HALF_W = -0.10, 0.45, 0.15   # footprint in the body frame [m]    (free)
 FOOTPRINT_LONG_PTS, FOOTPRINT_SHORT_PTS = 12, 5
 
+# --- per-episode domain randomization (include/racecar_hip.h, rc_set_vehicle_randomization) ----------
+# The five per-car vehicle parameters of the integrator, in column order, and their nominal values (= the constants above as
+# float32, bit for bit; the steering slew is stored per sub-step: STEER_RATE * DT as the literal the kernels use).
+VEHICLE_PARAMS = ("wheel_max", "accel_max", "drag", "max_vel", "steer_step")
+VEHICLE_NOMINAL = (0.19, 4.0, 0.8, 5.0, 0.032)
+# The one named preset: the steering lock of the reference's deployment nodes, which scale the policy's steering by
+# k = 0.4 (ros_agent/agents/acme/src/agent.py:90, ros_agent/agents/sb3/src/agent.py:90), 0.6 or 0.7
+# (ros_agent/agents/dreamer/src/agent.py:111-112) times MAX_STEER 0.42: wheel_max in [0.168, 0.294] rad, the rest nominal.
+DR_DEPLOYMENT_LOCK = {"lo": (0.4 * 0.42, 4.0, 0.8, 5.0, 0.032), "hi": (0.7 * 0.42, 4.0, 0.8, 5.0, 0.032)}
+
 # --- task (dreamer/scenarios/max_progress/columbia.yml:9-10) ------------------------
 N_CHECKPOINTS = 20            # (free)
 PROGRESS_REWARD = 100.0       # (free; racecar_gym default)
