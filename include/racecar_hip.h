@@ -259,6 +259,51 @@ int rc_set_vehicle_params(rc_env *env, const float *params_dev);
 int rc_vehicle_params(rc_env *env, void **dev_ptr, size_t *bytes);
 int rc_set_lidar_noise(rc_env *env, float sigma, float p_drop, uint64_t seed);
 
+/* ---- Track set: a new track at every reset (the reference's ChangingTrackSingleAgentRaceEnv, per env, on the device) --------
+ * A handle may carry a track set: T tracks, 1 <= T <= 8 (RC_GROUP_MAX).  Each env has a current track track[e], an int32 in [0, T).
+ *   Shared track: all cars of an env are on the env's track.  Car-car collision is unchanged.
+ *   Which resets switch: every reset of an env draws its next track BEFORE the spawn draw, then spawns on that track by the
+ *   unchanged reset law (grid / random / random_ball, spawn_safe of that track).  This covers rc_reset with or without a mask and
+ *   the auto-reset inside rc_step.  One exception: an env's first reset after the track set is installed keeps its initial
+ *   assignment.  This is per env, so a masked rc_reset starts only the envs it resets (_ChangingTrack.reset's _started flag).
+ *   Orders:
+ *     RC_TRACK_ORDER_SEQUENTIAL  track = (track + 1) mod T.
+ *     RC_TRACK_ORDER_RANDOM      r = word 0 (x) of Philox4x32-10 keyed by the set's own `seed`, counter (global env id, the episode
+ *                                value that reset's spawn draw uses, 0, 3) - counter word 3 = 3 is free: the spawn and the random
+ *                                actions use 0, vehicle randomization 2, window sampling 0x57494e44.  track = (r * T) >> 32 (the
+ *                                law of the spawn bin).  With weights w_0..w_{T-1} (finite, > 0): track = the number of k in
+ *                                [1, T) with c_k <= r, c_k = min(floor(2^32 * S_k / S + 0.5), 2^32 - 1), S_k = w_0 + ... + w_{k-1}
+ *                                and S = w_0 + ... + w_{T-1} summed in binary64 from the binary32 weights (rounded half up once).
+ *     RC_TRACK_ORDER_MANUAL      track = next[e], a device int32 array the caller writes (rc_set_next_track).  It persists and is
+ *                                read at each reset; a value outside [0, T) keeps the current track.
+ *   Sharding: the draw depends only on the global env id and the episode, so a shard (first_env) sees the tracks of the full job.
+ *   Outputs: after a step track[e] names the track of the observation in the arena; after an auto-reset that is the new episode's
+ *   track, and the first patch stays all zeros as before.
+ *   Layout: the track ids are state, not record: rc_arena_bytes, the trajectory slab, the compact slab and RC_ABI_VERSION do not
+ *   change.
+ *   Vehicle randomization and LiDAR noise compose with a track set.
+ *   Refused (RC_ERR_INVALID): obs_type RC_OBS_LIDAR_OCCUPANCY_REFERENCE (its exact render holds per-handle scratch from
+ *   rc_set_source_frame); a track-set handle in rc_step_group / rc_step_random_group; a lab scan variant, the bounded validation
+ *   build and the instrumented scan (at the next observation, as the noise scan); rc_set_pose.
+ *
+ * rc_set_track_set: tracks[0..n) are handles that went through rc_load_track on the same device (the owner itself may be one of
+ * them; a small handle, 1 env, is enough: only its track tables are used).  They must outlive the owner, or the next
+ * rc_set_track_set.  order: RC_TRACK_ORDER_*.  weights_or_null: T floats (order random only).  initial_dev_or_null: int32
+ * [num_envs] in DEVICE memory, each in [0, n) (copied and checked at the call); NULL = contiguous blocks of near-equal size, the
+ * first num_envs % n tracks one env longer (MixedTrackEnv's split).  The next-track array of manual order starts as the initial
+ * assignment.  Takes effect at each env's next reset (the first keeps `initial`).  n = 0 turns the feature off: the production
+ * kernels run again and rc_scan_kernel_name reports their name.
+ * rc_set_next_track: copies int32 [num_envs] from DEVICE memory (stream-ordered) into the next-track array of manual order.
+ * rc_track_ids: the handle's device array of the current tracks, int32 [num_envs] (*bytes = num_envs * 4); valid once a track
+ * set has been installed.
+ * Kernels: rc_dynamics_ts_kernel / rc_reset_ts_kernel (per-lane track tables), rc_ts_count / start / place_kernel (the cars track-major every
+ * observation), rc_raycast_ts_kernel (rc_scan_kernel_name: "rc_raycast_ts_kernel<A, split, noise>"), rc_patch_ts_kernel. */
+enum { RC_TRACK_ORDER_SEQUENTIAL = 0, RC_TRACK_ORDER_RANDOM = 1, RC_TRACK_ORDER_MANUAL = 2 };
+int rc_set_track_set(rc_env *env, rc_env *const *tracks, int32_t n, int32_t order, const float *weights_or_null,
+                     const int32_t *initial_dev_or_null, uint64_t seed);
+int rc_set_next_track(rc_env *env, const int32_t *next_dev);
+int rc_track_ids(rc_env *env, void **dev_ptr, size_t *bytes);
+
 /* Batched follow-the-gap agent on the device (the prefill / baseline agent of dreamer/dream.py:211-216, whose
  * host form is agents.gap_follower.GapFollower): from the current LiDAR scan of every car, clip to 6 m,
  * 5-beam smoothing over the forward 202.5 deg, safety bubble of +-60 beams around the closest return, point the wheels at

@@ -70,6 +70,9 @@ SYMBOLS = {
     "rc_set_vehicle_params": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rc_vehicle_params": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
     "rc_set_lidar_noise": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_uint64]),
+    "rc_set_track_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "rc_set_next_track": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rc_track_ids": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
     "rc_follow_the_gap": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     "rc_follow_the_gap_reference": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
     "rc_fill_random_actions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),

@@ -56,6 +56,7 @@ _FIELD_VIEWS = {
 OBS_TYPES = {"lidar": 0, "lidar_occupancy": 1, "lidar_occupancy_reference": 2}
 # scaling fused into the scan's store: metres | dreamer (x/15 - 0.5, tools.py:274) | unit (x/15, single_agent.py:92-99)
 LIDAR_TRANSFORMS = {"metres": 0, "dreamer": 1, "unit": 2}
+TRACK_ORDERS = {"sequential": 0, "random": 1, "manual": 2}         # include/racecar_hip.h, RC_TRACK_ORDER_*
 TASKS = {"maximize_progress": spec.TASK_MAX_PROGRESS, "max_progress": spec.TASK_MAX_PROGRESS,
          "max_speed": spec.TASK_MAX_SPEED, "n_step_progress": spec.TASK_N_STEP_PROGRESS}
 
@@ -81,12 +82,12 @@ class _BorrowedDeviceArray:
     """A float32 array in device memory that the library owns, handed to torch through DLPack without a copy (no deleter: the
     memory stays the library's).  Valid while the handle lives."""
 
-    def __init__(self, ptr: int, shape, device: torch.device, kind: int = 10):      # 10 = kDLROCM (1 = kDLCPU)
+    def __init__(self, ptr: int, shape, device: torch.device, kind: int = 10, code: int = 2):   # 10 = kDLROCM (1 = kDLCPU); code 2 = float, 0 = int
         self._shape = (C.c_int64 * len(shape))(*shape)
         self._managed = _DLManagedTensor()
         t = self._managed.dl_tensor
         t.data, t.device, t.ndim = ptr, _DLDevice(kind, device.index or 0), len(shape)
-        t.dtype, t.shape, t.strides, t.byte_offset = _DLDataType(2, 32, 1), self._shape, None, 0     # float32, row-major
+        t.dtype, t.shape, t.strides, t.byte_offset = _DLDataType(code, 32, 1), self._shape, None, 0     # 32-bit, row-major
         self._kind, self._index = kind, device.index or 0
 
     def __dlpack_device__(self):
@@ -233,6 +234,8 @@ class BatchedRaceEnv:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.rc_destroy(self._h)
             self._h = C.c_void_p()
+        for src in getattr(self, "_ts_sources", ()):       # (a track set's source handles outlive the owner)
+            src.close()
 
     def __del__(self):
         try:
@@ -343,6 +346,58 @@ class BatchedRaceEnv:
         with probability `p_drop`) on the `lidar` scan, counter-based per (seed, global car, episode, sub-step, beam).
         sigma = p_drop = 0: off."""
         L.check(self._lib.rc_set_lidar_noise(self._h, float(sigma), float(p_drop), C.c_uint64(int(seed))))
+
+    # ------------------------------------------------------------------ track set (include/racecar_hip.h, rc_set_track_set)
+    @classmethod
+    def with_track_set(cls, tracks, num_envs: int, cars_per_env: int = 1, order: str = "sequential", initial=None, weights=None,
+                       seed: int = 0, **kw) -> "BatchedRaceEnv":
+        """A batch whose envs switch track at every reset, on the device (the reference's ChangingTrackSingleAgentRaceEnv per env):
+        `tracks` (names or Tracks, 1..8), order "sequential" (k + 1 mod T), "random" (Philox keyed by `seed`, the global env id and
+        the episode; optional `weights`) or "manual" (`set_next_track`).  `initial`: int [num_envs] track per env, default
+        contiguous blocks of near-equal size (MixedTrackEnv's split).  Each env's first reset keeps its initial track.  The handle
+        is built on tracks[0]; every other keyword goes to the constructor (vehicle_randomization=, lidar_noise=, ...).
+        `env.track_id` is a zero-copy int32 [num_envs] device view of the current tracks, `env.track_names` their names."""
+        tracks = list(tracks)
+        if not 1 <= len(tracks) <= 8:
+            raise ValueError(f"a track set has 1..8 tracks, got {len(tracks)}")
+        if order not in TRACK_ORDERS:
+            raise ValueError(f"order must be one of {sorted(TRACK_ORDERS)}, got {order!r}")
+        loaded = [load_track(t) if isinstance(t, str) else t for t in tracks]
+        env = cls(loaded[0], num_envs, cars_per_env, **kw)
+        dev = env.device.index or 0
+        env._ts_sources = [cls(t, 1, 1, device=dev) for t in loaded[1:]]         # small handles: only their track tables are used
+        handles = (C.c_void_p * len(loaded))(env._h, *[h._h for h in env._ts_sources])
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(len(loaded)))
+        init_ptr = None
+        if initial is not None:
+            init_t = torch.as_tensor(initial, dtype=torch.int32).to(env.device).reshape(env.num_envs).contiguous()
+            init_ptr = init_t.data_ptr()
+        env._enter()
+        L.check(env._lib.rc_set_track_set(env._h, handles, len(loaded), TRACK_ORDERS[order], None if w is None else w.ctypes.data,
+                                          init_ptr, C.c_uint64(int(seed))))
+        env._exit()
+        env.track_names = [t.name for t in loaded]
+        env.track_order = order
+        ptr, nb = C.c_void_p(), C.c_size_t()
+        L.check(env._lib.rc_track_ids(env._h, C.byref(ptr), C.byref(nb)))
+        env._track_array = _BorrowedDeviceArray(ptr.value, (env.num_envs,), env.device, code=0)
+        env.track_id = torch.utils.dlpack.from_dlpack(env._track_array)
+        return env
+
+    def set_next_track(self, ids) -> None:
+        """Order "manual": int [num_envs] track of each env's next reset (persists; read at every reset)."""
+        t = torch.as_tensor(ids, dtype=torch.int32).to(self.device).reshape(self.num_envs).contiguous()
+        self._enter()
+        L.check(self._lib.rc_set_next_track(self._h, t.data_ptr()))
+        self._exit()
+        self._next_source = t                # (the copy is stream-ordered: keep the source alive until the next call)
+
+    def clear_track_set(self) -> None:
+        """Turn the track set off (rc_set_track_set with n = 0): the production kernels run again, every env on the handle's own
+        track (tracks[0]) - reset before stepping on."""
+        L.check(self._lib.rc_set_track_set(self._h, None, 0, 0, None, None, C.c_uint64(0)))
 
     def set_raycast_variant(self, variant: int) -> None:
         """0 = plain traversal, 1 = free-rectangle skipping, 2 = tuned skipping, 3 = tuned + packed block table

@@ -96,9 +96,11 @@ def needs_build(lib_path: str = LIB_PATH, csrc: str = CSRC) -> bool:
 # occupancy the launch geometry assumes.
 NO_SPILL_KERNELS = ("rc_raycast_car_kernel", "rc_raycast_car_stamps_kernel", "rc_raycast_kernel", "rc_patch_car_kernel",
                     "rc_patch_exact_prefilter_kernel", "rc_patch_exact_sample_kernel",
-                    "rc_raycast_car_noise_kernel", "rc_raycast_group_noise_kernel")     # (the scan with LiDAR noise: same trip loop)
+                    "rc_raycast_car_noise_kernel", "rc_raycast_group_noise_kernel",     # (the scan with LiDAR noise: same trip loop)
+                    "rc_raycast_ts_kernel", "rc_patch_ts_kernel")                        # (a track set: the same scan and render)
 # (the exact prefilter holds a line per lane in 161 + registers: one wave per SIMD by design - what it must not do is spill)
-MIN_WAVES_PER_SIMD = {"rc_raycast_car_kernel": 8, "rc_patch_car_kernel": 8, "rc_patch_exact_sample_kernel": 4, "rc_raycast_car_noise_kernel": 8}
+MIN_WAVES_PER_SIMD = {"rc_raycast_car_kernel": 8, "rc_patch_car_kernel": 8, "rc_patch_exact_sample_kernel": 4, "rc_raycast_car_noise_kernel": 8,
+                      "rc_raycast_ts_kernel": 8, "rc_patch_ts_kernel": 8}
 
 
 def check_resource_usage(remarks: str, required=("rc_raycast_car_kernel", "rc_patch_car_kernel"), min_waves=None) -> None:
@@ -132,7 +134,8 @@ def check_resource_usage(remarks: str, required=("rc_raycast_car_kernel", "rc_pa
 
 
 def check_async_load_registers(asm_text: str, kernels=("rc_raycast_car_kernel", "rc_raycast_car_stamps_kernel", "rc_raycast_kernel",
-                                                       "rc_raycast_car_noise_kernel", "rc_raycast_group_noise_kernel")) -> int:
+                                                       "rc_raycast_car_noise_kernel", "rc_raycast_group_noise_kernel",
+                                                       "rc_raycast_ts_kernel")) -> int:
     """The scan requests a table entry with an inline-assembly `global_load_ushort` and waits for it in a LATER statement
     (`s_waitcnt vmcnt(0)`): until then the destination register is not the compiler's to read, copy or overwrite, and
     nothing tells it so.  This walks the generated assembly of the scan kernels and raises if any instruction between such
@@ -235,7 +238,7 @@ def build(force: bool = False, verbose: bool = True, csrc: str = CSRC, lib_path:
     try:
         check_resource_usage(r.stderr, required=("rc_raycast_car_kernel", "rc_patch_car_kernel", "rc_patch_exact_prefilter_kernel",
                                                  "rc_patch_exact_sample_kernel", "rc_raycast_car_noise_kernel",
-                                                 "rc_raycast_group_noise_kernel"))
+                                                 "rc_raycast_group_noise_kernel", "rc_raycast_ts_kernel", "rc_patch_ts_kernel"))
         verify_scan_assembly(verbose, csrc)
     except RuntimeError:
         os.remove(tmp)

@@ -239,6 +239,18 @@ struct rc_env {
     uint32_t group_slot = 0;
     int group_n = 0;
     RcParams group_last[RC_GROUP_MAX];
+    // track set (rc_set_track_set): the source handles, the per-env arrays, the table of RcParams (one per track) on the device and
+    // its pinned staging slots (as the group's), the render's LDS bytes
+    std::vector<rc_env *> ts_src;
+    void *ts_mem = nullptr;            // track [num_envs] | next [num_envs] | list [n_cars] | start [RC_TS_MAX + 1] | counts, cursors
+                                       // [2 RC_TS_MAX] | started [num_envs]
+    RcParams *ts_dev = nullptr;
+    RcParams *ts_host = nullptr;       // [4][RC_TS_MAX], pinned
+    hipEvent_t ts_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t ts_slot = 0;
+    bool ts_table_valid = false;
+    RcParams ts_last[RC_TS_MAX];
+    size_t ts_patch_lds = 0;
 };
 
 namespace {
@@ -446,7 +458,50 @@ int render_reference_patches(rc_env *env) {
     return RC_OK;
 }
 
+// Track set: the device table follows the handle's parameters (and its sources' tables) in stream order - a copy is queued only
+// when an entry changed, from a pinned slot that is not rewritten before its copy has run (as rc_step_group's table)
+int ts_sync_table(rc_env *env) {
+    const int n = env->params.ts_n;
+    RcParams want[RC_TS_MAX];
+    for (int k = 0; k < n; ++k) {
+        want[k] = env->params;
+        want[k].trk = env->ts_src[k]->params.trk;
+    }
+    if (env->ts_table_valid && std::memcmp(want, env->ts_last, sizeof(RcParams) * n) == 0) return RC_OK;
+    const uint32_t slot = env->ts_slot++ & 3u;
+    HIP_TRY(hipEventSynchronize(env->ts_ev[slot]));
+    RcParams *host = env->ts_host + (size_t)slot * RC_TS_MAX;
+    std::memcpy(host, want, sizeof(RcParams) * n);
+    std::memcpy(env->ts_last, want, sizeof(RcParams) * n);
+    HIP_TRY(hipMemcpyAsync(env->ts_dev, host, sizeof(RcParams) * n, hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipEventRecord(env->ts_ev[slot], env->stream));
+    env->ts_table_valid = true;
+    return RC_OK;
+}
+
+// the observation with a track set: the cars track-major, then the scan and the render by track
+int observe_track_set(rc_env *env) {
+    if (env->launch.raycast_variant != 7 || env->launch.scan_guarded || env->launch.scan_stamps)
+        return fail(RC_ERR_INVALID, "a track set (rc_set_track_set) is scanned by the default scan (variant 7) only, not by a lab variant, "
+                                  "the bounded validation build or the instrumented build");
+    int rc = sort_cars_if_due(env);
+    if (rc) return rc;
+    rc = ts_sync_table(env);
+    if (rc) return rc;
+    HIP_TRY(rck_launch_ts_list(env->params, env->stream));
+    TIMED(env, RC_K_RAYCAST, rck_launch_ts_raycast(env->params, env->launch, env->stream));
+    env->last_scan_rows = env->params.out.lidar;
+    if (env->params.render_patch)
+        TIMED(env, RC_K_PATCH, rck_launch_ts_patch(env->params, env->launch, env->ts_patch_lds, env->stream));
+    if (env->compact_slab)
+        HIP_TRY(hipMemcpyAsync((char *)env->compact_slab + env->compact.lidar_bytes,
+                               (const char *)env->out_arena + env->compact.summary_src_off, env->compact.summary_bytes,
+                               hipMemcpyDeviceToDevice, env->stream));
+    return RC_OK;
+}
+
 int observe(rc_env *env) {
+    if (env->params.ts_n > 0) return observe_track_set(env);
     if (env->params.noise_on && (env->launch.raycast_variant != 7 || env->launch.scan_guarded || env->launch.scan_stamps))
         return fail(RC_ERR_INVALID, "LiDAR noise (rc_set_lidar_noise) is applied by the default scan (variant 7) only, not by a lab variant, "
                                   "the bounded validation build or the instrumented build");
@@ -864,6 +919,10 @@ void rc_destroy(rc_env *env) {
     if (env->group_dev) (void)hipFree(env->group_dev);
     if (env->group_host) (void)hipHostFree(env->group_host);
     for (hipEvent_t e : env->group_ev) if (e) (void)hipEventDestroy(e);
+    if (env->ts_mem) (void)hipFree(env->ts_mem);
+    if (env->ts_dev) (void)hipFree(env->ts_dev);
+    if (env->ts_host) (void)hipHostFree(env->ts_host);
+    for (hipEvent_t e : env->ts_ev) if (e) (void)hipEventDestroy(e);
     env->track.reset();
     if (env->mask_dev) (void)hipFree(env->mask_dev);
     if (env->own_stream && env->stream) (void)hipStreamDestroy(env->stream);
@@ -1176,7 +1235,13 @@ int rc_reset(rc_env *env, const uint8_t *mask_or_null, int32_t mode, uint64_t se
         HIP_TRY(hipStreamSynchronize(env->stream));
         mask_dev = env->mask_dev;
     }
-    TIMED(env, RC_K_RESET, rck_launch_reset(env->params, mask_dev, env->stream));
+    if (env->params.ts_n > 0) {
+        int rc = ts_sync_table(env);
+        if (rc) return rc;
+        TIMED(env, RC_K_RESET, rck_launch_ts_reset(env->params, mask_dev, env->stream));
+    } else {
+        TIMED(env, RC_K_RESET, rck_launch_reset(env->params, mask_dev, env->stream));
+    }
     env->was_reset = true;
     if (!mask_or_null) env->order_age = 0xffffffffu;      // every car has a new place: sort before this observation
     return observe(env);
@@ -1191,6 +1256,12 @@ int rc_step(rc_env *env, const float *actions_dev, int32_t repeat) {
     // the kernel only reads the caller's buffer (its actions pointer is written in random-action mode alone)
     float *act = actions_dev ? const_cast<float *>(actions_dev) : env->actions_in;
     const RcRandomActions none{0, 0u, 0u, 0u};
+    if (env->params.ts_n > 0) {
+        int rc = ts_sync_table(env);
+        if (rc) return rc;
+        TIMED(env, RC_K_DYNAMICS, rck_launch_ts_dynamics(env->params, act, repeat, none, env->stream));
+        return observe(env);
+    }
     TIMED(env, RC_K_DYNAMICS, rck_launch_dynamics(env->params, act, repeat, none, env->stream));
     return observe(env);
 }
@@ -1202,6 +1273,12 @@ int rc_step_random(rc_env *env, uint64_t seed, uint32_t step, int32_t repeat) {
     if (repeat < 1) return fail(RC_ERR_INVALID, "repeat must be >= 1 (got %d)", repeat);
     HIP_TRY(hipSetDevice(env->cfg.device));
     const RcRandomActions ra{1, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), step};
+    if (env->params.ts_n > 0) {
+        int rc = ts_sync_table(env);
+        if (rc) return rc;
+        TIMED(env, RC_K_DYNAMICS, rck_launch_ts_dynamics(env->params, env->actions_in, repeat, ra, env->stream));
+        return observe(env);
+    }
     TIMED(env, RC_K_DYNAMICS, rck_launch_dynamics(env->params, env->actions_in, repeat, ra, env->stream));
     return observe(env);
 }
@@ -1221,6 +1298,8 @@ static int group_step(rc_env **envs, int32_t n, const float *actions_dev, int32_
             return fail(RC_ERR_INVALID, "%s: the handles of a group share one device and one stream (handle %d does not)", who, b);
         if (e->cfg.cars_per_env != lead->cfg.cars_per_env)
             return fail(RC_ERR_INVALID, "%s: the handles of a group have the same cars_per_env", who);
+        if (e->params.ts_n > 0)
+            return fail(RC_ERR_INVALID, "%s: handle %d carries a track set (rc_set_track_set), which a group launch does not", who, b);
         if (e->launch.raycast_variant != 7 || e->launch.scan_guarded || e->launch.scan_stamps || e->compact_slab)
             return fail(RC_ERR_INVALID, "%s: handle %d runs a scan variant / validation build / uint16 copy that a group launch does not carry", who, b);
         for (int c = 0; c < b; ++c)
@@ -1353,6 +1432,124 @@ int rc_set_lidar_noise(rc_env *env, float sigma, float p_drop, uint64_t seed) {
     return RC_OK;
 }
 
+// ---- track set ---------------------------------------------------------------------------------------------------------------
+int rc_set_track_set(rc_env *env, rc_env *const *tracks, int32_t n, int32_t order, const float *weights_or_null,
+                     const int32_t *initial_dev_or_null, uint64_t seed) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    if (n == 0) {                                         // off: the production kernels again
+        env->params.ts_n = 0;
+        env->ts_src.clear();
+        env->ts_table_valid = false;
+        return RC_OK;
+    }
+    if (n < 1 || n > RC_TS_MAX) return fail(RC_ERR_INVALID, "track set: 1 <= n <= %d tracks (got %d)", RC_TS_MAX, n);
+    if (!tracks) return fail(RC_ERR_INVALID, "track set: tracks is NULL");
+    if (order < RC_TRACK_ORDER_SEQUENTIAL || order > RC_TRACK_ORDER_MANUAL) return fail(RC_ERR_INVALID, "track set: unknown order %d", order);
+    if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called before rc_set_track_set");
+    if (env->cfg.obs_type == RC_OBS_LIDAR_OCCUPANCY_REFERENCE)
+        return fail(RC_ERR_INVALID, "track set: obs_type lidar_occupancy_reference renders from one source frame (rc_set_source_frame) per "
+                                  "handle and does not take a track set");
+    for (int k = 0; k < n; ++k) {
+        const rc_env *t = tracks[k];
+        if (!t) return fail(RC_ERR_INVALID, "track set: handle %d is NULL", k);
+        if (!t->has_track) return fail(RC_ERR_NO_TRACK, "track set: handle %d has no track (rc_load_track)", k);
+        if (t->cfg.device != env->cfg.device) return fail(RC_ERR_INVALID, "track set: handle %d lives on another device", k);
+    }
+    uint32_t cum[RC_TS_MAX] = {0};
+    int weighted = 0;
+    if (weights_or_null) {
+        if (order != RC_TRACK_ORDER_RANDOM) return fail(RC_ERR_INVALID, "track set: weights belong to order random");
+        double total = 0.0;
+        for (int k = 0; k < n; ++k) {
+            if (!(weights_or_null[k] > 0.0f) || !std::isfinite(weights_or_null[k]))
+                return fail(RC_ERR_INVALID, "track set: weight %d must be finite and > 0 (got %g)", k, (double)weights_or_null[k]);
+            total += (double)weights_or_null[k];
+        }
+        double part = 0.0;                                // c_k = min(floor(2^32 S_k / S + 0.5), 2^32 - 1), S_k = w_0 + ... + w_{k-1}
+        for (int k = 1; k < n; ++k) {
+            part += (double)weights_or_null[k - 1];
+            const double c = std::floor(4294967296.0 * part / total + 0.5);
+            cum[k - 1] = c >= 4294967295.0 ? 0xffffffffu : (uint32_t)c;
+        }
+        weighted = 1;
+    }
+    const int B = env->cfg.num_envs;
+    std::vector<int32_t> init((size_t)B);
+    if (initial_dev_or_null) {
+        HIP_TRY(hipMemcpyAsync(init.data(), initial_dev_or_null, (size_t)B * 4, hipMemcpyDeviceToHost, env->stream));
+        HIP_TRY(hipStreamSynchronize(env->stream));
+        for (int e = 0; e < B; ++e)
+            if (init[(size_t)e] < 0 || init[(size_t)e] >= n)
+                return fail(RC_ERR_INVALID, "track set: initial track of env %d is %d, outside [0, %d)", e, init[(size_t)e], n);
+    } else {                                              // contiguous blocks of near-equal size: the first B % n one env longer
+        int e = 0;
+        for (int k = 0; k < n; ++k)
+            for (int c = 0; c < B / n + (k < B % n ? 1 : 0); ++c) init[(size_t)e++] = k;
+    }
+    if (!env->ts_mem) {
+        const size_t bytes = (size_t)B * 4 * 2 + (size_t)env->n_cars * 4 + (3 * RC_TS_MAX + 1) * 4 + (size_t)B;
+        HIP_TRY(hipMalloc(&env->ts_mem, bytes));
+        HIP_TRY(hipMemsetAsync(env->ts_mem, 0, bytes, env->stream));
+        HIP_TRY(hipMalloc((void **)&env->ts_dev, sizeof(RcParams) * RC_TS_MAX));
+        HIP_TRY(hipHostMalloc((void **)&env->ts_host, sizeof(RcParams) * RC_TS_MAX * 4, hipHostMallocDefault));
+        for (hipEvent_t &ev : env->ts_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    }
+    RcParams &p = env->params;
+    int32_t *base = (int32_t *)env->ts_mem;
+    p.ts_track = base;
+    p.ts_next = base + B;
+    p.ts_list = base + 2 * (size_t)B;
+    p.ts_start = p.ts_list + env->n_cars;
+    p.ts_started = (uint8_t *)(p.ts_start + 3 * RC_TS_MAX + 1);      // (the counts start and stay zero: rc_ts_start_kernel clears them)
+    HIP_TRY(hipMemcpyAsync(p.ts_track, init.data(), (size_t)B * 4, hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipMemcpyAsync(const_cast<int32_t *>(p.ts_next), init.data(), (size_t)B * 4, hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipMemsetAsync(p.ts_started, 0, (size_t)B, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));           // (init is a host vector)
+    env->ts_src.assign(tracks, tracks + n);
+    size_t lds = 0;
+    for (int k = 0; k < RC_TS_MAX; ++k) p.ts_pad_bytes[k] = 0;
+    for (int k = 0; k < n; ++k) {
+        const RcTrackDev &t = tracks[k]->params.trk;
+        const size_t padded = (env->launch.patch_variant & 4) ? 0 : rc_patch_padded_bytes(t.h, t.w);
+        p.ts_pad_bytes[k] = (int32_t)padded;
+        const size_t need = padded ? padded : tracks[k]->launch.lds_bytes;
+        if (p.render_patch && need == 0) return fail(RC_ERR_INVALID, "track set: track %d's bitmap does not fit the render's LDS", k);
+        lds = need > lds ? need : lds;
+    }
+    if (p.render_patch) {
+        if (lds > 160 * 1024) return fail(RC_ERR_INVALID, "track set: a track's bitmap does not fit the render's 160 KiB of LDS");
+        HIP_TRY(rck_set_ts_lds_limit(lds));
+    }
+    env->ts_patch_lds = lds;
+    p.ts_table = env->ts_dev;
+    p.ts_order = order;
+    p.ts_weighted = weighted;
+    for (int k = 0; k < RC_TS_MAX; ++k) p.ts_cum[k] = cum[k];
+    p.ts_seed_lo = (uint32_t)(seed & 0xffffffffu);
+    p.ts_seed_hi = (uint32_t)(seed >> 32);
+    p.ts_n = n;
+    env->ts_table_valid = false;
+    return RC_OK;
+}
+
+int rc_set_next_track(rc_env *env, const int32_t *next_dev) {
+    if (!env || !next_dev) return fail(RC_ERR_INVALID, "NULL argument");
+    if (env->params.ts_n == 0) return fail(RC_ERR_INVALID, "rc_set_next_track: no track set (rc_set_track_set)");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(hipMemcpyAsync(const_cast<int32_t *>(env->params.ts_next), next_dev, (size_t)env->cfg.num_envs * 4, hipMemcpyDeviceToDevice,
+                           env->stream));
+    return RC_OK;
+}
+
+int rc_track_ids(rc_env *env, void **dev_ptr, size_t *bytes) {
+    if (!env || !dev_ptr) return fail(RC_ERR_INVALID, "NULL argument");
+    if (!env->ts_mem) return fail(RC_ERR_INVALID, "rc_track_ids: no track set was installed (rc_set_track_set)");
+    *dev_ptr = env->params.ts_track;
+    if (bytes) *bytes = (size_t)env->cfg.num_envs * 4;
+    return RC_OK;
+}
+
 int rc_step_host(rc_env *env, const float *actions_host, int32_t repeat) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
     if (!actions_host) return fail(RC_ERR_INVALID, "actions_host is NULL");
@@ -1367,6 +1564,7 @@ int rc_set_pose(rc_env *env, const float *xyyaw_host) {
     if (!xyyaw_host) return fail(RC_ERR_INVALID, "xyyaw_host is NULL");
     if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called before rc_set_pose");
     if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
+    if (env->params.ts_n > 0) return fail(RC_ERR_INVALID, "rc_set_pose does not take a track set (rc_set_track_set): a pose belongs to one track");
     HIP_TRY(hipSetDevice(env->cfg.device));
     // stage through the lidar section of the arena: it is rewritten by the observation pass right after
     float *staging = env->params.out.lidar;
@@ -2030,7 +2228,9 @@ int rc_scan_kernel_name(rc_env *env, char *out, size_t bytes) {
     if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called first");
     const RcLaunchInfo &li = env->launch;
     const int a = env->cfg.cars_per_env;
-    if (li.raycast_variant != 7) snprintf(out, bytes, "rc_raycast_kernel<%d, %d>", a, li.raycast_variant);
+    if (env->params.ts_n > 0 && li.raycast_variant == 7 && !li.scan_guarded && !li.scan_stamps)
+        snprintf(out, bytes, "rc_raycast_ts_kernel<%d, %s, %s>", a, li.car_split > 1 ? "true" : "false", env->params.noise_on ? "true" : "false");
+    else if (li.raycast_variant != 7) snprintf(out, bytes, "rc_raycast_kernel<%d, %d>", a, li.raycast_variant);
     else if (li.scan_stamps != nullptr && a == 1) snprintf(out, bytes, "rc_raycast_car_stamps_kernel");
     else if (li.scan_guarded) snprintf(out, bytes, "rc_raycast_car_kernel<%d, false, true>", a);
     else if (env->params.noise_on) snprintf(out, bytes, "rc_raycast_car_noise_kernel<%d, %s>", a, li.car_split > 1 ? "true" : "false");

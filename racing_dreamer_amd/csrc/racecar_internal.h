@@ -105,7 +105,22 @@ struct RcParams {
     float noise_scale;           // sigma * RC_NOISE_Z_SCALE, rounded once (host)
     uint32_t noise_drop;         // dropout threshold on 16 bits: floor(p_drop * 65536 + 0.5)
     uint32_t noise_seed_lo, noise_seed_hi;
+    // ---- track set (rc_set_track_set; include/racecar_hip.h).  Appended like the fields above.  ts_n = 0: off.
+    const RcParams *ts_table;    // [ts_n] device: this handle's parameters with track k's tables (trk) in entry k
+    int32_t *ts_track;           // [num_envs] the env's current track
+    uint8_t *ts_started;         // [num_envs] 1 once the env's first reset after the install has run
+    const int32_t *ts_next;      // [num_envs] order manual: the track of the env's next reset
+    int32_t *ts_list;            // [n_cars] the cars track-major (track, then the progress order), rebuilt every observation
+    int32_t *ts_start;           // [RC_TS_MAX + 1] first position of every track in ts_list, and n_cars; then counts, cursors [2][RC_TS_MAX]
+    int32_t ts_n, ts_order;      // RC_TSO_SEQUENTIAL | RC_TSO_RANDOM | RC_TSO_MANUAL
+    int32_t ts_weighted;         // random: 1 = the thresholds below, 0 = (r * ts_n) >> 32
+    uint32_t ts_cum[8];          // random, weighted: track = #{k < ts_n - 1 : ts_cum[k] <= r}
+    uint32_t ts_seed_lo, ts_seed_hi;
+    int32_t ts_pad_bytes[8];     // the render's padded bitmap bytes for track k (rc_patch_padded_bytes), 0 = unpadded
 };
+#define RC_TS_MAX 8
+enum { RC_TSO_SEQUENTIAL = 0, RC_TSO_RANDOM = 1, RC_TSO_MANUAL = 2 };   // = RC_TRACK_ORDER_* of include/racecar_hip.h
+#define RC_TS_TAG 3u                             // Philox counter word 3 of the track draw (spawn 0, DR 2)
 
 #define RC_PATCH_SKIP 0x7fffffff
 // The render's bitmap in LDS with a border of RC_PATCH_PAD zero cells on every side (a tap lies at most 110 sqrt 2 = 155.6 cells
@@ -199,6 +214,13 @@ hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStrea
 hipError_t rck_launch_set_pose(const RcParams &p, const float *xyyaw_dev, hipStream_t s);
 hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
 hipError_t rck_launch_patch(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
+// track set (rc_set_track_set): the dynamics / reset with a track per env, the track-major car list, the scan and the render
+hipError_t rck_launch_ts_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s);
+hipError_t rck_launch_ts_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s);
+hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s);
+hipError_t rck_launch_ts_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
+hipError_t rck_launch_ts_patch(const RcParams &p, const RcLaunchInfo &li, size_t lds_bytes, hipStream_t s);
+hipError_t rck_set_ts_lds_limit(size_t lds_bytes);
 #define RC_EXACT_CAR_DOUBLES (220 * 220)         // scratch per car of a chunk: the 220 x 220 binary64 spline coefficients (387 200 B)
 #ifndef RC_EXACT_CHUNK_CARS
 #define RC_EXACT_CHUNK_CARS 6144                 // cars per chunk of the exact render (2.4 GB of scratch)

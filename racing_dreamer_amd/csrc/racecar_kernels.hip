@@ -232,8 +232,7 @@ __device__ __forceinline__ int obb_overlap_spawn(const Spawn &a, const Spawn &b)
 // heading room, RCS_HEADING_JITTER wherever w > 0) off the track's direction; (u, v) = words 1, 2 of call 0 for car 0, words (0, 1) / (2, 3) of call 1 + (a - 1) / 2 for the others.
 // If two proposed cars overlap, ALL cars of the env take the centre-line poses.
 template <int A>
-__device__ __forceinline__ void prepare_reset(const RcParams &p, int e, uint32_t ep, Spawn (&sp)[A]) {
-    const RcTrackDev &t = p.trk;
+__device__ __forceinline__ void prepare_reset(const RcParams &p, const RcTrackDev &t, int e, uint32_t ep, Spawn (&sp)[A]) {
     const uint32_t g = p.first_env + (uint32_t)e;
     const bool jitter = p.reset_mode != 0;
     rcd::u32x4 r[1 + A / 2];
@@ -357,7 +356,7 @@ __device__ __forceinline__ void load_cars(const RcParams &p, int e, Car (&car)[A
 }
 
 template <int A>
-__device__ __forceinline__ void store_state_and_obs(const RcParams &p, int e, const Car (&car)[A], int steps,
+__device__ __forceinline__ void store_state_and_obs(const RcParams &p, const RcTrackDev &t, int e, const Car (&car)[A], int steps,
                                                     int agent_steps) {
 #pragma unroll
     for (int a = 0; a < A; ++a) {
@@ -369,7 +368,7 @@ __device__ __forceinline__ void store_state_and_obs(const RcParams &p, int e, co
         p.st.wall[i] = c.wall; p.st.opp[i] = c.opp; p.st.wrong[i] = c.wrong;
         p.st.done[i] = c.done; p.st.trunc[i] = c.trunc; p.st.fresh[i] = c.fresh;
         p.st.scan_pose[i] = make_float4(c.x, c.y, c.ct, c.st);
-        if (p.render_patch) p.st.patch_pose[i] = patch_pose_of(p.trk, c.x, c.y, c.ct, c.st, c.fresh);
+        if (p.render_patch) p.st.patch_pose[i] = patch_pose_of(t, c.x, c.y, c.ct, c.st, c.fresh);
         // observation of the current state (post auto-reset)
         float *pose = p.out.pose + 6 * i, *vel = p.out.velocity + 6 * i;
         pose[0] = c.x; pose[1] = c.y; pose[2] = 0.0f; pose[3] = 0.0f; pose[4] = 0.0f; pose[5] = c.th;
@@ -406,23 +405,65 @@ __device__ __forceinline__ void store_step_results(const RcParams &p, int e, con
     }
 }
 
+// ---- track set (rc_set_track_set): the env's track k is a lane value; the dynamics reads the few fields of track k's RcTrackDev
+// that it uses (walls, progress grid, spawn table, geometry) with per-lane loads from the owner's table, the rest stays zero.
+__device__ __forceinline__ int ts_track_of(const RcParams &p, int e) {
+    const int k = p.ts_track[e];
+    return (unsigned)k < (unsigned)p.ts_n ? k : 0;          // (a value written from outside [0, T) reads as track 0)
+}
+
+__device__ __forceinline__ void lane_track(const RcParams &p, int k, RcTrackDev &t) {
+    const RcTrackDev &s = p.ts_table[k].trk;
+    t.ray_words = s.ray_words; t.progress = s.progress; t.spawn = s.spawn;
+    t.w = s.w; t.h = s.h; t.pitch = s.pitch; t.n_centerline = s.n_centerline;
+    t.org_x = s.org_x; t.org_y = s.org_y; t.inv_res = s.inv_res;
+}
+
+// The track of the episode that a reset with episode value ep starts (include/racecar_hip.h, rc_set_track_set): sequential
+// k + 1 mod T; random word 0 of Philox(global env id, ep, 0, RC_TS_TAG) r, (r T) >> 32 or #{c_i <= r} with weights; manual
+// next[e] (a value outside [0, T) keeps the current track).
+__device__ __forceinline__ int ts_next_track(const RcParams &p, int e, uint32_t ep, int cur) {
+    const int n = p.ts_n;
+    if (p.ts_order == RC_TSO_SEQUENTIAL) return cur + 1 < n ? cur + 1 : 0;
+    if (p.ts_order == RC_TSO_MANUAL) {
+        const int k = p.ts_next[e];
+        return (unsigned)k < (unsigned)n ? k : cur;
+    }
+    const uint32_t r = rcd::philox4x32(p.first_env + (uint32_t)e, ep, 0u, RC_TS_TAG, p.ts_seed_lo, p.ts_seed_hi).x;
+    if (!p.ts_weighted) return (int)__umulhi(r, (uint32_t)n);
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < RC_TS_MAX - 1; ++i) k += (i < n - 1 && p.ts_cum[i] <= r) ? 1 : 0;
+    return k;
+}
+
 // ------------------------------------------------------------------------------------------------
-template <int A, bool DR = false>
+template <int A, bool DR = false, bool TS = false>
 // rand_on != 0: the actions are not read but drawn here, U(-1, 1)^2 from Philox keyed by (seed, step, global car id) -
 // the same numbers rc_random_actions_kernel writes (synthetic random-action rollouts without a launch of their own);
 // they are stored to `actions` as well, so the buffer shows what was applied.
 // DR: the five vehicle parameters of the integrator come from the car (RcParams::vparams) instead of the spec's constants - the
 // same operations in the same order, only the operand differs - and a reset in random mode draws them anew (draw_vehicle).
+// TS: the env steps on its track (ts_track) and a reset starts on the next one (ts_next_track), drawn before the spawn.
 __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restrict__ actions, const int repeat, const int rand_on,
                                              const uint32_t rand_lo, const uint32_t rand_hi, const uint32_t rand_step, const int e) {
-    const RcTrackDev &t = p.trk;
+    RcTrackDev tc_l = {}, tn_l = {};
+    const RcTrackDev &t = TS ? tc_l : p.trk;
+    const RcTrackDev &tn = TS ? tn_l : p.trk;
     // the episode counter first: it is the oldest load in flight, so the reset's Philox draw can wait for it alone
     const uint32_t episode = p.auto_reset ? p.st.episode[e] : 0u;
+    int tr_next = 0;
+    if (TS) {
+        const int tr = ts_track_of(p, e);
+        tr_next = (p.auto_reset && p.ts_started[e]) ? ts_next_track(p, e, episode, tr) : tr;
+        lane_track(p, tr, tc_l);
+        lane_track(p, tr_next, tn_l);
+    }
     Car car[A];
     load_cars<A>(p, e, car);
     int steps = p.st.steps[e], agent_steps = p.st.agent_steps[e];
     Spawn spawn[A];
-    if (p.auto_reset) prepare_reset<A>(p, e, episode, spawn);      // ahead of the step: see prepare_reset
+    if (p.auto_reset) prepare_reset<A>(p, tn, e, episode, spawn);      // ahead of the step: see prepare_reset
     float vp[A][RC_VP_COUNT];
     if (DR) {
 #pragma unroll
@@ -564,9 +605,14 @@ __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restric
                 draw_vehicle<A>(p, e, episode, vp);
                 store_vehicle<A>(p, e, vp);
             }
+            if (TS) {
+                p.ts_track[e] = tr_next;
+                p.ts_started[e] = 1;
+                tc_l = tn_l;                                       // the observation is the new episode's, on its track
+            }
         }
     }
-    store_state_and_obs<A>(p, e, car, steps, agent_steps);
+    store_state_and_obs<A>(p, t, e, car, steps, agent_steps);
 }
 
 template <int A>
@@ -585,6 +631,15 @@ __global__ __launch_bounds__(256) void rc_dynamics_dr_kernel(RcParams p, float *
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= p.num_envs) return;
     dynamics_env<A, true>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+}
+
+// The same with a track per env (rc_set_track_set): launched only while the handle's track set is on.
+template <int A, bool DR>
+__global__ __launch_bounds__(256) void rc_dynamics_ts_kernel(RcParams p, float *__restrict__ actions, int repeat,
+                                                             int rand_on, uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.num_envs) return;
+    dynamics_env<A, DR, true>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
 }
 
 // Where the car of rank r (position along the track) stands in RcStateDev::order - see rc_order_place_kernel.
@@ -633,20 +688,13 @@ __global__ __launch_bounds__(256) void rc_dynamics_dr_group_kernel(const RcParam
 }
 
 template <int A>
-__global__ __launch_bounds__(256) void rc_reset_kernel(RcParams p, const uint8_t *__restrict__ mask) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.num_envs) return;
-    if (mask != nullptr && mask[e] == 0) {
-        // an env that keeps running: its next observation is no longer the first of an episode
-        return;
-    }
+__device__ __forceinline__ void reset_env(const RcParams &p, const RcTrackDev &t, int e, uint32_t episode) {
     Car car[A];
     int steps, agent_steps;
 #pragma unroll
     for (int a = 0; a < A; ++a) car[a].rew = 0.0f;
     Spawn spawn[A];
-    const uint32_t episode = p.st.episode[e];
-    prepare_reset<A>(p, e, episode, spawn);
+    prepare_reset<A>(p, t, e, episode, spawn);
     apply_reset<A>(p, e, car, spawn, episode, steps, agent_steps);
 #pragma unroll
     for (int a = 0; a < A; ++a) {
@@ -655,7 +703,36 @@ __global__ __launch_bounds__(256) void rc_reset_kernel(RcParams p, const uint8_t
         p.out.action[2 * i + 1] = 0.0f;
     }
     store_step_results<A>(p, e, car, steps);
-    store_state_and_obs<A>(p, e, car, steps, agent_steps);
+    store_state_and_obs<A>(p, t, e, car, steps, agent_steps);
+}
+
+template <int A>
+__global__ __launch_bounds__(256) void rc_reset_kernel(RcParams p, const uint8_t *__restrict__ mask) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.num_envs) return;
+    if (mask != nullptr && mask[e] == 0) {
+        // an env that keeps running: its next observation is no longer the first of an episode
+        return;
+    }
+    const uint32_t episode = p.st.episode[e];
+    reset_env<A>(p, p.trk, e, episode);
+}
+
+// rc_reset with a track set: the env's next track first (its first reset after the install keeps the initial one), then the
+// reset above on that track
+template <int A>
+__global__ __launch_bounds__(256) void rc_reset_ts_kernel(RcParams p, const uint8_t *__restrict__ mask) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= p.num_envs) return;
+    if (mask != nullptr && mask[e] == 0) return;
+    const uint32_t episode = p.st.episode[e];
+    const int tr = ts_track_of(p, e);
+    const int tr_next = p.ts_started[e] ? ts_next_track(p, e, episode, tr) : tr;
+    RcTrackDev t = {};
+    lane_track(p, tr_next, t);
+    reset_env<A>(p, t, e, episode);
+    p.ts_track[e] = tr_next;
+    p.ts_started[e] = 1;
 }
 
 // rc_reset with vehicle randomization in random mode: the reset above, then the new episode's vehicle parameters
@@ -891,6 +968,83 @@ __global__ __launch_bounds__(256) void rc_raycast_group_noise_kernel(const RcPar
     if (slot >= (unsigned)p.n_cars) return;
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[order_slot_of_rank(slot, (uint32_t)p.n_cars)] : slot;
     scan_car<A, false, OVERLAP, false, true>(p, car, part, split, threadIdx.x & 63u, lds_row);
+}
+
+// ---- track set (rc_set_track_set).  The cars track-major: ts_list = the cars grouped by their env's track, each track's cars in
+// the progress order (RcStateDev::order, by rank; car index order without it) as far as the waves' arrival order keeps it (a
+// matter of locality, not of results), ts_start = where each track begins.  Three small launches at every observation (tracks
+// change at every episode end; the progress part follows the sort's RC_ORDER_PERIOD): a ballot per track and wave counts the cars
+// (one atomic per track and wave), one wave turns the counts into starts and cursors (and clears the counts for the next
+// observation), and every wave takes its places per track with one atomic and writes its cars.  ts_count = ts_start + RC_TS_MAX + 1,
+// the cursors behind it.
+__device__ __forceinline__ int ts_car_at(const RcParams &p, int r) {
+    return p.st.order != nullptr ? p.st.order[order_slot_of_rank((uint32_t)r, (uint32_t)p.n_cars)] : r;
+}
+
+__global__ __launch_bounds__(256) void rc_ts_count_kernel(RcParams p) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = r < p.n_cars ? ts_track_of(p, ts_car_at(p, r) / p.cars_per_env) : -1;
+    int32_t *count = p.ts_start + RC_TS_MAX + 1;
+#pragma unroll
+    for (int j = 0; j < RC_TS_MAX; ++j) {
+        const int c = __builtin_popcountll(__builtin_amdgcn_ballot_w64(k == j));
+        if ((threadIdx.x & 63u) == 0 && c != 0) atomicAdd(count + j, c);
+    }
+}
+
+__global__ __launch_bounds__(64) void rc_ts_start_kernel(RcParams p) {
+    int32_t *count = p.ts_start + RC_TS_MAX + 1, *cursor = count + RC_TS_MAX;
+    const int lane = (int)threadIdx.x;
+    int c[RC_TS_MAX];
+#pragma unroll
+    for (int j = 0; j < RC_TS_MAX; ++j) c[j] = count[j];
+    int start = 0;
+#pragma unroll
+    for (int j = 0; j < RC_TS_MAX; ++j) start += (j < lane && j < p.ts_n) ? c[j] : 0;
+    if (lane <= RC_TS_MAX) p.ts_start[lane] = start;
+    if (lane < RC_TS_MAX) {
+        cursor[lane] = start;
+        count[lane] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void rc_ts_place_kernel(RcParams p) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    const int car = r < p.n_cars ? ts_car_at(p, r) : 0;
+    const int k = r < p.n_cars ? ts_track_of(p, car / p.cars_per_env) : -1;
+    int32_t *cursor = p.ts_start + RC_TS_MAX + 1 + RC_TS_MAX;
+    const int lane = (int)(threadIdx.x & 63u);
+#pragma unroll
+    for (int j = 0; j < RC_TS_MAX; ++j) {
+        const uint64_t m = __builtin_amdgcn_ballot_w64(k == j);
+        if (m == 0) continue;                                              // (wave-uniform)
+        const int leader = __builtin_ctzll(m);
+        int base = 0;
+        if (lane == leader) base = atomicAdd(cursor + j, __builtin_popcountll(m));
+        base = __shfl(base, leader);
+        const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (k == j) p.ts_list[base + below] = car;
+    }
+}
+
+// The scan with a track per car: one wave per car (or 1 / split of one) as rc_raycast_group_kernel, the car taken from ts_list
+// (every XCD a stretch of it: one or two tracks' tables in its L2) and its parameters - the owner's with its track's tables - from
+// the table by its env's track with scalar loads.  NOISE: scan_car's LiDAR noise.
+template <int A, bool OVERLAP, bool NOISE>
+__global__ __launch_bounds__(256) void rc_raycast_ts_kernel(RcParams p0, int split) {
+    extern __shared__ uint32_t lds_words[];
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
+    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const int launched = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+    const int total = p0.n_cars * split;
+    const int per_xcd = (total + 7) >> 3;
+    const int wave = (launched & 7) * per_xcd + (launched >> 3);
+    if ((launched >> 3) >= per_xcd || wave >= total) return;
+    const unsigned slot = (unsigned)wave / (unsigned)split, part = (unsigned)wave - slot * (unsigned)split;
+    const unsigned car = (unsigned)__builtin_amdgcn_readfirstlane(p0.ts_list[slot]);
+    const int k = __builtin_amdgcn_readfirstlane(ts_track_of(p0, (int)(car / (unsigned)A)));
+    const RcParams p = p0.ts_table[k];      // (a copy: see rc_dynamics_group_kernel)
+    scan_car<A, false, OVERLAP, false, NOISE>(p, car, part, split, threadIdx.x & 63u, lds_row);
 }
 
 // lidar_occupancy (H11, dreamer/wrappers.py:390-408): ego-aligned 64x64 patch of the drivable area,
@@ -1177,6 +1331,98 @@ __global__ __launch_bounds__(1024) void rc_patch_car_kernel(RcParams p, int padd
         if (inside) patch_car<false, NT>(p, img, car, lane, icx, icy, a, b, all_tested);
         else patch_car<true, NT>(p, img, car, lane, icx, icy, a, b, all_tested);
     }
+}
+
+// rc_patch_car_kernel's body for one workgroup of rc_patch_ts_kernel: p.trk's bitmap staged in LDS, then the cars list[first],
+// list[first + stride], ... below `count` (first / stride count waves; the kernel above deals every car to the grid's waves in turn).
+// A copy, not a shared function: the production kernel's code stays what it was.
+template <bool NT>
+__device__ __forceinline__ void patch_list_block(const RcParams &p, const int padded_bytes, const int32_t *list, const unsigned first,
+                                                 const unsigned stride, const unsigned count) {
+    extern __shared__ uint32_t lds_words[];
+    const RcTrackDev &t = p.trk;
+    const int pad = padded_bytes > 0 ? RC_PATCH_PAD : 0;
+    PatchImage img;
+    if (pad) {
+        // the bitmap inside a border of `pad` zero cells (pad = 5 words: rows keep their word alignment)
+        const int pw = (t.w + 2 * pad + 31) / 32, rows = t.h + 2 * pad;
+        uint4 *d4 = reinterpret_cast<uint4 *>(lds_words);
+        const uint4 z4 = {0u, 0u, 0u, 0u};
+        for (int i = threadIdx.x; i < (padded_bytes >> 4); i += blockDim.x) d4[i] = z4;
+        __syncthreads();
+        for (int i = threadIdx.x; i < t.h * t.pitch; i += blockDim.x) {
+            const int row = i / t.pitch, word = i - row * t.pitch;
+            if (word < pw - pad / 32) lds_words[(row + pad) * pw + pad / 32 + word] = t.drv_words[i];
+        }
+        img.pitch_b = (uint32_t)pw * 4u; img.w_cells = (uint32_t)(pw * 32); img.h_cells = (uint32_t)rows; img.zero_addr = 0u;
+    } else {
+        stage_bitmap(lds_words, t.drv_words, t.h * t.pitch + 1);        // + the all-zero word behind the bitmap (rc_load_track)
+        img.pitch_b = (uint32_t)t.pitch * 4u; img.w_cells = (uint32_t)t.w; img.h_cells = (uint32_t)t.h;
+        img.zero_addr = (uint32_t)(t.h * t.pitch) * 4u;
+    }
+    __syncthreads();
+    const unsigned lane = threadIdx.x & 63u;
+    typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+    // cars are dealt to the waves of the grid in turn (a wave's cars are `waves` apart: neighbouring waves write
+    // neighbouring patches).  The car is wave-uniform, so its header comes through the SCALAR unit: vector loads share one
+    // in-order counter with the stores, and every car would start by waiting for the previous car's 4 KB to be
+    // acknowledged.  (Inline assembly with its own wait: the compiler takes the load for a vector one because the kernel
+    // also stores.)
+    for (unsigned idx = __builtin_amdgcn_readfirstlane(first); idx < count; idx = __builtin_amdgcn_readfirstlane(idx + stride)) {
+        unsigned car;
+        asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(car) : "s"(list + idx) : "memory");
+        typedef int v4i_t __attribute__((ext_vector_type(4)));
+        v4i_t h;
+        asm volatile("s_load_dwordx4 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(h) : "s"(p.st.patch_pose + car) : "memory");
+        const int a = h.z, b = h.w;
+        if (h.x == RC_PATCH_SKIP) {              // reset observation is all zeros, dreamer/wrappers.py:413; a diverged car sees nothing
+            v4u_t *out = reinterpret_cast<v4u_t *>(p.out.patch) + (size_t)car * 256u + lane;
+            const v4u_t z = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                if (NT) __builtin_nontemporal_store(z, out + 64 * g);
+                else out[64 * g] = z;
+            }
+            continue;
+        }
+        // No tap can leave the image, and nothing is clamped, if the crop window lies inside the grid - or, with the zero border,
+        // if the car's own cell does (the border is wider than any tap is far)
+        const int lx = h.x - RCS_PATCH_WINDOW_I, ly = h.y - RCS_PATCH_WINDOW_I, span = 2 * RCS_PATCH_WINDOW_I - 1;
+        const bool inside = pad ? ((unsigned)h.x < (unsigned)t.w && (unsigned)(h.y - 1) < (unsigned)t.h)
+                                : (lx >= 0 && ly >= 0 && lx + span <= t.w - 1 && ly + span <= t.h - 1);
+        const int icx = h.x + pad, icy = h.y + pad;            // the start cell in the image's coordinates
+        // runs outside the corner blocks stay inside the window: |offset| <= (63 |a| + 31 |b|) / 2 + 1 on either axis (and with a, b exchanged)
+        const int aa = a < 0 ? -a : a, ab = b < 0 ? -b : b;
+        const int reach = (63 * (aa > ab ? aa : ab) + 31 * (aa > ab ? ab : aa)) / 2 + 2;
+        const bool all_tested = reach > RCS_PATCH_WINDOW_I * 65536 - 2;
+        if (inside) patch_car<false, NT>(p, img, car, lane, icx, icy, a, b, all_tested);
+        else patch_car<true, NT>(p, img, car, lane, icx, icy, a, b, all_tested);
+    }
+}
+
+
+// The render with a track set: workgroups only render cars of the track whose bitmap they staged.  The grid of G workgroups is
+// partitioned over the tracks in proportion to their car counts (ts_start, on the device): track k takes workgroups [F(k), F(k + 1)),
+// F(k) = (tracks before k that have cars) + floor((G - T) start[k] / n), so that every track with cars has one at least (G >= T).
+template <bool NT>
+__global__ __launch_bounds__(1024) void rc_patch_ts_kernel(RcParams p0) {
+    const int T = p0.ts_n, n = p0.n_cars, G = (int)gridDim.x, wg = (int)blockIdx.x;
+    int k = -1, lo = 0, hi = 0, s0 = 0, s1 = 0, nonempty = 0;
+#pragma unroll
+    for (int j = 0; j < RC_TS_MAX; ++j) {
+        if (j < T) {
+            const int a = p0.ts_start[j], b = p0.ts_start[j + 1];
+            const int f0 = nonempty + (int)((long long)(G - T) * a / n);
+            nonempty += b > a ? 1 : 0;
+            const int f1 = nonempty + (int)((long long)(G - T) * b / n);
+            if (wg >= f0 && wg < f1) { k = j; lo = f0; hi = f1; s0 = a; s1 = b; }
+        }
+    }
+    if (k < 0) return;
+    const RcParams p = p0.ts_table[k];
+    const unsigned per = blockDim.x >> 6;
+    patch_list_block<NT>(p, p0.ts_pad_bytes[k], p0.ts_list + s0, (unsigned)(wg - lo) * per + (threadIdx.x >> 6), (unsigned)(hi - lo) * per,
+                    (unsigned)(s1 - s0));
 }
 
 // Follow-the-gap on the device: one wave per car, lane l owns the 13 consecutive beams FTG_LO + 13 l ...
@@ -2137,6 +2383,71 @@ hipError_t rck_launch_patch(const RcParams &p, const RcLaunchInfo &li, hipStream
     const int blocks = (int)(need < resident ? need : resident);
     if (li.patch_variant & 2) launch(rc_patch_car_kernel<false>, dim3(blocks), dim3(1024), lds, s, p, padded);     // experiment: plain stores
     else launch(rc_patch_car_kernel<true>, dim3(blocks), dim3(1024), lds, s, p, padded);
+    return hipGetLastError();
+}
+
+// ---- track set launchers
+hipError_t rck_launch_ts_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s) {
+    const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
+    if (p.vp_mode != RC_VP_OFF) {
+        DISPATCH_A(p.cars_per_env, launch((rc_dynamics_ts_kernel<kA, true>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
+    } else {
+        DISPATCH_A(p.cars_per_env, launch((rc_dynamics_ts_kernel<kA, false>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
+    }
+    return hipGetLastError();
+}
+
+hipError_t rck_launch_ts_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s) {
+    const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
+    if (p.vp_mode == RC_VP_RANDOM)        // (as rck_launch_reset: the draw reads the episode value the reset increments)
+        DISPATCH_A(p.cars_per_env, hipLaunchKernelGGL((rc_reset_dr_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
+    DISPATCH_A(p.cars_per_env, launch((rc_reset_ts_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
+    return hipGetLastError();
+}
+
+hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s) {
+    const dim3 blocks((unsigned)((p.n_cars + 255) / 256));
+    hipLaunchKernelGGL(rc_ts_count_kernel, blocks, dim3(256), 0, s, p);
+    hipLaunchKernelGGL(rc_ts_start_kernel, dim3(1), dim3(64), 0, s, p);
+    hipLaunchKernelGGL(rc_ts_place_kernel, blocks, dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t rck_launch_ts_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s) {
+    const int split = li.car_split;
+    const long long waves = (((long long)p.n_cars * split + 7) / 8) * 8;      // one wave per workgroup; whole turns of the 8 XCDs
+    const dim3 grid((unsigned)waves), block(64);
+    if (p.noise_on) {
+        if (split > 1) { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, true, true>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
+        else { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, false, true>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
+    } else {
+        if (split > 1) { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, true, false>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
+        else { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, false, false>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
+    }
+    return hipGetLastError();
+}
+
+hipError_t rck_set_ts_lds_limit(size_t lds_bytes) {
+    hipError_t e;
+    for (const void *k : {reinterpret_cast<const void *>(rc_patch_ts_kernel<true>), reinterpret_cast<const void *>(rc_patch_ts_kernel<false>)}) {
+        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return e;
+        hipFuncAttributes fa;                   // (the bitmap is addressed from LDS address 0: no static LDS)
+        e = hipFuncGetAttributes(&fa, k);
+        if (e != hipSuccess) return e;
+        if (fa.sharedSizeBytes != 0) return hipErrorInvalidValue;
+    }
+    return hipSuccess;
+}
+
+// lds_bytes: the largest bitmap image of the set's tracks (padded or not, per track)
+hipError_t rck_launch_ts_patch(const RcParams &p, const RcLaunchInfo &li, size_t lds_bytes, hipStream_t s) {
+    const int per_cu = lds_bytes <= 80 * 1024 ? 2 : 1;
+    const long long need = ((long long)p.n_cars + 15) / 16, resident = (long long)li.n_cu * per_cu;
+    long long blocks = need < resident ? need : resident;
+    if (blocks < p.ts_n) blocks = p.ts_n;
+    if (li.patch_variant & 2) launch(rc_patch_ts_kernel<false>, dim3((unsigned)blocks), dim3(1024), lds_bytes, s, p);
+    else launch(rc_patch_ts_kernel<true>, dim3((unsigned)blocks), dim3(1024), lds_bytes, s, p);
     return hipGetLastError();
 }
 
