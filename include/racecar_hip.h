@@ -112,7 +112,7 @@ typedef enum rc_field {
 } rc_field;
 
 /* Kernels, for rc_kernel_time(). */
-enum { RC_K_DYNAMICS = 0, RC_K_RAYCAST = 1, RC_K_PATCH = 2, RC_K_RESET = 3, RC_K_ACTIONS = 4, RC_K_FTG = 5, RC_K_COUNT = 6 };
+enum { RC_K_DYNAMICS = 0, RC_K_RAYCAST = 1, RC_K_PATCH = 2, RC_K_RESET = 3, RC_K_ACTIONS = 4, RC_K_FTG = 5, RC_K_POLICY = 6, RC_K_COUNT = 7 };
 
 typedef struct rc_config {
     uint32_t struct_size;          /* = sizeof(rc_config), for ABI evolution                   */
@@ -322,6 +322,46 @@ int rc_follow_the_gap(rc_env *env, float motor_straight, float motor_corner);
  * command).  detail_dev: optional device float32 [n, 4] = heading [rad], free distance [m], steering angle [rad], speed
  * [m/s].  The generic bubble / widest-gap agent above stays available as rc_follow_the_gap. */
 int rc_follow_the_gap_reference(rc_env *env, float dt, float *detail_dev);
+
+/* The reference's trained Dreamer agent on the device, deterministic mode (ros_agent/models/dreamer/racing_dreamer.py:61-80
+ * `action`: obs_step from the previous latent and the previous RAW action, feature = [stoch, deter], actor mode;
+ * models.py:61-87 RSSM.obs_step / img_step, :339-364 ActionDecoder 'tanh_normal' and actor_version "normalized") - the posterior
+ * MEAN instead of a sample and tanh(mean) instead of the best of 100 draws, in the binary32 arithmetic of DESIGN.md §2 item 12
+ * (tests/policy_spec.c is its CPU restatement; the device equals it bit for bit).  The sampled agent, the reward head and the
+ * decoder are not part of it.
+ *
+ * rc_policy_weights: host pointers and shapes of the checkpoint's arrays in `tf.Module.variables` order (rssm.pkl: 13 arrays,
+ * actor.pkl: 10, or 14 with the batch normalisation's four).  One-dimensional arrays have rows = 1. */
+typedef struct rc_policy_array { const float *data; int32_t rows, cols; } rc_policy_array;
+typedef struct rc_policy_weights {
+    uint32_t struct_size;          /* = sizeof(rc_policy_weights) */
+    rc_policy_array gru_kernel, gru_recurrent, gru_bias;      /* [200, 600] x 2, [2, 600]: gates z, r, candidate; reset_after */
+    rc_policy_array img1_w, img1_b;                            /* [32, 200], [200]    input [stoch 30, previous action 2]      */
+    rc_policy_array img2_w, img2_b, img3_w, img3_b;            /* the prior's layers: not read by the agent (data may be NULL;
+                                                                  checked when given: [200, 200], [200], [200, 60], [60])      */
+    rc_policy_array obs1_w, obs1_b, obs2_w, obs2_b;            /* [1280, 200], [200], [200, 60], [60]   input [deter, scan]    */
+    rc_policy_array h0_w, h0_b, h1_w, h1_b, h2_w, h2_b, h3_w, h3_b;   /* [230, 400], [400], 3 x ([400, 400], [400])            */
+    rc_policy_array hout_w, hout_b;                            /* [400, 4], [4]                                                */
+    rc_policy_array hnorm_mean, hnorm_var, hnorm_gamma, hnorm_beta;   /* [4] each, or all four data = NULL: the plain actor     */
+} rc_policy_weights;
+/* rc_policy_load (racing_dreamer.py:9-41, the constructor's load of rssm.pkl / actor.pkl): checks the shapes (RC_ERR_INVALID
+ * names the first that is wrong - before anything else, so a caller can validate a checkpoint without a handle), copies the
+ * weights to the handle's device and allocates the agent's state, zeroed: float32 [n_cars, 232] = stoch 30 | deter 200 | raw
+ * previous action 2.  A second load replaces the weights and zeroes the state.  rc_policy_unload frees both. */
+int rc_policy_load(rc_env *env, const rc_policy_weights *w);
+int rc_policy_unload(rc_env *env);
+/* rc_policy_act (racing_dreamer.py:61-80): one agent step for every car whose slot (car index within its env) is in slot_mask
+ * (bit a = slot a).  Reads RC_F_LIDAR in place - in metres: refused under another lidar_transform - and RC_F_FRESH: a car whose
+ * observation opens an episode starts from a zero latent and a zero previous action (racing_dreamer.py:66-70).  Writes the
+ * car's state and its command into RC_F_ACTION_IN in the caller's action convention: the raw action in [-1, 1]^2 when
+ * rc_config.remap_actions is on (the env applies ReduceActionSpace), else postprocess_action's image of it
+ * (racing_dreamer.py:53-59) in [action_low, action_high].  The state always keeps the raw action.  Cars outside the mask keep
+ * their RC_F_ACTION_IN and state rows.  RC_ERR_INVALID: no policy loaded, empty mask, bits beyond cars_per_env, scan not in
+ * metres.  Kernel: rc_policy_kernel (RC_K_POLICY). */
+int rc_policy_act(rc_env *env, uint32_t slot_mask);
+/* The agent's state (models.py:61-87: the RSSM's stoch and deter; racing_dreamer.py:76: the previous action), zero-copy:
+ * device float32 [n_cars, 232], readable and writable between calls. */
+int rc_policy_state(rc_env *env, void **dev_ptr, size_t *bytes);
 
 int rc_get(rc_env *env, int32_t field, void **dev_ptr, size_t *bytes);
 int rc_copy_out(rc_env *env, int32_t field, void *host_dst, size_t bytes);

@@ -32,9 +32,9 @@ DEBUG_KNOBS = {"ray_threads": DBG_RAY_THREADS, "ray_split": DBG_RAY_SPLIT, "ray_
                "scan_order": DBG_SCAN_ORDER, "exact_chunk": DBG_EXACT_CHUNK}
 P2P_EXPORT_BYTES = 256
 
-K_DYNAMICS, K_RAYCAST, K_PATCH, K_RESET, K_ACTIONS, K_FTG, K_COUNT = range(7)
+K_DYNAMICS, K_RAYCAST, K_PATCH, K_RESET, K_ACTIONS, K_FTG, K_POLICY, K_COUNT = range(8)
 KERNEL_NAMES = {K_DYNAMICS: "rc_dynamics_kernel", K_RAYCAST: "rc_raycast_kernel", K_PATCH: "rc_patch_kernel",
-                K_RESET: "rc_reset_kernel", K_ACTIONS: "rc_random_actions_kernel", K_FTG: "rc_ftg_kernel"}
+                K_RESET: "rc_reset_kernel", K_ACTIONS: "rc_random_actions_kernel", K_FTG: "rc_ftg_kernel", K_POLICY: "rc_policy_kernel"}
 
 
 class RcConfig(C.Structure):
@@ -49,6 +49,47 @@ class RcConfig(C.Structure):
         ("car_task", C.c_int32 * 4), ("n_steps", C.c_int32),
         ("arena_total_cars", C.c_int32), ("arena_first_car", C.c_int32),
     ]
+
+
+class RcPolicyArray(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
+
+
+# rc_policy_weights: the checkpoint's arrays in order (oracle-independent: the names are the fixture's keys)
+POLICY_KEYS = ("gru_kernel", "gru_recurrent", "gru_bias", "img1_w", "img1_b", "img2_w", "img2_b", "img3_w", "img3_b",
+               "obs1_w", "obs1_b", "obs2_w", "obs2_b", "h0_w", "h0_b", "h1_w", "h1_b", "h2_w", "h2_b", "h3_w", "h3_b",
+               "hout_w", "hout_b", "hnorm_mean", "hnorm_var", "hnorm_gamma", "hnorm_beta")
+POLICY_OPTIONAL = ("img2_w", "img2_b", "img3_w", "img3_b", "hnorm_mean", "hnorm_var", "hnorm_gamma", "hnorm_beta")
+POLICY_STATE = 232          # stoch 30 | deter 200 | raw previous action 2
+
+
+class RcPolicyWeights(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, RcPolicyArray) for k in POLICY_KEYS]
+
+
+def policy_weights(weights):
+    """rc_policy_weights over a mapping of float32 arrays (or an .npz path).  Returns (struct, the arrays it points into -
+    keep them alive until rc_policy_load has returned)."""
+    import numpy as np
+    if isinstance(weights, (str, os.PathLike)):
+        weights = np.load(weights)
+    keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
+    w = RcPolicyWeights()
+    w.struct_size = C.sizeof(RcPolicyWeights)
+    keep = []
+    for k in POLICY_KEYS:
+        if k not in keys:
+            if k in POLICY_OPTIONAL:
+                continue
+            raise KeyError(f"policy weights lack {k!r}")
+        a = np.ascontiguousarray(weights[k], np.float32)
+        if a.ndim not in (1, 2):
+            raise ValueError(f"policy weights: {k} has {a.ndim} dimensions")
+        keep.append(a)
+        arr = getattr(w, k)
+        arr.data = a.ctypes.data
+        arr.rows, arr.cols = (1, a.shape[0]) if a.ndim == 1 else a.shape
+    return w, keep
 
 
 # every symbol include/racecar_hip.h declares: name -> (restype, argtypes)
@@ -75,6 +116,10 @@ SYMBOLS = {
     "rc_track_ids": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
     "rc_follow_the_gap": (C.c_int, [C.c_void_p, C.c_float, C.c_float]),
     "rc_follow_the_gap_reference": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
+    "rc_policy_load": (C.c_int, [C.c_void_p, _P(RcPolicyWeights)]),
+    "rc_policy_unload": (C.c_int, [C.c_void_p]),
+    "rc_policy_act": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "rc_policy_state": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
     "rc_fill_random_actions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "rc_step_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]),
     "rc_step_group": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),

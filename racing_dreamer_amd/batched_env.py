@@ -15,6 +15,7 @@ must be kept.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, Optional, Union
 
 import numpy as np
@@ -577,6 +578,41 @@ class BatchedRaceEnv:
         self._exit()
         return (self.views["action_in"], det) if detail else self.views["action_in"]
 
+    # ------------------------------------------------------------------ the reference's trained Dreamer agent
+    def load_policy(self, weights) -> None:
+        """Load a checkpoint of the reference's deployed Dreamer agent (mapping of float32 arrays with the keys of
+        tests/golden/dreamer_policy_*.npz, or an .npz path) onto the device (`rc_policy_load`): the weights are copied, the agent's
+        state starts at zero.  Shapes are checked by the library."""
+        w, keep = L.policy_weights(weights)
+        L.check(self._lib.rc_policy_load(self._h, C.byref(w)))
+        del keep
+        ptr, nb = C.c_void_p(), C.c_size_t()
+        L.check(self._lib.rc_policy_state(self._h, C.byref(ptr), C.byref(nb)))
+        self._policy_array = _BorrowedDeviceArray(ptr.value, (self.n_cars, L.POLICY_STATE), self.device)
+        self._policy_state = torch.utils.dlpack.from_dlpack(self._policy_array)
+
+    def policy_act(self, slots=None) -> torch.Tensor:
+        """One step of the loaded agent, deterministic mode, for every car (or the cars in the listed slots = car indices within
+        an env, e.g. `slots=(1, 2, 3)`: trained opponents B-D next to a learner in slot A): reads `lidar` and `fresh` in place,
+        fills and returns `action_in` in this env's action convention, so `step(None)` applies it."""
+        mask = (1 << self.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
+        self._enter()
+        L.check(self._lib.rc_policy_act(self._h, C.c_uint32(mask)))
+        self._exit()
+        return self.views["action_in"]
+
+    @property
+    def policy_state(self) -> torch.Tensor:
+        """Device view float32 [n_cars, 232] = stoch 30 | deter 200 | raw previous action 2 of the loaded agent: readable and
+        writable between calls (on the env's stream, or after `sync()`)."""
+        if getattr(self, "_policy_state", None) is None:
+            raise L.RacecarHipError("no policy loaded (load_policy)")
+        return self._policy_state
+
+    def unload_policy(self) -> None:
+        self._policy_state = None
+        L.check(self._lib.rc_policy_unload(self._h))
+
     def fill_random_actions(self, seed: int, step: int) -> None:
         L.check(self._lib.rc_fill_random_actions(self._h, C.c_uint64(seed), C.c_uint32(step)))
 
@@ -883,6 +919,27 @@ class MixedTrackEnv:
     def follow_the_gap_reference(self, dt: Optional[float] = None):
         self._fork_join(lambda p, blk: p._lib.rc_follow_the_gap_reference(p._h, 0.01 * p.action_repeat if dt is None else float(dt), None))
         return self.views["action_in"]
+
+    def load_policy(self, weights) -> None:
+        """The reference's trained Dreamer agent on every block (BatchedRaceEnv.load_policy)."""
+        if isinstance(weights, (str, os.PathLike)):
+            weights = dict(np.load(weights))
+        for p in self.parts:
+            p.load_policy(weights)
+
+    def policy_act(self, slots=None):
+        mask = (1 << self.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
+        self._fork_join(lambda p, blk: p._lib.rc_policy_act(p._h, C.c_uint32(mask)))
+        return self.views["action_in"]
+
+    @property
+    def policy_state(self) -> torch.Tensor:
+        """float32 [n_cars, 232] in arena order: a COPY gathered from the blocks (each handle holds its own)."""
+        return torch.cat([p.policy_state for p in self.parts])
+
+    def unload_policy(self) -> None:
+        for p in self.parts:
+            p.unload_policy()
 
     def sync(self):
         for p in self.parts:

@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libracecar_hip.so")
-SOURCES = ["racecar_kernels.hip", "racecar_abi.hip"]
-HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_spec.h", "racecar_scan.h", "racecar_patch_exact.h", os.path.join("..", "..", "include", "racecar_hip.h")]
+SOURCES = ["racecar_kernels.hip", "racecar_abi.hip", "racecar_policy.hip"]
+HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_spec.h", "racecar_scan.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", os.path.join("..", "..", "include", "racecar_hip.h")]
 # The lab library: scan variants 0-6 and the instrumented build of the scan (racecar_lab.hip).  NOT part of the shipped
 # library; built by build_lab() - which tools/ and the variant tests call - and loaded by libracecar_hip.so on first use.
 LAB_PATH = os.path.join(LIB_DIR, "libracecar_lab.so")
@@ -97,7 +97,8 @@ def needs_build(lib_path: str = LIB_PATH, csrc: str = CSRC) -> bool:
 NO_SPILL_KERNELS = ("rc_raycast_car_kernel", "rc_raycast_car_stamps_kernel", "rc_raycast_kernel", "rc_patch_car_kernel",
                     "rc_patch_exact_prefilter_kernel", "rc_patch_exact_sample_kernel",
                     "rc_raycast_car_noise_kernel", "rc_raycast_group_noise_kernel",     # (the scan with LiDAR noise: same trip loop)
-                    "rc_raycast_ts_kernel", "rc_patch_ts_kernel")                        # (a track set: the same scan and render)
+                    "rc_raycast_ts_kernel", "rc_patch_ts_kernel",                        # (a track set: the same scan and render)
+                    "rc_policy_kernel")     # (the Dreamer agent: 4 to 6 MFMA accumulator tiles per wave - a spill would sit in its k loops)
 # (the exact prefilter holds a line per lane in 161 + registers: one wave per SIMD by design - what it must not do is spill)
 MIN_WAVES_PER_SIMD = {"rc_raycast_car_kernel": 8, "rc_patch_car_kernel": 8, "rc_patch_exact_sample_kernel": 4, "rc_raycast_car_noise_kernel": 8,
                       "rc_raycast_ts_kernel": 8, "rc_patch_ts_kernel": 8}
@@ -238,7 +239,8 @@ def build(force: bool = False, verbose: bool = True, csrc: str = CSRC, lib_path:
     try:
         check_resource_usage(r.stderr, required=("rc_raycast_car_kernel", "rc_patch_car_kernel", "rc_patch_exact_prefilter_kernel",
                                                  "rc_patch_exact_sample_kernel", "rc_raycast_car_noise_kernel",
-                                                 "rc_raycast_group_noise_kernel", "rc_raycast_ts_kernel", "rc_patch_ts_kernel"))
+                                                 "rc_raycast_group_noise_kernel", "rc_raycast_ts_kernel", "rc_patch_ts_kernel",
+                                                 "rc_policy_kernel"))
         verify_scan_assembly(verbose, csrc)
     except RuntimeError:
         os.remove(tmp)

@@ -1867,6 +1867,8 @@ inline void launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, A
 }  // namespace
 
 void rck_set_launch_events(hipEvent_t start, hipEvent_t stop) { g_ev_start = start; g_ev_stop = stop; }
+// ... and takes them back, for a launch made in another file (racecar_policy.hip)
+void rck_take_launch_events(hipEvent_t *start, hipEvent_t *stop) { *start = g_ev_start; *stop = g_ev_stop; g_ev_start = g_ev_stop = nullptr; }
 
 hipError_t rck_build_quad_planes(const RcTrackDev &t, uint16_t *quad_rect_dev, hipStream_t s) {
     uint8_t *runs = nullptr;

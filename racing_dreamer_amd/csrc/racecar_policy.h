@@ -1,0 +1,45 @@
+// The deterministic Dreamer agent on the device (racecar_policy.hip): what the C-ABI layer and the kernel share.
+// Not part of the public interface.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define RC_POLICY_STOCH 30
+#define RC_POLICY_DETER 200
+#define RC_POLICY_STATE (RC_POLICY_STOCH + RC_POLICY_DETER + 2)   // stoch | deter | raw previous action
+#define RC_POLICY_UNITS 400                                       // actor width
+#define RC_POLICY_TILE 32                                         // cars per workgroup = rows of one 32x32x2 MFMA tile
+// Weight matrices are kept [K][ld] on the device with ld = the column count rounded up to whole 32-column tiles, the padding
+// zero (weights and biases): a tile past the last output computes zeros that are never stored.  The GRU's two [200][600]
+// matrices keep their three gates (z, r, candidate) at columns 0, 224 and 448 of ld = 672.
+#define RC_POLICY_LD200 224
+#define RC_POLICY_LD400 416
+#define RC_POLICY_LDGRU (3 * RC_POLICY_LD200)
+#define RC_POLICY_LDSMALL 32                                      // obs2 (30 mean columns), hout (2 mean columns)
+
+struct RcPolicyDev {
+    const float *img1_w, *img1_b;            // [32][224], [224]
+    const float *gru_k, *gru_r, *gru_b;      // [200][672] x 2, [2][672]
+    const float *obs1_w, *obs1_b;            // [1280][224], [224]      rows: deter 200, then the 1080 beams
+    const float *obs2_w, *obs2_b;            // [200][32], [32]         the 30 mean columns
+    const float *h_w[4], *h_b[4];            // [230][416], 3 x [400][416]; [416]
+    const float *hout_w, *hout_b;            // [400][32], [32]         the 2 mean columns
+    const float *hnorm;                      // [4][2] mean, sqrt(var + eps), gamma, beta of the 2 mean columns; null = plain actor
+};
+
+struct RcPolicyCall {
+    RcPolicyDev w;
+    const float *lidar;                      // [n_cars][1080] metres
+    const uint8_t *fresh;                    // [n_cars]
+    float *state;                            // [n_cars][RC_POLICY_STATE]
+    float *actions;                          // [n_cars][2] RC_F_ACTION_IN
+    int32_t n_active;                        // num_envs x (slots in the mask): the rows of this call
+    int32_t cars_per_env, n_slots;
+    uint32_t slots;                          // slot of the mask's k-th set bit in byte k
+    int32_t raw_actions;                     // rc_config.remap_actions: the env maps [-1, 1]^2 itself
+    float lo0, lo1, hi0, hi1;                // else: postprocess_action's range
+};
+
+hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS limit (once per process and device is enough)
+hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);
+void rck_take_launch_events(hipEvent_t *start, hipEvent_t *stop);   // racecar_kernels.hip: the events rck_set_launch_events left

@@ -1,0 +1,257 @@
+// rc_policy_act: one step of the reference's deployed Dreamer agent (ros_agent/models/dreamer/racing_dreamer.py:61-80 `action`;
+// models.py:61-87 RSSM.obs_step / img_step, :339-364 ActionDecoder) for every car, deterministic mode (posterior mean,
+// tanh(mean)), in the binary32 arithmetic of DESIGN.md §2 item 12: every dense layer is acc = bias, then acc = fmaf(x[k], W[k][j], acc)
+// for k ascending - which is what the f32-input MFMA computes from its C operand.
+//
+// One workgroup of four waves owns 32 cars = the rows of v_mfma_f32_32x32x2_f32 tiles and runs the whole network on them: the
+// activations stay in two [32][417] LDS buffers (X, Y), the weights are read from L2 straight into the B operand (lane l reads
+// W[2s + (l >> 5)][col + (l & 31)]: two 128-byte rows per request), the A operand from LDS (lane l: row l & 31, k = 2s + (l >> 5);
+// stride 417 = 33 mod 64 keeps the 32 rows on 32 banks).  A wave takes the 32-column tiles w, w + 4, ... of a layer, all of them
+// over the whole k range with one accumulator each: no split over k, no reduction across waves.  DESIGN.md §4 (rc_policy_kernel) has the
+// arithmetic behind the choice (M = 32 cars per pass over the 4.4 MB of weights) and the measured cost.
+#include "racecar_policy.h"
+#include "racecar_policy_math.h"
+#include <hip/hip_ext.h>
+
+typedef float pm_f32x16 __attribute__((ext_vector_type(16)));
+
+namespace {
+
+constexpr int PT = 256;                        // threads per workgroup
+constexpr int PM = RC_POLICY_TILE;             // cars per workgroup
+constexpr int XS = 417;                        // row stride of X and Y [floats]
+constexpr int PD = 4;                          // k-steps (of 2) whose operands are requested one block ahead
+constexpr int SCK = 120;                       // beams per staged piece of the scan (9 pieces)
+constexpr int N_BEAMS = 1080;
+constexpr size_t kLdsBytes = (size_t)2 * PM * XS * sizeof(float) + PM * sizeof(int);
+
+// row q of the call -> car index (the mask's slots of env q / n_slots), -1 past the end
+__device__ __forceinline__ int pm_car(const RcPolicyCall &c, int q) {
+    if (q >= c.n_active) return -1;
+    const int e = q / c.n_slots, k = q - e * c.n_slots;
+    return e * c.cars_per_env + (int)((c.slots >> (8 * k)) & 0xffu);
+}
+
+// acc[t] += A[32 x 2 ksteps] W[2 ksteps x 32 columns at col[t]], k ascending.  a = &A[lane & 31][lane >> 5] (LDS),
+// w = &W[lane >> 5][lane & 31] (global).  The operands of the next PD k-steps are requested before this block's MFMAs issue;
+// past the end the last step is requested again (a valid address) and not used.
+template <int TN>
+__device__ __forceinline__ void pm_gemm(pm_f32x16 (&acc)[TN], const float *a, int ksteps, const float *__restrict__ w, int ld,
+                                        const int (&col)[TN]) {
+    float ac[PD], bc[PD][TN], an[PD], bn[PD][TN];
+#pragma unroll
+    for (int u = 0; u < PD; ++u) {
+        const int s = u < ksteps ? u : ksteps - 1;
+        ac[u] = a[2 * s];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) bc[u][t] = w[(size_t)(2 * s) * ld + col[t]];
+    }
+#pragma unroll 1
+    for (int s0 = 0; s0 < ksteps; s0 += PD) {
+#pragma unroll
+        for (int u = 0; u < PD; ++u) {
+            int s = s0 + PD + u;
+            s = s < ksteps ? s : ksteps - 1;
+            an[u] = a[2 * s];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) bn[u][t] = w[(size_t)(2 * s) * ld + col[t]];
+        }
+#pragma unroll
+        for (int u = 0; u < PD; ++u) {
+            if (s0 + u < ksteps) {
+#pragma unroll
+                for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u], bc[u][t], acc[t], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < PD; ++u) {
+            ac[u] = an[u];
+#pragma unroll
+            for (int t = 0; t < TN; ++t) bc[u][t] = bn[u][t];
+        }
+    }
+}
+
+template <int TN>
+__device__ __forceinline__ void pm_bias(pm_f32x16 (&acc)[TN], const float *__restrict__ b, const int (&col)[TN], int c) {
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+        const float v = b[col[t] + c];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[t][r] = v;
+    }
+}
+
+// C/D map of the 32x32 tile: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+__device__ __forceinline__ int pm_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+
+enum { PK_ELU = 0, PK_STOCH = 1, PK_ACTION = 2 };
+
+struct PmLayer {
+    const float *a;          // LDS input [32][XS], first column of the layer's input
+    int k;
+    const float *w, *b;
+    int ld, n;
+    float *d;                // LDS output, first column
+    int kind;
+};
+
+template <int TN>
+__device__ __forceinline__ void pm_dense_tiles(const RcPolicyCall &c, const PmLayer &L, const int *cars, int wave, int lane) {
+    const int cc = lane & 31, half = lane >> 5;
+    int col[TN];
+#pragma unroll
+    for (int t = 0; t < TN; ++t) col[t] = 32 * (wave + 4 * t);
+    pm_f32x16 acc[TN];
+    pm_bias<TN>(acc, L.b, col, cc);
+    pm_gemm<TN>(acc, L.a + cc * XS + half, L.k / 2, L.w + (size_t)half * L.ld + cc, L.ld, col);
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+        const int j = col[t] + cc;
+        if (j >= L.n) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = pm_row(r, half);
+            const float v = acc[t][r];
+            if (L.kind == PK_ELU) {
+                L.d[row * XS + j] = pm_elu(v);
+            } else if (L.kind == PK_STOCH) {          // posterior mean = the new stoch: next layer's input and the state
+                L.d[row * XS + j] = v;
+                const int car = cars[row];
+                if (car >= 0) c.state[(size_t)car * RC_POLICY_STATE + j] = v;
+            } else {                                   // the 2 mean columns of the actor's output layer
+                const int car = cars[row];
+                if (car < 0) continue;
+                const float *hn = c.w.hnorm;
+                const float act = hn ? pm_action_normalized(v, hn[j], hn[2 + j], hn[4 + j], hn[6 + j]) : pm_action_plain(v);
+                c.state[(size_t)car * RC_POLICY_STATE + RC_POLICY_STOCH + RC_POLICY_DETER + j] = act;
+                c.actions[2 * (size_t)car + j] = c.raw_actions ? act : pm_postprocess(act, j ? c.lo1 : c.lo0, j ? c.hi1 : c.hi0);
+            }
+        }
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(PT) void rc_policy_kernel(RcPolicyCall c) {
+    extern __shared__ float pm_lds[];
+    float *X = pm_lds, *Y = pm_lds + PM * XS;
+    int *cars = (int *)(pm_lds + 2 * PM * XS);
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, cc = lane & 31, half = lane >> 5;
+    const int row0 = blockIdx.x * PM;
+
+    if (tid < PM) cars[tid] = pm_car(c, row0 + tid);
+    // the latent of the cars: Y[0, 200) = deter, Y[200, 232) = stoch | previous raw action; zero for a car whose observation opens
+    // an episode (racing_dreamer.py:66-70: state None) and for rows past the end
+    for (int idx = tid; idx < PM * RC_POLICY_STATE; idx += PT) {
+        const int row = idx / RC_POLICY_STATE, j = idx - row * RC_POLICY_STATE;
+        const int car = pm_car(c, row0 + row);
+        float v = 0.0f;
+        if (car >= 0 && c.fresh[car] == 0) v = c.state[(size_t)car * RC_POLICY_STATE + j];
+        int dst;
+        if (j < RC_POLICY_STOCH) dst = RC_POLICY_DETER + j;
+        else if (j < RC_POLICY_STOCH + RC_POLICY_DETER) dst = j - RC_POLICY_STOCH;
+        else dst = j;                                               // (the action's 2 columns follow stoch's 30)
+        Y[row * XS + dst] = v;
+    }
+    __syncthreads();
+
+#pragma unroll 1
+    for (int layer = 0; layer < 7; ++layer) {
+        PmLayer L;
+        switch (layer) {
+        case 0: L = {Y + RC_POLICY_DETER, 32, c.w.img1_w, c.w.img1_b, RC_POLICY_LD200, RC_POLICY_DETER, X, PK_ELU}; break;
+        case 1: L = {Y, RC_POLICY_DETER, c.w.obs2_w, c.w.obs2_b, RC_POLICY_LDSMALL, RC_POLICY_STOCH, X + 170, PK_STOCH}; break;
+        case 2: L = {X + 170, 230, c.w.h_w[0], c.w.h_b[0], RC_POLICY_LD400, RC_POLICY_UNITS, Y, PK_ELU}; break;
+        case 3: L = {Y, RC_POLICY_UNITS, c.w.h_w[1], c.w.h_b[1], RC_POLICY_LD400, RC_POLICY_UNITS, X, PK_ELU}; break;
+        case 4: L = {X, RC_POLICY_UNITS, c.w.h_w[2], c.w.h_b[2], RC_POLICY_LD400, RC_POLICY_UNITS, Y, PK_ELU}; break;
+        case 5: L = {Y, RC_POLICY_UNITS, c.w.h_w[3], c.w.h_b[3], RC_POLICY_LD400, RC_POLICY_UNITS, X, PK_ELU}; break;
+        default: L = {X, RC_POLICY_UNITS, c.w.hout_w, c.w.hout_b, RC_POLICY_LDSMALL, 2, nullptr, PK_ACTION}; break;
+        }
+        const int n_tiles = L.ld / 32;
+        const int mine = wave < n_tiles ? (n_tiles - wave + 3) / 4 : 0;      // tiles wave, wave + 4, ...
+        if (mine == 1) pm_dense_tiles<1>(c, L, cars, wave, lane);
+        else if (mine == 2) pm_dense_tiles<2>(c, L, cars, wave, lane);
+        else if (mine == 3) pm_dense_tiles<3>(c, L, cars, wave, lane);
+        else if (mine == 4) pm_dense_tiles<4>(c, L, cars, wave, lane);
+        __syncthreads();
+        if (layer != 0) continue;
+
+        // ---- GRU on x = X[0, 200) and h = Y[0, 200): the new deter goes to X[200, 400) and to the state
+#pragma unroll 1
+        for (int jt = wave; jt < RC_POLICY_LD200 / 32; jt += 4) {
+            const int col[3] = {32 * jt, RC_POLICY_LD200 + 32 * jt, 2 * RC_POLICY_LD200 + 32 * jt};
+            pm_f32x16 mx[3], mh[3];
+            pm_bias<3>(mx, c.w.gru_b, col, cc);
+            pm_gemm<3>(mx, X + cc * XS + half, RC_POLICY_DETER / 2, c.w.gru_k + (size_t)half * RC_POLICY_LDGRU + cc, RC_POLICY_LDGRU, col);
+            pm_bias<3>(mh, c.w.gru_b + RC_POLICY_LDGRU, col, cc);
+            pm_gemm<3>(mh, Y + cc * XS + half, RC_POLICY_DETER / 2, c.w.gru_r + (size_t)half * RC_POLICY_LDGRU + cc, RC_POLICY_LDGRU, col);
+            const int j = 32 * jt + cc;
+            if (j < RC_POLICY_DETER) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = pm_row(r, half);
+                    const float h = pm_gru(mx[0][r], mx[1][r], mx[2][r], mh[0][r], mh[1][r], mh[2][r], Y[row * XS + j]);
+                    X[row * XS + RC_POLICY_DETER + j] = h;
+                    const int car = cars[row];
+                    if (car >= 0) c.state[(size_t)car * RC_POLICY_STATE + RC_POLICY_STOCH + j] = h;
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- obs1 on [deter, embed]: deter from X[200, 400), the scan in 9 pieces of 120 beams staged through X[0, 120)
+        // (clip / 15 - 0.5 applied on the way in); ELU -> Y[0, 200)
+        {
+            constexpr int PER = PM * SCK / PT;                       // 15 beams per thread and piece
+            float pre[PER];
+            auto request = [&](int piece) {
+#pragma unroll
+                for (int i = 0; i < PER; ++i) {
+                    const int idx = tid + PT * i, row = idx / SCK, b = idx - row * SCK;
+                    const int car = cars[row];
+                    pre[i] = car >= 0 ? c.lidar[(size_t)car * N_BEAMS + piece * SCK + b] : 0.0f;
+                }
+            };
+            request(0);
+            const int mine1 = (RC_POLICY_LD200 / 32 - wave + 3) / 4;      // 2, 2, 2, 1
+            int col[2] = {32 * wave, 32 * (wave + 4)};
+            if (mine1 < 2) col[1] = col[0];                                // (second tile unused: a valid column, never stored)
+            pm_f32x16 acc[2];
+            pm_bias<2>(acc, c.w.obs1_b, col, cc);
+            pm_gemm<2>(acc, X + RC_POLICY_DETER + cc * XS + half, RC_POLICY_DETER / 2, c.w.obs1_w + (size_t)half * RC_POLICY_LD200 + cc,
+                       RC_POLICY_LD200, col);
+#pragma unroll 1
+            for (int piece = 0; piece < N_BEAMS / SCK; ++piece) {
+                __syncthreads();                                           // the readers of the previous piece (and of x) are through
+#pragma unroll
+                for (int i = 0; i < PER; ++i) {
+                    const int idx = tid + PT * i, row = idx / SCK, b = idx - row * SCK;
+                    X[row * XS + b] = pm_preprocess(pre[i]);
+                }
+                __syncthreads();
+                if (piece + 1 < N_BEAMS / SCK) request(piece + 1);
+                pm_gemm<2>(acc, X + cc * XS + half, SCK / 2,
+                           c.w.obs1_w + (size_t)(RC_POLICY_DETER + piece * SCK + half) * RC_POLICY_LD200 + cc, RC_POLICY_LD200, col);
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int j = col[t] + cc;
+                if (t >= mine1 || j >= RC_POLICY_DETER) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Y[pm_row(r, half) * XS + j] = pm_elu(acc[t][r]);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t rck_policy_prepare() {
+    return hipFuncSetAttribute((const void *)rc_policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+}
+
+hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s) {
+    const unsigned blocks = (unsigned)((c.n_active + PM - 1) / PM);
+    hipExtLaunchKernelGGL(rc_policy_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytes, s, start, stop, 0u, c);
+    return hipGetLastError();
+}
