@@ -363,6 +363,71 @@ int rc_policy_act(rc_env *env, uint32_t slot_mask);
  * device float32 [n_cars, 232], readable and writable between calls. */
 int rc_policy_state(rc_env *env, void **dev_ptr, size_t *bytes);
 
+/* ---- Episode log: return, length, progress and time of every episode, kept on the device (opt-in; off = the launches of a step
+ * are what they are without it) ---------------------------------------------------------------------------------------------------
+ * What the reference computes on the host from each recorded episode (dreamer/callbacks.py:56-100, summarize_episode /
+ * summarize_eval_episode: return = reward.sum(), length = len(reward) - 1, progress = max(progress), time = max(time)) and
+ * what dreamer/evaluations/run_evaluation.py:43-64 loops over.  With auto_reset the terminal reward, progress and time of an
+ * env are in the arena for exactly one call; the log sums them per car in handle-owned device memory and appends one
+ * rc_episode_row per car in the call in which the env's episode ends.  No host round trip; rc_arena_bytes, the trajectory
+ * slab, the compact record and RC_ABI_VERSION do not change.
+ *
+ * An episode is an ENV's: it ends for all its cars in the call in which any car's RC_F_DONE becomes 1 (that is how the env is
+ * reset, and how the reference's Collect fires, dreamer/wrappers.py:221-226).  Per car, over the rc_step / rc_step_random /
+ * rc_step_group calls of the episode (one call = one agent step = one Collect transition), from the values the call leaves in
+ * the CURRENT arena (rc_set_arena) - the terminal values on the last call, also under auto-reset:
+ *   env       global env id (first_env + index in the handle): does not depend on the sharding
+ *   slot      car slot 0 .. cars_per_env - 1
+ *   track     the track the episode was DRIVEN on: the track-set id latched when the episode started (after an auto-reset
+ *             rc_track_ids already names the next one); 0 without a track set
+ *   episode   ordinal of the episode among this env's episodes that ended since enable / clear (dropped and skipped ones count), from 0
+ *   call      index of the step call, counted since enable / clear, in which it ended
+ *   length    calls in the episode = the reference's len(reward) - 1
+ *   ret       binary32 sum of RC_F_REWARD in call order, starting from +0.0f (the reset row adds 0)
+ *   progress  max over -1.0f (the reset row, wrappers.py:232-236) and every call's RC_F_PROGRESS_TOTAL
+ *   time      max over 0.0f and every call's RC_F_TIME
+ *   laps      terminal RC_F_LAP - 1
+ *   flags     bit 0 terminal wall collision, 1 terminal opponent collision, 2 truncated (RC_F_TRUNCATED), 3 wrong_way seen in any
+ *             call of the episode, 4 this car's own done was set (0 = the episode ended because a team-mate's did)
+ * Rules:
+ *   - an episode is logged ONCE.  Without auto_reset a finished env is frozen and keeps done = 1 in every later call: no second
+ *     row and no further sums until it is reset.
+ *   - rc_reset (with or without a mask) of an env whose episode is running discards its sums without a row and adds 1 to
+ *     `abandoned` (one per env, whatever cars_per_env; a reset right after a reset abandons an episode of length 0).
+ *     rc_set_pose changes nothing in the log.
+ *   - the log follows an env from its next reset on - rc_reset or the auto-reset inside a step: enabled in the middle of an
+ *     episode it logs nothing for that partial episode.
+ *   - rows are ordered by call, then env, then slot - strictly, not up to a permutation: two runs with the same seeds give
+ *     byte-identical row buffers.
+ *   - capacity is fixed at enable.  A row that does not fit is counted in `dropped`; rows already written are never
+ *     overwritten (not a ring: the first k episodes of every env survive).  max_episodes > 0 is a quota per env: an episode
+ *     whose ordinal is >= the quota gets no rows, its cars are counted in `skipped`, and `envs_at_quota` counts the envs whose
+ *     ordinal has reached the quota - one integer to poll for "every env has finished max_episodes episodes", after which the log
+ *     holds exactly n_cars * max_episodes rows if the capacity allows.
+ *   - counters: uint64 [6] in device memory = written, dropped, skipped (rows), abandoned (episodes), envs_at_quota (envs), calls.
+ * rc_episode_log_enable allocates; called again it clears and, if the capacity differs, reallocates the rows (running episodes keep
+ * their sums).  rc_episode_log gives the device pointers: the rows (capacity_rows x 48 bytes, the first `written` valid) and the
+ * counters.  rc_episode_log_clear: rows, counters and ordinals to zero, `call` restarts at 0, running episodes keep their sums.
+ * rc_episode_log_disable frees everything (synchronises the handle's stream).  In a group launch each handle keeps its own log.
+ * RC_ERR_INVALID: env NULL, capacity_rows < 1, max_episodes < 0, rc_episode_log / rc_episode_log_clear before enable.
+ * Kernels: rc_episode_count_kernel + rc_episode_update_kernel behind every step's dynamics launch, rc_episode_reset_kernel behind
+ * rc_reset's.  They have no RC_K_* timer; while rc_set_profiling is on, rc_episode_log_time reports the summed time between two
+ * events around the log's launches of every step (and their number); rc_reset_kernel_times zeroes it. */
+typedef struct rc_episode_row {
+    int32_t  env, slot, track;
+    uint32_t episode, call;
+    int32_t  length;
+    float    ret, progress, time;
+    int32_t  laps;
+    uint32_t flags, reserved;      /* reserved = 0 */
+} rc_episode_row;                  /* 48 bytes */
+enum { RC_EP_WALL = 1, RC_EP_OPPONENT = 2, RC_EP_TRUNCATED = 4, RC_EP_WRONG_WAY = 8, RC_EP_OWN_DONE = 16 };   /* rc_episode_row.flags */
+int rc_episode_log_enable(rc_env *env, int64_t capacity_rows, int32_t max_episodes);
+int rc_episode_log_disable(rc_env *env);
+int rc_episode_log(rc_env *env, void **rows_dev, size_t *capacity_rows, void **counters_dev, size_t *counters_bytes);
+int rc_episode_log_clear(rc_env *env);
+int rc_episode_log_time(rc_env *env, double *total_ms, uint64_t *launches);
+
 int rc_get(rc_env *env, int32_t field, void **dev_ptr, size_t *bytes);
 int rc_copy_out(rc_env *env, int32_t field, void *host_dst, size_t bytes);
 /* The trajectory record of the last step as one contiguous device slab (fields LIDAR..TIME,

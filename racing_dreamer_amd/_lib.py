@@ -51,6 +51,17 @@ class RcConfig(C.Structure):
     ]
 
 
+class RcEpisodeRow(C.Structure):
+    """rc_episode_row (include/racecar_hip.h): one car's episode, 48 bytes."""
+    _fields_ = [("env", C.c_int32), ("slot", C.c_int32), ("track", C.c_int32), ("episode", C.c_uint32), ("call", C.c_uint32),
+                ("length", C.c_int32), ("ret", C.c_float), ("progress", C.c_float), ("time", C.c_float), ("laps", C.c_int32),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+EPISODE_COUNTERS = ("written", "dropped", "skipped", "abandoned", "envs_at_quota", "calls")      # uint64 each, in this order
+EP_WALL, EP_OPPONENT, EP_TRUNCATED, EP_WRONG_WAY, EP_OWN_DONE = 1, 2, 4, 8, 16                  # rc_episode_row.flags
+
+
 class RcPolicyArray(C.Structure):
     _fields_ = [("data", C.c_void_p), ("rows", C.c_int32), ("cols", C.c_int32)]
 
@@ -120,6 +131,11 @@ SYMBOLS = {
     "rc_policy_unload": (C.c_int, [C.c_void_p]),
     "rc_policy_act": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rc_policy_state": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
+    "rc_episode_log_enable": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
+    "rc_episode_log_disable": (C.c_int, [C.c_void_p]),
+    "rc_episode_log": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p), _P(C.c_size_t)]),
+    "rc_episode_log_clear": (C.c_int, [C.c_void_p]),
+    "rc_episode_log_time": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint64)]),
     "rc_fill_random_actions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "rc_step_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]),
     "rc_step_group": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),

@@ -613,6 +613,80 @@ class BatchedRaceEnv:
         self._policy_state = None
         L.check(self._lib.rc_policy_unload(self._h))
 
+    # ------------------------------------------------------------------ episode log (include/racecar_hip.h, rc_episode_log_*)
+    def enable_episode_log(self, capacity: int, max_episodes: int = 0) -> None:
+        """Keep return, length, progress and time of every episode on the device (the reference's summarize_episode,
+        dreamer/callbacks.py:56-100): per-car running sums and, in the call in which an env's episode ends, one row per car appended
+        to a buffer of `capacity` rows in (call, env, slot) order.  `max_episodes` > 0: only each env's first `max_episodes`
+        episodes get rows.  An env is followed from its next reset on (enabled mid-episode, nothing is logged for the partial
+        episode).  Called again: clears, and resizes if the capacity differs."""
+        L.check(self._lib.rc_episode_log_enable(self._h, C.c_int64(int(capacity)), int(max_episodes)))
+        rows, cap, ctr, nb = C.c_void_p(), C.c_size_t(), C.c_void_p(), C.c_size_t()
+        L.check(self._lib.rc_episode_log(self._h, C.byref(rows), C.byref(cap), C.byref(ctr), C.byref(nb)))
+        words = C.sizeof(L.RcEpisodeRow) // 4
+        arrays = (_BorrowedDeviceArray(rows.value, (cap.value, words), self.device, code=0),
+                  _BorrowedDeviceArray(ctr.value, (nb.value // 4,), self.device, code=0))
+        # (the DLPack descriptors of earlier enables stay alive with the env: a caller may still hold views made from them)
+        self._ep_arrays = getattr(self, "_ep_arrays", None) or []
+        self._ep_arrays.extend(arrays)
+        self._ep_rows = torch.utils.dlpack.from_dlpack(arrays[0])           # int32 [capacity, 12]: a structured view
+        self._ep_counters = torch.utils.dlpack.from_dlpack(arrays[1])
+
+    def _ep_check(self) -> None:
+        if getattr(self, "_ep_rows", None) is None:
+            raise L.RacecarHipError("the episode log is not enabled (enable_episode_log)")
+
+    @property
+    def episode_counters(self) -> Dict[str, int]:
+        """written, dropped, skipped (rows), abandoned (episodes), envs_at_quota (envs), calls: one synchronising host read."""
+        self._ep_check()
+        self._enter()
+        with torch.cuda.stream(self.stream):
+            host = self._ep_counters.cpu().numpy()
+        return dict(zip(L.EPISODE_COUNTERS, (int(v) for v in host.view(np.uint64))))
+
+    @property
+    def episode_rows(self) -> torch.Tensor:
+        """The whole row buffer as int32 [capacity, 12] (48-byte rc_episode_row per row), zero-copy."""
+        self._ep_check()
+        return self._ep_rows
+
+    def episode_log(self, clear: bool = False) -> Dict[str, torch.Tensor]:
+        """The rows written so far as device tensors [written] named as rc_episode_row's fields - env, slot, track, episode, call,
+        length, laps, flags (int32 views; flags: L.EP_WALL / EP_OPPONENT / EP_TRUNCATED / EP_WRONG_WAY / EP_OWN_DONE) and ret,
+        progress, time (float32) - in (call, env, slot) order.  One host read (the counter); the columns are zero-copy strided
+        views of the row buffer, valid until the log is cleared or resized (clear=True returns copies, then clears)."""
+        n = self.episode_counters["written"]
+        rows = self._ep_rows[:n]
+        out = {}
+        for k, (name, ctype) in enumerate(L.RcEpisodeRow._fields_):
+            if name == "reserved":
+                continue
+            col = rows[:, k:k + 1]
+            out[name] = (col.view(torch.float32) if ctype is C.c_float else col)[:, 0]
+        if clear:
+            with torch.cuda.stream(self.stream):
+                out = {k: v.clone() for k, v in out.items()}
+            self.clear_episode_log()
+        return out
+
+    def clear_episode_log(self) -> None:
+        """Rows, counters and ordinals to zero (stream-ordered); running episodes keep their sums."""
+        self._ep_check()
+        self._enter()
+        L.check(self._lib.rc_episode_log_clear(self._h))
+        self._exit()
+
+    def disable_episode_log(self) -> None:
+        self._ep_rows = self._ep_counters = None
+        L.check(self._lib.rc_episode_log_disable(self._h))
+
+    def episode_log_time(self):
+        """(total ms, steps) between events around the log's launches, summed over the steps taken while profiling was on."""
+        ms, n = C.c_double(), C.c_uint64()
+        L.check(self._lib.rc_episode_log_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, int(n.value)
+
     def fill_random_actions(self, seed: int, step: int) -> None:
         L.check(self._lib.rc_fill_random_actions(self._h, C.c_uint64(seed), C.c_uint32(step)))
 
@@ -940,6 +1014,38 @@ class MixedTrackEnv:
     def unload_policy(self) -> None:
         for p in self.parts:
             p.unload_policy()
+
+    # episode log: each block's handle keeps its own; the merged view is in (call, env, slot) order with `track` = the block's index
+    def enable_episode_log(self, capacity: int, max_episodes: int = 0) -> None:
+        """`capacity` rows for the whole batch, shared out by each block's share of the envs (rounded up)."""
+        for p in self.parts:
+            p.enable_episode_log(-(-int(capacity) * p.num_envs // self.num_envs), max_episodes)
+
+    @property
+    def episode_counters(self) -> Dict[str, int]:
+        parts = [p.episode_counters for p in self.parts]
+        out = {k: sum(c[k] for c in parts) for k in L.EPISODE_COUNTERS}
+        out["calls"] = max(c["calls"] for c in parts)
+        return out
+
+    def episode_log(self, clear: bool = False) -> Dict[str, torch.Tensor]:
+        """The blocks' logs merged (copies) into (call, env, slot) order: `env` in the batch's own numbering (first_env + row of the
+        arena), `track` = the index of the env's block."""
+        logs = [p.episode_log(clear=clear) for p in self.parts]
+        for i, lg in enumerate(logs):
+            lg["track"] = torch.full_like(lg["track"], i)
+        cat = {k: torch.cat([lg[k] for lg in logs]) for k in logs[0]}
+        # blocks hold disjoint, ascending env ranges and each is already ordered: a stable sort by call restores the order
+        order = torch.sort(cat["call"].to(torch.int64) & 0xFFFFFFFF, stable=True).indices
+        return {k: v[order] for k, v in cat.items()}
+
+    def clear_episode_log(self) -> None:
+        for p in self.parts:
+            p.clear_episode_log()
+
+    def disable_episode_log(self) -> None:
+        for p in self.parts:
+            p.disable_episode_log()
 
     def sync(self):
         for p in self.parts:

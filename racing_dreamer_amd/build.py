@@ -10,8 +10,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libracecar_hip.so")
-SOURCES = ["racecar_kernels.hip", "racecar_abi.hip", "racecar_policy.hip"]
-HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_spec.h", "racecar_scan.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", os.path.join("..", "..", "include", "racecar_hip.h")]
+SOURCES = ["racecar_kernels.hip", "racecar_abi.hip", "racecar_policy.hip", "racecar_episode.hip"]
+HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_spec.h", "racecar_scan.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", "racecar_episode.h", os.path.join("..", "..", "include", "racecar_hip.h")]
 # The lab library: scan variants 0-6 and the instrumented build of the scan (racecar_lab.hip).  NOT part of the shipped
 # library; built by build_lab() - which tools/ and the variant tests call - and loaded by libracecar_hip.so on first use.
 LAB_PATH = os.path.join(LIB_DIR, "libracecar_lab.so")

@@ -21,6 +21,7 @@
 #include "../../include/racecar_hip.h"
 #include "racecar_internal.h"
 #include "racecar_policy.h"
+#include "racecar_episode.h"
 #include "racecar_spec.h"
 
 namespace {
@@ -256,6 +257,16 @@ struct rc_env {
     bool ts_table_valid = false;
     RcParams ts_last[RC_TS_MAX];
     size_t ts_patch_lds = 0;
+    // episode log (rc_episode_log_enable): the running sums, counters, cursor and workgroup counts (one allocation), the rows,
+    // the calls since enable / clear, and - while rc_set_profiling is on - event pairs around the log's launches of a step
+    bool ep_on = false;
+    void *ep_mem = nullptr;
+    void *ep_rows = nullptr;
+    uint64_t ep_calls = 0;
+    RcEpisodeDev ep{};
+    std::vector<EventPair> ep_pending;
+    double ep_ms = 0.0;
+    uint64_t ep_n = 0;
 };
 
 namespace {
@@ -530,6 +541,61 @@ int observe(rc_env *env) {
 Rccl g_rccl;
 std::string g_rccl_path;
 std::mutex g_rccl_mutex;
+
+// ---- episode log: the launches behind a step's dynamics and a reset (racecar_episode.hip) ---------------------------------------
+// The log reads the arena the outputs point at NOW (rc_set_arena re-points them between steps) and the current track ids.
+void episode_bind(rc_env *env) {
+    RcEpisodeDev &d = env->ep;
+    const RcOutDev &o = env->params.out;
+    d.reward = o.reward; d.progress_total = o.progress_total; d.time = o.time; d.lap = o.lap;
+    d.done = o.done; d.trunc = o.trunc; d.wall = o.wall; d.opp = o.opp; d.wrong = o.wrong; d.fresh = o.fresh;
+    d.ts_n = env->params.ts_n;
+    d.ts_track = env->params.ts_n > 0 ? env->params.ts_track : nullptr;
+    d.call = (uint32_t)env->ep_calls;
+}
+
+int episode_drain(rc_env *env) {
+    if (env->ep_pending.empty()) return RC_OK;
+    HIP_TRY(hipStreamSynchronize(env->stream));
+    for (EventPair &ep : env->ep_pending) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ep.a, ep.b));
+        env->ep_ms += ms;
+        env->ep_n += 1;
+        env->free_events.push_back(ep);
+    }
+    env->ep_pending.clear();
+    return RC_OK;
+}
+
+// After the dynamics launch and before the scan: the few fields the log reads are the ones that launch has just written (they
+// are still in L2; behind the scan's 280 MB of rows they would not be), and the scan does not depend on the log.
+int episode_step(rc_env *env) {
+    episode_bind(env);
+    EventPair ep{};
+    const bool timed = env->profiling != 0;
+    if (timed) {
+        if (env->ep_pending.size() >= 4096) {
+            int rc = episode_drain(env);
+            if (rc) return rc;
+        }
+        if (!env->free_events.empty()) {
+            ep = env->free_events.back();
+            env->free_events.pop_back();
+        } else {
+            HIP_TRY(hipEventCreate(&ep.a));
+            HIP_TRY(hipEventCreate(&ep.b));
+        }
+        HIP_TRY(hipEventRecord(ep.a, env->stream));
+    }
+    HIP_TRY(rck_launch_episode_step(env->ep, env->stream));
+    if (timed) {
+        HIP_TRY(hipEventRecord(ep.b, env->stream));
+        env->ep_pending.push_back(ep);
+    }
+    env->ep_calls += 1;
+    return RC_OK;
+}
 
 int load_rccl() {
     std::lock_guard<std::mutex> lock(g_rccl_mutex);       // handles may be set up from different threads
@@ -926,6 +992,9 @@ void rc_destroy(rc_env *env) {
     if (env->group_dev) (void)hipFree(env->group_dev);
     if (env->group_host) (void)hipHostFree(env->group_host);
     for (hipEvent_t e : env->group_ev) if (e) (void)hipEventDestroy(e);
+    if (env->ep_mem) (void)hipFree(env->ep_mem);
+    if (env->ep_rows) (void)hipFree(env->ep_rows);
+    for (EventPair &ep : env->ep_pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     if (env->ts_mem) (void)hipFree(env->ts_mem);
     if (env->ts_dev) (void)hipFree(env->ts_dev);
     if (env->ts_host) (void)hipHostFree(env->ts_host);
@@ -1249,6 +1318,10 @@ int rc_reset(rc_env *env, const uint8_t *mask_or_null, int32_t mode, uint64_t se
     } else {
         TIMED(env, RC_K_RESET, rck_launch_reset(env->params, mask_dev, env->stream));
     }
+    if (env->ep_on) {
+        episode_bind(env);
+        HIP_TRY(rck_launch_episode_reset(env->ep, mask_dev, env->stream));
+    }
     env->was_reset = true;
     if (!mask_or_null) env->order_age = 0xffffffffu;      // every car has a new place: sort before this observation
     return observe(env);
@@ -1267,9 +1340,14 @@ int rc_step(rc_env *env, const float *actions_dev, int32_t repeat) {
         int rc = ts_sync_table(env);
         if (rc) return rc;
         TIMED(env, RC_K_DYNAMICS, rck_launch_ts_dynamics(env->params, act, repeat, none, env->stream));
+        if (env->ep_on && (rc = episode_step(env))) return rc;
         return observe(env);
     }
     TIMED(env, RC_K_DYNAMICS, rck_launch_dynamics(env->params, act, repeat, none, env->stream));
+    if (env->ep_on) {
+        int rc = episode_step(env);
+        if (rc) return rc;
+    }
     return observe(env);
 }
 
@@ -1284,9 +1362,14 @@ int rc_step_random(rc_env *env, uint64_t seed, uint32_t step, int32_t repeat) {
         int rc = ts_sync_table(env);
         if (rc) return rc;
         TIMED(env, RC_K_DYNAMICS, rck_launch_ts_dynamics(env->params, env->actions_in, repeat, ra, env->stream));
+        if (env->ep_on && (rc = episode_step(env))) return rc;
         return observe(env);
     }
     TIMED(env, RC_K_DYNAMICS, rck_launch_dynamics(env->params, env->actions_in, repeat, ra, env->stream));
+    if (env->ep_on) {
+        int rc = episode_step(env);
+        if (rc) return rc;
+    }
     return observe(env);
 }
 
@@ -1356,6 +1439,11 @@ static int group_step(rc_env **envs, int32_t n, const float *actions_dev, int32_
         noise |= envs[b]->params.noise_on != 0;
     }
     TIMED(lead, RC_K_DYNAMICS, rck_launch_dynamics_group(g, lead->cfg.cars_per_env, repeat, ra, lead->stream, dr));
+    for (int b = 0; b < n; ++b)
+        if (envs[b]->ep_on) {             // each handle keeps its own log
+            int rc_ep = episode_step(envs[b]);
+            if (rc_ep) return rc_ep;
+        }
     // scan: a wave = one car (or 1 / split of one); the split follows the group's total, as one handle of that size would
     int split = lead->dbg[RC_DBG_RAY_SPLIT];
     if (split < 1 || split > 17) split = scan_split(cars, lead->launch.n_cu);
@@ -1554,6 +1642,104 @@ int rc_track_ids(rc_env *env, void **dev_ptr, size_t *bytes) {
     if (!env->ts_mem) return fail(RC_ERR_INVALID, "rc_track_ids: no track set was installed (rc_set_track_set)");
     *dev_ptr = env->params.ts_track;
     if (bytes) *bytes = (size_t)env->cfg.num_envs * 4;
+    return RC_OK;
+}
+
+// ---- episode log -------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(rc_episode_row) == 48 && sizeof(RcEpisodeRow) == sizeof(rc_episode_row), "rc_episode_row is 48 bytes");
+
+int rc_episode_log_enable(rc_env *env, int64_t capacity_rows, int32_t max_episodes) {
+    if (capacity_rows < 1) return fail(RC_ERR_INVALID, "rc_episode_log_enable: capacity_rows must be >= 1 (got %lld)", (long long)capacity_rows);
+    if (max_episodes < 0) return fail(RC_ERR_INVALID, "rc_episode_log_enable: max_episodes must be >= 0 (got %d)", max_episodes);
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)env->cfg.num_envs, N = (size_t)env->n_cars, blocks = (B + RC_EP_BLOCK - 1) / RC_EP_BLOCK;
+    RcEpisodeDev &d = env->ep;
+    if (!env->ep_mem) {
+        // counters [8] | cursor [2] | ordinal, length, track [B] | ret, prog_max, time_max [N] | block counts | active [B] | wrong_seen [N]
+        const size_t bytes = 10 * 8 + 3 * B * 4 + 3 * N * 4 + blocks * 4 + B + N;
+        HIP_TRY(hipMalloc(&env->ep_mem, bytes));
+        HIP_TRY(hipMemsetAsync(env->ep_mem, 0, bytes, env->stream));      // active = 0: every env starts counting at its next reset
+        d = RcEpisodeDev{};
+        d.counters = (unsigned long long *)env->ep_mem;
+        d.cursor = d.counters + 8;
+        d.ordinal = (uint32_t *)(d.cursor + 2);
+        d.length = (int32_t *)(d.ordinal + B);
+        d.track = d.length + B;
+        d.ret = (float *)(d.track + B);
+        d.prog_max = d.ret + N;
+        d.time_max = d.prog_max + N;
+        d.block_counts = (uint32_t *)(d.time_max + N);
+        d.active = (uint8_t *)(d.block_counts + blocks);
+        d.wrong_seen = d.active + B;
+        d.num_envs = env->cfg.num_envs;
+        d.cars_per_env = env->cfg.cars_per_env;
+        d.first_env = (uint32_t)env->cfg.first_env;
+    }
+    if (!env->ep_rows || d.capacity != (unsigned long long)capacity_rows) {
+        if (env->ep_rows) {
+            HIP_TRY(hipStreamSynchronize(env->stream));       // (launches that write the old rows may still be queued)
+            HIP_TRY(hipFree(env->ep_rows));
+            env->ep_rows = nullptr;
+            env->ep_on = false;
+        }
+        if (hipMalloc(&env->ep_rows, (size_t)capacity_rows * sizeof(RcEpisodeRow)) != hipSuccess) {
+            env->ep_rows = nullptr;
+            return fail(RC_ERR_NOMEM, "rc_episode_log_enable: no device memory for %lld rows", (long long)capacity_rows);
+        }
+        d.rows = (RcEpisodeRow *)env->ep_rows;
+        d.capacity = (unsigned long long)capacity_rows;
+    }
+    d.max_episodes = (uint32_t)max_episodes;
+    env->ep_on = true;
+    return rc_episode_log_clear(env);
+}
+
+int rc_episode_log_disable(rc_env *env) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->ep_mem) return RC_OK;
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(hipStreamSynchronize(env->stream));
+    int rc = episode_drain(env);
+    if (rc) return rc;
+    HIP_TRY(hipFree(env->ep_mem));
+    env->ep_mem = nullptr;
+    if (env->ep_rows) HIP_TRY(hipFree(env->ep_rows));
+    env->ep_rows = nullptr;
+    env->ep_on = false;
+    env->ep = RcEpisodeDev{};
+    return RC_OK;
+}
+
+int rc_episode_log(rc_env *env, void **rows_dev, size_t *capacity_rows, void **counters_dev, size_t *counters_bytes) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->ep_on) return fail(RC_ERR_INVALID, "rc_episode_log: the episode log is not enabled (rc_episode_log_enable)");
+    if (rows_dev) *rows_dev = env->ep_rows;
+    if (capacity_rows) *capacity_rows = (size_t)env->ep.capacity;
+    if (counters_dev) *counters_dev = env->ep.counters;
+    if (counters_bytes) *counters_bytes = RC_EPC_COUNT * sizeof(uint64_t);
+    return RC_OK;
+}
+
+int rc_episode_log_clear(rc_env *env) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->ep_on) return fail(RC_ERR_INVALID, "rc_episode_log_clear: the episode log is not enabled (rc_episode_log_enable)");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    const RcEpisodeDev &d = env->ep;
+    HIP_TRY(hipMemsetAsync(d.rows, 0, (size_t)d.capacity * sizeof(RcEpisodeRow), env->stream));
+    HIP_TRY(hipMemsetAsync(d.counters, 0, 10 * 8, env->stream));                                  // the counters and the cursor pair
+    HIP_TRY(hipMemsetAsync(d.ordinal, 0, (size_t)env->cfg.num_envs * 4, env->stream));
+    env->ep_calls = 0;
+    return RC_OK;
+}
+
+int rc_episode_log_time(rc_env *env, double *total_ms, uint64_t *launches) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    int rc = episode_drain(env);
+    if (rc) return rc;
+    if (total_ms) *total_ms = env->ep_ms;
+    if (launches) *launches = env->ep_n;
     return RC_OK;
 }
 
@@ -1969,6 +2155,10 @@ int rc_reset_kernel_times(rc_env *env) {
     int rc = drain_events(env);
     if (rc) return rc;
     for (int k = 0; k < RC_K_COUNT; ++k) { env->k_ms[k] = 0; env->k_n[k] = 0; }
+    rc = episode_drain(env);
+    if (rc) return rc;
+    env->ep_ms = 0.0;
+    env->ep_n = 0;
     return RC_OK;
 }
 
