@@ -46,6 +46,8 @@ int fail(int code, const char *fmt, ...) {
     } while (0)
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+uint32_t seed_lo(uint64_t seed) { return (uint32_t)(seed & 0xffffffffu); }      // the halves the kernels' Philox keys take
+uint32_t seed_hi(uint64_t seed) { return (uint32_t)(seed >> 32); }
 
 struct RcUid { char internal[128]; };      // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES = 128), passed by value
 
@@ -150,6 +152,47 @@ struct EventPair {
     hipEvent_t a, b;
     int kernel;
 };
+// The episode log's launches of a step are timed like a kernel, under an accumulator of their own behind the public ones
+// (rc_kernel_time does not know it: rc_episode_log_time reads it).
+constexpr int kTimeEpisodeLog = RC_K_COUNT;
+
+// A table of up to 8 RcParams on the device that follows its host-side contents in stream order (rc_step_group: one entry per
+// handle; a track set: one per track).  A copy is queued only when an entry or the count changed since the last upload, from one
+// of four pinned slots taken in turn, none rewritten before its copy has run.
+static_assert(RC_GROUP_MAX == RC_TS_MAX, "one staged table type serves the group and the track set");
+struct StagedTable {
+    RcParams *dev = nullptr;
+    RcParams *host = nullptr;      // [4][RC_GROUP_MAX], pinned
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t slot = 0;
+    int n = 0;                     // entries of the last upload; 0: the next sync uploads
+    RcParams last[RC_GROUP_MAX];
+    int alloc() {                  // on first use (a failure half way is made up for by the next call)
+        if (!dev) HIP_TRY(hipMalloc((void **)&dev, sizeof(RcParams) * RC_GROUP_MAX));
+        if (!host) HIP_TRY(hipHostMalloc((void **)&host, sizeof(RcParams) * RC_GROUP_MAX * 4, hipHostMallocDefault));
+        for (hipEvent_t &e : ev)
+            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        return RC_OK;
+    }
+    int sync(const RcParams *want, int n_want, hipStream_t stream) {
+        if (n == n_want && std::memcmp(want, last, sizeof(RcParams) * n_want) == 0) return RC_OK;
+        n = 0;
+        const uint32_t k = slot++ & 3u;
+        HIP_TRY(hipEventSynchronize(ev[k]));
+        RcParams *stage = host + (size_t)k * RC_GROUP_MAX;
+        std::memcpy(stage, want, sizeof(RcParams) * n_want);
+        std::memcpy(last, want, sizeof(RcParams) * n_want);
+        HIP_TRY(hipMemcpyAsync(dev, stage, sizeof(RcParams) * n_want, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipEventRecord(ev[k], stream));
+        n = n_want;
+        return RC_OK;
+    }
+    void free() {
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+    }
+};
 
 // ---- peer-copy all-gather (on the xGMI full mesh every shard crosses exactly one link once if each rank
 // copies its record straight into every peer's buffer - N - 1 concurrent copies - where a ring passes it N - 1 times).
@@ -207,11 +250,11 @@ struct rc_env {
     bool has_track = false;
     bool was_reset = false;
     // profiling
-    uint32_t profiling = 0;        // bit k set: time kernel k with HIP events
+    uint32_t profiling = 0;        // bit k set: time kernel k with HIP events (the episode log's launches: any bit)
     std::vector<EventPair> pending;
     std::vector<EventPair> free_events;
-    double k_ms[RC_K_COUNT] = {0};
-    uint64_t k_n[RC_K_COUNT] = {0};
+    double k_ms[RC_K_COUNT + 1] = {0};     // (the last entry: kTimeEpisodeLog)
+    uint64_t k_n[RC_K_COUNT + 1] = {0};
     int32_t dbg[RC_DBG_COUNT] = {0};   // rc_debug_set: experiment / validation knobs, all 0 = production behaviour
     // half-size record + multi-GPU gather
     CompactLayout compact{};
@@ -237,36 +280,20 @@ struct rc_env {
     void *order_mem = nullptr;         // RcStateDev::order + the sort's bucket counters (batches of RC_ORDER_MIN_CARS cars and more)
     uint32_t order_age = 0;            // observations since the cars were last sorted by track position
     const float *last_scan_rows = nullptr;   // the LiDAR rows the last scan of this handle wrote (the small batches' cost keys)
-    // rc_step_group (this handle as the first of a group): the blocks' RcParams as the last launch saw them, on the device
-    // and on the host (pinned staging slots taken in turn, each with the event of its copy)
-    RcParams *group_dev = nullptr;
-    RcParams *group_host = nullptr;    // [kGroupSlots][RC_GROUP_MAX], pinned
-    hipEvent_t group_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t group_slot = 0;
-    int group_n = 0;
-    RcParams group_last[RC_GROUP_MAX];
-    // track set (rc_set_track_set): the source handles, the per-env arrays, the table of RcParams (one per track) on the device and
-    // its pinned staging slots (as the group's), the render's LDS bytes
+    StagedTable group_table;           // rc_step_group (this handle as the first of a group): the blocks' RcParams as the last launch saw them
+    // track set (rc_set_track_set): the source handles, the per-env arrays, the table of RcParams (one per track), the render's LDS bytes
     std::vector<rc_env *> ts_src;
     void *ts_mem = nullptr;            // track [num_envs] | next [num_envs] | list [n_cars] | start [RC_TS_MAX + 1] | counts, cursors
                                        // [2 RC_TS_MAX] | started [num_envs]
-    RcParams *ts_dev = nullptr;
-    RcParams *ts_host = nullptr;       // [4][RC_TS_MAX], pinned
-    hipEvent_t ts_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t ts_slot = 0;
-    bool ts_table_valid = false;
-    RcParams ts_last[RC_TS_MAX];
+    StagedTable ts_table;
     size_t ts_patch_lds = 0;
     // episode log (rc_episode_log_enable): the running sums, counters, cursor and workgroup counts (one allocation), the rows,
-    // the calls since enable / clear, and - while rc_set_profiling is on - event pairs around the log's launches of a step
+    // the calls since enable / clear
     bool ep_on = false;
     void *ep_mem = nullptr;
     void *ep_rows = nullptr;
     uint64_t ep_calls = 0;
     RcEpisodeDev ep{};
-    std::vector<EventPair> ep_pending;
-    double ep_ms = 0.0;
-    uint64_t ep_n = 0;
 };
 
 namespace {
@@ -286,13 +313,17 @@ int drain_events(rc_env *env) {
     return RC_OK;
 }
 
+// Times what lies between begin() and end() under accumulator `kernel`.  One launch: the launch itself carries the two timestamps
+// (rck_set_launch_events).  `bracket`: the pair is recorded on the stream around whatever is queued in between (the episode log's
+// step is two dependent launches).
 struct KernelTimer {
     rc_env *env;
     EventPair ep{};
-    bool on = false;
-    int begin(rc_env *e, int kernel) {
+    bool on = false, bracket = false;
+    int begin(rc_env *e, int kernel, bool bracket_mode = false) {
         env = e;
-        if (!((e->profiling >> kernel) & 1u)) return RC_OK;
+        bracket = bracket_mode;
+        if (kernel == kTimeEpisodeLog ? e->profiling == 0 : !((e->profiling >> kernel) & 1u)) return RC_OK;
         if (e->pending.size() >= 4096) {
             int rc = drain_events(e);
             if (rc) return rc;
@@ -305,12 +336,14 @@ struct KernelTimer {
             HIP_TRY(hipEventCreate(&ep.b));
         }
         ep.kernel = kernel;
-        rck_set_launch_events(ep.a, ep.b);      // the launch that follows carries the two timestamps itself
+        if (bracket) HIP_TRY(hipEventRecord(ep.a, e->stream));
+        else rck_set_launch_events(ep.a, ep.b);      // the launch that follows carries the two timestamps itself
         on = true;
         return RC_OK;
     }
     int end() {
         if (!on) return RC_OK;
+        if (bracket) HIP_TRY(hipEventRecord(ep.b, env->stream));
         env->pending.push_back(ep);
         return RC_OK;
     }
@@ -474,63 +507,51 @@ int render_reference_patches(rc_env *env) {
     return RC_OK;
 }
 
-// Track set: the device table follows the handle's parameters (and its sources' tables) in stream order - a copy is queued only
-// when an entry changed, from a pinned slot that is not rewritten before its copy has run (as rc_step_group's table)
+// Track set: entry k of the device table is the handle's parameters with track k's tables
 int ts_sync_table(rc_env *env) {
     const int n = env->params.ts_n;
     RcParams want[RC_TS_MAX];
     for (int k = 0; k < n; ++k) {
-        want[k] = env->params;
+        std::memcpy(&want[k], &env->params, sizeof(RcParams));
         want[k].trk = env->ts_src[k]->params.trk;
     }
-    if (env->ts_table_valid && std::memcmp(want, env->ts_last, sizeof(RcParams) * n) == 0) return RC_OK;
-    const uint32_t slot = env->ts_slot++ & 3u;
-    HIP_TRY(hipEventSynchronize(env->ts_ev[slot]));
-    RcParams *host = env->ts_host + (size_t)slot * RC_TS_MAX;
-    std::memcpy(host, want, sizeof(RcParams) * n);
-    std::memcpy(env->ts_last, want, sizeof(RcParams) * n);
-    HIP_TRY(hipMemcpyAsync(env->ts_dev, host, sizeof(RcParams) * n, hipMemcpyHostToDevice, env->stream));
-    HIP_TRY(hipEventRecord(env->ts_ev[slot], env->stream));
-    env->ts_table_valid = true;
+    return env->ts_table.sync(want, n, env->stream);
+}
+
+// the default scan: variant 7, neither the bounded validation build nor the instrumented build (what LiDAR noise, a track set and
+// a group launch are written for)
+bool on_default_scan(const rc_env *env) {
+    return env->launch.raycast_variant == 7 && !env->launch.scan_guarded && !env->launch.scan_stamps;
+}
+
+// the renders behind a scan: the fast patch (by track with a track set) and the reference's own
+int render_patches(rc_env *env) {
+    if (env->params.render_patch)
+        TIMED(env, RC_K_PATCH, env->params.ts_n > 0 ? rck_launch_ts_patch(env->params, env->launch, env->ts_patch_lds, env->stream)
+                                                    : rck_launch_patch(env->params, env->launch, env->stream));
+    if (env->cfg.obs_type == RC_OBS_LIDAR_OCCUPANCY_REFERENCE) return render_reference_patches(env);      // (never with a track set)
     return RC_OK;
 }
 
-// the observation with a track set: the cars track-major, then the scan and the render by track
-int observe_track_set(rc_env *env) {
-    if (env->launch.raycast_variant != 7 || env->launch.scan_guarded || env->launch.scan_stamps)
+// The observation: sort if due, scan, render, compact summary.  With a track set the cars are listed track-major first, and the
+// scan and the render go by track.
+int observe(rc_env *env) {
+    const bool ts = env->params.ts_n > 0;
+    if (ts && !on_default_scan(env))
         return fail(RC_ERR_INVALID, "a track set (rc_set_track_set) is scanned by the default scan (variant 7) only, not by a lab variant, "
+                                  "the bounded validation build or the instrumented build");
+    if (env->params.noise_on && !on_default_scan(env))
+        return fail(RC_ERR_INVALID, "LiDAR noise (rc_set_lidar_noise) is applied by the default scan (variant 7) only, not by a lab variant, "
                                   "the bounded validation build or the instrumented build");
     int rc = sort_cars_if_due(env);
     if (rc) return rc;
-    rc = ts_sync_table(env);
-    if (rc) return rc;
-    HIP_TRY(rck_launch_ts_list(env->params, env->stream));
-    TIMED(env, RC_K_RAYCAST, rck_launch_ts_raycast(env->params, env->launch, env->stream));
-    env->last_scan_rows = env->params.out.lidar;
-    if (env->params.render_patch)
-        TIMED(env, RC_K_PATCH, rck_launch_ts_patch(env->params, env->launch, env->ts_patch_lds, env->stream));
-    if (env->compact_slab)
-        HIP_TRY(hipMemcpyAsync((char *)env->compact_slab + env->compact.lidar_bytes,
-                               (const char *)env->out_arena + env->compact.summary_src_off, env->compact.summary_bytes,
-                               hipMemcpyDeviceToDevice, env->stream));
-    return RC_OK;
-}
-
-int observe(rc_env *env) {
-    if (env->params.ts_n > 0) return observe_track_set(env);
-    if (env->params.noise_on && (env->launch.raycast_variant != 7 || env->launch.scan_guarded || env->launch.scan_stamps))
-        return fail(RC_ERR_INVALID, "LiDAR noise (rc_set_lidar_noise) is applied by the default scan (variant 7) only, not by a lab variant, "
-                                  "the bounded validation build or the instrumented build");
-    int rc_sort = sort_cars_if_due(env);
-    if (rc_sort) return rc_sort;
-    TIMED(env, RC_K_RAYCAST, rck_launch_raycast(env->params, env->launch, env->stream));
-    env->last_scan_rows = env->params.out.lidar;
-    if (env->params.render_patch)
-        TIMED(env, RC_K_PATCH, rck_launch_patch(env->params, env->launch, env->stream));
-    if (env->cfg.obs_type == RC_OBS_LIDAR_OCCUPANCY_REFERENCE) {
-        int rc_px = render_reference_patches(env);
-        if (rc_px) return rc_px;
+    if (ts) {
+        if ((rc = ts_sync_table(env))) return rc;
+        HIP_TRY(rck_launch_ts_list(env->params, env->stream));
     }
+    TIMED(env, RC_K_RAYCAST, ts ? rck_launch_ts_raycast(env->params, env->launch, env->stream) : rck_launch_raycast(env->params, env->launch, env->stream));
+    env->last_scan_rows = env->params.out.lidar;
+    if ((rc = render_patches(env))) return rc;
     if (env->compact_slab)      // the scan has written the uint16 rows; the 76 B/car summary follows them
         HIP_TRY(hipMemcpyAsync((char *)env->compact_slab + env->compact.lidar_bytes,
                                (const char *)env->out_arena + env->compact.summary_src_off, env->compact.summary_bytes,
@@ -554,45 +575,15 @@ void episode_bind(rc_env *env) {
     d.call = (uint32_t)env->ep_calls;
 }
 
-int episode_drain(rc_env *env) {
-    if (env->ep_pending.empty()) return RC_OK;
-    HIP_TRY(hipStreamSynchronize(env->stream));
-    for (EventPair &ep : env->ep_pending) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ep.a, ep.b));
-        env->ep_ms += ms;
-        env->ep_n += 1;
-        env->free_events.push_back(ep);
-    }
-    env->ep_pending.clear();
-    return RC_OK;
-}
-
 // After the dynamics launch and before the scan: the few fields the log reads are the ones that launch has just written (they
 // are still in L2; behind the scan's 280 MB of rows they would not be), and the scan does not depend on the log.
 int episode_step(rc_env *env) {
     episode_bind(env);
-    EventPair ep{};
-    const bool timed = env->profiling != 0;
-    if (timed) {
-        if (env->ep_pending.size() >= 4096) {
-            int rc = episode_drain(env);
-            if (rc) return rc;
-        }
-        if (!env->free_events.empty()) {
-            ep = env->free_events.back();
-            env->free_events.pop_back();
-        } else {
-            HIP_TRY(hipEventCreate(&ep.a));
-            HIP_TRY(hipEventCreate(&ep.b));
-        }
-        HIP_TRY(hipEventRecord(ep.a, env->stream));
-    }
+    KernelTimer t;
+    int rc = t.begin(env, kTimeEpisodeLog, true);
+    if (rc) return rc;
     HIP_TRY(rck_launch_episode_step(env->ep, env->stream));
-    if (timed) {
-        HIP_TRY(hipEventRecord(ep.b, env->stream));
-        env->ep_pending.push_back(ep);
-    }
+    if ((rc = t.end())) return rc;
     env->ep_calls += 1;
     return RC_OK;
 }
@@ -989,16 +980,11 @@ void rc_destroy(rc_env *env) {
     if (env->vp_mem) (void)hipFree(env->vp_mem);
     if (env->exact_mem) (void)hipFree(env->exact_mem);
     if (env->order_mem) (void)hipFree(env->order_mem);
-    if (env->group_dev) (void)hipFree(env->group_dev);
-    if (env->group_host) (void)hipHostFree(env->group_host);
-    for (hipEvent_t e : env->group_ev) if (e) (void)hipEventDestroy(e);
+    env->group_table.free();
     if (env->ep_mem) (void)hipFree(env->ep_mem);
     if (env->ep_rows) (void)hipFree(env->ep_rows);
-    for (EventPair &ep : env->ep_pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     if (env->ts_mem) (void)hipFree(env->ts_mem);
-    if (env->ts_dev) (void)hipFree(env->ts_dev);
-    if (env->ts_host) (void)hipHostFree(env->ts_host);
-    for (hipEvent_t e : env->ts_ev) if (e) (void)hipEventDestroy(e);
+    env->ts_table.free();
     env->track.reset();
     if (env->mask_dev) (void)hipFree(env->mask_dev);
     if (env->own_stream && env->stream) (void)hipStreamDestroy(env->stream);
@@ -1302,8 +1288,7 @@ int rc_reset(rc_env *env, const uint8_t *mask_or_null, int32_t mode, uint64_t se
     if (mask_or_null && !env->was_reset) return fail(RC_ERR_INVALID, "the first rc_reset must reset every env (mask = NULL)");
     HIP_TRY(hipSetDevice(env->cfg.device));
     env->params.reset_mode = mode;
-    env->params.seed_lo = (uint32_t)(seed & 0xffffffffu);
-    env->params.seed_hi = (uint32_t)(seed >> 32);
+    env->params.seed_lo = seed_lo(seed); env->params.seed_hi = seed_hi(seed);
     const uint8_t *mask_dev = nullptr;
     if (mask_or_null) {
         HIP_TRY(hipMemcpyAsync(env->mask_dev, mask_or_null, (size_t)env->cfg.num_envs, hipMemcpyHostToDevice, env->stream));
@@ -1311,13 +1296,12 @@ int rc_reset(rc_env *env, const uint8_t *mask_or_null, int32_t mode, uint64_t se
         HIP_TRY(hipStreamSynchronize(env->stream));
         mask_dev = env->mask_dev;
     }
-    if (env->params.ts_n > 0) {
+    const bool ts = env->params.ts_n > 0;
+    if (ts) {
         int rc = ts_sync_table(env);
         if (rc) return rc;
-        TIMED(env, RC_K_RESET, rck_launch_ts_reset(env->params, mask_dev, env->stream));
-    } else {
-        TIMED(env, RC_K_RESET, rck_launch_reset(env->params, mask_dev, env->stream));
     }
+    TIMED(env, RC_K_RESET, ts ? rck_launch_ts_reset(env->params, mask_dev, env->stream) : rck_launch_reset(env->params, mask_dev, env->stream));
     if (env->ep_on) {
         episode_bind(env);
         HIP_TRY(rck_launch_episode_reset(env->ep, mask_dev, env->stream));
@@ -1327,50 +1311,31 @@ int rc_reset(rc_env *env, const uint8_t *mask_or_null, int32_t mode, uint64_t se
     return observe(env);
 }
 
-int rc_step(rc_env *env, const float *actions_dev, int32_t repeat) {
+// One agent step of one handle: dynamics, the episode log, the observation.  With a track set the dynamics go by the env's track
+// (and the table of tracks is brought up to date first).  `actions` null: the handle's own action buffer.
+static int single_step(rc_env *env, float *actions, int32_t repeat, const RcRandomActions &ra, const char *who) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called before rc_step");
+    if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called before %s", who);
     if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
     if (repeat < 1) return fail(RC_ERR_INVALID, "repeat must be >= 1 (got %d)", repeat);
     HIP_TRY(hipSetDevice(env->cfg.device));
-    // the kernel only reads the caller's buffer (its actions pointer is written in random-action mode alone)
-    float *act = actions_dev ? const_cast<float *>(actions_dev) : env->actions_in;
-    const RcRandomActions none{0, 0u, 0u, 0u};
-    if (env->params.ts_n > 0) {
-        int rc = ts_sync_table(env);
-        if (rc) return rc;
-        TIMED(env, RC_K_DYNAMICS, rck_launch_ts_dynamics(env->params, act, repeat, none, env->stream));
-        if (env->ep_on && (rc = episode_step(env))) return rc;
-        return observe(env);
-    }
-    TIMED(env, RC_K_DYNAMICS, rck_launch_dynamics(env->params, act, repeat, none, env->stream));
-    if (env->ep_on) {
-        int rc = episode_step(env);
-        if (rc) return rc;
-    }
+    if (!actions) actions = env->actions_in;
+    const bool ts = env->params.ts_n > 0;
+    int rc = ts ? ts_sync_table(env) : RC_OK;
+    if (rc) return rc;
+    TIMED(env, RC_K_DYNAMICS, ts ? rck_launch_ts_dynamics(env->params, actions, repeat, ra, env->stream)
+                                 : rck_launch_dynamics(env->params, actions, repeat, ra, env->stream));
+    if (env->ep_on && (rc = episode_step(env))) return rc;
     return observe(env);
 }
 
+int rc_step(rc_env *env, const float *actions_dev, int32_t repeat) {
+    // the kernel only reads the caller's buffer (its actions pointer is written in random-action mode alone)
+    return single_step(env, const_cast<float *>(actions_dev), repeat, RcRandomActions{0, 0u, 0u, 0u}, "rc_step");
+}
+
 int rc_step_random(rc_env *env, uint64_t seed, uint32_t step, int32_t repeat) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called before rc_step_random");
-    if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
-    if (repeat < 1) return fail(RC_ERR_INVALID, "repeat must be >= 1 (got %d)", repeat);
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    const RcRandomActions ra{1, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), step};
-    if (env->params.ts_n > 0) {
-        int rc = ts_sync_table(env);
-        if (rc) return rc;
-        TIMED(env, RC_K_DYNAMICS, rck_launch_ts_dynamics(env->params, env->actions_in, repeat, ra, env->stream));
-        if (env->ep_on && (rc = episode_step(env))) return rc;
-        return observe(env);
-    }
-    TIMED(env, RC_K_DYNAMICS, rck_launch_dynamics(env->params, env->actions_in, repeat, ra, env->stream));
-    if (env->ep_on) {
-        int rc = episode_step(env);
-        if (rc) return rc;
-    }
-    return observe(env);
+    return single_step(env, nullptr, repeat, RcRandomActions{1, seed_lo(seed), seed_hi(seed), step}, "rc_step_random");
 }
 
 // ---- several handles, one launch per kernel --------------------------------------------------------------------------
@@ -1390,38 +1355,22 @@ static int group_step(rc_env **envs, int32_t n, const float *actions_dev, int32_
             return fail(RC_ERR_INVALID, "%s: the handles of a group have the same cars_per_env", who);
         if (e->params.ts_n > 0)
             return fail(RC_ERR_INVALID, "%s: handle %d carries a track set (rc_set_track_set), which a group launch does not", who, b);
-        if (e->launch.raycast_variant != 7 || e->launch.scan_guarded || e->launch.scan_stamps || e->compact_slab)
+        if (!on_default_scan(e) || e->compact_slab)
             return fail(RC_ERR_INVALID, "%s: handle %d runs a scan variant / validation build / uint16 copy that a group launch does not carry", who, b);
         for (int c = 0; c < b; ++c)
             if (envs[c] == e) return fail(RC_ERR_INVALID, "%s: handle %d appears twice", who, b);
     }
     HIP_TRY(hipSetDevice(lead->cfg.device));
-    for (int b = 0; b < n; ++b) {
-        // (the sort reads last step's progress: the order is a matter of locality, not of results)
-        int rc_sort = sort_cars_if_due(envs[b]);
-        if (rc_sort) return rc_sort;
-    }
-    if (!lead->group_dev) {
-        HIP_TRY(hipMalloc((void **)&lead->group_dev, sizeof(RcParams) * RC_GROUP_MAX));
-        HIP_TRY(hipHostMalloc((void **)&lead->group_host, sizeof(RcParams) * RC_GROUP_MAX * 4, hipHostMallocDefault));
-        for (hipEvent_t &ev : lead->group_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        lead->group_n = 0;
-    }
-    // the device table follows the handles' parameters in stream order: a copy is queued only when something changed (an arena
-    // re-pointed by rc_set_arena, a knob), from a pinned slot that is not rewritten before its copy has run
-    bool changed = lead->group_n != n;
-    for (int b = 0; b < n && !changed; ++b) changed = std::memcmp(&lead->group_last[b], &envs[b]->params, sizeof(RcParams)) != 0;
-    if (changed) {
-        const uint32_t slot = lead->group_slot++ & 3u;
-        HIP_TRY(hipEventSynchronize(lead->group_ev[slot]));
-        RcParams *host = lead->group_host + (size_t)slot * RC_GROUP_MAX;
-        for (int b = 0; b < n; ++b) { host[b] = envs[b]->params; lead->group_last[b] = envs[b]->params; }
-        HIP_TRY(hipMemcpyAsync(lead->group_dev, host, sizeof(RcParams) * n, hipMemcpyHostToDevice, lead->stream));
-        HIP_TRY(hipEventRecord(lead->group_ev[slot], lead->stream));
-        lead->group_n = n;
-    }
+    int rc;
+    for (int b = 0; b < n; ++b)      // (the sort reads last step's progress: the order is a matter of locality, not of results)
+        if ((rc = sort_cars_if_due(envs[b]))) return rc;
+    // the device table follows the handles' parameters (an arena re-pointed by rc_set_arena, a knob)
+    if ((rc = lead->group_table.alloc())) return rc;
+    RcParams want[RC_GROUP_MAX];
+    for (int b = 0; b < n; ++b) std::memcpy(&want[b], &envs[b]->params, sizeof(RcParams));
+    if ((rc = lead->group_table.sync(want, n, lead->stream))) return rc;
     RcGroup g{};
-    g.params = lead->group_dev;
+    g.params = lead->group_table.dev;
     g.n = n;
     // dynamics: a wave = 64 envs of one block
     int waves = 0, cars = 0;
@@ -1439,11 +1388,8 @@ static int group_step(rc_env **envs, int32_t n, const float *actions_dev, int32_
         noise |= envs[b]->params.noise_on != 0;
     }
     TIMED(lead, RC_K_DYNAMICS, rck_launch_dynamics_group(g, lead->cfg.cars_per_env, repeat, ra, lead->stream, dr));
-    for (int b = 0; b < n; ++b)
-        if (envs[b]->ep_on) {             // each handle keeps its own log
-            int rc_ep = episode_step(envs[b]);
-            if (rc_ep) return rc_ep;
-        }
+    for (int b = 0; b < n; ++b)           // each handle keeps its own log
+        if (envs[b]->ep_on && (rc = episode_step(envs[b]))) return rc;
     // scan: a wave = one car (or 1 / split of one); the split follows the group's total, as one handle of that size would
     int split = lead->dbg[RC_DBG_RAY_SPLIT];
     if (split < 1 || split > 17) split = scan_split(cars, lead->launch.n_cu);
@@ -1455,25 +1401,17 @@ static int group_step(rc_env **envs, int32_t n, const float *actions_dev, int32_
     g.wave_start[n] = waves;
     TIMED(lead, RC_K_RAYCAST, rck_launch_raycast_group(g, lead->cfg.cars_per_env, split, lead->stream, noise));
     for (int b = 0; b < n; ++b) envs[b]->last_scan_rows = envs[b]->params.out.lidar;
-    for (int b = 0; b < n; ++b) {
-        if (envs[b]->params.render_patch)
-            TIMED(envs[b], RC_K_PATCH, rck_launch_patch(envs[b]->params, envs[b]->launch, envs[b]->stream));
-        if (envs[b]->cfg.obs_type == RC_OBS_LIDAR_OCCUPANCY_REFERENCE) {
-            int rc_px = render_reference_patches(envs[b]);
-            if (rc_px) return rc_px;
-        }
-    }
+    for (int b = 0; b < n; ++b)
+        if ((rc = render_patches(envs[b]))) return rc;
     return RC_OK;
 }
 
 int rc_step_group(rc_env **envs, int32_t n, const float *actions_dev, int32_t repeat) {
-    const RcRandomActions none{0, 0u, 0u, 0u};
-    return group_step(envs, n, actions_dev, repeat, none, "rc_step_group");
+    return group_step(envs, n, actions_dev, repeat, RcRandomActions{0, 0u, 0u, 0u}, "rc_step_group");
 }
 
 int rc_step_random_group(rc_env **envs, int32_t n, uint64_t seed, uint32_t step, int32_t repeat) {
-    const RcRandomActions ra{1, (uint32_t)(seed & 0xffffffffu), (uint32_t)(seed >> 32), step};
-    return group_step(envs, n, nullptr, repeat, ra, "rc_step_random_group");
+    return group_step(envs, n, nullptr, repeat, RcRandomActions{1, seed_lo(seed), seed_hi(seed), step}, "rc_step_random_group");
 }
 
 // ---- domain randomization ------------------------------------------------------------------------------------------------
@@ -1488,8 +1426,8 @@ int rc_set_vehicle_randomization(rc_env *env, const float *lo, const float *hi, 
         if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || lo[i] > hi[i])
             return fail(RC_ERR_INVALID, "vehicle randomization: parameter %d needs finite lo <= hi (got %g, %g)", i, (double)lo[i], (double)hi[i]);
     for (int i = 0; i < RC_VP_COUNT; ++i) { env->params.vp_lo[i] = lo[i]; env->params.vp_hi[i] = hi[i]; }
-    env->params.vp_seed_lo = (uint32_t)(seed & 0xffffffffu);
-    env->params.vp_seed_hi = (uint32_t)(seed >> 32);
+    env->params.vp_seed_lo = seed_lo(seed);
+    env->params.vp_seed_hi = seed_hi(seed);
     env->params.vp_mode = RC_VP_RANDOM;
     return RC_OK;
 }
@@ -1522,8 +1460,8 @@ int rc_set_lidar_noise(rc_env *env, float sigma, float p_drop, uint64_t seed) {
     const float z_scale = RC_NOISE_Z_SCALE;
     p.noise_scale = sigma * z_scale;                                     // one binary32 rounding
     p.noise_drop = (uint32_t)std::floor((double)p_drop * 65536.0 + 0.5);   // 0 .. 65536
-    p.noise_seed_lo = (uint32_t)(seed & 0xffffffffu);
-    p.noise_seed_hi = (uint32_t)(seed >> 32);
+    p.noise_seed_lo = seed_lo(seed);
+    p.noise_seed_hi = seed_hi(seed);
     return RC_OK;
 }
 
@@ -1535,7 +1473,7 @@ int rc_set_track_set(rc_env *env, rc_env *const *tracks, int32_t n, int32_t orde
     if (n == 0) {                                         // off: the production kernels again
         env->params.ts_n = 0;
         env->ts_src.clear();
-        env->ts_table_valid = false;
+        env->ts_table.n = 0;
         return RC_OK;
     }
     if (n < 1 || n > RC_TS_MAX) return fail(RC_ERR_INVALID, "track set: 1 <= n <= %d tracks (got %d)", RC_TS_MAX, n);
@@ -1586,10 +1524,9 @@ int rc_set_track_set(rc_env *env, rc_env *const *tracks, int32_t n, int32_t orde
         const size_t bytes = (size_t)B * 4 * 2 + (size_t)env->n_cars * 4 + (3 * RC_TS_MAX + 1) * 4 + (size_t)B;
         HIP_TRY(hipMalloc(&env->ts_mem, bytes));
         HIP_TRY(hipMemsetAsync(env->ts_mem, 0, bytes, env->stream));
-        HIP_TRY(hipMalloc((void **)&env->ts_dev, sizeof(RcParams) * RC_TS_MAX));
-        HIP_TRY(hipHostMalloc((void **)&env->ts_host, sizeof(RcParams) * RC_TS_MAX * 4, hipHostMallocDefault));
-        for (hipEvent_t &ev : env->ts_ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     }
+    int rc_table = env->ts_table.alloc();
+    if (rc_table) return rc_table;
     RcParams &p = env->params;
     int32_t *base = (int32_t *)env->ts_mem;
     p.ts_track = base;
@@ -1617,14 +1554,14 @@ int rc_set_track_set(rc_env *env, rc_env *const *tracks, int32_t n, int32_t orde
         HIP_TRY(rck_set_ts_lds_limit(lds));
     }
     env->ts_patch_lds = lds;
-    p.ts_table = env->ts_dev;
+    p.ts_table = env->ts_table.dev;
     p.ts_order = order;
     p.ts_weighted = weighted;
     for (int k = 0; k < RC_TS_MAX; ++k) p.ts_cum[k] = cum[k];
-    p.ts_seed_lo = (uint32_t)(seed & 0xffffffffu);
-    p.ts_seed_hi = (uint32_t)(seed >> 32);
+    p.ts_seed_lo = seed_lo(seed);
+    p.ts_seed_hi = seed_hi(seed);
     p.ts_n = n;
-    env->ts_table_valid = false;
+    env->ts_table.n = 0;
     return RC_OK;
 }
 
@@ -1700,8 +1637,6 @@ int rc_episode_log_disable(rc_env *env) {
     if (!env->ep_mem) return RC_OK;
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(hipStreamSynchronize(env->stream));
-    int rc = episode_drain(env);
-    if (rc) return rc;
     HIP_TRY(hipFree(env->ep_mem));
     env->ep_mem = nullptr;
     if (env->ep_rows) HIP_TRY(hipFree(env->ep_rows));
@@ -1735,11 +1670,10 @@ int rc_episode_log_clear(rc_env *env) {
 
 int rc_episode_log_time(rc_env *env, double *total_ms, uint64_t *launches) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    int rc = episode_drain(env);
+    int rc = drain_events(env);
     if (rc) return rc;
-    if (total_ms) *total_ms = env->ep_ms;
-    if (launches) *launches = env->ep_n;
+    if (total_ms) *total_ms = env->k_ms[kTimeEpisodeLog];
+    if (launches) *launches = env->k_n[kTimeEpisodeLog];
     return RC_OK;
 }
 
@@ -1939,8 +1873,7 @@ int rc_fill_random_actions(rc_env *env, uint64_t seed, uint32_t step) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
     HIP_TRY(hipSetDevice(env->cfg.device));
     const uint32_t first_car = env->params.first_env * (uint32_t)env->cfg.cars_per_env;
-    TIMED(env, RC_K_ACTIONS, rck_launch_random_actions(env->actions_in, env->n_cars, first_car, (uint32_t)(seed & 0xffffffffu),
-                                                       (uint32_t)(seed >> 32), step, env->stream));
+    TIMED(env, RC_K_ACTIONS, rck_launch_random_actions(env->actions_in, env->n_cars, first_car, seed_lo(seed), seed_hi(seed), step, env->stream));
     return RC_OK;
 }
 
@@ -1975,37 +1908,58 @@ int rc_trajectory_slab(rc_env *env, void **dev_ptr, size_t *bytes) {
     return RC_OK;
 }
 
+namespace {
+// The field table of a row gather: for every field of the mask, in field order, where its section starts in an arena, where its
+// rows go in the output (sections of `n_rows` rows, 64-byte aligned) and its bytes per car; `total` is the output's size.
+// `bad` is the first field of the mask that a recorded arena of this configuration does not hold (the action input buffer, a
+// section that is off), or -1: such a mask is refused by every caller but rc_gather_rows_bytes, which has no error to return.
+struct GatherFields {
+    size_t src[RC_GATHER_MAX_FIELDS], dst[RC_GATHER_MAX_FIELDS], total;
+    uint32_t bpc[RC_GATHER_MAX_FIELDS];
+    int field[RC_GATHER_MAX_FIELDS], n, bad;
+};
+GatherFields gather_fields(const rc_env *env, uint32_t field_mask, size_t n_rows) {
+    GatherFields g{};
+    g.bad = -1;
+    for (int f = 0; f < RC_F_COUNT; ++f) {
+        if (!((field_mask >> f) & 1u)) continue;
+        if ((f == RC_F_ACTION_IN || !env->layout.bytes[f]) && g.bad < 0) g.bad = f;
+        if (!env->layout.bytes[f]) continue;
+        g.field[g.n] = f; g.src[g.n] = env->layout.offset[f]; g.dst[g.n] = g.total; g.bpc[g.n] = (uint32_t)kFieldBytes[f];
+        g.total = align_up(g.total + kFieldBytes[f] * n_rows, 64);
+        ++g.n;
+    }
+    return g;
+}
+
+// what rc_gather_rows and rc_sample_windows ask of a ring of recorded arenas
+int check_ring(const rc_env *env, const void *ring_base, size_t slot_bytes, const char *who) {
+    if (slot_bytes < env->layout.total) return fail(RC_ERR_INVALID, "slot_bytes %zu is smaller than an arena (%zu)", slot_bytes, env->layout.total);
+    // (the row gather moves 16 bytes per lane: every slot must start as rc_set_arena demands of an arena)
+    if (((uintptr_t)ring_base & 63u) != 0 || (slot_bytes & 63u) != 0)
+        return fail(RC_ERR_INVALID, "ring_base (%p) and slot_bytes (%zu) must be multiples of 64", ring_base, slot_bytes);
+    if (env->shared_arena) return fail(RC_ERR_INVALID, "%s works on whole arenas, not on a slice handle", who);
+    return RC_OK;
+}
+}  // namespace
+
 size_t rc_gather_rows_bytes(rc_env *env, uint32_t field_mask, int32_t n_rows) {
     if (!env || n_rows < 1) return 0;
-    size_t off = 0;
-    for (int f = 0; f < RC_F_COUNT; ++f)
-        if (((field_mask >> f) & 1u) && env->layout.bytes[f]) off = align_up(off + kFieldBytes[f] * (size_t)n_rows, 64);
-    return off;
+    return gather_fields(env, field_mask, (size_t)n_rows).total;
 }
 
 int rc_gather_rows(rc_env *env, const void *ring_base, size_t slot_bytes, const int32_t *slot_idx_dev, const int32_t *car_idx_dev,
                    int32_t n_rows, uint32_t field_mask, void *out_dev, size_t out_bytes) {
     if (!env || !ring_base || !slot_idx_dev || !car_idx_dev || !out_dev) return fail(RC_ERR_INVALID, "NULL argument");
     if (n_rows < 1) return fail(RC_ERR_INVALID, "n_rows must be >= 1");
-    if (slot_bytes < env->layout.total) return fail(RC_ERR_INVALID, "slot_bytes %zu is smaller than an arena (%zu)", slot_bytes, env->layout.total);
-    // (the row gather moves 16 bytes per lane: every slot must start as rc_set_arena demands of an arena)
-    if (((uintptr_t)ring_base & 63u) != 0 || (slot_bytes & 63u) != 0)
-        return fail(RC_ERR_INVALID, "ring_base (%p) and slot_bytes (%zu) must be multiples of 64", ring_base, slot_bytes);
-    if (env->shared_arena) return fail(RC_ERR_INVALID, "rc_gather_rows works on whole arenas, not on a slice handle");
-    size_t src[RC_GATHER_MAX_FIELDS], dst[RC_GATHER_MAX_FIELDS], off = 0;
-    uint32_t bpc[RC_GATHER_MAX_FIELDS];
-    int n = 0;
-    for (int f = 0; f < RC_F_COUNT; ++f) {
-        if (!((field_mask >> f) & 1u)) continue;
-        if (f == RC_F_ACTION_IN || !env->layout.bytes[f]) return fail(RC_ERR_INVALID, "field %d is not part of a recorded arena in this configuration", f);
-        src[n] = env->layout.offset[f]; dst[n] = off; bpc[n] = (uint32_t)kFieldBytes[f];
-        off = align_up(off + kFieldBytes[f] * (size_t)n_rows, 64);
-        ++n;
-    }
-    if (n == 0) return fail(RC_ERR_INVALID, "empty field mask");
-    if (out_bytes < off) return fail(RC_ERR_INVALID, "output too small: %zu < %zu", out_bytes, off);
+    int rc = check_ring(env, ring_base, slot_bytes, "rc_gather_rows");
+    if (rc) return rc;
+    const GatherFields g = gather_fields(env, field_mask, (size_t)n_rows);
+    if (g.bad >= 0) return fail(RC_ERR_INVALID, "field %d is not part of a recorded arena in this configuration", g.bad);
+    if (g.n == 0) return fail(RC_ERR_INVALID, "empty field mask");
+    if (out_bytes < g.total) return fail(RC_ERR_INVALID, "output too small: %zu < %zu", out_bytes, g.total);
     HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(rck_gather_rows(ring_base, slot_bytes, slot_idx_dev, car_idx_dev, n_rows, src, dst, bpc, n, out_dev, env->stream));
+    HIP_TRY(rck_gather_rows(ring_base, slot_bytes, slot_idx_dev, car_idx_dev, n_rows, g.src, g.dst, g.bpc, g.n, out_dev, env->stream));
     return RC_OK;
 }
 
@@ -2013,11 +1967,8 @@ int rc_sample_windows(rc_env *env, const void *ring_base, size_t slot_bytes, int
                       int32_t length, int32_t n_windows, uint64_t seed, uint32_t draw, int32_t max_tries, int32_t *slot_idx_dev,
                       int32_t *slot_obs_idx_dev, int32_t *car_idx_dev, int32_t *meta_dev, uint32_t *failed_dev) {
     if (!env || !ring_base || !slot_idx_dev || !slot_obs_idx_dev || !car_idx_dev || !meta_dev || !failed_dev) return fail(RC_ERR_INVALID, "NULL argument");
-    if (slot_bytes < env->layout.total) return fail(RC_ERR_INVALID, "slot_bytes %zu is smaller than an arena (%zu)", slot_bytes, env->layout.total);
-    // (the row gather moves 16 bytes per lane: every slot must start as rc_set_arena demands of an arena)
-    if (((uintptr_t)ring_base & 63u) != 0 || (slot_bytes & 63u) != 0)
-        return fail(RC_ERR_INVALID, "ring_base (%p) and slot_bytes (%zu) must be multiples of 64", ring_base, slot_bytes);
-    if (env->shared_arena) return fail(RC_ERR_INVALID, "rc_sample_windows works on whole arenas, not on a slice handle");
+    int rc = check_ring(env, ring_base, slot_bytes, "rc_sample_windows");
+    if (rc) return rc;
     if (capacity < 1 || oldest < 0 || oldest >= capacity || count < 1 || count > capacity) return fail(RC_ERR_INVALID, "ring of %d slots, oldest %d, %d filled", capacity, oldest, count);
     if (length < 1 || length > count) return fail(RC_ERR_INVALID, "a window of %d records does not fit the %d records of the ring", length, count);
     if (n_windows < 1 || max_tries < 1) return fail(RC_ERR_INVALID, "n_windows and max_tries must be >= 1");
@@ -2026,7 +1977,7 @@ int rc_sample_windows(rc_env *env, const void *ring_base, size_t slot_bytes, int
     a.fresh_off = env->layout.offset[RC_F_FRESH]; a.done_off = env->layout.offset[RC_F_DONE];
     a.capacity = capacity; a.oldest = oldest; a.n_start = count - length + 1; a.length = length; a.n_windows = n_windows;
     a.n_cars = env->n_cars; a.max_tries = max_tries;
-    a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.draw = draw;
+    a.seed_lo = seed_lo(seed); a.seed_hi = seed_hi(seed); a.draw = draw;
     a.slot_idx = slot_idx_dev; a.slot_obs_idx = slot_obs_idx_dev; a.car_idx = car_idx_dev; a.meta = meta_dev; a.failed = failed_dev;
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(rck_sample_windows(a, env->stream));
@@ -2036,16 +1987,12 @@ int rc_sample_windows(rc_env *env, const void *ring_base, size_t slot_bytes, int
 // One training batch as ONE packed buffer: field sections (64-byte aligned, field order), meta, the failure counter - the
 // payload a sharded replay store exchanges - then the sampler's row indices (scratch).
 namespace {
-struct BatchLayout { size_t field_off[RC_F_COUNT]; size_t meta, failed, payload, slot, slot_obs, car, total; };
+struct BatchLayout { GatherFields fields; size_t meta, failed, payload, slot, slot_obs, car, total; };
 bool batch_layout(const rc_env *env, uint32_t field_mask, int32_t n_windows, int32_t length, BatchLayout *bl) {
     const size_t rows = (size_t)n_windows * (size_t)length;
-    size_t off = 0;
-    for (int f = 0; f < RC_F_COUNT; ++f) {
-        bl->field_off[f] = off;
-        if (!((field_mask >> f) & 1u)) continue;
-        if (f == RC_F_ACTION_IN || !env->layout.bytes[f]) return false;
-        off = align_up(off + kFieldBytes[f] * rows, 64);
-    }
+    bl->fields = gather_fields(env, field_mask, rows);
+    if (bl->fields.bad >= 0) return false;
+    size_t off = bl->fields.total;
     bl->meta = off;     off = align_up(off + 16u * (size_t)n_windows, 64);
     bl->failed = off;   off += 64;
     bl->payload = off;
@@ -2086,24 +2033,20 @@ int rc_sample_batch(rc_env *env, const void *ring_base, size_t slot_bytes, int32
     // the observation part of a record: what a terminal row borrows from the row before it
     const uint32_t obs_fields = (1u << RC_F_LIDAR) | (1u << RC_F_OCCUPANCY) | (1u << RC_F_POSE) | (1u << RC_F_VELOCITY) | (1u << RC_F_SPEED) |
                                 (1u << RC_F_ACCELERATION) | (1u << RC_F_STEERING_ANGLE);
-    size_t src[RC_GATHER_MAX_FIELDS], dst[RC_GATHER_MAX_FIELDS];
-    uint32_t bpc[RC_GATHER_MAX_FIELDS];
+    const GatherFields &g = bl.fields;
     RcBatchRows br{};
     br.slot_obs_idx = (const int32_t *)(out + bl.slot_obs); br.meta = (const int32_t *)(out + bl.meta); br.length = length;
-    int n = 0;
-    for (int f = 0; f < RC_F_COUNT; ++f) {
-        if (!((field_mask >> f) & 1u)) continue;
-        src[n] = env->layout.offset[f]; dst[n] = bl.field_off[f]; bpc[n] = (uint32_t)kFieldBytes[f];
-        if ((obs_fields >> f) & 1u) br.obs_mask |= 1u << n;
+    for (int i = 0; i < g.n; ++i) {
+        const int f = g.field[i];
+        if ((obs_fields >> f) & 1u) br.obs_mask |= 1u << i;
         if (reset_rows && (f == RC_F_ACTION || f == RC_F_REWARD || f == RC_F_DISCOUNT || f == RC_F_TIME || f == RC_F_PROGRESS_TOTAL)) {
             const float v = f == RC_F_DISCOUNT ? 1.0f : (f == RC_F_PROGRESS_TOTAL ? -1.0f : 0.0f);
-            br.reset_mask |= 1u << n;
-            std::memcpy(&br.reset_word[n], &v, 4);
+            br.reset_mask |= 1u << i;
+            std::memcpy(&br.reset_word[i], &v, 4);
         }
-        ++n;
     }
     HIP_TRY(rck_gather_rows(ring_base, slot_bytes, (const int32_t *)(out + bl.slot), (const int32_t *)(out + bl.car), n_windows * length,
-                            src, dst, bpc, n, out, env->stream, &br));
+                            g.src, g.dst, g.bpc, g.n, out, env->stream, &br));
     return RC_OK;
 }
 
@@ -2154,11 +2097,7 @@ int rc_reset_kernel_times(rc_env *env) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
     int rc = drain_events(env);
     if (rc) return rc;
-    for (int k = 0; k < RC_K_COUNT; ++k) { env->k_ms[k] = 0; env->k_n[k] = 0; }
-    rc = episode_drain(env);
-    if (rc) return rc;
-    env->ep_ms = 0.0;
-    env->ep_n = 0;
+    for (int k = 0; k <= RC_K_COUNT; ++k) { env->k_ms[k] = 0; env->k_n[k] = 0; }      // (the episode log's accumulator with them)
     return RC_OK;
 }
 
@@ -2571,7 +2510,7 @@ int rc_scan_kernel_name(rc_env *env, char *out, size_t bytes) {
     if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called first");
     const RcLaunchInfo &li = env->launch;
     const int a = env->cfg.cars_per_env;
-    if (env->params.ts_n > 0 && li.raycast_variant == 7 && !li.scan_guarded && !li.scan_stamps)
+    if (env->params.ts_n > 0 && on_default_scan(env))
         snprintf(out, bytes, "rc_raycast_ts_kernel<%d, %s, %s>", a, li.car_split > 1 ? "true" : "false", env->params.noise_on ? "true" : "false");
     else if (li.raycast_variant != 7) snprintf(out, bytes, "rc_raycast_kernel<%d, %d>", a, li.raycast_variant);
     else if (li.scan_stamps != nullptr && a == 1) snprintf(out, bytes, "rc_raycast_car_stamps_kernel");
