@@ -10,8 +10,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libracecar_hip.so")
-SOURCES = ["racecar_kernels.hip", "racecar_abi.hip", "racecar_policy.hip", "racecar_episode.hip"]
-HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_spec.h", "racecar_scan.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", "racecar_episode.h", os.path.join("..", "..", "include", "racecar_hip.h")]
+# one unit per subsystem ("where things live"); SCAN_SOURCE holds the scan kernels that verify_scan_assembly reads
+SCAN_SOURCE = "racecar_kernels.hip"
+SOURCES = [SCAN_SOURCE, "racecar_tracks.hip", "racecar_agents.hip", "racecar_gather.hip", "racecar_abi.hip", "racecar_policy.hip", "racecar_episode.hip"]
+HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_env.h", "racecar_car.h", "racecar_spec.h", "racecar_scan.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", "racecar_episode.h", os.path.join("..", "..", "include", "racecar_hip.h")]
 # The lab library: scan variants 0-6 and the instrumented build of the scan (racecar_lab.hip).  NOT part of the shipped
 # library; built by build_lab() - which tools/ and the variant tests call - and loaded by libracecar_hip.so on first use.
 LAB_PATH = os.path.join(LIB_DIR, "libracecar_lab.so")
@@ -21,8 +23,9 @@ LAB_SOURCES = ["racecar_lab.hip"]
 # -fno-slp-vectorize: packed fp32 (v_pk_*_f32) issues at half rate on gfx950, i.e. buys nothing over two scalar
 # operations, and costs register-pair copies, explicit |x| / -x operands and wait states (tools/ubench/valu_issue4.hip);
 # the places where a packed form does help are written as explicit vector types.
+# -fvisibility=hidden: the libraries export their C interface (rc_*, rclab_*: declared under a visibility pragma) and nothing else.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17", "-Wall",
-         "-Wno-unused-function"]
+         "-Wno-unused-function", "-fvisibility=hidden"]
 
 
 def find_hipcc() -> str:
@@ -89,19 +92,34 @@ def needs_build(lib_path: str = LIB_PATH, csrc: str = CSRC) -> bool:
 
 
 # Kernels that hand a register to an asynchronous load through inline assembly and wait for it in a LATER assembly
-# statement (the scan's table request, racecar_kernels.hip: trip_head / trip_tail): between the two the compiler believes
+# statement (the scan's table request, racecar_scan.h: trip_head / trip_tail): between the two the compiler believes
 # the value is there.  That is safe as long as it keeps the value where the load will write it - it does not copy a live
 # register without need - but a spill of that register to scratch would store it BEFORE the load has landed.  So the build
 # refuses a library in which one of these kernels spills or uses scratch at all, and one that has fallen below the
 # occupancy the launch geometry assumes.
-NO_SPILL_KERNELS = ("rc_raycast_car_kernel", "rc_raycast_car_stamps_kernel", "rc_raycast_kernel", "rc_patch_car_kernel",
-                    "rc_patch_exact_prefilter_kernel", "rc_patch_exact_sample_kernel",
-                    "rc_raycast_car_noise_kernel", "rc_raycast_group_noise_kernel",     # (the scan with LiDAR noise: same trip loop)
-                    "rc_raycast_ts_kernel", "rc_patch_ts_kernel",                        # (a track set: the same scan and render)
-                    "rc_policy_kernel")     # (the Dreamer agent: 4 to 6 MFMA accumulator tiles per wave - a spill would sit in its k loops)
-# (the exact prefilter holds a line per lane in 161 + registers: one wave per SIMD by design - what it must not do is spill)
-MIN_WAVES_PER_SIMD = {"rc_raycast_car_kernel": 8, "rc_patch_car_kernel": 8, "rc_patch_exact_sample_kernel": 4, "rc_raycast_car_noise_kernel": 8,
-                      "rc_raycast_ts_kernel": 8, "rc_patch_ts_kernel": 8}
+# One row per checked kernel: (name, minimum waves per SIMD or None, its in-flight loads are checked, the library that must
+# show it: "shipped" | "lab" | None).  Every row is a no-spill kernel.
+CHECKED_KERNELS = (
+    ("rc_raycast_car_kernel", 8, True, "shipped"),
+    ("rc_raycast_car_stamps_kernel", None, True, "lab"),
+    ("rc_raycast_kernel", None, True, "lab"),
+    ("rc_patch_car_kernel", 8, False, "shipped"),
+    # (the exact prefilter holds a line per lane in 161 + registers: one wave per SIMD by design - what it must not do is spill)
+    ("rc_patch_exact_prefilter_kernel", None, False, "shipped"),
+    ("rc_patch_exact_sample_kernel", 4, False, "shipped"),
+    ("rc_raycast_car_noise_kernel", 8, True, "shipped"),        # (the scan with LiDAR noise: same trip loop)
+    ("rc_raycast_group_noise_kernel", None, True, "shipped"),
+    ("rc_raycast_ts_kernel", 8, True, "shipped"),               # (a track set: the same scan and render)
+    ("rc_patch_ts_kernel", 8, False, "shipped"),
+    ("rc_policy_kernel", None, False, "shipped"),               # (the Dreamer agent: 4 to 6 MFMA accumulator tiles per wave - a spill would sit in its k loops)
+)
+NO_SPILL_KERNELS = tuple(k for k, _, _, _ in CHECKED_KERNELS)
+MIN_WAVES_PER_SIMD = {k: w for k, w, _, _ in CHECKED_KERNELS if w is not None}
+ASYNC_LOAD_KERNELS = tuple(k for k, _, load, _ in CHECKED_KERNELS if load)
+
+
+def required_kernels(library: str):
+    return tuple(k for k, _, _, lib in CHECKED_KERNELS if lib == library)
 
 
 def check_resource_usage(remarks: str, required=("rc_raycast_car_kernel", "rc_patch_car_kernel"), min_waves=None) -> None:
@@ -134,9 +152,7 @@ def check_resource_usage(remarks: str, required=("rc_raycast_car_kernel", "rc_pa
         raise RuntimeError("build refused (see racing_dreamer_amd/build.py, NO_SPILL_KERNELS):\n  " + "\n  ".join(problems))
 
 
-def check_async_load_registers(asm_text: str, kernels=("rc_raycast_car_kernel", "rc_raycast_car_stamps_kernel", "rc_raycast_kernel",
-                                                       "rc_raycast_car_noise_kernel", "rc_raycast_group_noise_kernel",
-                                                       "rc_raycast_ts_kernel")) -> int:
+def check_async_load_registers(asm_text: str, kernels=ASYNC_LOAD_KERNELS) -> int:
     """The scan requests a table entry with an inline-assembly `global_load_ushort` and waits for it in a LATER statement
     (`s_waitcnt vmcnt(0)`): until then the destination register is not the compiler's to read, copy or overwrite, and
     nothing tells it so.  This walks the generated assembly of the scan kernels and raises if any instruction between such
@@ -192,12 +208,12 @@ def check_async_load_registers(asm_text: str, kernels=("rc_raycast_car_kernel", 
 
 
 def verify_scan_assembly(verbose: bool = True, csrc: str = CSRC, source: str = None) -> int:
-    """Compile the kernels to assembly once more (device only) and run check_async_load_registers on it."""
+    """Compile the unit that holds the scan kernels to assembly once more (device only) and run check_async_load_registers on it."""
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "kernels.s")
         flags = [f for f in FLAGS if f not in ("-fPIC", "-shared")]
-        cmd = [find_hipcc(), *flags, "-S", "--cuda-device-only", os.path.join(csrc, source or SOURCES[0]), "-o", out]
+        cmd = [find_hipcc(), *flags, "-S", "--cuda-device-only", os.path.join(csrc, source or SCAN_SOURCE), "-o", out]
         r = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
         if r.returncode != 0:
             sys.stderr.write(r.stderr[-4000:])
@@ -212,21 +228,17 @@ def verify_scan_assembly(verbose: bool = True, csrc: str = CSRC, source: str = N
 LAST_BUILD = {"action": None, "build_id": None}      # what the last build() call did: "compiled" | "reused"
 
 
-def build(force: bool = False, verbose: bool = True, csrc: str = CSRC, lib_path: str = LIB_PATH) -> str:
-    """Compile `csrc` into `lib_path` unless the library there already carries the hash of those sources and the flags
-    (`LAST_BUILD["action"]` says which happened).  The defaults are the package's own tree; the tests build copies."""
-    want = source_hash(csrc)
-    LAST_BUILD.update(action="reused", build_id=want)
-    if not force and library_build_id(lib_path) == want:
-        if verbose:
-            print(f"[racing_dreamer_amd.build] reused {lib_path}: its build id {want} is the hash of the sources and flags", flush=True)
-        return lib_path
-    os.makedirs(os.path.dirname(lib_path), exist_ok=True)
-    tmp = _tmp_beside(lib_path)
+def _compile(what: str, sources, want: str, out_path: str, csrc: str, verbose: bool, required, min_waves, scan_source: str) -> None:
+    """One hipcc command over `sources` into `out_path` (through a temporary beside it), refused if a checked kernel spills, has
+    fallen below its occupancy or touches a register under an asynchronous load."""
+    import time
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    tmp = _tmp_beside(out_path)
     cmd = [find_hipcc(), *FLAGS, f'-DRC_BUILD_ID="{want}"', f'-DRC_HEADERS_ID="{headers_hash(csrc)}"', "-Rpass-analysis=kernel-resource-usage",
-           *[os.path.join(csrc, s) for s in SOURCES], "-o", tmp]
+           *[os.path.join(csrc, s) for s in sources], "-o", tmp]
     if verbose:
         print("[racing_dreamer_amd.build]", " ".join(cmd), flush=True)
+    t0 = time.time()
     r = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
     other = [l for l in r.stderr.splitlines() if "kernel-resource-usage" not in l and not l.startswith(("      |", " ")) and "hip-link" not in l]
     if r.returncode != 0:
@@ -237,56 +249,42 @@ def build(force: bool = False, verbose: bool = True, csrc: str = CSRC, lib_path:
     if other and verbose:
         print("\n".join(other), file=sys.stderr)
     try:
-        check_resource_usage(r.stderr, required=("rc_raycast_car_kernel", "rc_patch_car_kernel", "rc_patch_exact_prefilter_kernel",
-                                                 "rc_patch_exact_sample_kernel", "rc_raycast_car_noise_kernel",
-                                                 "rc_raycast_group_noise_kernel", "rc_raycast_ts_kernel", "rc_patch_ts_kernel",
-                                                 "rc_policy_kernel"))
-        verify_scan_assembly(verbose, csrc)
+        check_resource_usage(r.stderr, required=required, min_waves=min_waves)
+        verify_scan_assembly(verbose, csrc, source=scan_source)
     except RuntimeError:
         os.remove(tmp)
         raise
     os.chmod(tmp, 0o755)
-    os.replace(tmp, lib_path)
-    LAST_BUILD.update(action="compiled")
-    if library_build_id(lib_path) != want:
-        raise RuntimeError(f"{lib_path} does not carry the build id it was compiled with ({library_build_id(lib_path)} != {want})")
+    os.replace(tmp, out_path)
+    if library_build_id(out_path) != want:
+        raise RuntimeError(f"{out_path} does not carry the build id it was compiled with ({library_build_id(out_path)} != {want})")
     if verbose:
-        print(f"[racing_dreamer_amd.build] compiled {lib_path} (build id {want})", flush=True)
+        print(f"[racing_dreamer_amd.build] compiled {out_path} in {time.time() - t0:.1f} s ({what}, build id {want})", flush=True)
+
+
+def build(force: bool = False, verbose: bool = True, csrc: str = CSRC, lib_path: str = LIB_PATH) -> str:
+    """Compile `csrc` into `lib_path` unless the library there already carries the hash of those sources and the flags
+    (`LAST_BUILD["action"]` says which happened).  The defaults are the package's own tree; the tests build copies."""
+    want = source_hash(csrc)
+    LAST_BUILD.update(action="reused", build_id=want)
+    if not force and library_build_id(lib_path) == want:
+        if verbose:
+            print(f"[racing_dreamer_amd.build] reused {lib_path}: its build id {want} is the hash of the sources and flags", flush=True)
+        return lib_path
+    _compile("the shipped library", SOURCES, want, lib_path, csrc, verbose, required_kernels("shipped"), None, SCAN_SOURCE)
+    LAST_BUILD.update(action="compiled")
     return lib_path
 
 
 def build_lab(force: bool = False, verbose: bool = True, csrc: str = CSRC, lab_path: str = LAB_PATH) -> str:
     """Compile the lab library (scan variants 0-6, the stamps build) unless the one at `lab_path` already carries the hash of
     its sources: same flags, same refusals (no spills in a scan kernel, no register touched under an asynchronous load)."""
-    import time
     want = source_hash(csrc, sources=LAB_SOURCES)
     if not force and library_build_id(lab_path) == want:
         if verbose:
             print(f"[racing_dreamer_amd.build] reused {lab_path}: its build id {want} is the hash of the lab's sources and flags", flush=True)
         return lab_path
-    os.makedirs(os.path.dirname(lab_path), exist_ok=True)
-    tmp = _tmp_beside(lab_path)
-    cmd = [find_hipcc(), *FLAGS, f'-DRC_BUILD_ID="{want}"', f'-DRC_HEADERS_ID="{headers_hash(csrc)}"', "-Rpass-analysis=kernel-resource-usage",
-           *[os.path.join(csrc, s) for s in LAB_SOURCES], "-o", tmp]
-    if verbose:
-        print("[racing_dreamer_amd.build]", " ".join(cmd), flush=True)
-    t0 = time.time()
-    r = subprocess.run(cmd, cwd=csrc, capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stderr[-8000:])
-        if os.path.exists(tmp):
-            os.remove(tmp)
-        raise subprocess.CalledProcessError(r.returncode, cmd)
-    try:
-        check_resource_usage(r.stderr, required=("rc_raycast_car_stamps_kernel", "rc_raycast_kernel"), min_waves={})
-        verify_scan_assembly(verbose, csrc, source=LAB_SOURCES[0])
-    except RuntimeError:
-        os.remove(tmp)
-        raise
-    os.chmod(tmp, 0o755)
-    os.replace(tmp, lab_path)
-    if verbose:
-        print(f"[racing_dreamer_amd.build] compiled {lab_path} in {time.time() - t0:.1f} s (build id {want})", flush=True)
+    _compile("the lab library", LAB_SOURCES, want, lab_path, csrc, verbose, required_kernels("lab"), {}, LAB_SOURCES[0])
     return lab_path
 
 

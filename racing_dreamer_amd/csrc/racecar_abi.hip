@@ -18,15 +18,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/racecar_hip.h"
-#include "racecar_internal.h"
-#include "racecar_policy.h"
-#include "racecar_episode.h"
+#include "racecar_env.h"
 #include "racecar_spec.h"
 
 namespace {
 
 thread_local std::string g_last_error;
+
+}  // namespace
 
 int fail(int code, const char *fmt, ...) {
     char buf[512];
@@ -38,101 +37,8 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t _e = (expr);                                                                    \
-        if (_e != hipSuccess)                                                                      \
-            return fail(RC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
+namespace {
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-uint32_t seed_lo(uint64_t seed) { return (uint32_t)(seed & 0xffffffffu); }      // the halves the kernels' Philox keys take
-uint32_t seed_hi(uint64_t seed) { return (uint32_t)(seed >> 32); }
-
-struct RcUid { char internal[128]; };      // ncclUniqueId (rccl.h: NCCL_UNIQUE_ID_BYTES = 128), passed by value
-
-// bytes per car of every rc_field, in arena order
-const size_t kFieldBytes[RC_F_COUNT] = {
-    RC_N_BEAMS * 4, 24, 24, 4, 8, 4, 4, 4, 4, RC_PATCH * RC_PATCH,   // LIDAR .. OCCUPANCY
-    4, 4, 4, 1, 1, 1, 1, 1, 1, 4, 4, 8,                               // PROGRESS .. ACTION_IN
-};
-
-struct Layout {
-    size_t offset[RC_F_COUNT];
-    size_t bytes[RC_F_COUNT];
-    size_t slab_bytes;   // LIDAR..TIME (+OCCUPANCY when rendered)
-    size_t total;
-};
-
-// The arena holds `n_cars` cars; a handle that owns only cars [first_car, first_car + n_own) of it (rc_config::arena_total_cars:
-// several handles - one per track - fill ONE set of output arrays) gets the offsets and sizes of ITS slice of every section.
-Layout make_layout(int n_cars, bool occupancy, int first_car = 0, int n_own = -1) {
-    Layout l{};
-    if (n_own < 0) n_own = n_cars;
-    size_t off = 0;
-    for (int f = 0; f < RC_F_COUNT; ++f) {
-        size_t b = kFieldBytes[f] * (size_t)n_cars;
-        if (f == RC_F_OCCUPANCY && !occupancy) b = 0;
-        l.offset[f] = off + (b ? kFieldBytes[f] * (size_t)first_car : 0);
-        l.bytes[f] = b ? kFieldBytes[f] * (size_t)n_own : 0;
-        if (f == (occupancy ? RC_F_OCCUPANCY : RC_F_TIME)) l.slab_bytes = off + b;
-        off = align_up(off + b, 64);
-    }
-    l.total = off;
-    return l;
-}
-
-// The half-size trajectory record (rc_set_compact_slab): uint16 LiDAR rows, then a copy of the arena's POSE..TIME
-// sections (same relative layout, 64-byte aligned sections).
-struct CompactLayout {
-    size_t lidar_bytes;      // n * 1080 * 2, rounded up to 64
-    size_t summary_src_off;  // offset of RC_F_POSE in the arena
-    size_t summary_bytes;    // RC_F_POSE .. end of RC_F_TIME
-    size_t total;
-};
-
-CompactLayout make_compact(const Layout &l, int n_cars) {
-    CompactLayout c{};
-    c.lidar_bytes = align_up((size_t)n_cars * RC_N_BEAMS * 2, 64);
-    c.summary_src_off = l.offset[RC_F_POSE];
-    c.summary_bytes = l.offset[RC_F_TIME] + l.bytes[RC_F_TIME] - l.offset[RC_F_POSE];
-    c.total = align_up(c.lidar_bytes + c.summary_bytes, 64);
-    return c;
-}
-
-// ---- RCCL, bound at run time (rc_comm_init): the library has no link-time dependency on it, so single-GPU clients
-// need no RCCL installed, and a process that already holds a copy (PyTorch bundles one) keeps using that copy.
-struct Rccl {
-    void *handle = nullptr;
-    int (*GetUniqueId)(void *) = nullptr;
-    int (*CommInitRank)(void **, int, /* ncclUniqueId by value */ struct RcUid, int) = nullptr;
-    int (*AllGather)(const void *, void *, size_t, int, void *, hipStream_t) = nullptr;
-    int (*CommDestroy)(void *) = nullptr;
-    int (*CommCount)(void *, int *) = nullptr;
-    const char *(*GetErrorString)(int) = nullptr;
-};
-
-// Device tables of one compiled track (bitmaps, progress grid, spawn table, the scan's rectangle planes and first-trip
-// table: 30 - 420 MB, built on the device in 20 - 100 ms).  They are read-only and depend on nothing but the track, so
-// handles of one process that load the same track on the same device share one copy: the second rc_load_track of a
-// track costs a hash of its inputs instead of an upload and a rebuild (tests and multi-handle clients create many).
-struct TrackTables {
-    int device = 0;
-    void *mem = nullptr;
-    // what the tables were built from, compared on a cache hit besides the 64-bit key: shape, geometry and a second,
-    // independent checksum of the arrays (a key collision must not hand a handle another track's tables)
-    int32_t h = 0, w = 0, pitch = 0, n_centerline = 0;
-    float res = 0.f, ox = 0.f, oy = 0.f;
-    uint64_t sum2 = 0;
-    RcTrackDev t{};
-    size_t lds_bytes = 0, lds_bytes_skip = 0, lds_bytes_packed = 0;
-    ~TrackTables() {
-        if (mem) {
-            (void)hipSetDevice(device);
-            (void)hipFree(mem);
-        }
-    }
-};
 std::mutex g_track_mutex;
 std::map<std::pair<int, uint64_t>, std::weak_ptr<TrackTables>> g_track_cache;
 
@@ -148,155 +54,7 @@ uint64_t wordsum(uint64_t acc, const void *data, size_t n) {     // position-wei
     return acc;
 }
 
-struct EventPair {
-    hipEvent_t a, b;
-    int kernel;
-};
-// The episode log's launches of a step are timed like a kernel, under an accumulator of their own behind the public ones
-// (rc_kernel_time does not know it: rc_episode_log_time reads it).
-constexpr int kTimeEpisodeLog = RC_K_COUNT;
-
-// A table of up to 8 RcParams on the device that follows its host-side contents in stream order (rc_step_group: one entry per
-// handle; a track set: one per track).  A copy is queued only when an entry or the count changed since the last upload, from one
-// of four pinned slots taken in turn, none rewritten before its copy has run.
-static_assert(RC_GROUP_MAX == RC_TS_MAX, "one staged table type serves the group and the track set");
-struct StagedTable {
-    RcParams *dev = nullptr;
-    RcParams *host = nullptr;      // [4][RC_GROUP_MAX], pinned
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t slot = 0;
-    int n = 0;                     // entries of the last upload; 0: the next sync uploads
-    RcParams last[RC_GROUP_MAX];
-    int alloc() {                  // on first use (a failure half way is made up for by the next call)
-        if (!dev) HIP_TRY(hipMalloc((void **)&dev, sizeof(RcParams) * RC_GROUP_MAX));
-        if (!host) HIP_TRY(hipHostMalloc((void **)&host, sizeof(RcParams) * RC_GROUP_MAX * 4, hipHostMallocDefault));
-        for (hipEvent_t &e : ev)
-            if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        return RC_OK;
-    }
-    int sync(const RcParams *want, int n_want, hipStream_t stream) {
-        if (n == n_want && std::memcmp(want, last, sizeof(RcParams) * n_want) == 0) return RC_OK;
-        n = 0;
-        const uint32_t k = slot++ & 3u;
-        HIP_TRY(hipEventSynchronize(ev[k]));
-        RcParams *stage = host + (size_t)k * RC_GROUP_MAX;
-        std::memcpy(stage, want, sizeof(RcParams) * n_want);
-        std::memcpy(last, want, sizeof(RcParams) * n_want);
-        HIP_TRY(hipMemcpyAsync(dev, stage, sizeof(RcParams) * n_want, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipEventRecord(ev[k], stream));
-        n = n_want;
-        return RC_OK;
-    }
-    void free() {
-        if (dev) (void)hipFree(dev);
-        if (host) (void)hipHostFree(host);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    }
-};
-
-// ---- peer-copy all-gather (on the xGMI full mesh every shard crosses exactly one link once if each rank
-// copies its record straight into every peer's buffer - N - 1 concurrent copies - where a ring passes it N - 1 times).
-// Every rank owns: the destination, two slots of world x bytes (hipMalloc, exported over hipIpc), and a block of
-// sequence flags in uncached device memory that its PEERS write: arrived[p] = k + 1 when peer p's shard of gather k has
-// landed, released[p] = k + 1 when peer p allows gather k to be written into ITS slot k & 1.
-struct P2pExport {                 // what a rank hands to its peers (RC_P2P_EXPORT_BYTES)
-    hipIpcMemHandle_t dst, flags;
-    uint64_t bytes;                // per rank and slot
-    int32_t rank, world, mode, pid;
-    char pci[32];
-    char pad[RC_P2P_EXPORT_BYTES - 2 * sizeof(hipIpcMemHandle_t) - 8 - 16 - 32];
-};
-static_assert(sizeof(P2pExport) == RC_P2P_EXPORT_BYTES, "export blob size");
-
-struct P2p {
-    int rank = 0, world = 0, mode = 0;
-    size_t bytes = 0;              // one rank's record in the current mode
-    size_t cap = 0;                // ... and in the largest one (RC_GATHER_FULL): what the slots are sized for
-    P2pExport blob{};              // what rc_p2p_setup handed out
-    char *dst = nullptr;           // [2][world][cap], mine
-    uint32_t *flags = nullptr;     // arrived[64] | released[64] | timeouts, mine (uncached)
-    std::vector<char *> peer_dst;          // peers' destinations, opened (null for me)
-    std::vector<uint32_t *> peer_flags;    // peers' flag blocks, opened (null for me)
-    std::vector<hipStream_t> push;         // one stream per peer (the local copy runs on push[rank])
-    hipStream_t ctrl = nullptr;            // release + wait-for-release kernels; arrival waits
-    hipEvent_t ev_ready = nullptr, ev_go = nullptr, ev_arrived = nullptr, ev_local = nullptr;
-    std::vector<hipEvent_t> ev_sent;       // per peer: my copy into its slot and the arrival flag behind it have been executed
-    uint32_t issued = 0;           // gathers issued so far
-    bool connected = false;
-    uint32_t *arrived() const { return flags; }
-    uint32_t *released() const { return flags + RC_P2P_MAX_RANKS; }
-    uint32_t *timeouts() const { return flags + 2 * RC_P2P_MAX_RANKS; }
-};
-
 }  // namespace
-
-struct rc_env {
-    rc_config cfg{};
-    int n_cars = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    // device memory
-    void *arena = nullptr;
-    bool own_arena = false;
-    bool shared_arena = false;     // this handle fills a slice of a larger arena (rc_config::arena_total_cars)
-    Layout layout{};
-    void *state_mem = nullptr;
-    std::shared_ptr<TrackTables> track;   // shared with the other handles that loaded the same track on this device
-    uint8_t *mask_dev = nullptr;
-    float *actions_in = nullptr;   // inside the arena the handle was created with (RC_F_ACTION_IN)
-    void *out_arena = nullptr;     // where the output fields currently point (rc_set_arena)
-    RcParams params{};
-    RcLaunchInfo launch{};
-    bool has_track = false;
-    bool was_reset = false;
-    // profiling
-    uint32_t profiling = 0;        // bit k set: time kernel k with HIP events (the episode log's launches: any bit)
-    std::vector<EventPair> pending;
-    std::vector<EventPair> free_events;
-    double k_ms[RC_K_COUNT + 1] = {0};     // (the last entry: kTimeEpisodeLog)
-    uint64_t k_n[RC_K_COUNT + 1] = {0};
-    int32_t dbg[RC_DBG_COUNT] = {0};   // rc_debug_set: experiment / validation knobs, all 0 = production behaviour
-    // half-size record + multi-GPU gather
-    CompactLayout compact{};
-    void *compact_slab = nullptr;      // caller-owned device buffer of compact.total bytes, or null
-    void *comm = nullptr;              // ncclComm_t
-    int comm_rank = 0, comm_world = 0;
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ev_ready = nullptr, ev_gathered = nullptr;
-    bool gather_pending = false;
-    P2p *p2p = nullptr;                // peer-copy all-gather (rc_p2p_setup), else null
-    // obs_type lidar_occupancy_reference (racecar_patch_exact.h): the source frame (rc_set_source_frame), the spline
-    // coefficients' scratch for one chunk of cars, Pillow's integer tables on the device
-    RcExactParams exact{};
-    bool has_frame = false;
-    int exact_chunk = 0;
-    void *exact_mem = nullptr;
-    // rc_policy_load: the padded weights (one allocation), the agent's state [n_cars][232], the pointers into the weights
-    float *pol_mem = nullptr;
-    float *pol_state = nullptr;
-    RcPolicyDev pol{};
-    float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
-    float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)
-    void *order_mem = nullptr;         // RcStateDev::order + the sort's bucket counters (batches of RC_ORDER_MIN_CARS cars and more)
-    uint32_t order_age = 0;            // observations since the cars were last sorted by track position
-    const float *last_scan_rows = nullptr;   // the LiDAR rows the last scan of this handle wrote (the small batches' cost keys)
-    StagedTable group_table;           // rc_step_group (this handle as the first of a group): the blocks' RcParams as the last launch saw them
-    // track set (rc_set_track_set): the source handles, the per-env arrays, the table of RcParams (one per track), the render's LDS bytes
-    std::vector<rc_env *> ts_src;
-    void *ts_mem = nullptr;            // track [num_envs] | next [num_envs] | list [n_cars] | start [RC_TS_MAX + 1] | counts, cursors
-                                       // [2 RC_TS_MAX] | started [num_envs]
-    StagedTable ts_table;
-    size_t ts_patch_lds = 0;
-    // episode log (rc_episode_log_enable): the running sums, counters, cursor and workgroup counts (one allocation), the rows,
-    // the calls since enable / clear
-    bool ep_on = false;
-    void *ep_mem = nullptr;
-    void *ep_rows = nullptr;
-    uint64_t ep_calls = 0;
-    RcEpisodeDev ep{};
-};
-
-namespace {
 
 int drain_events(rc_env *env) {
     if (env->pending.empty()) return RC_OK;
@@ -313,51 +71,7 @@ int drain_events(rc_env *env) {
     return RC_OK;
 }
 
-// Times what lies between begin() and end() under accumulator `kernel`.  One launch: the launch itself carries the two timestamps
-// (rck_set_launch_events).  `bracket`: the pair is recorded on the stream around whatever is queued in between (the episode log's
-// step is two dependent launches).
-struct KernelTimer {
-    rc_env *env;
-    EventPair ep{};
-    bool on = false, bracket = false;
-    int begin(rc_env *e, int kernel, bool bracket_mode = false) {
-        env = e;
-        bracket = bracket_mode;
-        if (kernel == kTimeEpisodeLog ? e->profiling == 0 : !((e->profiling >> kernel) & 1u)) return RC_OK;
-        if (e->pending.size() >= 4096) {
-            int rc = drain_events(e);
-            if (rc) return rc;
-        }
-        if (!e->free_events.empty()) {
-            ep = e->free_events.back();
-            e->free_events.pop_back();
-        } else {
-            HIP_TRY(hipEventCreate(&ep.a));
-            HIP_TRY(hipEventCreate(&ep.b));
-        }
-        ep.kernel = kernel;
-        if (bracket) HIP_TRY(hipEventRecord(ep.a, e->stream));
-        else rck_set_launch_events(ep.a, ep.b);      // the launch that follows carries the two timestamps itself
-        on = true;
-        return RC_OK;
-    }
-    int end() {
-        if (!on) return RC_OK;
-        if (bracket) HIP_TRY(hipEventRecord(ep.b, env->stream));
-        env->pending.push_back(ep);
-        return RC_OK;
-    }
-};
-
-#define TIMED(env, kernel, launch_expr)                 \
-    do {                                                \
-        KernelTimer _t;                                 \
-        int _rc = _t.begin(env, kernel);                \
-        if (_rc) return _rc;                            \
-        HIP_TRY(launch_expr);                           \
-        _rc = _t.end();                                 \
-        if (_rc) return _rc;                            \
-    } while (0)
+namespace {
 
 // Waves per car of the one-wave-per-car scan (the measurements: set_launch_geometry, tools/split_sweep.py).
 static int scan_split(long long cars, int n_cu) {
@@ -557,93 +271,6 @@ int observe(rc_env *env) {
                                (const char *)env->out_arena + env->compact.summary_src_off, env->compact.summary_bytes,
                                hipMemcpyDeviceToDevice, env->stream));
     return RC_OK;
-}
-
-Rccl g_rccl;
-std::string g_rccl_path;
-std::mutex g_rccl_mutex;
-
-// ---- episode log: the launches behind a step's dynamics and a reset (racecar_episode.hip) ---------------------------------------
-// The log reads the arena the outputs point at NOW (rc_set_arena re-points them between steps) and the current track ids.
-void episode_bind(rc_env *env) {
-    RcEpisodeDev &d = env->ep;
-    const RcOutDev &o = env->params.out;
-    d.reward = o.reward; d.progress_total = o.progress_total; d.time = o.time; d.lap = o.lap;
-    d.done = o.done; d.trunc = o.trunc; d.wall = o.wall; d.opp = o.opp; d.wrong = o.wrong; d.fresh = o.fresh;
-    d.ts_n = env->params.ts_n;
-    d.ts_track = env->params.ts_n > 0 ? env->params.ts_track : nullptr;
-    d.call = (uint32_t)env->ep_calls;
-}
-
-// After the dynamics launch and before the scan: the few fields the log reads are the ones that launch has just written (they
-// are still in L2; behind the scan's 280 MB of rows they would not be), and the scan does not depend on the log.
-int episode_step(rc_env *env) {
-    episode_bind(env);
-    KernelTimer t;
-    int rc = t.begin(env, kTimeEpisodeLog, true);
-    if (rc) return rc;
-    HIP_TRY(rck_launch_episode_step(env->ep, env->stream));
-    if ((rc = t.end())) return rc;
-    env->ep_calls += 1;
-    return RC_OK;
-}
-
-int load_rccl() {
-    std::lock_guard<std::mutex> lock(g_rccl_mutex);       // handles may be set up from different threads
-    if (g_rccl.handle) return RC_OK;
-    void *h = nullptr;
-    if (!g_rccl_path.empty()) {
-        h = dlopen(g_rccl_path.c_str(), RTLD_NOW | RTLD_LOCAL);
-        if (!h) return fail(RC_ERR_COMM, "dlopen(%s) failed: %s", g_rccl_path.c_str(), dlerror());
-    } else {
-        const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
-        for (const char *n : names)                       // a copy the process already holds wins
-            if ((h = dlopen(n, RTLD_NOW | RTLD_LOCAL | RTLD_NOLOAD))) break;
-        if (!h)
-            for (const char *n : names)
-                if ((h = dlopen(n, RTLD_NOW | RTLD_LOCAL))) break;
-        if (!h) return fail(RC_ERR_COMM, "RCCL not found (tried librccl.so.1, librccl.so, /opt/rocm/lib): %s", dlerror());
-    }
-    Rccl r;
-    r.handle = h;
-    r.GetUniqueId = (decltype(r.GetUniqueId))dlsym(h, "ncclGetUniqueId");
-    r.CommInitRank = (decltype(r.CommInitRank))dlsym(h, "ncclCommInitRank");
-    r.AllGather = (decltype(r.AllGather))dlsym(h, "ncclAllGather");
-    r.CommDestroy = (decltype(r.CommDestroy))dlsym(h, "ncclCommDestroy");
-    r.CommCount = (decltype(r.CommCount))dlsym(h, "ncclCommCount");
-    r.GetErrorString = (decltype(r.GetErrorString))dlsym(h, "ncclGetErrorString");
-    if (!r.GetUniqueId || !r.CommInitRank || !r.AllGather || !r.CommDestroy || !r.GetErrorString)
-        return fail(RC_ERR_COMM, "the RCCL library lacks an expected symbol");
-    g_rccl = r;
-    return RC_OK;
-}
-
-#define NCCL_TRY(expr)                                                                                     \
-    do {                                                                                                   \
-        int _r = (expr);                                                                                   \
-        if (_r != 0) return fail(RC_ERR_COMM, "%s failed: %s", #expr, g_rccl.GetErrorString(_r));          \
-    } while (0)
-
-// source pointer and size of what one gather mode sends
-int gather_source(rc_env *env, int mode, const void **src, size_t *bytes) {
-    switch (mode) {
-    case RC_GATHER_FULL:
-        if (env->shared_arena) return fail(RC_ERR_INVALID, "this handle fills a slice of a shared arena: gather the arena itself");
-        *src = env->out_arena;
-        *bytes = env->layout.slab_bytes;
-        return RC_OK;
-    case RC_GATHER_SUMMARY:
-        if (env->shared_arena) return fail(RC_ERR_INVALID, "this handle fills a slice of a shared arena: gather the arena itself");
-        *src = (const char *)env->out_arena + env->compact.summary_src_off;
-        *bytes = env->compact.summary_bytes;
-        return RC_OK;
-    case RC_GATHER_FULL_U16:
-        if (!env->compact_slab) return fail(RC_ERR_INVALID, "RC_GATHER_FULL_U16 needs rc_set_compact_slab first");
-        *src = env->compact_slab;
-        *bytes = env->compact.total;
-        return RC_OK;
-    }
-    return fail(RC_ERR_INVALID, "unknown gather mode %d", mode);
 }
 
 int check_cfg(const rc_config *cfg) {
@@ -958,18 +585,12 @@ int rc_create(const rc_config *cfg, rc_env **out) {
     return RC_OK;
 }
 
-static void p2p_free(rc_env *env);
 
 void rc_destroy(rc_env *env) {
     if (!env) return;
     (void)hipSetDevice(env->cfg.device);
     if (env->stream) (void)hipStreamSynchronize(env->stream);
-    p2p_free(env);
-    if (env->comm_stream) (void)hipStreamSynchronize(env->comm_stream);
-    if (env->comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(env->comm);
-    if (env->ev_ready) (void)hipEventDestroy(env->ev_ready);
-    if (env->ev_gathered) (void)hipEventDestroy(env->ev_gathered);
-    if (env->comm_stream) (void)hipStreamDestroy(env->comm_stream);
+    gather_release(env);
     for (EventPair &ep : env->pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (EventPair &ep : env->free_events) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     if (env->own_arena && env->arena) (void)hipFree(env->arena);
@@ -1301,7 +922,7 @@ int rc_reset(rc_env *env, const uint8_t *mask_or_null, int32_t mode, uint64_t se
         int rc = ts_sync_table(env);
         if (rc) return rc;
     }
-    TIMED(env, RC_K_RESET, ts ? rck_launch_ts_reset(env->params, mask_dev, env->stream) : rck_launch_reset(env->params, mask_dev, env->stream));
+    TIMED(env, RC_K_RESET, rck_launch_reset(env->params, mask_dev, env->stream));
     if (env->ep_on) {
         episode_bind(env);
         HIP_TRY(rck_launch_episode_reset(env->ep, mask_dev, env->stream));
@@ -1323,8 +944,7 @@ static int single_step(rc_env *env, float *actions, int32_t repeat, const RcRand
     const bool ts = env->params.ts_n > 0;
     int rc = ts ? ts_sync_table(env) : RC_OK;
     if (rc) return rc;
-    TIMED(env, RC_K_DYNAMICS, ts ? rck_launch_ts_dynamics(env->params, actions, repeat, ra, env->stream)
-                                 : rck_launch_dynamics(env->params, actions, repeat, ra, env->stream));
+    TIMED(env, RC_K_DYNAMICS, rck_launch_dynamics(env->params, actions, repeat, ra, env->stream));
     if (env->ep_on && (rc = episode_step(env))) return rc;
     return observe(env);
 }
@@ -1582,101 +1202,6 @@ int rc_track_ids(rc_env *env, void **dev_ptr, size_t *bytes) {
     return RC_OK;
 }
 
-// ---- episode log -------------------------------------------------------------------------------------------------------------
-static_assert(sizeof(rc_episode_row) == 48 && sizeof(RcEpisodeRow) == sizeof(rc_episode_row), "rc_episode_row is 48 bytes");
-
-int rc_episode_log_enable(rc_env *env, int64_t capacity_rows, int32_t max_episodes) {
-    if (capacity_rows < 1) return fail(RC_ERR_INVALID, "rc_episode_log_enable: capacity_rows must be >= 1 (got %lld)", (long long)capacity_rows);
-    if (max_episodes < 0) return fail(RC_ERR_INVALID, "rc_episode_log_enable: max_episodes must be >= 0 (got %d)", max_episodes);
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    const size_t B = (size_t)env->cfg.num_envs, N = (size_t)env->n_cars, blocks = (B + RC_EP_BLOCK - 1) / RC_EP_BLOCK;
-    RcEpisodeDev &d = env->ep;
-    if (!env->ep_mem) {
-        // counters [8] | cursor [2] | ordinal, length, track [B] | ret, prog_max, time_max [N] | block counts | active [B] | wrong_seen [N]
-        const size_t bytes = 10 * 8 + 3 * B * 4 + 3 * N * 4 + blocks * 4 + B + N;
-        HIP_TRY(hipMalloc(&env->ep_mem, bytes));
-        HIP_TRY(hipMemsetAsync(env->ep_mem, 0, bytes, env->stream));      // active = 0: every env starts counting at its next reset
-        d = RcEpisodeDev{};
-        d.counters = (unsigned long long *)env->ep_mem;
-        d.cursor = d.counters + 8;
-        d.ordinal = (uint32_t *)(d.cursor + 2);
-        d.length = (int32_t *)(d.ordinal + B);
-        d.track = d.length + B;
-        d.ret = (float *)(d.track + B);
-        d.prog_max = d.ret + N;
-        d.time_max = d.prog_max + N;
-        d.block_counts = (uint32_t *)(d.time_max + N);
-        d.active = (uint8_t *)(d.block_counts + blocks);
-        d.wrong_seen = d.active + B;
-        d.num_envs = env->cfg.num_envs;
-        d.cars_per_env = env->cfg.cars_per_env;
-        d.first_env = (uint32_t)env->cfg.first_env;
-    }
-    if (!env->ep_rows || d.capacity != (unsigned long long)capacity_rows) {
-        if (env->ep_rows) {
-            HIP_TRY(hipStreamSynchronize(env->stream));       // (launches that write the old rows may still be queued)
-            HIP_TRY(hipFree(env->ep_rows));
-            env->ep_rows = nullptr;
-            env->ep_on = false;
-        }
-        if (hipMalloc(&env->ep_rows, (size_t)capacity_rows * sizeof(RcEpisodeRow)) != hipSuccess) {
-            env->ep_rows = nullptr;
-            return fail(RC_ERR_NOMEM, "rc_episode_log_enable: no device memory for %lld rows", (long long)capacity_rows);
-        }
-        d.rows = (RcEpisodeRow *)env->ep_rows;
-        d.capacity = (unsigned long long)capacity_rows;
-    }
-    d.max_episodes = (uint32_t)max_episodes;
-    env->ep_on = true;
-    return rc_episode_log_clear(env);
-}
-
-int rc_episode_log_disable(rc_env *env) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->ep_mem) return RC_OK;
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(hipStreamSynchronize(env->stream));
-    HIP_TRY(hipFree(env->ep_mem));
-    env->ep_mem = nullptr;
-    if (env->ep_rows) HIP_TRY(hipFree(env->ep_rows));
-    env->ep_rows = nullptr;
-    env->ep_on = false;
-    env->ep = RcEpisodeDev{};
-    return RC_OK;
-}
-
-int rc_episode_log(rc_env *env, void **rows_dev, size_t *capacity_rows, void **counters_dev, size_t *counters_bytes) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->ep_on) return fail(RC_ERR_INVALID, "rc_episode_log: the episode log is not enabled (rc_episode_log_enable)");
-    if (rows_dev) *rows_dev = env->ep_rows;
-    if (capacity_rows) *capacity_rows = (size_t)env->ep.capacity;
-    if (counters_dev) *counters_dev = env->ep.counters;
-    if (counters_bytes) *counters_bytes = RC_EPC_COUNT * sizeof(uint64_t);
-    return RC_OK;
-}
-
-int rc_episode_log_clear(rc_env *env) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->ep_on) return fail(RC_ERR_INVALID, "rc_episode_log_clear: the episode log is not enabled (rc_episode_log_enable)");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    const RcEpisodeDev &d = env->ep;
-    HIP_TRY(hipMemsetAsync(d.rows, 0, (size_t)d.capacity * sizeof(RcEpisodeRow), env->stream));
-    HIP_TRY(hipMemsetAsync(d.counters, 0, 10 * 8, env->stream));                                  // the counters and the cursor pair
-    HIP_TRY(hipMemsetAsync(d.ordinal, 0, (size_t)env->cfg.num_envs * 4, env->stream));
-    env->ep_calls = 0;
-    return RC_OK;
-}
-
-int rc_episode_log_time(rc_env *env, double *total_ms, uint64_t *launches) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    int rc = drain_events(env);
-    if (rc) return rc;
-    if (total_ms) *total_ms = env->k_ms[kTimeEpisodeLog];
-    if (launches) *launches = env->k_n[kTimeEpisodeLog];
-    return RC_OK;
-}
-
 int rc_step_host(rc_env *env, const float *actions_host, int32_t repeat) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
     if (!actions_host) return fail(RC_ERR_INVALID, "actions_host is NULL");
@@ -1699,174 +1224,6 @@ int rc_set_pose(rc_env *env, const float *xyyaw_host) {
     HIP_TRY(hipStreamSynchronize(env->stream));
     HIP_TRY(rck_launch_set_pose(env->params, staging, env->stream));
     return observe(env);
-}
-
-int rc_follow_the_gap(rc_env *env, float motor_straight, float motor_corner) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    TIMED(env, RC_K_FTG, rck_launch_ftg(env->params, env->actions_in, motor_straight, motor_corner, env->stream));
-    return RC_OK;
-}
-
-int rc_follow_the_gap_reference(rc_env *env, float dt, float *detail_dev) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
-    if (!(dt > 0.f)) return fail(RC_ERR_INVALID, "dt must be > 0 (seconds per agent step)");
-    if (env->cfg.lidar_transform != RC_LIDAR_METRES) return fail(RC_ERR_INVALID, "rc_follow_the_gap_reference reads the scan in metres (lidar_transform RC_LIDAR_METRES)");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    if (!env->ftg_prev) {
-        HIP_TRY(hipMalloc((void **)&env->ftg_prev, (size_t)env->n_cars * sizeof(float)));
-        HIP_TRY(hipMemsetAsync(env->ftg_prev, 0xff, (size_t)env->n_cars * sizeof(float), env->stream));      // all ones: a NaN
-    }
-    TIMED(env, RC_K_FTG, rck_launch_ftg_reference(env->params, env->actions_in, env->ftg_prev, dt, detail_dev, env->stream));
-    return RC_OK;
-}
-
-// ---- the trained Dreamer agent (racecar_policy.hip)
-
-namespace {
-struct PolShape { const char *name; const rc_policy_array rc_policy_weights::*arr; int rows, cols; bool used, optional; };
-const PolShape kPolShapes[] = {
-    {"gru_kernel", &rc_policy_weights::gru_kernel, 200, 600, true, false}, {"gru_recurrent", &rc_policy_weights::gru_recurrent, 200, 600, true, false},
-    {"gru_bias", &rc_policy_weights::gru_bias, 2, 600, true, false},
-    {"img1_w", &rc_policy_weights::img1_w, 32, 200, true, false}, {"img1_b", &rc_policy_weights::img1_b, 1, 200, true, false},
-    {"img2_w", &rc_policy_weights::img2_w, 200, 200, false, true}, {"img2_b", &rc_policy_weights::img2_b, 1, 200, false, true},
-    {"img3_w", &rc_policy_weights::img3_w, 200, 60, false, true}, {"img3_b", &rc_policy_weights::img3_b, 1, 60, false, true},
-    {"obs1_w", &rc_policy_weights::obs1_w, 1280, 200, true, false}, {"obs1_b", &rc_policy_weights::obs1_b, 1, 200, true, false},
-    {"obs2_w", &rc_policy_weights::obs2_w, 200, 60, true, false}, {"obs2_b", &rc_policy_weights::obs2_b, 1, 60, true, false},
-    {"h0_w", &rc_policy_weights::h0_w, 230, 400, true, false}, {"h0_b", &rc_policy_weights::h0_b, 1, 400, true, false},
-    {"h1_w", &rc_policy_weights::h1_w, 400, 400, true, false}, {"h1_b", &rc_policy_weights::h1_b, 1, 400, true, false},
-    {"h2_w", &rc_policy_weights::h2_w, 400, 400, true, false}, {"h2_b", &rc_policy_weights::h2_b, 1, 400, true, false},
-    {"h3_w", &rc_policy_weights::h3_w, 400, 400, true, false}, {"h3_b", &rc_policy_weights::h3_b, 1, 400, true, false},
-    {"hout_w", &rc_policy_weights::hout_w, 400, 4, true, false}, {"hout_b", &rc_policy_weights::hout_b, 1, 4, true, false},
-    {"hnorm_mean", &rc_policy_weights::hnorm_mean, 1, 4, true, true}, {"hnorm_var", &rc_policy_weights::hnorm_var, 1, 4, true, true},
-    {"hnorm_gamma", &rc_policy_weights::hnorm_gamma, 1, 4, true, true}, {"hnorm_beta", &rc_policy_weights::hnorm_beta, 1, 4, true, true},
-};
-
-// [rows][n_src] (first `take` columns of every one of `gates` groups of `group` columns) -> [rows][gates * ld], zero padded
-void pol_pad(std::vector<float> &dst, size_t at, const float *src, int rows, int n_src, int gates, int group, int take, int ld) {
-    for (int k = 0; k < rows; ++k)
-        for (int g = 0; g < gates; ++g)
-            for (int j = 0; j < take; ++j) dst[at + (size_t)k * gates * ld + (size_t)g * ld + j] = src[(size_t)k * n_src + g * group + j];
-}
-}  // namespace
-
-int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
-    if (!w) return fail(RC_ERR_INVALID, "rc_policy_weights is NULL");
-    if (w->struct_size != sizeof(rc_policy_weights))
-        return fail(RC_ERR_INVALID, "rc_policy_weights.struct_size %u != %zu", w->struct_size, sizeof(rc_policy_weights));
-    int n_norm = 0;
-    for (const PolShape &sh : kPolShapes) {
-        const rc_policy_array &a = w->*(sh.arr);
-        if (!a.data) {
-            if (!sh.optional) return fail(RC_ERR_INVALID, "rc_policy_load: %s is missing", sh.name);
-            continue;
-        }
-        if (a.rows != sh.rows || a.cols != sh.cols)
-            return fail(RC_ERR_INVALID, "rc_policy_load: %s has shape [%d, %d], the agent's is [%d, %d]", sh.name, a.rows, a.cols, sh.rows, sh.cols);
-        n_norm += sh.name[1] == 'n';                      // hnorm_*
-    }
-    if (n_norm != 0 && n_norm != 4) return fail(RC_ERR_INVALID, "rc_policy_load: %d of the four hnorm_* arrays given (all or none)", n_norm);
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    // the padded device image (racecar_policy.h): offsets in floats
-    const size_t LD2 = RC_POLICY_LD200, LD4 = RC_POLICY_LD400, LDG = RC_POLICY_LDGRU, LDS = RC_POLICY_LDSMALL;
-    size_t at = 0;
-    auto take = [&](size_t n) { const size_t o = at; at += (n + 63) / 64 * 64; return o; };
-    const size_t o_img1 = take(32 * LD2), o_img1b = take(LD2), o_gk = take(200 * LDG), o_gr = take(200 * LDG), o_gb = take(2 * LDG),
-                 o_obs1 = take(1280 * LD2), o_obs1b = take(LD2), o_obs2 = take(200 * LDS), o_obs2b = take(LDS),
-                 o_h0 = take(230 * LD4), o_h1 = take(400 * LD4), o_h2 = take(400 * LD4), o_h3 = take(400 * LD4),
-                 o_hb = take(4 * LD4), o_hout = take(400 * LDS), o_houtb = take(LDS), o_norm = take(8);
-    std::vector<float> img(at, 0.0f);
-    pol_pad(img, o_img1, w->img1_w.data, 32, 200, 1, 200, 200, (int)LD2);
-    pol_pad(img, o_img1b, w->img1_b.data, 1, 200, 1, 200, 200, (int)LD2);
-    pol_pad(img, o_gk, w->gru_kernel.data, 200, 600, 3, 200, 200, (int)LD2);
-    pol_pad(img, o_gr, w->gru_recurrent.data, 200, 600, 3, 200, 200, (int)LD2);
-    pol_pad(img, o_gb, w->gru_bias.data, 2, 600, 3, 200, 200, (int)LD2);
-    pol_pad(img, o_obs1, w->obs1_w.data, 1280, 200, 1, 200, 200, (int)LD2);
-    pol_pad(img, o_obs1b, w->obs1_b.data, 1, 200, 1, 200, 200, (int)LD2);
-    pol_pad(img, o_obs2, w->obs2_w.data, 200, 60, 1, 60, RC_POLICY_STOCH, (int)LDS);          // the mean columns only
-    pol_pad(img, o_obs2b, w->obs2_b.data, 1, 60, 1, 60, RC_POLICY_STOCH, (int)LDS);
-    const rc_policy_array *hw[4] = {&w->h0_w, &w->h1_w, &w->h2_w, &w->h3_w}, *hb[4] = {&w->h0_b, &w->h1_b, &w->h2_b, &w->h3_b};
-    const size_t o_h[4] = {o_h0, o_h1, o_h2, o_h3};
-    for (int i = 0; i < 4; ++i) {
-        pol_pad(img, o_h[i], hw[i]->data, hw[i]->rows, 400, 1, 400, 400, (int)LD4);
-        pol_pad(img, o_hb + i * LD4, hb[i]->data, 1, 400, 1, 400, 400, (int)LD4);
-    }
-    pol_pad(img, o_hout, w->hout_w.data, 400, 4, 1, 4, 2, (int)LDS);
-    pol_pad(img, o_houtb, w->hout_b.data, 1, 4, 1, 4, 2, (int)LDS);
-    if (n_norm) {
-        for (int j = 0; j < 2; ++j) {
-            img[o_norm + j] = w->hnorm_mean.data[j];
-            img[o_norm + 2 + j] = std::sqrt(w->hnorm_var.data[j] + 1e-3f);        // binary32: Keras' epsilon, IEEE square root
-            img[o_norm + 4 + j] = w->hnorm_gamma.data[j];
-            img[o_norm + 6 + j] = w->hnorm_beta.data[j];
-        }
-    }
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(rck_policy_prepare());
-    if (!env->pol_mem) HIP_TRY(hipMalloc((void **)&env->pol_mem, at * sizeof(float)));
-    const size_t state_bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
-    if (!env->pol_state) HIP_TRY(hipMalloc((void **)&env->pol_state, state_bytes));
-    HIP_TRY(hipMemcpyAsync(env->pol_mem, img.data(), at * sizeof(float), hipMemcpyHostToDevice, env->stream));
-    HIP_TRY(hipMemsetAsync(env->pol_state, 0, state_bytes, env->stream));
-    HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
-    const float *m = env->pol_mem;
-    RcPolicyDev &d = env->pol;
-    d.img1_w = m + o_img1; d.img1_b = m + o_img1b; d.gru_k = m + o_gk; d.gru_r = m + o_gr; d.gru_b = m + o_gb;
-    d.obs1_w = m + o_obs1; d.obs1_b = m + o_obs1b; d.obs2_w = m + o_obs2; d.obs2_b = m + o_obs2b;
-    for (int i = 0; i < 4; ++i) { d.h_w[i] = m + o_h[i]; d.h_b[i] = m + o_hb + i * LD4; }
-    d.hout_w = m + o_hout; d.hout_b = m + o_houtb;
-    d.hnorm = n_norm ? m + o_norm : nullptr;
-    return RC_OK;
-}
-
-int rc_policy_unload(rc_env *env) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(hipStreamSynchronize(env->stream));
-    if (env->pol_mem) (void)hipFree(env->pol_mem);
-    if (env->pol_state) (void)hipFree(env->pol_state);
-    env->pol_mem = env->pol_state = nullptr;
-    env->pol = RcPolicyDev{};
-    return RC_OK;
-}
-
-int rc_policy_act(rc_env *env, uint32_t slot_mask) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_act: no policy loaded (rc_policy_load)");
-    if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
-    if (slot_mask == 0) return fail(RC_ERR_INVALID, "rc_policy_act: the slot mask is empty");
-    if (slot_mask >> env->cfg.cars_per_env) return fail(RC_ERR_INVALID, "rc_policy_act: slot mask 0x%x names slots beyond cars_per_env = %d", slot_mask, env->cfg.cars_per_env);
-    if (env->cfg.lidar_transform != RC_LIDAR_METRES) return fail(RC_ERR_INVALID, "rc_policy_act reads the scan in metres (lidar_transform RC_LIDAR_METRES)");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    RcPolicyCall c{};
-    c.w = env->pol;
-    c.lidar = env->params.out.lidar;
-    c.fresh = env->params.out.fresh;
-    c.state = env->pol_state;
-    c.actions = env->actions_in;
-    c.cars_per_env = env->cfg.cars_per_env;
-    for (int a = 0; a < env->cfg.cars_per_env; ++a)
-        if ((slot_mask >> a) & 1u) c.slots |= (uint32_t)a << (8 * c.n_slots++);
-    c.n_active = env->cfg.num_envs * c.n_slots;
-    c.raw_actions = env->cfg.remap_actions != 0;
-    c.lo0 = env->cfg.action_low[0]; c.lo1 = env->cfg.action_low[1]; c.hi0 = env->cfg.action_high[0]; c.hi1 = env->cfg.action_high[1];
-    KernelTimer t;
-    int rc = t.begin(env, RC_K_POLICY);
-    if (rc) return rc;
-    hipEvent_t ea = nullptr, eb = nullptr;
-    rck_take_launch_events(&ea, &eb);
-    HIP_TRY(rck_launch_policy(c, ea, eb, env->stream));
-    return t.end();
-}
-
-int rc_policy_state(rc_env *env, void **dev_ptr, size_t *bytes) {
-    if (!env || !dev_ptr || !bytes) return fail(RC_ERR_INVALID, "NULL argument");
-    if (!env->pol_state) return fail(RC_ERR_INVALID, "rc_policy_state: no policy loaded (rc_policy_load)");
-    *dev_ptr = env->pol_state;
-    *bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
-    return RC_OK;
 }
 
 int rc_fill_random_actions(rc_env *env, uint64_t seed, uint32_t step) {
@@ -1905,148 +1262,6 @@ int rc_trajectory_slab(rc_env *env, void **dev_ptr, size_t *bytes) {
     if (env->shared_arena) return fail(RC_ERR_INVALID, "this handle fills a slice of a shared arena: the slab is the head of the arena itself");
     *dev_ptr = env->out_arena;
     *bytes = env->layout.slab_bytes;
-    return RC_OK;
-}
-
-namespace {
-// The field table of a row gather: for every field of the mask, in field order, where its section starts in an arena, where its
-// rows go in the output (sections of `n_rows` rows, 64-byte aligned) and its bytes per car; `total` is the output's size.
-// `bad` is the first field of the mask that a recorded arena of this configuration does not hold (the action input buffer, a
-// section that is off), or -1: such a mask is refused by every caller but rc_gather_rows_bytes, which has no error to return.
-struct GatherFields {
-    size_t src[RC_GATHER_MAX_FIELDS], dst[RC_GATHER_MAX_FIELDS], total;
-    uint32_t bpc[RC_GATHER_MAX_FIELDS];
-    int field[RC_GATHER_MAX_FIELDS], n, bad;
-};
-GatherFields gather_fields(const rc_env *env, uint32_t field_mask, size_t n_rows) {
-    GatherFields g{};
-    g.bad = -1;
-    for (int f = 0; f < RC_F_COUNT; ++f) {
-        if (!((field_mask >> f) & 1u)) continue;
-        if ((f == RC_F_ACTION_IN || !env->layout.bytes[f]) && g.bad < 0) g.bad = f;
-        if (!env->layout.bytes[f]) continue;
-        g.field[g.n] = f; g.src[g.n] = env->layout.offset[f]; g.dst[g.n] = g.total; g.bpc[g.n] = (uint32_t)kFieldBytes[f];
-        g.total = align_up(g.total + kFieldBytes[f] * n_rows, 64);
-        ++g.n;
-    }
-    return g;
-}
-
-// what rc_gather_rows and rc_sample_windows ask of a ring of recorded arenas
-int check_ring(const rc_env *env, const void *ring_base, size_t slot_bytes, const char *who) {
-    if (slot_bytes < env->layout.total) return fail(RC_ERR_INVALID, "slot_bytes %zu is smaller than an arena (%zu)", slot_bytes, env->layout.total);
-    // (the row gather moves 16 bytes per lane: every slot must start as rc_set_arena demands of an arena)
-    if (((uintptr_t)ring_base & 63u) != 0 || (slot_bytes & 63u) != 0)
-        return fail(RC_ERR_INVALID, "ring_base (%p) and slot_bytes (%zu) must be multiples of 64", ring_base, slot_bytes);
-    if (env->shared_arena) return fail(RC_ERR_INVALID, "%s works on whole arenas, not on a slice handle", who);
-    return RC_OK;
-}
-}  // namespace
-
-size_t rc_gather_rows_bytes(rc_env *env, uint32_t field_mask, int32_t n_rows) {
-    if (!env || n_rows < 1) return 0;
-    return gather_fields(env, field_mask, (size_t)n_rows).total;
-}
-
-int rc_gather_rows(rc_env *env, const void *ring_base, size_t slot_bytes, const int32_t *slot_idx_dev, const int32_t *car_idx_dev,
-                   int32_t n_rows, uint32_t field_mask, void *out_dev, size_t out_bytes) {
-    if (!env || !ring_base || !slot_idx_dev || !car_idx_dev || !out_dev) return fail(RC_ERR_INVALID, "NULL argument");
-    if (n_rows < 1) return fail(RC_ERR_INVALID, "n_rows must be >= 1");
-    int rc = check_ring(env, ring_base, slot_bytes, "rc_gather_rows");
-    if (rc) return rc;
-    const GatherFields g = gather_fields(env, field_mask, (size_t)n_rows);
-    if (g.bad >= 0) return fail(RC_ERR_INVALID, "field %d is not part of a recorded arena in this configuration", g.bad);
-    if (g.n == 0) return fail(RC_ERR_INVALID, "empty field mask");
-    if (out_bytes < g.total) return fail(RC_ERR_INVALID, "output too small: %zu < %zu", out_bytes, g.total);
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(rck_gather_rows(ring_base, slot_bytes, slot_idx_dev, car_idx_dev, n_rows, g.src, g.dst, g.bpc, g.n, out_dev, env->stream));
-    return RC_OK;
-}
-
-int rc_sample_windows(rc_env *env, const void *ring_base, size_t slot_bytes, int32_t capacity, int32_t oldest, int32_t count,
-                      int32_t length, int32_t n_windows, uint64_t seed, uint32_t draw, int32_t max_tries, int32_t *slot_idx_dev,
-                      int32_t *slot_obs_idx_dev, int32_t *car_idx_dev, int32_t *meta_dev, uint32_t *failed_dev) {
-    if (!env || !ring_base || !slot_idx_dev || !slot_obs_idx_dev || !car_idx_dev || !meta_dev || !failed_dev) return fail(RC_ERR_INVALID, "NULL argument");
-    int rc = check_ring(env, ring_base, slot_bytes, "rc_sample_windows");
-    if (rc) return rc;
-    if (capacity < 1 || oldest < 0 || oldest >= capacity || count < 1 || count > capacity) return fail(RC_ERR_INVALID, "ring of %d slots, oldest %d, %d filled", capacity, oldest, count);
-    if (length < 1 || length > count) return fail(RC_ERR_INVALID, "a window of %d records does not fit the %d records of the ring", length, count);
-    if (n_windows < 1 || max_tries < 1) return fail(RC_ERR_INVALID, "n_windows and max_tries must be >= 1");
-    RcSampleWindows a{};
-    a.ring = (const unsigned char *)ring_base; a.slot_bytes = slot_bytes;
-    a.fresh_off = env->layout.offset[RC_F_FRESH]; a.done_off = env->layout.offset[RC_F_DONE];
-    a.capacity = capacity; a.oldest = oldest; a.n_start = count - length + 1; a.length = length; a.n_windows = n_windows;
-    a.n_cars = env->n_cars; a.max_tries = max_tries;
-    a.seed_lo = seed_lo(seed); a.seed_hi = seed_hi(seed); a.draw = draw;
-    a.slot_idx = slot_idx_dev; a.slot_obs_idx = slot_obs_idx_dev; a.car_idx = car_idx_dev; a.meta = meta_dev; a.failed = failed_dev;
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(rck_sample_windows(a, env->stream));
-    return RC_OK;
-}
-
-// One training batch as ONE packed buffer: field sections (64-byte aligned, field order), meta, the failure counter - the
-// payload a sharded replay store exchanges - then the sampler's row indices (scratch).
-namespace {
-struct BatchLayout { GatherFields fields; size_t meta, failed, payload, slot, slot_obs, car, total; };
-bool batch_layout(const rc_env *env, uint32_t field_mask, int32_t n_windows, int32_t length, BatchLayout *bl) {
-    const size_t rows = (size_t)n_windows * (size_t)length;
-    bl->fields = gather_fields(env, field_mask, rows);
-    if (bl->fields.bad >= 0) return false;
-    size_t off = bl->fields.total;
-    bl->meta = off;     off = align_up(off + 16u * (size_t)n_windows, 64);
-    bl->failed = off;   off += 64;
-    bl->payload = off;
-    bl->slot = off;     off = align_up(off + 4u * rows, 64);
-    bl->slot_obs = off; off = align_up(off + 4u * rows, 64);
-    bl->car = off;      off = align_up(off + 4u * rows, 64);
-    bl->total = off;
-    return true;
-}
-}  // namespace
-
-size_t rc_sample_batch_bytes(rc_env *env, uint32_t field_mask, int32_t n_windows, int32_t length, size_t *payload_bytes, size_t *meta_offset) {
-    if (!env || n_windows < 1 || length < 1 || field_mask == 0u) return 0;
-    BatchLayout bl;
-    if (!batch_layout(env, field_mask, n_windows, length, &bl)) return 0;
-    if (payload_bytes) *payload_bytes = bl.payload;
-    if (meta_offset) *meta_offset = bl.meta;
-    return bl.total;
-}
-
-int rc_sample_batch(rc_env *env, const void *ring_base, size_t slot_bytes, int32_t capacity, int32_t oldest, int32_t count, int32_t length,
-                    int32_t n_windows, uint64_t seed, uint32_t draw, int32_t max_tries, uint32_t field_mask, int32_t reset_rows,
-                    void *out_dev, size_t out_bytes) {
-    if (!env || !ring_base || !out_dev) return fail(RC_ERR_INVALID, "NULL argument");
-    if (n_windows < 1 || length < 1) return fail(RC_ERR_INVALID, "n_windows and length must be >= 1");
-    BatchLayout bl;
-    if (field_mask == 0u || !batch_layout(env, field_mask, n_windows, length, &bl))
-        return fail(RC_ERR_INVALID, "field mask 0x%x names no field, or one that is not part of a recorded arena in this configuration", field_mask);
-    if (out_bytes < bl.total) return fail(RC_ERR_INVALID, "output too small: %zu < %zu (rc_sample_batch_bytes)", out_bytes, bl.total);
-    if (((uintptr_t)out_dev & 63u) != 0) return fail(RC_ERR_INVALID, "out_dev must be 64-byte aligned");
-    char *out = (char *)out_dev;
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(hipMemsetAsync(out + bl.failed, 0, 64, env->stream));
-    int rc = rc_sample_windows(env, ring_base, slot_bytes, capacity, oldest, count, length, n_windows, seed, draw, max_tries,
-                               (int32_t *)(out + bl.slot), (int32_t *)(out + bl.slot_obs), (int32_t *)(out + bl.car),
-                               (int32_t *)(out + bl.meta), (uint32_t *)(out + bl.failed));
-    if (rc) return rc;
-    // the observation part of a record: what a terminal row borrows from the row before it
-    const uint32_t obs_fields = (1u << RC_F_LIDAR) | (1u << RC_F_OCCUPANCY) | (1u << RC_F_POSE) | (1u << RC_F_VELOCITY) | (1u << RC_F_SPEED) |
-                                (1u << RC_F_ACCELERATION) | (1u << RC_F_STEERING_ANGLE);
-    const GatherFields &g = bl.fields;
-    RcBatchRows br{};
-    br.slot_obs_idx = (const int32_t *)(out + bl.slot_obs); br.meta = (const int32_t *)(out + bl.meta); br.length = length;
-    for (int i = 0; i < g.n; ++i) {
-        const int f = g.field[i];
-        if ((obs_fields >> f) & 1u) br.obs_mask |= 1u << i;
-        if (reset_rows && (f == RC_F_ACTION || f == RC_F_REWARD || f == RC_F_DISCOUNT || f == RC_F_TIME || f == RC_F_PROGRESS_TOTAL)) {
-            const float v = f == RC_F_DISCOUNT ? 1.0f : (f == RC_F_PROGRESS_TOTAL ? -1.0f : 0.0f);
-            br.reset_mask |= 1u << i;
-            std::memcpy(&br.reset_word[i], &v, 4);
-        }
-    }
-    HIP_TRY(rck_gather_rows(ring_base, slot_bytes, (const int32_t *)(out + bl.slot), (const int32_t *)(out + bl.car), n_windows * length,
-                            g.src, g.dst, g.bpc, g.n, out, env->stream, &br));
     return RC_OK;
 }
 
@@ -2168,307 +1383,6 @@ int rc_compact_layout(rc_env *env, size_t *lidar_u16_bytes, size_t *summary_offs
     *lidar_u16_bytes = (size_t)env->n_cars * RC_N_BEAMS * 2;
     *summary_offset = env->compact.lidar_bytes;
     *summary_bytes = env->compact.summary_bytes;
-    return RC_OK;
-}
-
-int rc_comm_library(const char *path) {
-    if (g_rccl.handle) return fail(RC_ERR_INVALID, "RCCL is already loaded");
-    g_rccl_path = path ? path : "";
-    return RC_OK;
-}
-
-int rc_comm_unique_id(void *out, size_t bytes) {
-    if (!out || bytes < sizeof(RcUid)) return fail(RC_ERR_INVALID, "unique id buffer must hold %zu bytes", sizeof(RcUid));
-    int rc = load_rccl();
-    if (rc) return rc;
-    NCCL_TRY(g_rccl.GetUniqueId(out));
-    return RC_OK;
-}
-
-int rc_comm_init(rc_env *env, const void *unique_id, size_t bytes, int32_t rank, int32_t world) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!unique_id || bytes < sizeof(RcUid)) return fail(RC_ERR_INVALID, "unique id must hold %zu bytes", sizeof(RcUid));
-    if (world < 1 || rank < 0 || rank >= world) return fail(RC_ERR_INVALID, "rank %d outside world of %d", rank, world);
-    if (env->comm) return fail(RC_ERR_INVALID, "the handle already has a communicator");
-    int rc = load_rccl();
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    RcUid id;
-    std::memcpy(&id, unique_id, sizeof(id));
-    NCCL_TRY(g_rccl.CommInitRank(&env->comm, world, id, rank));
-    env->comm_rank = rank;
-    env->comm_world = world;
-    HIP_TRY(hipStreamCreateWithFlags(&env->comm_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&env->ev_ready, hipEventDisableTiming));
-    HIP_TRY(hipEventCreateWithFlags(&env->ev_gathered, hipEventDisableTiming));
-    return RC_OK;
-}
-
-int rc_comm_count(rc_env *env, int32_t *ranks) {
-    if (!env || !ranks) return fail(RC_ERR_INVALID, "NULL argument");
-    if (!env->comm) return fail(RC_ERR_INVALID, "rc_comm_init has not been called on this handle");
-    if (!g_rccl.CommCount) return fail(RC_ERR_COMM, "the RCCL library lacks ncclCommCount");
-    int n = 0;
-    NCCL_TRY(g_rccl.CommCount(env->comm, &n));
-    *ranks = n;
-    return RC_OK;
-}
-
-size_t rc_gather_bytes(rc_env *env, int32_t mode) {
-    if (!env) return 0;
-    switch (mode) {
-    case RC_GATHER_FULL: return env->layout.slab_bytes;
-    case RC_GATHER_FULL_U16: return env->compact.total;
-    case RC_GATHER_SUMMARY: return env->compact.summary_bytes;
-    }
-    return 0;
-}
-
-int rc_gather_trajectory(rc_env *env, int32_t mode, void *dev_dst, size_t dst_bytes) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->comm) return fail(RC_ERR_INVALID, "rc_comm_init has not been called on this handle");
-    if (!dev_dst) return fail(RC_ERR_INVALID, "dev_dst is NULL");
-    const void *src;
-    size_t n;
-    int rc = gather_source(env, mode, &src, &n);
-    if (rc) return rc;
-    if (dst_bytes < n * (size_t)env->comm_world)
-        return fail(RC_ERR_INVALID, "gather destination too small: %zu < %d x %zu", dst_bytes, env->comm_world, n);
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    // ordered after everything queued on the env's stream (the step that produced the record), but on a stream of
-    // its own: the following steps' kernels overlap the collective
-    HIP_TRY(hipEventRecord(env->ev_ready, env->stream));
-    HIP_TRY(hipStreamWaitEvent(env->comm_stream, env->ev_ready, 0));
-    NCCL_TRY(g_rccl.AllGather(src, dev_dst, n, /* ncclUint8 */ 1, env->comm, env->comm_stream));
-    HIP_TRY(hipEventRecord(env->ev_gathered, env->comm_stream));
-    env->gather_pending = true;
-    return RC_OK;
-}
-
-int rc_gather_wait(rc_env *env, int32_t host_sync) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!env->gather_pending) return RC_OK;
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(hipStreamWaitEvent(env->stream, env->ev_gathered, 0));     // later work on the env's stream sees the result
-    if (host_sync) {
-        HIP_TRY(hipEventSynchronize(env->ev_gathered));
-        env->gather_pending = false;
-    }
-    return RC_OK;
-}
-
-// ---- peer-copy all-gather ------------------------------------------------------------------------------------------
-static void p2p_disconnect(rc_env *env) {          // my copies done, the peers' buffers unmapped; mine stay
-    P2p *x = env->p2p;
-    if (!x) return;
-    (void)hipSetDevice(env->cfg.device);
-    for (hipStream_t st : x->push) if (st) { (void)hipStreamSynchronize(st); }
-    if (x->ctrl) (void)hipStreamSynchronize(x->ctrl);
-    for (char *&d : x->peer_dst) if (d) { (void)hipIpcCloseMemHandle(d); d = nullptr; }
-    for (uint32_t *&f : x->peer_flags) if (f) { (void)hipIpcCloseMemHandle(f); f = nullptr; }
-    x->connected = false;
-}
-
-static void p2p_free(rc_env *env) {
-    P2p *x = env->p2p;
-    if (!x) return;
-    p2p_disconnect(env);
-    for (hipStream_t st : x->push) if (st) (void)hipStreamDestroy(st);
-    if (x->ctrl) (void)hipStreamDestroy(x->ctrl);
-    for (hipEvent_t e : {x->ev_ready, x->ev_go, x->ev_arrived, x->ev_local}) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : x->ev_sent) if (e) (void)hipEventDestroy(e);
-    if (x->dst) (void)hipFree(x->dst);
-    if (x->flags) (void)hipFree(x->flags);
-    delete x;
-    env->p2p = nullptr;
-}
-
-int rc_p2p_setup(rc_env *env, int32_t mode, int32_t rank, int32_t world, void *export_out, size_t bytes) {
-    if (!env || !export_out) return fail(RC_ERR_INVALID, "NULL argument");
-    if (bytes < RC_P2P_EXPORT_BYTES) return fail(RC_ERR_INVALID, "export buffer must hold %d bytes", RC_P2P_EXPORT_BYTES);
-    if (world < 1 || world > RC_P2P_MAX_RANKS || rank < 0 || rank >= world)
-        return fail(RC_ERR_INVALID, "rank %d outside world of %d (at most %d ranks)", rank, world, RC_P2P_MAX_RANKS);
-    const size_t n = rc_gather_bytes(env, mode);
-    if (n == 0) return fail(RC_ERR_INVALID, "unknown gather mode %d", mode);
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    if (P2p *x = env->p2p) {
-        // Already set up: only the payload changes.  The buffers, their exports and the peers' mappings stay - they are
-        // sized for the largest payload, and exporting fresh allocations again and again is what the runtime likes least
-        // (a re-export at a recycled address failed with "invalid argument" now and then).  Sequence numbers run on.
-        if (x->rank != rank || x->world != world) return fail(RC_ERR_INVALID, "set up as rank %d of %d: rc_p2p_teardown first", x->rank, x->world);
-        for (hipStream_t st : x->push) HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipStreamSynchronize(x->ctrl));
-        x->mode = mode; x->bytes = n;
-        std::memcpy(export_out, &x->blob, sizeof(x->blob));
-        return RC_OK;
-    }
-    P2p *x = new (std::nothrow) P2p();
-    if (!x) return fail(RC_ERR_NOMEM, "out of host memory");
-    env->p2p = x;
-    x->rank = rank; x->world = world; x->mode = mode; x->bytes = n;
-    x->cap = align_up(std::max(n, env->layout.slab_bytes), 256);
-    x->peer_dst.assign(world, nullptr);
-    x->peer_flags.assign(world, nullptr);
-    x->push.assign(world, nullptr);
-    x->ev_sent.assign(world, nullptr);
-#define P2P_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { p2p_free(env); return fail(RC_ERR_HIP, "%s failed: %s (payload %zu B x %d ranks)", #expr, hipGetErrorString(_e), n, world); } } while (0)
-    P2P_TRY(hipMalloc((void **)&x->dst, 2 * (size_t)world * x->cap));
-    // the flags are written by other GPUs' kernels and polled by this one's: uncached memory, so that a poll sees them
-    P2P_TRY(hipExtMallocWithFlags((void **)&x->flags, 4096, hipDeviceMallocUncached));
-    P2P_TRY(hipMemset(x->flags, 0, 4096));
-    for (int p = 0; p < world; ++p) P2P_TRY(hipStreamCreateWithFlags(&x->push[p], hipStreamNonBlocking));
-    P2P_TRY(hipStreamCreateWithFlags(&x->ctrl, hipStreamNonBlocking));
-    for (hipEvent_t *e : {&x->ev_ready, &x->ev_go, &x->ev_arrived, &x->ev_local}) P2P_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    for (int p = 0; p < world; ++p) if (p != rank) P2P_TRY(hipEventCreateWithFlags(&x->ev_sent[p], hipEventDisableTiming));
-    P2pExport &ex = x->blob;
-    std::memset(&ex, 0, sizeof(ex));
-    P2P_TRY(hipIpcGetMemHandle(&ex.dst, x->dst));
-    P2P_TRY(hipIpcGetMemHandle(&ex.flags, x->flags));
-    ex.bytes = x->cap; ex.rank = rank; ex.world = world; ex.mode = 0; ex.pid = (int32_t)getpid();
-    P2P_TRY(hipDeviceGetPCIBusId(ex.pci, sizeof(ex.pci), env->cfg.device));
-    std::memcpy(export_out, &ex, sizeof(ex));
-    return RC_OK;
-}
-
-int rc_p2p_connect(rc_env *env, const void *exports, size_t bytes) {
-    if (!env || !exports) return fail(RC_ERR_INVALID, "NULL argument");
-    P2p *x = env->p2p;
-    if (!x) return fail(RC_ERR_INVALID, "rc_p2p_setup has not been called on this handle");
-    if (x->connected) return RC_OK;                      // (a mode switch: the peers' buffers are mapped already)
-    if (bytes < (size_t)x->world * RC_P2P_EXPORT_BYTES) return fail(RC_ERR_INVALID, "need %d export blobs of %d bytes", x->world, RC_P2P_EXPORT_BYTES);
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    for (int p = 0; p < x->world; ++p) {
-        P2pExport ex;
-        std::memcpy(&ex, (const char *)exports + (size_t)p * RC_P2P_EXPORT_BYTES, sizeof(ex));
-        if (ex.rank != p || ex.world != x->world || ex.bytes != x->cap) {
-            p2p_disconnect(env);
-            return fail(RC_ERR_INVALID, "export blob %d does not match (rank %d, world %d, %llu bytes per slot entry; mine %zu)", p, ex.rank, ex.world,
-                        (unsigned long long)ex.bytes, x->cap);
-        }
-        if (p == x->rank) continue;
-        // a peer on another GPU: let this device's copy engines and kernels reach its memory
-        int pdev = -1;
-        if (hipDeviceGetByPCIBusId(&pdev, ex.pci) == hipSuccess && pdev >= 0 && pdev != env->cfg.device) {
-            hipError_t pe = hipDeviceEnablePeerAccess(pdev, 0);
-            if (pe != hipSuccess && pe != hipErrorPeerAccessAlreadyEnabled) {
-                p2p_disconnect(env);
-                return fail(RC_ERR_HIP, "hipDeviceEnablePeerAccess(%d) failed: %s", pdev, hipGetErrorString(pe));
-            }
-            (void)hipGetLastError();
-        }
-        // (a failure half way leaves nothing mapped: the call can be repeated)
-        hipError_t oe = hipIpcOpenMemHandle((void **)&x->peer_dst[p], ex.dst, hipIpcMemLazyEnablePeerAccess);
-        if (oe == hipSuccess) oe = hipIpcOpenMemHandle((void **)&x->peer_flags[p], ex.flags, hipIpcMemLazyEnablePeerAccess);
-        if (oe != hipSuccess) {
-            p2p_disconnect(env);
-            return fail(RC_ERR_HIP, "hipIpcOpenMemHandle of rank %d's buffers failed: %s", p, hipGetErrorString(oe));
-        }
-    }
-    x->connected = true;
-    return RC_OK;
-}
-
-int rc_gather_trajectory_p2p(rc_env *env) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    P2p *x = env->p2p;
-    if (!x || !x->connected) return fail(RC_ERR_INVALID, "rc_p2p_setup / rc_p2p_connect have not been called on this handle");
-    const void *src;
-    size_t n;
-    int rc = gather_source(env, x->mode, &src, &n);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    const uint32_t k = x->issued, seq = k + 1u;
-    // slot k & 1 of every rank: world entries of `cap` bytes, of which the current payload fills the first n
-    const size_t slot_off = (size_t)(k & 1u) * x->world * x->cap, mine = slot_off + (size_t)x->rank * x->cap;
-    // everything below is ordered behind what the env's stream holds now: the step that produced the record, and the
-    // caller's use of the slot that gather k overwrites (the buffer of gather k - 2)
-    HIP_TRY(hipEventRecord(x->ev_ready, env->stream));
-    HIP_TRY(hipStreamWaitEvent(x->ctrl, x->ev_ready, 0));
-    // 1. tell every peer that its gather k may be written into my slot k & 1 ...
-    RcP2pPost post;
-    std::memset(&post, 0, sizeof(post));
-    post.n = x->world; post.value = seq;
-    for (int p = 0; p < x->world; ++p) post.flag[p] = p == x->rank ? nullptr : x->peer_flags[p] + RC_P2P_MAX_RANKS + x->rank;
-    HIP_TRY(rck_p2p_post(post, x->ctrl));
-    // 2. ... and wait until every peer has said the same to me (posting comes first on every rank: no cycle)
-    HIP_TRY(rck_p2p_wait(x->released(), x->world, x->rank, seq, x->timeouts(), RC_P2P_TIMEOUT_S, x->ctrl));
-    HIP_TRY(hipEventRecord(x->ev_go, x->ctrl));
-    // 3. my record into every peer's slot, one stream (one link) per peer, each followed by its arrival flag
-    for (int p = 0; p < x->world; ++p) {
-        hipStream_t st = x->push[p];
-        if (p == x->rank) {
-            HIP_TRY(hipStreamWaitEvent(st, x->ev_ready, 0));
-            HIP_TRY(hipMemcpyAsync(x->dst + mine, src, n, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipEventRecord(x->ev_local, st));
-            continue;
-        }
-        HIP_TRY(hipStreamWaitEvent(st, x->ev_go, 0));
-        HIP_TRY(hipMemcpyAsync(x->peer_dst[p] + mine, src, n, hipMemcpyDefault, st));
-        RcP2pPost arrived;
-        std::memset(&arrived, 0, sizeof(arrived));
-        arrived.n = 1; arrived.value = seq;
-        arrived.flag[0] = x->peer_flags[p] + x->rank;
-        HIP_TRY(rck_p2p_post(arrived, st));
-        HIP_TRY(hipEventRecord(x->ev_sent[p], st));
-    }
-    // 4. arrival of every peer's shard in my slot: polled on the control stream, behind the release handshake
-    HIP_TRY(rck_p2p_wait(x->arrived(), x->world, x->rank, seq, x->timeouts(), RC_P2P_TIMEOUT_S, x->ctrl));
-    HIP_TRY(hipStreamWaitEvent(x->ctrl, x->ev_local, 0));
-    // 5. ... and the DEPARTURE of mine: `ev_arrived` stands for "gather k is complete as far as this rank can tell" - the peers'
-    // shards are here AND my outbound copies have read the source to the end - so that a caller who puts its stream behind it
-    // (rc_gather_p2p_wait, host_sync 0) may let the next step but one rewrite the source, as with rc_gather_trajectory
-    for (int p = 0; p < x->world; ++p) if (p != x->rank) HIP_TRY(hipStreamWaitEvent(x->ctrl, x->ev_sent[p], 0));
-    HIP_TRY(hipEventRecord(x->ev_arrived, x->ctrl));
-    x->issued = seq;
-    return RC_OK;
-}
-
-int rc_gather_p2p_wait(rc_env *env, int32_t host_sync, void **gathered_dev, size_t *gathered_bytes) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    P2p *x = env->p2p;
-    if (!x || !x->connected) return fail(RC_ERR_INVALID, "rc_p2p_setup / rc_p2p_connect have not been called on this handle");
-    if (x->issued == 0) return fail(RC_ERR_INVALID, "no gather has been issued");
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(hipStreamWaitEvent(env->stream, x->ev_arrived, 0));       // later work on the env's stream sees the gathered bytes
-    if (host_sync) {
-        HIP_TRY(hipEventSynchronize(x->ev_arrived));
-        // my record has left when my copies are done (the peers' arrival flags follow them on the same streams)
-        for (int p = 0; p < x->world; ++p) HIP_TRY(hipStreamSynchronize(x->push[p]));
-        uint32_t late = 0;
-        HIP_TRY(hipMemcpy(&late, x->timeouts(), sizeof(late), hipMemcpyDeviceToHost));
-        if (late != 0) {
-            // reported once: the counter starts again (everything queued has run: the streams were synchronised above).  A
-            // release wait that timed out has let its copies go into slots that were never released: the records of this
-            // and of the previous gather are not to be trusted, on any rank - tear the transport down and set it up again
-            HIP_TRY(hipMemset(x->timeouts(), 0, sizeof(uint32_t)));
-            return fail(RC_ERR_COMM, "peer-copy gather: %u flag wait(s) timed out after %.0f s (a peer did not post); the gathered "
-                        "slots are not valid - rc_p2p_teardown and set up again", late, (double)RC_P2P_TIMEOUT_S);
-        }
-    }
-    if (gathered_dev) *gathered_dev = x->dst + (size_t)((x->issued - 1u) & 1u) * x->world * x->cap;
-    if (gathered_bytes) *gathered_bytes = (size_t)x->world * x->cap;
-    return RC_OK;
-}
-
-int rc_p2p_slot(rc_env *env, int32_t back, void **gathered_dev, size_t *gathered_bytes) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    P2p *x = env->p2p;
-    if (!x) return fail(RC_ERR_INVALID, "rc_p2p_setup has not been called on this handle");
-    if (back < 0 || back > 1 || x->issued < (uint32_t)back + 1u) return fail(RC_ERR_INVALID, "no gather %d before the last one (issued: %u)", back, x->issued);
-    if (gathered_dev) *gathered_dev = x->dst + (size_t)((x->issued - 1u - (uint32_t)back) & 1u) * x->world * x->cap;
-    if (gathered_bytes) *gathered_bytes = (size_t)x->world * x->cap;
-    return RC_OK;
-}
-
-int rc_p2p_disconnect(rc_env *env) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    p2p_disconnect(env);
-    return RC_OK;
-}
-
-int rc_p2p_teardown(rc_env *env) {
-    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    p2p_free(env);
     return RC_OK;
 }
 

@@ -18,7 +18,7 @@
 // that only the second one changes.  The running row cursor is kept twice, by call parity: every workgroup reads
 // cursor[call & 1], workgroup 0 writes cursor[(call + 1) & 1] - no workgroup can see the value of the next call.
 // Sums that do not depend on order (skipped, abandoned, envs_at_quota) are 64-bit atomicAdd, one per wave.
-#include "racecar_episode.h"
+#include "racecar_env.h"
 
 namespace {
 
@@ -194,3 +194,126 @@ hipError_t rck_launch_episode_reset(const RcEpisodeDev &d, const uint8_t *mask_d
     hipLaunchKernelGGL(rc_episode_reset_kernel, dim3(blocks), dim3(RC_EP_BLOCK), 0, s, d, mask_dev);
     return hipGetLastError();
 }
+
+// ---- the launches behind a step's dynamics and a reset, and the entry points (include/racecar_hip.h, rc_episode_log_*)
+// The log reads the arena the outputs point at NOW (rc_set_arena re-points them between steps) and the current track ids.
+void episode_bind(rc_env *env) {
+    RcEpisodeDev &d = env->ep;
+    const RcOutDev &o = env->params.out;
+    d.reward = o.reward; d.progress_total = o.progress_total; d.time = o.time; d.lap = o.lap;
+    d.done = o.done; d.trunc = o.trunc; d.wall = o.wall; d.opp = o.opp; d.wrong = o.wrong; d.fresh = o.fresh;
+    d.ts_n = env->params.ts_n;
+    d.ts_track = env->params.ts_n > 0 ? env->params.ts_track : nullptr;
+    d.call = (uint32_t)env->ep_calls;
+}
+
+// After the dynamics launch and before the scan: the few fields the log reads are the ones that launch has just written (they
+// are still in L2; behind the scan's 280 MB of rows they would not be), and the scan does not depend on the log.
+int episode_step(rc_env *env) {
+    episode_bind(env);
+    KernelTimer t;
+    int rc = t.begin(env, kTimeEpisodeLog, true);
+    if (rc) return rc;
+    HIP_TRY(rck_launch_episode_step(env->ep, env->stream));
+    if ((rc = t.end())) return rc;
+    env->ep_calls += 1;
+    return RC_OK;
+}
+
+extern "C" {
+
+static_assert(sizeof(rc_episode_row) == 48 && sizeof(RcEpisodeRow) == sizeof(rc_episode_row), "rc_episode_row is 48 bytes");
+
+int rc_episode_log_enable(rc_env *env, int64_t capacity_rows, int32_t max_episodes) {
+    if (capacity_rows < 1) return fail(RC_ERR_INVALID, "rc_episode_log_enable: capacity_rows must be >= 1 (got %lld)", (long long)capacity_rows);
+    if (max_episodes < 0) return fail(RC_ERR_INVALID, "rc_episode_log_enable: max_episodes must be >= 0 (got %d)", max_episodes);
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    const size_t B = (size_t)env->cfg.num_envs, N = (size_t)env->n_cars, blocks = (B + RC_EP_BLOCK - 1) / RC_EP_BLOCK;
+    RcEpisodeDev &d = env->ep;
+    if (!env->ep_mem) {
+        // counters [8] | cursor [2] | ordinal, length, track [B] | ret, prog_max, time_max [N] | block counts | active [B] | wrong_seen [N]
+        const size_t bytes = 10 * 8 + 3 * B * 4 + 3 * N * 4 + blocks * 4 + B + N;
+        HIP_TRY(hipMalloc(&env->ep_mem, bytes));
+        HIP_TRY(hipMemsetAsync(env->ep_mem, 0, bytes, env->stream));      // active = 0: every env starts counting at its next reset
+        d = RcEpisodeDev{};
+        d.counters = (unsigned long long *)env->ep_mem;
+        d.cursor = d.counters + 8;
+        d.ordinal = (uint32_t *)(d.cursor + 2);
+        d.length = (int32_t *)(d.ordinal + B);
+        d.track = d.length + B;
+        d.ret = (float *)(d.track + B);
+        d.prog_max = d.ret + N;
+        d.time_max = d.prog_max + N;
+        d.block_counts = (uint32_t *)(d.time_max + N);
+        d.active = (uint8_t *)(d.block_counts + blocks);
+        d.wrong_seen = d.active + B;
+        d.num_envs = env->cfg.num_envs;
+        d.cars_per_env = env->cfg.cars_per_env;
+        d.first_env = (uint32_t)env->cfg.first_env;
+    }
+    if (!env->ep_rows || d.capacity != (unsigned long long)capacity_rows) {
+        if (env->ep_rows) {
+            HIP_TRY(hipStreamSynchronize(env->stream));       // (launches that write the old rows may still be queued)
+            HIP_TRY(hipFree(env->ep_rows));
+            env->ep_rows = nullptr;
+            env->ep_on = false;
+        }
+        if (hipMalloc(&env->ep_rows, (size_t)capacity_rows * sizeof(RcEpisodeRow)) != hipSuccess) {
+            env->ep_rows = nullptr;
+            return fail(RC_ERR_NOMEM, "rc_episode_log_enable: no device memory for %lld rows", (long long)capacity_rows);
+        }
+        d.rows = (RcEpisodeRow *)env->ep_rows;
+        d.capacity = (unsigned long long)capacity_rows;
+    }
+    d.max_episodes = (uint32_t)max_episodes;
+    env->ep_on = true;
+    return rc_episode_log_clear(env);
+}
+
+int rc_episode_log_disable(rc_env *env) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->ep_mem) return RC_OK;
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(hipStreamSynchronize(env->stream));
+    HIP_TRY(hipFree(env->ep_mem));
+    env->ep_mem = nullptr;
+    if (env->ep_rows) HIP_TRY(hipFree(env->ep_rows));
+    env->ep_rows = nullptr;
+    env->ep_on = false;
+    env->ep = RcEpisodeDev{};
+    return RC_OK;
+}
+
+int rc_episode_log(rc_env *env, void **rows_dev, size_t *capacity_rows, void **counters_dev, size_t *counters_bytes) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->ep_on) return fail(RC_ERR_INVALID, "rc_episode_log: the episode log is not enabled (rc_episode_log_enable)");
+    if (rows_dev) *rows_dev = env->ep_rows;
+    if (capacity_rows) *capacity_rows = (size_t)env->ep.capacity;
+    if (counters_dev) *counters_dev = env->ep.counters;
+    if (counters_bytes) *counters_bytes = RC_EPC_COUNT * sizeof(uint64_t);
+    return RC_OK;
+}
+
+int rc_episode_log_clear(rc_env *env) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->ep_on) return fail(RC_ERR_INVALID, "rc_episode_log_clear: the episode log is not enabled (rc_episode_log_enable)");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    const RcEpisodeDev &d = env->ep;
+    HIP_TRY(hipMemsetAsync(d.rows, 0, (size_t)d.capacity * sizeof(RcEpisodeRow), env->stream));
+    HIP_TRY(hipMemsetAsync(d.counters, 0, 10 * 8, env->stream));                                  // the counters and the cursor pair
+    HIP_TRY(hipMemsetAsync(d.ordinal, 0, (size_t)env->cfg.num_envs * 4, env->stream));
+    env->ep_calls = 0;
+    return RC_OK;
+}
+
+int rc_episode_log_time(rc_env *env, double *total_ms, uint64_t *launches) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    int rc = drain_events(env);
+    if (rc) return rc;
+    if (total_ms) *total_ms = env->k_ms[kTimeEpisodeLog];
+    if (launches) *launches = env->k_n[kTimeEpisodeLog];
+    return RC_OK;
+}
+
+}  // extern "C"

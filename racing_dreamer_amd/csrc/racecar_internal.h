@@ -1,7 +1,8 @@
-// Internal structures shared by the C-ABI layer (racecar_abi.hip) and the kernels
-// (racecar_kernels.hip).  Not part of the public interface.
+// Internal structures and launcher declarations shared by the units with entry points (racecar_env.h) and the units with
+// kernels.  Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #define RC_NSTEP_MAX 16                        // longest n_step_progress window (sub-steps)
@@ -199,8 +200,16 @@ struct RcP2pPost {               // one store per lane: flag[p] = value (null en
 hipError_t rck_p2p_post(const RcP2pPost &post, hipStream_t s);
 hipError_t rck_p2p_wait(const uint32_t *flags, int n, int skip, uint32_t value, uint32_t *timeouts, double limit_s, hipStream_t s);
 
-// kernel launchers (racecar_kernels.hip); all asynchronous on `s`
+// kernel launchers (racecar_kernels.hip, racecar_tracks.hip, racecar_agents.hip, racecar_gather.hip); all asynchronous on `s`
 void rck_set_launch_events(hipEvent_t start, hipEvent_t stop);   // attach start / stop timestamps to the NEXT launch of this thread
+void rck_take_launch_events(hipEvent_t *start, hipEvent_t *stop);   // ... and take them back (null, null if none were set)
+// A launch that carries the pending events, if any (the pair is this thread's, defined once in racecar_kernels.hip)
+template <typename K, typename... Args>
+inline void launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
+    hipEvent_t a, b;
+    rck_take_launch_events(&a, &b);
+    hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, s, a, b, 0u, args...);
+}
 hipError_t rck_set_lds_limits(size_t lds_bytes);
 const char *rck_lab_abi_string();   // sizes of RcParams / RcLaunchInfo + the hash of the headers: what a lab library must have been built against
 const char *rck_lab_unavailable();   // nullptr if the lab library (scan variants 0-6, stamps build: racecar_lab.hip) can be used, else why not
@@ -214,9 +223,7 @@ hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStrea
 hipError_t rck_launch_set_pose(const RcParams &p, const float *xyyaw_dev, hipStream_t s);
 hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
 hipError_t rck_launch_patch(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
-// track set (rc_set_track_set): the dynamics / reset with a track per env, the track-major car list, the scan and the render
-hipError_t rck_launch_ts_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s);
-hipError_t rck_launch_ts_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s);
+// track set (rc_set_track_set): the track-major car list, the scan and the render (the dynamics and the reset above go by RcParams::ts_n)
 hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s);
 hipError_t rck_launch_ts_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
 hipError_t rck_launch_ts_patch(const RcParams &p, const RcLaunchInfo &li, size_t lds_bytes, hipStream_t s);

@@ -21,31 +21,12 @@
 #include <string>
 
 #include "racecar_scan.h"      // the traversal and scan_car (shared with the lab library, racecar_lab.hip)
+#include "racecar_car.h"          // Car, wall_hit, obb_overlap (shared with the spawn-table builder, racecar_tracks.hip)
 #include "racecar_patch_exact.h"   // obs_type lidar_occupancy_reference
 
 #define RC_PATCH 64
 
 namespace {
-
-__device__ __forceinline__ void cell_of(const RcTrackDev &t, float wx, float wy, int &ix, int &iy) {
-    ix = (int)floorf((wx - t.org_x) * t.inv_res);
-    iy = (int)floorf((wy - t.org_y) * t.inv_res);
-}
-
-__device__ __forceinline__ float progress_at(const RcTrackDev &t, float wx, float wy) {
-    int ix, iy;
-    cell_of(t, wx, wy, ix, iy);
-    // branch-free (an off-grid car reads cell (0, 0) and discards it), so the load is issued next to the footprint's
-    const bool inb = (unsigned)ix < (unsigned)t.w && (unsigned)iy < (unsigned)t.h;
-    const float pr = t.progress[inb ? iy * t.w + ix : 0];
-    return inb ? pr : -1.0f;
-}
-
-struct Car {
-    float x, y, th, ct, st, v, dl, om, ac, pr, rew;
-    int lap, cp;
-    int wall, opp, wrong, done, trunc, fresh;
-};
 
 // What rc_patch_car_kernel needs of a car (RcStateDev::patch_pose): the start cell, the pixel step of the 64 x 64 patch in
 // 16.16 cells (heading = + column, 3.125 cells per pixel) - or the mark of an all-zero patch: the first observation of an
@@ -61,161 +42,12 @@ __device__ __forceinline__ int4 patch_pose_of(const RcTrackDev &t, float x, floa
     return make_int4((fresh != 0 || !sane) ? RC_PATCH_SKIP : icx, icy, a, b);
 }
 
-// Footprint perimeter vs occupancy (H5): the 34 border points of the 12 x 7 body lattice (0.05 m pitch, rear axle at
-// lattice node (2, 3)) in 16.16 fixed-point cell coordinates - oracle/racecar_oracle.py, _wall_hit.  With the lattice
-// vectors e = rne(65536 k (cos, sin)) and f = (-e.y, e.x) a point is two integer multiply-adds of the rear-axle
-// position, its cell two shifts, and "outside the grid counts as wall" is one unsigned min per axis: a negative or
-// too large index clamps to the last row / column, which belongs to the sentinel ring and is always set.  About 10
-// vector instructions per point, all 34 words requested back to back and waited for once (the fp32 rotation +
-// floor + bounds select of the first version took 30 per point: 2/3 of the kernel, which runs one wave per SIMD and
-// is therefore bound by its own instruction stream).
-__device__ __forceinline__ int wall_hit(const RcTrackDev &t, const Car &c) {
-    const float k = RCS_FOOT_STEP * t.inv_res;
-    const float gx = (c.x - t.org_x) * t.inv_res, gy = (c.y - t.org_y) * t.inv_res;
-    const bool bad = !(fabsf(gx) <= 8192.0f && fabsf(gy) <= 8192.0f);      // not a position: counts as contact
-    const int ex = (int)__builtin_rintf((c.ct * k) * 65536.0f), ey = (int)__builtin_rintf((c.st * k) * 65536.0f);
-    const int x0 = (int)__builtin_rintf(gx * 65536.0f), y0 = (int)__builtin_rintf(gy * 65536.0f);
-    const uint32_t wm1 = (uint32_t)(t.w - 1), hm1 = (uint32_t)(t.h - 1);
-    uint32_t hit = bad ? 1u : 0u;
-    auto probe = [&](int li, int lj) {
-        const int px = x0 + (li - 2) * ex - (lj - 3) * ey, py = y0 + (li - 2) * ey + (lj - 3) * ex;
-        const uint32_t ix = min((uint32_t)(px >> 16), wm1), iy = min((uint32_t)(py >> 16), hm1);
-        hit |= t.ray_words[iy * (uint32_t)t.pitch + (ix >> 5)] >> (ix & 31u);
-    };
-#pragma unroll
-    for (int i = 0; i < 12; ++i) { probe(i, 0); probe(i, 6); }
-#pragma unroll
-    for (int j = 1; j < 6; ++j) { probe(0, j); probe(11, j); }
-    return (int)(hit & 1u);
-}
-
-// Oriented-rectangle overlap by separating axes (car-car collision, H5/H18).
-__device__ __forceinline__ int obb_overlap(const Car &a, const Car &b) {
-    const float ax = a.x + RCS_BOX_CX * a.ct, ay = a.y + RCS_BOX_CX * a.st;
-    const float bx = b.x + RCS_BOX_CX * b.ct, by = b.y + RCS_BOX_CX * b.st;
-    const float dx = bx - ax, dy = by - ay;
-    const float c = fabsf(a.ct * b.ct + a.st * b.st);
-    const float s = fabsf(a.st * b.ct - a.ct * b.st);
-    const float ra = RCS_BOX_HL + (RCS_BOX_HL * c + RCS_BOX_HW * s);
-    const float rb = RCS_BOX_HW + (RCS_BOX_HL * s + RCS_BOX_HW * c);
-    bool sep = fabsf(dx * a.ct + dy * a.st) > ra;
-    sep |= fabsf(dy * a.ct - dx * a.st) > rb;
-    sep |= fabsf(dx * b.ct + dy * b.st) > ra;
-    sep |= fabsf(dy * b.ct - dx * b.st) > rb;
-    return sep ? 0 : 1;
-}
-
 // Reset of one env in two halves.  `prepare_reset` is everything that does not depend on how the current step ends -
 // the Philox draw keyed by (global env id, episode counter) and the gather of the spawn poses - so the dynamics kernel
 // issues it next to the state loads, ahead of the integrator, instead of behind the step (that kernel runs one wave
 // per SIMD: its duration is the length of its dependent chain, and a reset used to add three round trips to it in
 // nearly every wave of a random-action rollout).  `apply_reset` installs the prepared poses when the env did finish.
 struct Spawn { float x, y, th, ct, st, pr; int cp; };
-
-// The spawn table (RcTrackDev::spawn): per row the pose, sin / cos of its heading (the spec's sincos32), the progress value of
-// its cell, its checkpoint (+ the anchor bin of a multi-car start, see below), and the room a random start has there - computed
-// once per track ON THE DEVICE with the very functions a reset would call, so the centre-line part of a reset is one 32-byte
-// gather with no arithmetic behind it.
-//   Row i is centre-line bin u(i) = the first USABLE bin among i, i + 1, ... (around the lap, RCS_SPAWN_SAFE_SEARCH of them; i if
-// none): usable = the footprint test of H5 on the bin's own pose finds no wall (oracle: spawn_usable, spawn_rows).  On hand-drawn
-// maps with boxes on the track the most central cell of a BFS distance bin can lie where a car does not fit; no start goes there.
-//   Lateral room (oracle: spawn_width): d2 = squared cell distance from the point's cell to the nearest cell that is not drivable
-// (outside the grid included) in the window of +- RCS_SPAWN_CLEAR_R cells, at most (R + 1)^2;
-// w = clamp(isqrt(d2) * res - RCS_SPAWN_MARGIN, 0, RCS_SPAWN_W_MAX) - integers up to the last two operations.
-//   Heading room (oracle: spawn_heading_room): RCS_HEADING_JITTER where w > 0 (the margin holds for every heading); where w = 0,
-// HEADING_ROOM[k], k = the smallest over the 34 footprint points of isqrt(squared cell distance to the nearest non-drivable cell
-// within +- RCS_SPAWN_FOOT_R), capped at 5.  The row's last word holds w if w > 0, else - (heading room): one float, no bit fields.
-__device__ __forceinline__ void foot_cell(const RcTrackDev &t, float x, float y, float ct, float st, int li, int lj, int &ix, int &iy) {
-    const float k = RCS_FOOT_STEP * t.inv_res;
-    const float gx = (x - t.org_x) * t.inv_res, gy = (y - t.org_y) * t.inv_res;
-    const int ex = (int)__builtin_rintf((ct * k) * 65536.0f), ey = (int)__builtin_rintf((st * k) * 65536.0f);
-    const int x0 = (int)__builtin_rintf(gx * 65536.0f), y0 = (int)__builtin_rintf(gy * 65536.0f);
-    ix = (x0 + (li - 2) * ex - (lj - 3) * ey) >> 16;
-    iy = (y0 + (li - 2) * ey + (lj - 3) * ex) >> 16;
-}
-
-template <typename F>
-__device__ __forceinline__ void for_each_foot_point(F &&f) {
-    for (int i = 0; i < 12; ++i) { f(i, 0); f(i, 6); }
-    for (int j = 1; j < 6; ++j) { f(0, j); f(11, j); }
-}
-
-__device__ __noinline__ bool bin_usable(const RcTrackDev &t, int i) {
-    Car c;
-    c.x = t.centerline[4 * i]; c.y = t.centerline[4 * i + 1];
-    sincos32(t.centerline[4 * i + 2], c.st, c.ct);
-    return wall_hit(t, c) == 0;
-}
-
-__global__ __launch_bounds__(256) void rc_build_spawn_kernel(RcTrackDev t, float4 *__restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const int n = t.n_centerline;
-    if (i >= n) return;
-    int u = i;
-    for (int s = 0; s < RCS_SPAWN_SAFE_SEARCH && s < n; ++s)
-        if (bin_usable(t, (i + s) % n)) { u = (i + s) % n; break; }
-    const float x = t.centerline[4 * u], y = t.centerline[4 * u + 1], th = t.centerline[4 * u + 2];
-    float sn, cs;
-    sincos32(th, sn, cs);
-    float pr = progress_at(t, x, y);
-    pr = pr < 0.0f ? 0.0f : pr;
-    int cp = (int)(pr * (float)RCS_N_CHECKPOINTS);
-    cp = cp < RCS_N_CHECKPOINTS - 1 ? cp : RCS_N_CHECKPOINTS - 1;
-    auto clearance2 = [&](int ix, int iy, int R) {           // squared cell distance to the nearest non-drivable cell within +- R
-        int d2 = (R + 1) * (R + 1);
-        if (!((unsigned)ix < (unsigned)t.w && (unsigned)iy < (unsigned)t.h)) return 0;
-        for (int dy = -R; dy <= R; ++dy)
-            for (int dx = -R; dx <= R; ++dx) {
-                const int jx = ix + dx, jy = iy + dy;
-                const bool inside = (unsigned)jx < (unsigned)t.w && (unsigned)jy < (unsigned)t.h;
-                const bool blocked = !inside || bit_at(t.drv_words, t.pitch, jx, jy) == 0;
-                const int q = dx * dx + dy * dy;
-                d2 = (blocked && q < d2) ? q : d2;
-            }
-        return d2;
-    };
-    auto isqrt = [](int d2) { int k = 0; while ((k + 1) * (k + 1) <= d2) ++k; return k; };
-    int ix, iy;
-    cell_of(t, x, y, ix, iy);
-    const float w = clampf((float)isqrt(clearance2(ix, iy, RCS_SPAWN_CLEAR_R)) * t.res - RCS_SPAWN_MARGIN, 0.0f, RCS_SPAWN_W_MAX);
-    float room = w;
-    if (!(w > 0.0f)) {
-        int kmin = RCS_SPAWN_FOOT_R;
-        for_each_foot_point([&](int li, int lj) {
-            int px, py;
-            foot_cell(t, x, y, cs, sn, li, lj, px, py);
-            const int k = isqrt(clearance2(px, py, RCS_SPAWN_FOOT_R));
-            kmin = k < kmin ? k : kmin;
-        });
-        const float rooms[6] = RCS_HEADING_ROOM_INIT;
-        room = -rooms[kmin];
-    }
-    // Where a multi-car start drawn at this bin really goes (oracle: spawn_safe): the first bin j among i, i + 1, ... (around the
-    // lap, RCS_SPAWN_SAFE_SEARCH of them) at which the centre-line poses of RC_MAX_CARS cars RCS_BALL_GAP_BINS apart touch no wall
-    // and do not overlap pairwise; i itself if there is none.  Where the progress grid's wavefronts fold (columbia_slam's last bins
-    // run back along the bins before them) bins 1.2 m apart along the table are centimetres apart on the ground.
-    int safe = i;
-    for (int s = 0; s < RCS_SPAWN_SAFE_SEARCH && s < n; ++s) {
-        const int j = (i + s) % n;
-        Car c[4];
-        int clash = 0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) {
-            int idx = (j - a * RCS_BALL_GAP_BINS) % n;
-            if (idx < 0) idx += n;
-            c[a].x = t.centerline[4 * idx]; c[a].y = t.centerline[4 * idx + 1];
-            sincos32(t.centerline[4 * idx + 2], c[a].st, c[a].ct);
-            clash |= bin_usable(t, idx) ? 0 : 1;
-        }
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = a + 1; b < 4; ++b) clash |= obb_overlap(c[a], c[b]);
-        if (!clash) { safe = j; break; }
-    }
-    out[2 * i] = make_float4(x, y, th, cs);
-    out[2 * i + 1] = make_float4(sn, pr, __int_as_float(cp | (safe << 8)), room);      // checkpoint < 256; the bin above it
-}
 
 __device__ __forceinline__ float unit_pm1(uint32_t w) { return ((float)(w >> 8) * 5.9604644775390625e-8f) * 2.0f - 1.0f; }   // [-1, 1), exact
 
@@ -764,132 +596,6 @@ __global__ __launch_bounds__(256) void rc_selftest_rcp_kernel(uint32_t exp_lo, u
     if (bad) atomicAdd(mismatches, bad);
 }
 
-// ---- First-trip table (RcTrackDev::first_rect) --------------------------------------------------------------
-// All 1080 rays of a car start in the same cell, so the FIRST rectangle of every ray can come from a much richer
-// table than the four quadrant planes without any cache cost: a car reads one 512-byte line per step.  Per cell
-// the line holds RC_FIRST_PLANES = 4 quadrants x RC_FIRST_BINS entries, the bin being the ray's slope |dy / dx|
-// in eight steps per octave over 2^-4 .. 2^4 (the outer bins open-ended): exactly what the scan gets from the float
-// bits of |dy| * |1 / dx| (exponent and three mantissa bits) in two instructions.  An entry is a rectangle anchored at the cell like the plane entries, but
-// it only has to be free INSIDE THE SECTOR that rays of its bin can touch (start point anywhere in the cell, slope
-// anywhere in the bin, both widened by a margin far above the traversal's rounding) - its far corners may lie
-// inside walls.  The exit arithmetic is unchanged: a ray of that bin visits only sector cells before it leaves
-// the rectangle, and those are free.  A ray heading down a diagonal straight thus crosses it in one trip where
-// fully free rectangles need one per stair of the wall.  tools/analysis/skip_stats.py firsttrip-slope / sector: 3.1 trips for the slowest
-// ray of a wave on austria against 4.1 with the quadrant planes alone; specialising the later trips as well
-// would need the big table in L2 and gain little more (tools/analysis/skip_stats.py firsttrip-angle).
-//
-// Bin parameters (set by rck_build_first_table): slope range in the bin's own frame (bins >= RC_FIRST_BINS / 2 are
-// y-dominant and handled with the axes swapped, slope = |dx / dy|) and 1/cos, 1/sin of two sample directions.
-struct RcFirstBin { float s1, s2, ka0, kb0, ka1, kb1; };
-__constant__ RcFirstBin c_first_bins[RC_FIRST_BINS];
-
-// One thread per (cell, quadrant, bin).  Column c of the rectangle (offset along the bin's dominant axis) is touched
-// by rays of the bin in rows floor(s1 (c - 1) - 0.01) .. floor(1 + s2 (c + 1) + 0.01): the ray is inside column c
-// for travelled distances in (c - 1, c + 1) along the dominant axis and starts anywhere in [0, 1]^2.  The first
-// stop cell in that range caps the height of every rectangle that includes the column; among the rectangles
-// (c + 1) x cap(c) the one at whose exit the most sample rays stop is kept, then the one with the largest summed exit
-// distance for two sample directions.
-__global__ __launch_bounds__(256) void rc_build_first_kernel(RcTrackDev t, uint16_t *__restrict__ out) {
-    const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned total = (unsigned)t.h * (unsigned)t.w * RC_FIRST_PLANES;
-    if (gid >= total) return;
-    const int bin = (int)(gid % RC_FIRST_BINS), q = (int)((gid / RC_FIRST_BINS) & 3u);
-    const unsigned cell = gid / RC_FIRST_PLANES;
-    const int ix = (int)(cell % (unsigned)t.w), iy = (int)(cell / (unsigned)t.w);
-    uint16_t &e = out[((size_t)iy * t.cell_pitch + ix) * RC_FIRST_PLANES + q * RC_FIRST_BINS + bin];
-    if (ix == 0 || iy == 0 || ix == t.w - 1 || iy == t.h - 1) { e = 0x0100; return; }     // sentinel ring: "no return"
-    if (bit_at(t.ray_words, t.pitch, ix, iy)) { e = 0; return; }                            // wall
-    const int sx = (q & 1) ? -1 : 1, sy = (q & 2) ? -1 : 1;       // plane group q = (dy < 0) * 2 + (dx < 0)
-    const bool swap = bin >= RC_FIRST_BINS / 2;
-    const RcFirstBin b = c_first_bins[bin];
-    const int cap = 255;
-    int hmax = cap, bw = 1, bh = 1;
-    float best = -1.0f;
-    for (int c = 0; c < cap; ++c) {
-        const int lo = max(0, (int)floorf(b.s1 * (float)max(0, c - 1) - 0.01f));
-        const int hi = min(hmax - 1, (int)floorf(1.0f + b.s2 * (float)(c + 1) + 0.01f));
-        for (int r = lo; r <= hi; ++r) {
-            const int x = swap ? ix + sx * r : ix + sx * c, y = swap ? iy + sy * c : iy + sy * r;
-            const bool stop = (unsigned)x >= (unsigned)t.w || (unsigned)y >= (unsigned)t.h || bit_at(t.ray_words, t.pitch, x, y);
-            if (stop) { hmax = r; break; }
-        }
-        if (hmax <= 0) break;
-        const int pw = swap ? hmax : c + 1, ph = swap ? c + 1 : hmax;          // extents along x and y
-        float sc = fminf((float)pw * b.ka0, (float)ph * b.kb0) + fminf((float)pw * b.ka1, (float)ph * b.kb1);
-        // ... after the number of sample rays (from the cell centre, five slopes across the bin) that STOP where they leave
-        // the rectangle, i.e. whose exit cell is a stop cell: such a ray is finished after one trip, and a wave's round is as
-        // long as its slowest ray (A/B on one box: 0.1845 -> 0.181 ms; the longest rectangle is not the one with the fewest
-        // second trips - thinner sectors from sub-cell start positions made longer rectangles AND more trips)
-        int stops = 0;
-        for (int k = 0; k < 5; ++k) {
-            const float m = b.s1 + (b.s2 - b.s1) * (0.1f + 0.2f * (float)k);         // own-frame slope (rows per column)
-            const float yfar = 0.5f + m * ((float)c + 0.5f);
-            int ec, er;                                                                 // exit cell, own-frame (column, row)
-            if (yfar < (float)hmax) { ec = c + 1; er = (int)floorf(yfar); }
-            else { ec = (int)floorf(0.5f + ((float)hmax - 0.5f) / fmaxf(m, 1e-6f)); er = hmax; }
-            const int x = swap ? ix + sx * er : ix + sx * ec, y = swap ? iy + sy * ec : iy + sy * er;
-            stops += ((unsigned)x >= (unsigned)t.w || (unsigned)y >= (unsigned)t.h || bit_at(t.ray_words, t.pitch, x, y)) ? 1 : 0;
-        }
-        sc += 1.0e4f * (float)stops;
-        if (sc > best) { best = sc; bw = pw; bh = ph; }
-    }
-    e = (uint16_t)(bw | (bh << 8));
-}
-
-// ---- Quadrant planes (RcTrackDev::quad_rect), built on the device --------------------------------------------------
-// Free run length from every cell towards -x and towards +x (capped at 255; 0 on a stop cell): one thread per row.
-__global__ __launch_bounds__(256) void rc_build_runs_kernel(RcTrackDev t, uint8_t *__restrict__ run_neg, uint8_t *__restrict__ run_pos) {
-    const int iy = blockIdx.x * blockDim.x + threadIdx.x;
-    if (iy >= t.h) return;
-    int r = 0;
-    for (int ix = 0; ix < t.w; ++ix) {                          // towards -x: cells ix, ix - 1, ... are free
-        r = bit_at(t.ray_words, t.pitch, ix, iy) ? 0 : min(r + 1, 255);
-        run_neg[(size_t)iy * t.w + ix] = (uint8_t)r;
-    }
-    r = 0;
-    for (int ix = t.w - 1; ix >= 0; --ix) {
-        r = bit_at(t.ray_words, t.pitch, ix, iy) ? 0 : min(r + 1, 255);
-        run_pos[(size_t)iy * t.w + ix] = (uint8_t)r;
-    }
-}
-
-// One thread per (cell, quadrant): among the free rectangles anchored at the cell (width = min over its rows of the free
-// run towards sx) the one with the largest geometric mean of the exit distances of rays at 11.25, 33.75, 56.25 and
-// 78.75 degrees inside the quadrant.
-__global__ __launch_bounds__(256) void rc_build_quad_kernel(RcTrackDev t, const uint8_t *__restrict__ run_neg,
-                                                            const uint8_t *__restrict__ run_pos, uint16_t *__restrict__ out) {
-    const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (unsigned)t.h * (unsigned)t.w * 4u) return;
-    const int q = (int)(gid & 3u);
-    const unsigned cell = gid >> 2;
-    const int ix = (int)(cell % (unsigned)t.w), iy = (int)(cell / (unsigned)t.w);
-    const int sx = (q & 1) ? -1 : 1, sy = (q & 2) ? -1 : 1;       // plane q = (dy < 0) * 2 + (dx < 0)
-    // mirrored storage: a ray heading -x reads its plane with the columns reversed (likewise -y and the rows)
-    const int rx = sx > 0 ? ix : t.w - 1 - ix, ry = sy > 0 ? iy : t.h - 1 - iy;
-    uint16_t &e = out[(size_t)q * (t.quad_plane_bytes / 2) + (size_t)ry * t.cell_pitch + rx];
-    if (ix == 0 || iy == 0 || ix == t.w - 1 || iy == t.h - 1) { e = 0x0100; return; }       // sentinel ring: "no return"
-    if (bit_at(t.ray_words, t.pitch, ix, iy)) { e = 0; return; }                              // wall
-    const uint8_t *run = sx > 0 ? run_pos : run_neg;
-    // 1 / cos and 1 / sin of the four sample directions
-    const float ka[4] = {1.0195911f, 1.2026898f, 1.7999525f, 5.1258309f};
-    const float kb[4] = {5.1258309f, 1.7999525f, 1.2026898f, 1.0195911f};
-    const float log_ka_sum = __logf(ka[0]) + __logf(ka[1]) + __logf(ka[2]) + __logf(ka[3]);
-    int cur = 255, bw = 1, bh = 1;
-    float best = -1.0e30f;
-    for (int n = 1; n <= 255; ++n) {
-        const int y = iy + (n - 1) * sy;
-        if (y < 0 || y >= t.h) break;
-        cur = min(cur, (int)run[(size_t)y * t.w + ix]);
-        // the width only shrinks from here on and the score is at most sum log(width * ka)
-        if (cur == 0 || 4.0f * __logf((float)cur) + log_ka_sum <= best) break;
-        float sc = 0.0f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) sc += __logf(fminf((float)cur * ka[k], (float)n * kb[k]));
-        if (sc > best) { best = sc; bw = cur; bh = n; }
-    }
-    e = (uint16_t)(bw | (bh << 8));
-}
-
 // Variant 7: the traversal of variant 6 with ONE WAVE PER CAR.  The car index is wave-uniform, so the car state
 // comes through scalar loads, everything that depends only on the car (sensor position, start cell, its range
 // test) is computed once instead of once per 64 beams, and the wave walks its car's 1080 beams in 17 rounds of
@@ -1425,402 +1131,6 @@ __global__ __launch_bounds__(1024) void rc_patch_ts_kernel(RcParams p0) {
                     (unsigned)(s1 - s0));
 }
 
-// Follow-the-gap on the device: one wave per car, lane l owns the 13 consecutive beams FTG_LO + 13 l ...
-// Wave-level steps use shuffles only: (value, index) arg-min for the closest return, and an ordered
-// tree reduction of run summaries (leading / trailing / best run of gap beams) for the widest gap.
-#define FTG_LO 135
-#define FTG_N 810
-#define FTG_PER_LANE 13
-#define FTG_BUBBLE 60
-#define FTG_GAP_RANGE 2.0f      // a beam belongs to a gap if its smoothed range exceeds this [m]
-#define FTG_CLIP 6.0f           // ranges are clipped here first (with the 0.19 rad lock the car must see a corner early)
-
-struct RunSummary { int len, pre, suf, best, bstart, all; };
-
-__device__ __forceinline__ RunSummary run_combine(const RunSummary &a, const RunSummary &b, int a_end) {
-    // a covers [.., a_end), b starts at a_end; ties keep the earlier run
-    RunSummary r;
-    r.len = a.len + b.len;
-    r.all = a.all & b.all;
-    r.pre = a.all ? a.len + b.pre : a.pre;
-    r.suf = b.all ? b.len + a.suf : b.suf;
-    const int cross = a.suf + b.pre, cstart = a_end - a.suf;
-    r.best = a.best; r.bstart = a.bstart;
-    if (cross > r.best) { r.best = cross; r.bstart = cstart; }
-    if (b.best > r.best) { r.best = b.best; r.bstart = b.bstart; }
-    return r;
-}
-
-__global__ __launch_bounds__(256) void rc_ftg_kernel(RcParams p, float *__restrict__ actions, float motor_straight,
-                                                      float motor_corner) {
-    const int lane = threadIdx.x & 63;
-    const int car = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (car >= p.n_cars) return;
-    const float *scan = p.out.lidar + (size_t)car * RC_N_BEAMS;
-    const int e0 = lane * FTG_PER_LANE;                              // first element (relative to FTG_LO)
-    // The arc goes through LDS: read from memory with consecutive lanes on consecutive beams (256-byte requests; a lane
-    // reading its own 17 beams directly makes every load touch 52 lines), clipped, then each lane takes its 13 beams
-    // plus a halo of 2 on each side (stride 13 dwords: conflict-free).  Slots -2, -1 and >= FTG_N are zero padding.
-    __shared__ float arc[4][FTG_PER_LANE * 64 + 8];
-    float *row = arc[threadIdx.x >> 6] + 2;
-#pragma unroll
-    for (int k = 0; k < FTG_PER_LANE; ++k) {
-        const int e = lane + 64 * k;
-        float v = 0.0f;
-        if (e < FTG_N) {
-            v = scan[FTG_LO + e];
-            v = v > FTG_CLIP ? FTG_CLIP : v;
-        }
-        row[e] = v;
-    }
-    if (lane < 2) { row[lane - 2] = 0.0f; row[FTG_PER_LANE * 64 + lane] = 0.0f; }
-    __builtin_amdgcn_wave_barrier();                                 // one wave per car: its own LDS writes, in order
-    float r[FTG_PER_LANE + 4];
-#pragma unroll
-    for (int k = 0; k < FTG_PER_LANE + 4; ++k) r[k] = row[e0 + k - 2];
-    float sm[FTG_PER_LANE];
-    float best_v = INFINITY;
-    int best_i = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < FTG_PER_LANE; ++k) {
-        const int e = e0 + k;
-        sm[k] = ((((r[k] + r[k + 1]) + r[k + 2]) + r[k + 3]) + r[k + 4]) * 0.2f;
-        if (e < FTG_N && sm[k] < best_v) { best_v = sm[k]; best_i = e; }
-    }
-    // closest return: wave arg-min, first index wins ties
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        const float ov = __shfl_xor(best_v, off);
-        const int oi = __shfl_xor(best_i, off);
-        if (ov < best_v || (ov == best_v && oi < best_i)) { best_v = ov; best_i = oi; }
-    }
-    const int closest = best_i;
-    // gap beams: positive after the bubble; summarise this lane's 13 beams
-    RunSummary s;
-    s.len = 0; s.pre = 0; s.suf = 0; s.best = 0; s.bstart = e0; s.all = 1;
-    int run = 0;
-#pragma unroll
-    for (int k = 0; k < FTG_PER_LANE; ++k) {
-        const int e = e0 + k;
-        const bool inside = e < FTG_N;
-        const bool gap = inside && sm[k] > FTG_GAP_RANGE && (e < closest - FTG_BUBBLE || e > closest + FTG_BUBBLE);
-        if (inside) {
-            s.len += 1;
-            if (gap) {
-                run += 1;
-                if (run > s.best) { s.best = run; s.bstart = e - run + 1; }
-            } else {
-                if (s.all) s.pre = run;
-                s.all = 0;
-                run = 0;
-            }
-        }
-    }
-    if (s.all) s.pre = run;
-    s.suf = run;
-    // ordered tree reduction: lane i absorbs lane i + off
-    int my_end = e0 + s.len;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        RunSummary o;
-        o.len = __shfl_down(s.len, off); o.pre = __shfl_down(s.pre, off); o.suf = __shfl_down(s.suf, off);
-        o.best = __shfl_down(s.best, off); o.bstart = __shfl_down(s.bstart, off); o.all = __shfl_down(s.all, off);
-        if ((lane & (2 * off - 1)) == 0 && lane + off < 64) {
-            s = run_combine(s, o, my_end);
-            my_end += o.len;
-        }
-    }
-    if (lane == 0) {
-        float motor = 0.0f, steering = 0.0f;
-        if (s.best > 0) {
-            const float centre = (float)FTG_LO + ((float)(2 * s.bstart + s.best - 1)) * 0.5f;
-            const float angle = 2.35619449019234492885f - centre * 0.00436737625568553f;   // 135 deg - i * 270/1079 deg
-            steering = clampf(angle / RCS_STEER_GAIN, -1.0f, 1.0f);          // the command that points the wheels at the gap (+ = right)
-            motor = fabsf(steering) > 0.35f ? motor_corner : motor_straight;
-        }
-        actions[2 * car] = motor;
-        actions[2 * car + 1] = steering;
-    }
-}
-
-// ---- The REFERENCE's follow-the-gap law on the device (ros_agent/agents/follow_the_gap/src/agent.py:128-234 of the
-// reference: disparity extender + percentile heading + P/D steering) - oracle/racecar_oracle.py, follow_the_gap_reference,
-// is the binary32 spec this kernel follows operation for operation; oracle/ftg_reference_port.py restates the node in
-// float64 and tests/golden/ftg_golden.npz pins both to the node's own outputs.  One wave per car; arc element
-// a = ROS beam 179 + a = this build's beam 900 - a, 721 of them, lane l holds a = l + 64 k.
-#define FR_FIRST 179
-#define FR_N 721
-#define FR_HALF 19                      // the 10-degree filter: 39 beams
-#define FR_PER_LANE 12
-// (binary32 values of the oracle's float64 expressions, as hexadecimal literals: no decimal rounding in between)
-constexpr float kFrInc = 0x1.1e3842p-8f;                 // fp32(1.5 pi / 1079) = 0.004367367
-constexpr float kFrAmin = -0x1.2d97c8p+1f;               // fp32(-0.75 pi)
-constexpr float kFrLookahead = 0x1.7ba938p+2f;           // fp32(2 x 7^2 / (2 x 8.26)) = 5.9322033
-constexpr float kFrW2 = 0x1.418c7p-3f;                   // fp32((1.2 x 0.3302)^2) = 0.15700614
-constexpr float kFrMaxSteer = 0x1.aceeap-2f;             // fp32(24 deg)
-constexpr float kFrDeg5 = 0x1.657184p-4f;                // fp32(5 deg)
-
-__device__ __forceinline__ float fr_asin_small(float t) {            // |t| <= 0.5 (cephes asinf)
-    const float z = t * t;
-    const float pz = ((((4.2163199048e-2f * z + 2.4181311049e-2f) * z + 4.5470025998e-2f) * z + 7.4953002686e-2f) * z + 1.6666752422e-1f) * z;
-    return pz * t + t;
-}
-// Correctly rounded binary32 square root for 2^-96 <= x < 2^96 (what the spec's np.sqrt is).  `__fsqrt_rn` compiles to the bare
-// v_sqrt_f32 here, which is good to 1 ulp only: one scan in ~150 000 put an extension's end within that ulp of a beam index and
-// the device agent's heading half a beam off the spec's (found in round 5 on the re-mapped columbia; tests/test_gpu_parity.py).
-// The fix-up is the standard one: with s the instruction's result and s-, s+ its neighbours, the residuals x - s- s and x - s+ s
-// (each ONE fma, exact enough to carry the sign) say on which side of s the root lies.
-__device__ __forceinline__ float fr_sqrt_rn(float x) {
-    const float s = __builtin_amdgcn_sqrtf(x);
-    const float s_dn = __uint_as_float(__float_as_uint(s) - 1u), s_up = __uint_as_float(__float_as_uint(s) + 1u);
-    const float r_dn = __builtin_fmaf(-s_dn, s, x), r_up = __builtin_fmaf(-s_up, s, x);
-    float r = r_dn <= 0.0f ? s_dn : s;
-    r = r_up > 0.0f ? s_up : r;
-    return (x == 0.0f || !(x == x)) ? s : r;                             // (zero and NaN: the instruction's own answer)
-}
-// Device self-test of that (rc_selftest_sqrt): every binary32 in [lo_bits, hi_bits] against the double-precision root rounded once
-__global__ __launch_bounds__(256) void rc_selftest_sqrt_kernel(uint32_t lo_bits, uint32_t hi_bits, unsigned long long *mismatches) {
-    unsigned long long bad = 0;
-    for (uint64_t b = (uint64_t)lo_bits + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; b <= hi_bits; b += (uint64_t)gridDim.x * blockDim.x) {
-        const float x = __uint_as_float((uint32_t)b);
-        bad += __float_as_uint(fr_sqrt_rn(x)) != __float_as_uint((float)sqrt((double)x));
-    }
-    if (bad) atomicAdd(mismatches, bad);
-}
-
-__device__ __forceinline__ float fr_acos(float x) {                  // racecar_oracle.acos32
-    const float ax = fabsf(x);
-    if (!(ax <= 1.0f)) return __builtin_nanf("");
-    if (ax > 0.5f) {
-        const float a = 2.0f * fr_asin_small(fr_sqrt_rn((1.0f - ax) * 0.5f));
-        return x < 0.0f ? 3.14159274101257324f - a : a;
-    }
-    return 1.57079637050628662f - fr_asin_small(x);
-}
-__device__ __forceinline__ float fr_angle(int a) { return (float)(FR_FIRST + a) * kFrInc + kFrAmin; }
-__device__ __forceinline__ int wave_count(bool c) { return __builtin_popcountll(__builtin_amdgcn_ballot_w64(c)); }
-// Reductions over the 64 lanes on the DPP paths of the vector unit (one instruction per step, no LDS crossbar): within rows of
-// 16 by quad permutes and mirrors, then lane 15 of a row into the next (row_bcast:15, rows 1 and 3) and lane 31 into the upper
-// half (row_bcast:31); lane 63 holds the result.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ uint32_t dpp_pull(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, CTRL, ROWS, 0xF, false); }
-template <typename Op>
-__device__ __forceinline__ uint32_t wave_reduce(uint32_t v, Op op) {
-    v = op(v, dpp_pull<0xB1, 0xF>(v));       // quad_perm:[1,0,3,2]
-    v = op(v, dpp_pull<0x4E, 0xF>(v));       // quad_perm:[2,3,0,1]
-    v = op(v, dpp_pull<0x141, 0xF>(v));      // row_half_mirror
-    v = op(v, dpp_pull<0x140, 0xF>(v));      // row_mirror: every lane of a row holds the row's result
-    const uint32_t r1 = dpp_pull<0x142, 0xA>(v);     // (rows not named keep their own value: see the selects)
-    v = (__lane_id() & 16) ? op(v, r1) : v;
-    const uint32_t r2 = dpp_pull<0x143, 0xC>(v);
-    v = (__lane_id() & 32) ? op(v, r2) : v;
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a < b ? a : b; }); }
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) { return wave_reduce(v, [](uint32_t a, uint32_t b) { return a + b; }); }
-
-__global__ __launch_bounds__(256) void rc_ftg_reference_kernel(RcParams p, float *__restrict__ actions, float *__restrict__ prev_heading,
-                                                               float dt, float *__restrict__ detail) {
-    const int lane = threadIdx.x & 63;
-    const int car = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (car >= p.n_cars) return;
-    // Two arrays of 832 floats per wave (6.6 KB: six waves per SIMD).  `ra`: the clipped arc r[a] - overwritten by the window
-    // maxima while they are built, written again from registers afterwards; `jp`: the jumps with 19 mirrored values on each
-    // side (jp[i] = jump[i - 19]), kept to the end.  Both end in zeros (reads beyond the data).
-    constexpr int kBuf = FR_PER_LANE * 64 + 64;
-    __shared__ float lds_a[4][kBuf], lds_b[4][kBuf];
-    float *ra = lds_a[threadIdx.x >> 6], *jp = lds_b[threadIdx.x >> 6];
-    const float *scan = p.out.lidar + (size_t)car * RC_N_BEAMS;
-    // the arc, clipped at the look-ahead distance (agent.py:141-146); consecutive lanes read consecutive beams
-    float rv[FR_PER_LANE];
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) {
-        const int a = lane + 64 * k;
-        float v = 0.0f;
-        if (a < FR_N) {
-            v = scan[900 - a];
-            v = v > 0.0f ? v : 0.0f;                                 // (also turns a NaN into 0)
-            v = v < kFrLookahead ? v : kFrLookahead;
-        }
-        rv[k] = v;
-        ra[a] = v;
-    }
-    ra[FR_PER_LANE * 64 + lane] = 0.0f;
-    jp[kBuf - 128 + lane] = 0.0f;                                    // [704, 768) - the jumps below overwrite what they own -
-    jp[kBuf - 64 + lane] = 0.0f;                                     // and [768, 832)
-    __builtin_amdgcn_wave_barrier();
-    // (758 padded values: 720 jumps + 2 x 19)
-    float jv[FR_PER_LANE];
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) {
-        const int a = lane + 64 * k;
-        jv[k] = a < FR_N - 1 ? fabsf(ra[a + 1] - rv[k]) : 0.0f;     // agent.py:148
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) {
-        const int a = lane + 64 * k;
-        if (a < FR_N - 1) jp[a + FR_HALF] = jv[k];
-        if (k == 0 && a < FR_HALF) jp[FR_HALF - 1 - a] = jv[k];                                  // scipy's 'reflect' border
-        if (k >= 10 && a >= FR_N - 1 - FR_HALF && a < FR_N - 1) jp[2 * (FR_N - 1) - 1 - a + FR_HALF] = jv[k];
-    }
-    __builtin_amdgcn_wave_barrier();
-    // The maximum of every 39-beam window (agent.py:154) by doubling: windows of 2, 4, 8, 16, 32 - each pass one neighbour read
-    // and one maximum per element, in place in `ra` (all reads of a pass before its writes) - and 39 = 32 and 32 seven further
-    // on.  The window of beam a is padded [a, a + 38].
-    // (jumps are >= +0 and never NaN: their bit patterns order like the values, and an integer maximum is ONE instruction
-    // where the floating-point select is a compare and a move)
-    uint32_t *rau = reinterpret_cast<uint32_t *>(ra);
-    const uint32_t *jpu = reinterpret_cast<const uint32_t *>(jp);
-    uint32_t w[FR_PER_LANE], o[FR_PER_LANE];
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) {
-        const int i = lane + 64 * k;
-        const uint32_t x = jpu[i], y = jpu[i + 1];
-        w[k] = y > x ? y : x;
-    }
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) rau[lane + 64 * k] = w[k];
-#pragma unroll
-    for (int sft = 2; sft <= 16; sft <<= 1) {
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < FR_PER_LANE; ++k) o[k] = rau[lane + 64 * k + sft];
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (int k = 0; k < FR_PER_LANE; ++k) {
-            w[k] = o[k] > w[k] ? o[k] : w[k];
-            rau[lane + 64 * k] = w[k];
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    // candidates (agent.py:150-156): a jump that is the maximum of its window and exceeds 0.2 m; bit k of `cbits` = this
-    // lane's element k is one
-    uint32_t cbits = 0u;
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) {
-        const int a = lane + 64 * k;
-        const uint32_t x = rau[a + 7];
-        const uint32_t peak = x > w[k] ? x : w[k];                    // windows [a, a + 31] and [a + 7, a + 38] of the padded array
-        if (a < FR_N - 1 && __float_as_uint(jv[k]) == peak && jv[k] > 0.2f) cbits |= 1u << k;
-    }
-    __builtin_amdgcn_wave_barrier();
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) ra[lane + 64 * k] = rv[k];  // the arc again (rv[] becomes the adjusted arc below)
-    __builtin_amdgcn_wave_barrier();
-    // One candidate at a time, the wave together (their order does not matter: the extension is a minimum).  A candidate is a
-    // disparity if it exceeds nine times the MEDIAN of its window (agent.py:157-159, ends repeated) - and since x -> fl(9 x) is
-    // monotone, "jump > 9 median" holds exactly when at least 20 of the 39 samples satisfy "jump > 9 sample": no sorting.
-    unsigned long long todo = __builtin_amdgcn_ballot_w64(cbits != 0u);
-    while (todo != 0) {
-        const int l = __builtin_ctzll(todo);
-        const uint32_t bits = (uint32_t)__builtin_amdgcn_readlane((int)cbits, l);
-        const int ac = l + 64 * __builtin_ctz(bits);                  // wave-uniform
-        if (lane == l) cbits &= cbits - 1u;
-        if ((bits & (bits - 1u)) == 0u) todo &= todo - 1;
-        int i = ac - FR_HALF + lane;
-        i = i < 0 ? 0 : (i > FR_N - 2 ? FR_N - 2 : i);
-        const float mine = jp[i + FR_HALF];
-        const float jc = jp[ac + FR_HALF];
-        if (wave_count(lane <= 2 * FR_HALF && jc > mine * 9.0f) <= FR_HALF) continue;
-        // extend the nearer side by the half-width of the vehicle as seen at that range (agent.py:165-176)
-        const float near = fminf(fminf(ra[ac > 0 ? ac - 1 : 0], ra[ac]), ra[ac + 1]);
-        const float two = 2.0f * (near * near);
-        const float half = fr_acos((two - kFrW2) / two);
-        int ia = 0, ib = 0;
-        if (half == half) {
-            const float a0 = fr_angle(0), at = fr_angle(ac);
-            const float lo = ((at - half) - a0) / kFrInc, hi = ((at + half) - a0) / kFrInc;
-            ia = (int)lo; ib = (int)hi;
-            ia = ia < 0 ? 0 : (ia > FR_N - 1 ? FR_N - 1 : ia);
-            ib = ib < 0 ? 0 : (ib > FR_N - 1 ? FR_N - 1 : ib);
-        }
-#pragma unroll
-        for (int e = 0; e < FR_PER_LANE; ++e) {
-            const int a = lane + 64 * e;
-            if (a >= ia && a <= ib) rv[e] = __uint_as_float(min(__float_as_uint(rv[e]), __float_as_uint(near)));      // (both >= +0)
-        }
-    }
-    float adj[FR_PER_LANE];
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) adj[k] = lane + 64 * k < FR_N ? rv[k] : INFINITY;   // (slots beyond the arc: above every rank)
-    // the 601st and 602nd smallest adjusted range (agent.py:183, np.percentile at q = 83.3): ranges are >= 0, so their
-    // bit patterns order like the values; binary search on the pattern, counts by ballot.  [lo, lo + 2^bit) always holds
-    // the wanted key (c_lo keys below it, c_hi below its end, c_lo <= 600 < c_hi): once it holds ONE key the search is
-    // over - about half way for a scan's spread of ranges; ties run to the last bit.
-    uint32_t key[FR_PER_LANE];
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) key[k] = __float_as_uint(adj[k]);
-    uint32_t x600 = 0u;
-    int c_lo = 0, c_hi = FR_PER_LANE * 64, bit = 30;
-    for (; bit >= 0; --bit) {
-        const uint32_t trial = x600 | (1u << bit);
-        int below = 0;
-#pragma unroll
-        for (int k = 0; k < FR_PER_LANE; ++k) below += wave_count(key[k] < trial);
-        if (below <= 600) { x600 = trial; c_lo = below; } else c_hi = below;
-        if (c_hi - c_lo == 1) break;
-    }
-    if (bit >= 0) {                                                   // the one key at or above the bucket's start
-        uint32_t only = 0xffffffffu;
-#pragma unroll
-        for (int k = 0; k < FR_PER_LANE; ++k) only = key[k] >= x600 && key[k] < only ? key[k] : only;
-        x600 = wave_min_u32(only);
-    }
-    int not_above = 0;
-    uint32_t next = 0x7f800000u;
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) {
-        not_above += wave_count(key[k] <= x600);
-        if (key[k] > x600 && key[k] < next) next = key[k];
-    }
-    const uint32_t x601 = not_above >= 602 ? x600 : wave_min_u32(next);
-    // NumPy's linear interpolation at virtual index 600.0000000000001: a + (b - a) * 2^-43 in binary64; a binary32 range is
-    // at or above that threshold exactly when it is at or above the threshold rounded UP to binary32
-    const double a64 = (double)__uint_as_float(x600), b64 = (double)__uint_as_float(x601);
-    const double thr = a64 + (b64 - a64) * 1.1368683772161603e-13;
-    float thr32 = (float)thr;
-    if ((double)thr32 < thr) thr32 = __uint_as_float(__float_as_uint(thr32) + 1u);      // (thr >= 0 and finite)
-    int count = 0;
-    uint32_t sum_k = 0u, sum_q = 0u;
-#pragma unroll
-    for (int k = 0; k < FR_PER_LANE; ++k) {
-        const int a = lane + 64 * k;
-        const bool chosen = a < FR_N && adj[k] >= thr32 && adj[k] < RCS_MAX_RANGE;           // np.digitize(...) == 2
-        count += wave_count(chosen);
-        sum_k += chosen ? (uint32_t)a : 0u;
-        sum_q += chosen ? (uint32_t)__builtin_rintf(ra[a] * 524288.0f) : 0u;
-    }
-    sum_k = wave_sum_u32(sum_k);
-    sum_q = wave_sum_u32(sum_q);
-    if (lane == 0) {
-        const float cnt = (float)count;
-        const float heading = (((float)(int)sum_k / cnt) + (float)FR_FIRST) * kFrInc + kFrAmin;          // agent.py:184
-        const float hd = ((float)sum_q / cnt) * (1.0f / 524288.0f);                                 // agent.py:185
-        // agent.py:200-234 with PID.calculate (kp 1.4, kd 0.1): no derivative term on an episode's first command
-        const float prev = p.st.fresh[car] ? __builtin_nanf("") : prev_heading[car];
-        const float d_term = prev == prev ? (0.1f * (prev - heading)) / dt : 0.0f;
-        float steer = 1.4f * heading - d_term;
-        steer = steer > -kFrMaxSteer ? steer : -kFrMaxSteer;
-        steer = steer < kFrMaxSteer ? steer : kFrMaxSteer;
-        float speed = fabsf(steer) > kFrDeg5 ? 6.0f - (fabsf(steer) / kFrMaxSteer) * 1.8f : 6.0f;
-        if (hd < 5.0f) { const float lim = (hd / 5.0f) * 4.0f; speed = lim < speed ? lim : speed; }
-        speed = speed > 1.5f ? speed : 1.5f;
-        prev_heading[car] = heading;
-        // the car's actuators: target speed over its top speed, steering angle over its steering limit
-        float motor = clampf(speed / RCS_MAX_VEL, -1.0f, 1.0f), steering = clampf(steer / RCS_STEER_GAIN, -1.0f, 1.0f);
-        if (p.remap_actions) {                 // the caller's convention is ReduceActionSpace's (wrappers.py:128-130): invert it
-            motor = ((motor - p.act_lo0) * 2.0f) / (p.act_hi0 - p.act_lo0) - 1.0f;
-            steering = ((steering - p.act_lo1) * 2.0f) / (p.act_hi1 - p.act_lo1) - 1.0f;
-        }
-        actions[2 * car] = motor;
-        actions[2 * car + 1] = steering;
-        if (detail != nullptr) {
-            detail[4 * car] = heading; detail[4 * car + 1] = hd; detail[4 * car + 2] = steer; detail[4 * car + 3] = speed;
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void rc_set_pose_kernel(RcParams p, const float *__restrict__ xyyaw) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.n_cars) return;
@@ -1855,180 +1165,13 @@ __global__ __launch_bounds__(256) void rc_random_actions_kernel(float *__restric
 // Kernel timing without extra packets on the queue: the events handed to rck_set_launch_events are attached to the
 // NEXT launch itself (hipExtLaunchKernelGGL: start / stop timestamps of the dispatch, what rocprofv3 reports), where a
 // hipEventRecord before and after costs two barrier packets, ~3 us of device time per timed kernel.
+// (the launch itself: `launch()` in racecar_internal.h, used by every unit)
 namespace {
 thread_local hipEvent_t g_ev_start = nullptr, g_ev_stop = nullptr;
-
-template <typename K, typename... Args>
-inline void launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, Args... args) {
-    const hipEvent_t a = g_ev_start, b = g_ev_stop;
-    g_ev_start = g_ev_stop = nullptr;
-    hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, s, a, b, 0u, args...);
-}
 }  // namespace
 
 void rck_set_launch_events(hipEvent_t start, hipEvent_t stop) { g_ev_start = start; g_ev_stop = stop; }
-// ... and takes them back, for a launch made in another file (racecar_policy.hip)
 void rck_take_launch_events(hipEvent_t *start, hipEvent_t *stop) { *start = g_ev_start; *stop = g_ev_stop; g_ev_start = g_ev_stop = nullptr; }
-
-hipError_t rck_build_quad_planes(const RcTrackDev &t, uint16_t *quad_rect_dev, hipStream_t s) {
-    uint8_t *runs = nullptr;
-    const size_t plane = (size_t)t.h * t.w;
-    hipError_t e = hipMalloc((void **)&runs, 2 * plane);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(rc_build_runs_kernel, dim3((unsigned)((t.h + 255) / 256)), dim3(256), 0, s, t, runs, runs + plane);
-    const long long total = (long long)plane * 4;
-    hipLaunchKernelGGL(rc_build_quad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, t, runs, runs + plane, quad_rect_dev);
-    e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(runs);
-    return e;
-}
-
-hipError_t rck_build_spawn_table(const RcTrackDev &t, float4 *spawn_dev, hipStream_t s) {
-    hipLaunchKernelGGL(rc_build_spawn_kernel, dim3((t.n_centerline + 255) / 256), dim3(256), 0, s, t, spawn_dev);
-    return hipGetLastError();
-}
-
-hipError_t rck_build_first_table(const RcTrackDev &t, uint16_t *first_rect_dev, hipStream_t s) {
-    RcFirstBin bins[RC_FIRST_BINS];
-    // bin b = the float bits of the slope >> RC_FIRST_SHIFT, less RC_FIRST_BIAS: exponent -4 + b / 8 and the top three
-    // mantissa bits b % 8, i.e. the slopes [2^e (1 + m / 8), 2^e (1 + (m + 1) / 8)) - eight LINEAR steps per octave
-    constexpr int kPerOctave = RC_FIRST_BINS / 8, kMantBits = 23 - RC_FIRST_SHIFT;
-    static_assert((1 << kMantBits) == kPerOctave && RC_FIRST_BIAS == (123u << kMantBits), "bins = exponent and top mantissa bits over 2^-4 .. 2^4");
-    auto edge = [](int b) { return std::exp2(-4.0 + (double)(b / kPerOctave)) * (1.0 + (double)(b % kPerOctave) / kPerOctave); };
-    for (int b = 0; b < RC_FIRST_BINS; ++b) {
-        const double lo = edge(b), hi = edge(b + 1);                 // slope |dy / dx| of the bin
-        const bool swap = b >= RC_FIRST_BINS / 2;
-        // slope range in the bin's own frame, widened by 1e-6; the outermost bins are open-ended
-        const double e1 = swap ? 1.0 / hi : lo, e2 = swap ? 1.0 / lo : hi;
-        bins[b].s1 = (b == 0 || b == RC_FIRST_BINS - 1) ? 0.0f : (float)(e1 * (1.0 - 1e-6));
-        bins[b].s2 = (float)(e2 * (1.0 + 1e-6));
-        for (int k = 0; k < 2; ++k) {
-            const double ang = std::atan(lo + (hi - lo) * (k ? 0.75 : 0.25));
-            (k ? bins[b].ka1 : bins[b].ka0) = (float)(1.0 / std::cos(ang));
-            (k ? bins[b].kb1 : bins[b].kb0) = (float)(1.0 / std::sin(ang));
-        }
-    }
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_first_bins), bins, sizeof(bins));
-    if (e != hipSuccess) return e;
-    const long long total = (long long)t.h * t.w * RC_FIRST_PLANES;
-    if (total >= (1LL << 32)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rc_build_first_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, t, first_rect_dev);
-    return hipGetLastError();
-}
-
-
-// Validation of a freshly built track's tables (rc_load_track): the BOUNDED build of the default scan from every cell a
-// sensor can stand in - the centre of every non-stop cell, two opposite headings, so that all 4 x 64 first-trip entries of
-// the cell and both signs of every direction are used - with no output kept.  A ray that uses up its trip budget (a table
-// entry that sends it in circles or off the grid's ring) is counted; the caller refuses the track if any did.
-__global__ __launch_bounds__(256) void rc_validation_poses_kernel(RcTrackDev t, float4 *__restrict__ poses, uint32_t *__restrict__ count) {
-    const unsigned gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= (unsigned)t.h * (unsigned)t.w) return;
-    const int ix = (int)(gid % (unsigned)t.w), iy = (int)(gid / (unsigned)t.w);
-    if (bit_at(t.ray_words, t.pitch, ix, iy)) return;                     // stop cell (wall or ring): no sensor scans from here
-    const float cx = t.org_x + ((float)ix + 0.5f) * t.res, cy = t.org_y + ((float)iy + 0.5f) * t.res;
-    float sn, cs;
-    sincos32(0.3f, sn, cs);
-    const unsigned k = atomicAdd(count, 2u);
-    poses[k] = make_float4(cx - RCS_LIDAR_X * cs, cy - RCS_LIDAR_X * sn, cs, sn);          // sensor at the cell's centre
-    poses[k + 1] = make_float4(cx + RCS_LIDAR_X * cs, cy + RCS_LIDAR_X * sn, -cs, -sn);
-}
-
-hipError_t rck_validate_tables(const RcTrackDev &t, float band, hipStream_t s, unsigned long long *n_scans, unsigned *n_overruns) {
-    const size_t cells = (size_t)t.h * t.w;
-    float4 *poses = nullptr;
-    uint32_t *counters = nullptr, host[2] = {0u, 0u};
-    hipError_t e = hipMalloc((void **)&poses, 2 * cells * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc((void **)&counters, 2 * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemsetAsync(counters, 0, 2 * sizeof(uint32_t), s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(rc_validation_poses_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, t, poses, counters);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, counters, sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && host[0] != 0u) {
-        RcParams p{};
-        p.trk = t;
-        p.trk.band = band; p.trk.band_mh = band - 0.5f; p.trk.band2 = 2.0f * band;
-        p.st.scan_pose = poses;
-        p.num_envs = p.n_cars = (int32_t)host[0];
-        p.cars_per_env = 1;
-        p.scan_overrun = counters + 1;
-        const int threads = 64;
-        hipLaunchKernelGGL((rc_raycast_car_kernel<1, false, true>), dim3(host[0]), dim3(threads), kCarLdsBytes, s, p, 1);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(host, counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-    }
-    if (poses) (void)hipFree(poses);
-    if (counters) (void)hipFree(counters);
-    *n_scans = host[0];
-    *n_overruns = host[1];
-    return e;
-}
-
-// ---- rows out of a ring of arenas (rc_gather_rows: the window gather of replay.TrajectoryRing.sample) --------------------
-// One wave per output row r: the record of car car_idx[r] in ring slot slot_idx[r], field by field, into the field's section
-// of the output (row r of section f at out + sec[f] + r * bpc[f]).  The LiDAR row goes as 270 16-byte vectors, the small
-// fields as words / bytes.
-struct RcGatherRows {
-    size_t src_off[RC_GATHER_MAX_FIELDS], dst_off[RC_GATHER_MAX_FIELDS];
-    uint32_t bpc[RC_GATHER_MAX_FIELDS];
-    int32_t n_fields;
-    // rc_sample_batch (one launch for a whole training batch): fields of `obs_mask` (by position in this table) read
-    // slot_obs_idx instead of slot_idx - a terminal row takes its observation from the record before it - and the first row
-    // of a window that starts an episode (meta[4 w + 3]) gets `reset_word` in the fields of `reset_mask`: the reference's
-    // reset row (action 0, reward 0, discount 1, time 0, progress -1: dreamer/wrappers.py:221-226).  length = 0: plain gather
-    uint32_t obs_mask, reset_mask;
-    uint32_t reset_word[RC_GATHER_MAX_FIELDS];
-    const int32_t *slot_obs_idx, *meta;
-    int32_t length;
-};
-__global__ __launch_bounds__(256) void rc_gather_rows_kernel(const char *__restrict__ ring, size_t slot_bytes, const int32_t *__restrict__ slot_idx,
-                                                             const int32_t *__restrict__ car_idx, int n_rows, RcGatherRows g, char *__restrict__ out) {
-    const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (row >= n_rows) return;
-    const unsigned lane = threadIdx.x & 63u;
-    const size_t slot_plain = (size_t)slot_idx[row] * slot_bytes;
-    const size_t slot_obs = g.length > 0 ? (size_t)g.slot_obs_idx[row] * slot_bytes : slot_plain;
-    const size_t car = (size_t)car_idx[row];
-    const bool reset_row = g.length > 0 && g.reset_mask != 0u && row % g.length == 0 && g.meta[4 * (row / g.length) + 3] != 0;
-    for (int f = 0; f < g.n_fields; ++f) {
-        const uint32_t n = g.bpc[f];
-        const size_t slot = ((g.obs_mask >> f) & 1u) ? slot_obs : slot_plain;
-        const char *src = ring + slot + g.src_off[f] + car * n;
-        char *dst = out + g.dst_off[f] + (size_t)row * n;
-        if (reset_row && ((g.reset_mask >> f) & 1u)) {          // (reset fields are 4 or 8 bytes of float32)
-            for (uint32_t o = lane * 4u; o < n; o += 64u * 4u) *reinterpret_cast<uint32_t *>(dst + o) = g.reset_word[f];
-            continue;
-        }
-        if ((n & 15u) == 0u) {                                   // (sections are 64-byte aligned and n is a multiple of 16: aligned vectors)
-            for (uint32_t o = lane * 16u; o < n; o += 64u * 16u) *reinterpret_cast<v4u *>(dst + o) = *reinterpret_cast<const v4u *>(src + o);
-        } else if ((n & 3u) == 0u) {
-            for (uint32_t o = lane * 4u; o < n; o += 64u * 4u) *reinterpret_cast<uint32_t *>(dst + o) = *reinterpret_cast<const uint32_t *>(src + o);
-        } else {
-            for (uint32_t o = lane; o < n; o += 64u) dst[o] = src[o];
-        }
-    }
-}
-
-hipError_t rck_gather_rows(const void *ring, size_t slot_bytes, const int32_t *slot_idx, const int32_t *car_idx, int n_rows,
-                           const size_t *src_off, const size_t *dst_off, const uint32_t *bpc, int n_fields, void *out, hipStream_t s,
-                           const RcBatchRows *batch) {
-    RcGatherRows g{};
-    g.n_fields = n_fields;
-    for (int f = 0; f < n_fields; ++f) { g.src_off[f] = src_off[f]; g.dst_off[f] = dst_off[f]; g.bpc[f] = bpc[f]; }
-    if (batch != nullptr) {
-        g.obs_mask = batch->obs_mask; g.reset_mask = batch->reset_mask; g.slot_obs_idx = batch->slot_obs_idx; g.meta = batch->meta;
-        g.length = batch->length;
-        for (int f = 0; f < n_fields; ++f) g.reset_word[f] = batch->reset_word[f];
-    }
-    hipLaunchKernelGGL(rc_gather_rows_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, (const char *)ring, slot_bytes, slot_idx, car_idx,
-                       n_rows, g, (char *)out);
-    return hipGetLastError();
-}
 
 // ---- the order in which the scan takes the cars (RcStateDev::order): a counting sort by progress along the track, RC_ORDER_BUCKETS
 // buckets; within a bucket the order is whatever the atomics give - results do not depend on it, every car is scanned on its own.
@@ -2092,88 +1235,6 @@ hipError_t rck_sort_cars(const float *progress_dev, int n_cars, uint32_t *counts
     hipLaunchKernelGGL(rc_order_count_kernel, dim3(blocks), dim3(256), 0, s, progress_dev, n_cars, counts_dev);
     hipLaunchKernelGGL(rc_order_offsets_kernel, dim3(1), dim3(RC_ORDER_BUCKETS), 0, s, counts_dev);
     hipLaunchKernelGGL(rc_order_place_kernel, dim3(blocks), dim3(256), 0, s, progress_dev, n_cars, counts_dev, order_dev);
-    return hipGetLastError();
-}
-
-// ---- window starts of a replay sampler (rc_sample_windows): one wave per window.  Draw (first record, car) - Philox keyed by
-// the caller's seed, counter (window, try, draw) - until the `length` records of that car from ring age t0 on stay inside one
-// episode: no fresh record strictly inside, a fresh LAST record only if it is the episode's terminal one (done, written by
-// auto-reset).  Lanes test the records of the window side by side.  Then the window's rows for rc_gather_rows.
-__global__ __launch_bounds__(256) void rc_sample_windows_kernel(RcSampleWindows a) {
-    const int win = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    if (win >= a.n_windows) return;
-    const int lane = threadIdx.x & 63;
-    int t0 = 0, car = 0;
-    bool ok = false;
-    for (int attempt = 0; attempt < a.max_tries && !ok; ++attempt) {
-        const rcd::u32x4 r = rcd::philox4x32((uint32_t)win, (uint32_t)attempt, a.draw, 0x57494e44u, a.seed_lo, a.seed_hi);
-        t0 = (int)(r.x % (uint32_t)a.n_start);
-        car = (int)(r.y % (uint32_t)a.n_cars);
-        bool bad = false;
-        for (int j = lane; j < a.length; j += 64) {
-            if (j == 0) continue;
-            const size_t slot = (size_t)((a.oldest + t0 + j) % a.capacity) * a.slot_bytes;
-            const bool fresh = a.ring[slot + a.fresh_off + car] != 0;
-            bad |= fresh && (j < a.length - 1 || a.ring[slot + a.done_off + car] == 0);
-        }
-        ok = __builtin_amdgcn_ballot_w64(bad) == 0ull;
-    }
-    if (!ok && lane == 0) atomicAdd(a.failed, 1u);
-    const size_t last = (size_t)((a.oldest + t0 + a.length - 1) % a.capacity) * a.slot_bytes;
-    const bool terminal = a.length > 1 && a.ring[last + a.fresh_off + car] != 0 && a.ring[last + a.done_off + car] != 0;
-    for (int j = lane; j < a.length; j += 64) {
-        const int slot = (a.oldest + t0 + j) % a.capacity;
-        const size_t o = (size_t)win * a.length + j;
-        a.slot_idx[o] = slot;
-        // a terminal row takes its OBSERVATION from the record before it: the new episode's observation is not this episode's
-        a.slot_obs_idx[o] = (terminal && j == a.length - 1) ? (a.oldest + t0 + j - 1) % a.capacity : slot;
-        a.car_idx[o] = car;
-    }
-    if (lane == 0) {
-        const size_t first = (size_t)((a.oldest + t0) % a.capacity) * a.slot_bytes;
-        a.meta[4 * win] = t0; a.meta[4 * win + 1] = car; a.meta[4 * win + 2] = terminal ? 1 : 0;
-        a.meta[4 * win + 3] = a.ring[first + a.fresh_off + car] != 0 ? 1 : 0;          // the window starts an episode
-    }
-}
-
-hipError_t rck_sample_windows(const RcSampleWindows &a, hipStream_t s) {
-    hipLaunchKernelGGL(rc_sample_windows_kernel, dim3((unsigned)((a.n_windows + 3) / 4)), dim3(256), 0, s, a);
-    return hipGetLastError();
-}
-
-// ---- flags of the peer-copy all-gather (rc_gather_trajectory_p2p): sequence numbers in uncached device memory that a
-// PEER's kernel writes (over xGMI) and the owner's kernel polls.  Both kernels are one wave; the poll is bounded (wall
-// clock) and reports a time-out instead of hanging the queue.
-__global__ __launch_bounds__(64) void rc_p2p_post_kernel(RcP2pPost post) {
-    // lane p stores `value` into flag p (a pointer into peer p's flag block, or null)
-    const unsigned l = threadIdx.x;
-    if (l < (unsigned)post.n && post.flag[l] != nullptr)
-        __hip_atomic_store(post.flag[l], post.value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__global__ __launch_bounds__(64) void rc_p2p_wait_kernel(const uint32_t *flags, int n, int skip, uint32_t value, uint32_t *timeouts,
-                                                         unsigned long long limit_ticks) {
-    // lane p waits until flags[p] >= value (sequence numbers only grow); every lane leaves the loop at the deadline
-    const unsigned l = threadIdx.x;
-    const unsigned long long t0 = wall_clock64();
-    bool late = false;
-    if (l < (unsigned)n && (int)l != skip) {
-        while (__hip_atomic_load(flags + l, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < value) {
-            if (wall_clock64() - t0 > limit_ticks) { late = true; break; }
-            __builtin_amdgcn_s_sleep(8);
-        }
-    }
-    if (late) atomicAdd(timeouts, 1u);
-}
-
-hipError_t rck_p2p_post(const RcP2pPost &post, hipStream_t s) {
-    hipLaunchKernelGGL(rc_p2p_post_kernel, dim3(1), dim3(64), 0, s, post);
-    return hipGetLastError();
-}
-
-hipError_t rck_p2p_wait(const uint32_t *flags, int n, int skip, uint32_t value, uint32_t *timeouts, double limit_s, hipStream_t s) {
-    hipLaunchKernelGGL(rc_p2p_wait_kernel, dim3(1), dim3(64), 0, s, flags, n, skip, value, timeouts,
-                       (unsigned long long)(limit_s * 1.0e8));        // wall_clock64 counts at 100 MHz
     return hipGetLastError();
 }
 
@@ -2259,31 +1320,55 @@ const char *rck_lab_unavailable() {
     return reason.c_str();
 }
 
+// Run-time (cars per env, flag) -> template arguments: f gets a std::integral_constant / std::bool_constant and names the
+// instantiation with its ::value.  Only what a launcher below spells is instantiated.
+template <typename F>
+inline void with_cars(int cars_per_env, F &&f) {
+    switch (cars_per_env) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
+template <typename F>
+inline void with_flag(bool on, F &&f) {
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The single-handle scan's instantiations, named in ONE place: what rck_launch_raycast launches and rck_set_lds_limits checks.
+// LiDAR noise has instantiations of its own (the ABI refuses it with the bounded build); the bounded build (a validation band
+// is in force: its trip loop counts its trips) never overlaps; else a small batch (several waves per car, few per SIMD)
+// prepares the next round under the first request.
+using ScanKernel = void (*)(RcParams, int);
+struct ScanChoice { bool noise, guard, overlap; };
+constexpr ScanChoice kScanChoices[] = {{false, false, false}, {false, false, true}, {false, true, false}, {true, false, false}, {true, false, true}};
+template <int A>
+ScanKernel scan_kernel(const ScanChoice &c) {
+    if (c.noise) return c.overlap ? rc_raycast_car_noise_kernel<A, true> : rc_raycast_car_noise_kernel<A, false>;
+    if (c.guard) return rc_raycast_car_kernel<A, false, true>;
+    return c.overlap ? rc_raycast_car_kernel<A, true, false> : rc_raycast_car_kernel<A, false, false>;
+}
+
 hipError_t rck_set_lds_limits(size_t lds_bytes) {
-    hipError_t e;
-    const int b = (int)lds_bytes;
-#define SET(k) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b); if (e != hipSuccess) return e;
-    SET(rc_patch_car_kernel<true>)
-    SET(rc_patch_car_kernel<false>)
-#undef SET
+    hipError_t e = hipSuccess;
     // rc_patch_car_kernel and rc_raycast_car_kernel address their dynamic LDS from LDS address 0: true only while they have
     // no static LDS
-    hipFuncAttributes fa;
-    for (const void *k : {reinterpret_cast<const void *>(rc_patch_car_kernel<true>), reinterpret_cast<const void *>(rc_patch_car_kernel<false>),
-                          reinterpret_cast<const void *>(rc_raycast_car_kernel<1, false, false>), reinterpret_cast<const void *>(rc_raycast_car_kernel<2, false, false>),
-                          reinterpret_cast<const void *>(rc_raycast_car_kernel<3, false, false>), reinterpret_cast<const void *>(rc_raycast_car_kernel<4, false, false>),
-                          reinterpret_cast<const void *>(rc_raycast_car_kernel<1, true, false>), reinterpret_cast<const void *>(rc_raycast_car_kernel<2, true, false>),
-                          reinterpret_cast<const void *>(rc_raycast_car_kernel<3, true, false>), reinterpret_cast<const void *>(rc_raycast_car_kernel<4, true, false>),
-                          reinterpret_cast<const void *>(rc_raycast_car_kernel<1, false, true>), reinterpret_cast<const void *>(rc_raycast_car_kernel<2, false, true>),
-                          reinterpret_cast<const void *>(rc_raycast_car_kernel<3, false, true>), reinterpret_cast<const void *>(rc_raycast_car_kernel<4, false, true>),
-                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<1, false>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<2, false>),
-                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<3, false>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<4, false>),
-                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<1, true>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<2, true>),
-                          reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<3, true>), reinterpret_cast<const void *>(rc_raycast_car_noise_kernel<4, true>)}) {
-        e = hipFuncGetAttributes(&fa, k);
-        if (e != hipSuccess) return e;
-        if (fa.sharedSizeBytes != 0) return hipErrorInvalidValue;
+    auto no_static_lds = [&](const void *k) {
+        hipFuncAttributes fa;
+        if (e == hipSuccess) e = hipFuncGetAttributes(&fa, k);
+        if (e == hipSuccess && fa.sharedSizeBytes != 0) e = hipErrorInvalidValue;
+    };
+    for (const void *k : {reinterpret_cast<const void *>(rc_patch_car_kernel<true>), reinterpret_cast<const void *>(rc_patch_car_kernel<false>)}) {
+        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        no_static_lds(k);
     }
+    for (int cars = 1; cars <= 4; ++cars)
+        with_cars(cars, [&](auto a) {
+            for (const ScanChoice &c : kScanChoices) no_static_lds(reinterpret_cast<const void *>(scan_kernel<decltype(a)::value>(c)));
+        });
+    if (e != hipSuccess) return e;
     {
         std::lock_guard<std::mutex> lock(g_lab_mutex);
         g_lds_limit = lds_bytes > g_lds_limit ? lds_bytes : g_lds_limit;
@@ -2292,57 +1377,52 @@ hipError_t rck_set_lds_limits(size_t lds_bytes) {
     return hipSuccess;
 }
 
-#define DISPATCH_A(A, ...)                                     \
-    switch (A) {                                               \
-        case 1: { constexpr int kA = 1; __VA_ARGS__; } break;  \
-        case 2: { constexpr int kA = 2; __VA_ARGS__; } break;  \
-        case 3: { constexpr int kA = 3; __VA_ARGS__; } break;  \
-        default: { constexpr int kA = 4; __VA_ARGS__; } break; \
-    }
-
+// The dynamics of one handle: by the env's track with a track set, with the vehicle parameters per car while vp_mode is on.
 hipError_t rck_launch_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s) {
     const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
-    if (p.vp_mode != RC_VP_OFF) {
-        DISPATCH_A(p.cars_per_env, launch((rc_dynamics_dr_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
-        return hipGetLastError();
-    }
-    DISPATCH_A(p.cars_per_env, launch((rc_dynamics_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
+    const bool dr = p.vp_mode != RC_VP_OFF;
+    with_cars(p.cars_per_env, [&](auto a) {
+        constexpr int A = decltype(a)::value;
+        auto go = [&](auto kernel) { launch(kernel, dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step); };
+        if (p.ts_n > 0) with_flag(dr, [&](auto d) { go(rc_dynamics_ts_kernel<A, decltype(d)::value>); });
+        else if (dr) go(rc_dynamics_dr_kernel<A>);
+        else go(rc_dynamics_kernel<A>);
+    });
     return hipGetLastError();
 }
 
 hipError_t rck_launch_dynamics_group(const RcGroup &g, int cars_per_env, int repeat, const RcRandomActions &ra, hipStream_t s, bool dr) {
     const int waves = g.wave_start[g.n], blocks = (waves + 3) / 4;
-    if (dr) {
-        DISPATCH_A(cars_per_env, launch((rc_dynamics_dr_group_kernel<kA>), dim3(blocks), dim3(256), 0, s, g.params, g, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
-        return hipGetLastError();
-    }
-    DISPATCH_A(cars_per_env, launch((rc_dynamics_group_kernel<kA>), dim3(blocks), dim3(256), 0, s, g.params, g, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
+    with_cars(cars_per_env, [&](auto a) {
+        constexpr int A = decltype(a)::value;
+        launch(dr ? rc_dynamics_dr_group_kernel<A> : rc_dynamics_group_kernel<A>, dim3(blocks), dim3(256), 0, s, g.params, g, repeat, ra.on, ra.seed_lo,
+               ra.seed_hi, ra.step);
+    });
     return hipGetLastError();
 }
 
 hipError_t rck_launch_raycast_group(const RcGroup &g, int cars_per_env, int split, hipStream_t s, bool noise) {
     const int waves = ((g.wave_start[g.n] + 7) / 8) * 8;     // one wave per workgroup, as the single-handle scan; whole turns of the 8 XCDs
-    if (noise) {
-        if (split > 1) {
-            DISPATCH_A(cars_per_env, launch((rc_raycast_group_noise_kernel<kA, true>), dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s, g.params, g, split));
-        } else {
-            DISPATCH_A(cars_per_env, launch((rc_raycast_group_noise_kernel<kA, false>), dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s, g.params, g, split));
-        }
-        return hipGetLastError();
-    }
-    if (split > 1) {
-        DISPATCH_A(cars_per_env, launch((rc_raycast_group_kernel<kA, true>), dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s, g.params, g, split));
-    } else {
-        DISPATCH_A(cars_per_env, launch((rc_raycast_group_kernel<kA, false>), dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s, g.params, g, split));
-    }
+    with_cars(cars_per_env, [&](auto a) {
+        with_flag(split > 1, [&](auto o) {
+            constexpr int A = decltype(a)::value;
+            constexpr bool O = decltype(o)::value;
+            launch(noise ? rc_raycast_group_noise_kernel<A, O> : rc_raycast_group_kernel<A, O>, dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes, s,
+                   g.params, g, split);
+        });
+    });
     return hipGetLastError();
 }
 
+// The reset of one handle: on the env's next track with a track set.
 hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s) {
     const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
-    if (p.vp_mode == RC_VP_RANDOM)        // the new episode's vehicle parameters first: the draw reads the episode value the reset increments
-        DISPATCH_A(p.cars_per_env, hipLaunchKernelGGL((rc_reset_dr_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
-    DISPATCH_A(p.cars_per_env, launch((rc_reset_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
+    with_cars(p.cars_per_env, [&](auto a) {
+        constexpr int A = decltype(a)::value;
+        if (p.vp_mode == RC_VP_RANDOM)        // the new episode's vehicle parameters first: the draw reads the episode value the reset increments
+            hipLaunchKernelGGL((rc_reset_dr_kernel<A>), dim3(blocks), dim3(threads), 0, s, p, mask_dev);
+        launch(p.ts_n > 0 ? rc_reset_ts_kernel<A> : rc_reset_kernel<A>, dim3(blocks), dim3(threads), 0, s, p, mask_dev);
+    });
     return hipGetLastError();
 }
 
@@ -2352,27 +1432,16 @@ hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, hipStre
         // a lab kernel (superseded variant or the instrumented build): racecar_lab.hip, loaded on first use
         const Lab l = lab();
         if (l.handle == nullptr) return hipErrorSharedObjectInitFailed;      // (rc_set_raycast_variant / rc_debug_scan_stamps refuse before it comes to this)
-        const hipEvent_t a = g_ev_start, b = g_ev_stop;
-        g_ev_start = g_ev_stop = nullptr;
+        hipEvent_t a, b;
+        rck_take_launch_events(&a, &b);
         return (hipError_t)l.launch_raycast(&p, &li, s, a, b);
     }
     const int threads = li.car_threads, per = threads / 64;                     // waves per workgroup
     const long long waves = (long long)p.n_cars * li.car_split;
-    if (p.noise_on) {                 // LiDAR noise: its own instantiations (the ABI refuses it with the bounded build)
-        if (li.car_split > 1) {
-            DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_noise_kernel<kA, true>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
-        } else {
-            DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_noise_kernel<kA, false>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
-        }
-        return hipGetLastError();
-    }
-    if (li.scan_guarded) {            // a validation band is in force: the build whose trip loop counts its trips
-        DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_kernel<kA, false, true>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
-    } else if (li.car_split > 1) {    // small batch, few waves per SIMD: prepare the next round under the first request
-        DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_kernel<kA, true, false>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
-    } else {
-        DISPATCH_A(p.cars_per_env, launch((rc_raycast_car_kernel<kA, false, false>), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split));
-    }
+    const ScanChoice choice = {p.noise_on != 0, li.scan_guarded != 0, li.car_split > 1};
+    with_cars(p.cars_per_env, [&](auto a) {
+        launch(scan_kernel<decltype(a)::value>(choice), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split);
+    });
     return hipGetLastError();
 }
 
@@ -2388,25 +1457,7 @@ hipError_t rck_launch_patch(const RcParams &p, const RcLaunchInfo &li, hipStream
     return hipGetLastError();
 }
 
-// ---- track set launchers
-hipError_t rck_launch_ts_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s) {
-    const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
-    if (p.vp_mode != RC_VP_OFF) {
-        DISPATCH_A(p.cars_per_env, launch((rc_dynamics_ts_kernel<kA, true>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
-    } else {
-        DISPATCH_A(p.cars_per_env, launch((rc_dynamics_ts_kernel<kA, false>), dim3(blocks), dim3(threads), 0, s, p, actions, repeat, ra.on, ra.seed_lo, ra.seed_hi, ra.step));
-    }
-    return hipGetLastError();
-}
-
-hipError_t rck_launch_ts_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s) {
-    const int threads = 256, blocks = (p.num_envs + threads - 1) / threads;
-    if (p.vp_mode == RC_VP_RANDOM)        // (as rck_launch_reset: the draw reads the episode value the reset increments)
-        DISPATCH_A(p.cars_per_env, hipLaunchKernelGGL((rc_reset_dr_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
-    DISPATCH_A(p.cars_per_env, launch((rc_reset_ts_kernel<kA>), dim3(blocks), dim3(threads), 0, s, p, mask_dev));
-    return hipGetLastError();
-}
-
+// ---- track set launchers (the dynamics and the reset: rck_launch_dynamics, rck_launch_reset)
 hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s) {
     const dim3 blocks((unsigned)((p.n_cars + 255) / 256));
     hipLaunchKernelGGL(rc_ts_count_kernel, blocks, dim3(256), 0, s, p);
@@ -2418,14 +1469,14 @@ hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s) {
 hipError_t rck_launch_ts_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s) {
     const int split = li.car_split;
     const long long waves = (((long long)p.n_cars * split + 7) / 8) * 8;      // one wave per workgroup; whole turns of the 8 XCDs
-    const dim3 grid((unsigned)waves), block(64);
-    if (p.noise_on) {
-        if (split > 1) { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, true, true>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
-        else { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, false, true>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
-    } else {
-        if (split > 1) { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, true, false>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
-        else { DISPATCH_A(p.cars_per_env, launch((rc_raycast_ts_kernel<kA, false, false>), grid, block, (size_t)kCarLdsBytes, s, p, split)); }
-    }
+    with_cars(p.cars_per_env, [&](auto a) {
+        with_flag(split > 1, [&](auto o) {
+            constexpr int A = decltype(a)::value;
+            constexpr bool O = decltype(o)::value;
+            launch(p.noise_on ? rc_raycast_ts_kernel<A, O, true> : rc_raycast_ts_kernel<A, O, false>, dim3((unsigned)waves), dim3(64), (size_t)kCarLdsBytes,
+                   s, p, split);
+        });
+    });
     return hipGetLastError();
 }
 
@@ -2456,8 +1507,8 @@ hipError_t rck_launch_ts_patch(const RcParams &p, const RcLaunchInfo &li, size_t
 hipError_t rck_launch_patch_exact(const RcExactParams &p0, int chunk_cars, hipStream_t s) {
     // a chunk of cars at a time: 387 KB of spline coefficients per car in flight (two kernels per chunk: the prefilter, then the
     // rotation + resize); the launch timer spans the first launch's start to the last one's end
-    const hipEvent_t a = g_ev_start, b = g_ev_stop;
-    g_ev_start = g_ev_stop = nullptr;
+    hipEvent_t a, b;
+    rck_take_launch_events(&a, &b);
     RcExactParams p = p0;
     for (int c0 = 0; c0 < p0.n_cars; c0 += chunk_cars) {
         const int n = p0.n_cars - c0 < chunk_cars ? p0.n_cars - c0 : chunk_cars;
@@ -2469,18 +1520,6 @@ hipError_t rck_launch_patch_exact(const RcExactParams &p0, int chunk_cars, hipSt
     return hipGetLastError();
 }
 
-hipError_t rck_launch_ftg(const RcParams &p, float *actions, float motor_straight, float motor_corner, hipStream_t s) {
-    const int threads = 256, blocks = (p.n_cars + 3) / 4;
-    launch(rc_ftg_kernel, dim3(blocks), dim3(threads), 0, s, p, actions, motor_straight, motor_corner);
-    return hipGetLastError();
-}
-
-hipError_t rck_launch_ftg_reference(const RcParams &p, float *actions, float *prev_heading, float dt, float *detail, hipStream_t s) {
-    const int threads = 256, blocks = (p.n_cars + 3) / 4;
-    launch(rc_ftg_reference_kernel, dim3(blocks), dim3(threads), 0, s, p, actions, prev_heading, dt, detail);
-    return hipGetLastError();
-}
-
 hipError_t rck_launch_set_pose(const RcParams &p, const float *xyyaw_dev, hipStream_t s) {
     const int threads = 256, blocks = (p.n_cars + threads - 1) / threads;
     launch(rc_set_pose_kernel, dim3(blocks), dim3(threads), 0, s, p, xyyaw_dev);
@@ -2489,11 +1528,6 @@ hipError_t rck_launch_set_pose(const RcParams &p, const float *xyyaw_dev, hipStr
 
 hipError_t rck_launch_selftest_div6(int blocks, int threads, int per_lane, unsigned long long *mismatches_dev, hipStream_t s) {
     hipLaunchKernelGGL(rc_selftest_div6_kernel, dim3(blocks), dim3(threads), 0, s, 0x243f6a8885a308d3ull, per_lane, mismatches_dev);
-    return hipGetLastError();
-}
-
-hipError_t rck_launch_selftest_sqrt(uint32_t lo_bits, uint32_t hi_bits, unsigned long long *mismatches_dev, hipStream_t s) {
-    hipLaunchKernelGGL(rc_selftest_sqrt_kernel, dim3(4096), dim3(256), 0, s, lo_bits, hi_bits, mismatches_dev);
     return hipGetLastError();
 }
 

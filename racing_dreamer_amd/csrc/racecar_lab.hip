@@ -446,6 +446,7 @@ inline void launch(hipEvent_t a, hipEvent_t b, K kernel, dim3 grid, dim3 block, 
 #define RC_BUILD_ID "unknown"
 #endif
 
+#pragma GCC visibility push(default)      // the lab's interface (entered through dlsym); everything else stays hidden (build.py)
 extern "C" {
 
 // (the marker build.py looks for in the file's bytes: RC_BUILD_ID=<hash of the lab's sources and flags>)
@@ -522,3 +523,4 @@ int rclab_launch_raycast(const RcParams *pp, const RcLaunchInfo *lp, hipStream_t
 }
 
 }  // extern "C"
+#pragma GCC visibility pop

@@ -42,4 +42,3 @@ struct RcPolicyCall {
 
 hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS limit (once per process and device is enough)
 hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);
-void rck_take_launch_events(hipEvent_t *start, hipEvent_t *stop);   // racecar_kernels.hip: the events rck_set_launch_events left

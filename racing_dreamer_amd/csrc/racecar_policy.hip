@@ -9,7 +9,7 @@
 // stride 417 = 33 mod 64 keeps the 32 rows on 32 banks).  A wave takes the 32-column tiles w, w + 4, ... of a layer, all of them
 // over the whole k range with one accumulator each: no split over k, no reduction across waves.  DESIGN.md §4 (rc_policy_kernel) has the
 // arithmetic behind the choice (M = 32 cars per pass over the 4.4 MB of weights) and the measured cost.
-#include "racecar_policy.h"
+#include "racecar_env.h"
 #include "racecar_policy_math.h"
 #include <hip/hip_ext.h>
 
@@ -255,3 +255,152 @@ hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t
     hipExtLaunchKernelGGL(rc_policy_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytes, s, start, stop, 0u, c);
     return hipGetLastError();
 }
+
+// ---- entry points (include/racecar_hip.h): the weight packer, rc_policy_*
+extern "C" {
+
+namespace {
+struct PolShape { const char *name; const rc_policy_array rc_policy_weights::*arr; int rows, cols; bool used, optional; };
+const PolShape kPolShapes[] = {
+    {"gru_kernel", &rc_policy_weights::gru_kernel, 200, 600, true, false}, {"gru_recurrent", &rc_policy_weights::gru_recurrent, 200, 600, true, false},
+    {"gru_bias", &rc_policy_weights::gru_bias, 2, 600, true, false},
+    {"img1_w", &rc_policy_weights::img1_w, 32, 200, true, false}, {"img1_b", &rc_policy_weights::img1_b, 1, 200, true, false},
+    {"img2_w", &rc_policy_weights::img2_w, 200, 200, false, true}, {"img2_b", &rc_policy_weights::img2_b, 1, 200, false, true},
+    {"img3_w", &rc_policy_weights::img3_w, 200, 60, false, true}, {"img3_b", &rc_policy_weights::img3_b, 1, 60, false, true},
+    {"obs1_w", &rc_policy_weights::obs1_w, 1280, 200, true, false}, {"obs1_b", &rc_policy_weights::obs1_b, 1, 200, true, false},
+    {"obs2_w", &rc_policy_weights::obs2_w, 200, 60, true, false}, {"obs2_b", &rc_policy_weights::obs2_b, 1, 60, true, false},
+    {"h0_w", &rc_policy_weights::h0_w, 230, 400, true, false}, {"h0_b", &rc_policy_weights::h0_b, 1, 400, true, false},
+    {"h1_w", &rc_policy_weights::h1_w, 400, 400, true, false}, {"h1_b", &rc_policy_weights::h1_b, 1, 400, true, false},
+    {"h2_w", &rc_policy_weights::h2_w, 400, 400, true, false}, {"h2_b", &rc_policy_weights::h2_b, 1, 400, true, false},
+    {"h3_w", &rc_policy_weights::h3_w, 400, 400, true, false}, {"h3_b", &rc_policy_weights::h3_b, 1, 400, true, false},
+    {"hout_w", &rc_policy_weights::hout_w, 400, 4, true, false}, {"hout_b", &rc_policy_weights::hout_b, 1, 4, true, false},
+    {"hnorm_mean", &rc_policy_weights::hnorm_mean, 1, 4, true, true}, {"hnorm_var", &rc_policy_weights::hnorm_var, 1, 4, true, true},
+    {"hnorm_gamma", &rc_policy_weights::hnorm_gamma, 1, 4, true, true}, {"hnorm_beta", &rc_policy_weights::hnorm_beta, 1, 4, true, true},
+};
+
+// [rows][n_src] (first `take` columns of every one of `gates` groups of `group` columns) -> [rows][gates * ld], zero padded
+void pol_pad(std::vector<float> &dst, size_t at, const float *src, int rows, int n_src, int gates, int group, int take, int ld) {
+    for (int k = 0; k < rows; ++k)
+        for (int g = 0; g < gates; ++g)
+            for (int j = 0; j < take; ++j) dst[at + (size_t)k * gates * ld + (size_t)g * ld + j] = src[(size_t)k * n_src + g * group + j];
+}
+}  // namespace
+
+int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
+    if (!w) return fail(RC_ERR_INVALID, "rc_policy_weights is NULL");
+    if (w->struct_size != sizeof(rc_policy_weights))
+        return fail(RC_ERR_INVALID, "rc_policy_weights.struct_size %u != %zu", w->struct_size, sizeof(rc_policy_weights));
+    int n_norm = 0;
+    for (const PolShape &sh : kPolShapes) {
+        const rc_policy_array &a = w->*(sh.arr);
+        if (!a.data) {
+            if (!sh.optional) return fail(RC_ERR_INVALID, "rc_policy_load: %s is missing", sh.name);
+            continue;
+        }
+        if (a.rows != sh.rows || a.cols != sh.cols)
+            return fail(RC_ERR_INVALID, "rc_policy_load: %s has shape [%d, %d], the agent's is [%d, %d]", sh.name, a.rows, a.cols, sh.rows, sh.cols);
+        n_norm += sh.name[1] == 'n';                      // hnorm_*
+    }
+    if (n_norm != 0 && n_norm != 4) return fail(RC_ERR_INVALID, "rc_policy_load: %d of the four hnorm_* arrays given (all or none)", n_norm);
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    // the padded device image (racecar_policy.h): offsets in floats
+    const size_t LD2 = RC_POLICY_LD200, LD4 = RC_POLICY_LD400, LDG = RC_POLICY_LDGRU, LDS = RC_POLICY_LDSMALL;
+    size_t at = 0;
+    auto take = [&](size_t n) { const size_t o = at; at += (n + 63) / 64 * 64; return o; };
+    const size_t o_img1 = take(32 * LD2), o_img1b = take(LD2), o_gk = take(200 * LDG), o_gr = take(200 * LDG), o_gb = take(2 * LDG),
+                 o_obs1 = take(1280 * LD2), o_obs1b = take(LD2), o_obs2 = take(200 * LDS), o_obs2b = take(LDS),
+                 o_h0 = take(230 * LD4), o_h1 = take(400 * LD4), o_h2 = take(400 * LD4), o_h3 = take(400 * LD4),
+                 o_hb = take(4 * LD4), o_hout = take(400 * LDS), o_houtb = take(LDS), o_norm = take(8);
+    std::vector<float> img(at, 0.0f);
+    pol_pad(img, o_img1, w->img1_w.data, 32, 200, 1, 200, 200, (int)LD2);
+    pol_pad(img, o_img1b, w->img1_b.data, 1, 200, 1, 200, 200, (int)LD2);
+    pol_pad(img, o_gk, w->gru_kernel.data, 200, 600, 3, 200, 200, (int)LD2);
+    pol_pad(img, o_gr, w->gru_recurrent.data, 200, 600, 3, 200, 200, (int)LD2);
+    pol_pad(img, o_gb, w->gru_bias.data, 2, 600, 3, 200, 200, (int)LD2);
+    pol_pad(img, o_obs1, w->obs1_w.data, 1280, 200, 1, 200, 200, (int)LD2);
+    pol_pad(img, o_obs1b, w->obs1_b.data, 1, 200, 1, 200, 200, (int)LD2);
+    pol_pad(img, o_obs2, w->obs2_w.data, 200, 60, 1, 60, RC_POLICY_STOCH, (int)LDS);          // the mean columns only
+    pol_pad(img, o_obs2b, w->obs2_b.data, 1, 60, 1, 60, RC_POLICY_STOCH, (int)LDS);
+    const rc_policy_array *hw[4] = {&w->h0_w, &w->h1_w, &w->h2_w, &w->h3_w}, *hb[4] = {&w->h0_b, &w->h1_b, &w->h2_b, &w->h3_b};
+    const size_t o_h[4] = {o_h0, o_h1, o_h2, o_h3};
+    for (int i = 0; i < 4; ++i) {
+        pol_pad(img, o_h[i], hw[i]->data, hw[i]->rows, 400, 1, 400, 400, (int)LD4);
+        pol_pad(img, o_hb + i * LD4, hb[i]->data, 1, 400, 1, 400, 400, (int)LD4);
+    }
+    pol_pad(img, o_hout, w->hout_w.data, 400, 4, 1, 4, 2, (int)LDS);
+    pol_pad(img, o_houtb, w->hout_b.data, 1, 4, 1, 4, 2, (int)LDS);
+    if (n_norm) {
+        for (int j = 0; j < 2; ++j) {
+            img[o_norm + j] = w->hnorm_mean.data[j];
+            img[o_norm + 2 + j] = std::sqrt(w->hnorm_var.data[j] + 1e-3f);        // binary32: Keras' epsilon, IEEE square root
+            img[o_norm + 4 + j] = w->hnorm_gamma.data[j];
+            img[o_norm + 6 + j] = w->hnorm_beta.data[j];
+        }
+    }
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(rck_policy_prepare());
+    if (!env->pol_mem) HIP_TRY(hipMalloc((void **)&env->pol_mem, at * sizeof(float)));
+    const size_t state_bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
+    if (!env->pol_state) HIP_TRY(hipMalloc((void **)&env->pol_state, state_bytes));
+    HIP_TRY(hipMemcpyAsync(env->pol_mem, img.data(), at * sizeof(float), hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipMemsetAsync(env->pol_state, 0, state_bytes, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
+    const float *m = env->pol_mem;
+    RcPolicyDev &d = env->pol;
+    d.img1_w = m + o_img1; d.img1_b = m + o_img1b; d.gru_k = m + o_gk; d.gru_r = m + o_gr; d.gru_b = m + o_gb;
+    d.obs1_w = m + o_obs1; d.obs1_b = m + o_obs1b; d.obs2_w = m + o_obs2; d.obs2_b = m + o_obs2b;
+    for (int i = 0; i < 4; ++i) { d.h_w[i] = m + o_h[i]; d.h_b[i] = m + o_hb + i * LD4; }
+    d.hout_w = m + o_hout; d.hout_b = m + o_houtb;
+    d.hnorm = n_norm ? m + o_norm : nullptr;
+    return RC_OK;
+}
+
+int rc_policy_unload(rc_env *env) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(hipStreamSynchronize(env->stream));
+    if (env->pol_mem) (void)hipFree(env->pol_mem);
+    if (env->pol_state) (void)hipFree(env->pol_state);
+    env->pol_mem = env->pol_state = nullptr;
+    env->pol = RcPolicyDev{};
+    return RC_OK;
+}
+
+int rc_policy_act(rc_env *env, uint32_t slot_mask) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_act: no policy loaded (rc_policy_load)");
+    if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
+    if (slot_mask == 0) return fail(RC_ERR_INVALID, "rc_policy_act: the slot mask is empty");
+    if (slot_mask >> env->cfg.cars_per_env) return fail(RC_ERR_INVALID, "rc_policy_act: slot mask 0x%x names slots beyond cars_per_env = %d", slot_mask, env->cfg.cars_per_env);
+    if (env->cfg.lidar_transform != RC_LIDAR_METRES) return fail(RC_ERR_INVALID, "rc_policy_act reads the scan in metres (lidar_transform RC_LIDAR_METRES)");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    RcPolicyCall c{};
+    c.w = env->pol;
+    c.lidar = env->params.out.lidar;
+    c.fresh = env->params.out.fresh;
+    c.state = env->pol_state;
+    c.actions = env->actions_in;
+    c.cars_per_env = env->cfg.cars_per_env;
+    for (int a = 0; a < env->cfg.cars_per_env; ++a)
+        if ((slot_mask >> a) & 1u) c.slots |= (uint32_t)a << (8 * c.n_slots++);
+    c.n_active = env->cfg.num_envs * c.n_slots;
+    c.raw_actions = env->cfg.remap_actions != 0;
+    c.lo0 = env->cfg.action_low[0]; c.lo1 = env->cfg.action_low[1]; c.hi0 = env->cfg.action_high[0]; c.hi1 = env->cfg.action_high[1];
+    KernelTimer t;
+    int rc = t.begin(env, RC_K_POLICY);
+    if (rc) return rc;
+    hipEvent_t ea = nullptr, eb = nullptr;
+    rck_take_launch_events(&ea, &eb);
+    HIP_TRY(rck_launch_policy(c, ea, eb, env->stream));
+    return t.end();
+}
+
+int rc_policy_state(rc_env *env, void **dev_ptr, size_t *bytes) {
+    if (!env || !dev_ptr || !bytes) return fail(RC_ERR_INVALID, "NULL argument");
+    if (!env->pol_state) return fail(RC_ERR_INVALID, "rc_policy_state: no policy loaded (rc_policy_load)");
+    *dev_ptr = env->pol_state;
+    *bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
+    return RC_OK;
+}
+
+}  // extern "C"

@@ -25,6 +25,23 @@ def test_every_declared_symbol_is_exported_and_bound(hip_lib):
     assert hip_lib.rc_abi_version() == _lib.RC_ABI_VERSION == 3
 
 
+def test_the_shipped_library_exports_the_abi_and_nothing_else(hip_lib):
+    """The library is built with -fvisibility=hidden: its dynamic function symbols are the prototypes of racecar_hip.h, one for
+    one - no rck_* launcher, no helper of a unit.  (Kernel handles and the compilation-unit ids are data symbols: not looked at.)"""
+    import shutil
+    import subprocess
+    from racing_dreamer_amd import build
+    nm = shutil.which("nm") or shutil.which("llvm-nm")
+    assert nm, "neither nm nor llvm-nm on PATH"
+    out = subprocess.run([nm, "-D", "--defined-only", build.LIB_PATH], check=True, capture_output=True, text=True).stdout
+    functions = [line.split()[-1] for line in out.splitlines() if len(line.split()) >= 3 and line.split()[-2] == "T"]
+    assert functions, out[:400]
+    assert [f for f in functions if not f.startswith("rc_")] == []
+    assert sorted(functions) == _declared_symbols()
+    with open(build.LIB_PATH, "rb") as f:
+        assert build.BUILD_ID_MARK in f.read()                              # rc_build_id_string survives (it is read from the file's bytes)
+
+
 def test_config_struct_matches_header(hip_lib):
     from racing_dreamer_amd import _lib
     cfg = _lib.RcConfig()
@@ -229,9 +246,10 @@ def test_the_shipped_library_carries_no_lab_kernels(hip_lib):
     for name in (b"rc_raycast_kernelILi", b"28rc_raycast_car_stamps_kernelE", b"rc_build_dir_table_kernel", b"g_dir_table"):     # (mangled: kernel symbols)
         assert name not in shipped, name
     assert b"rc_raycast_car_kernelILi1ELb0ELb0E" in shipped                # the scan that is shipped
-    with open(os.path.join(build.CSRC, "racecar_kernels.hip")) as f:
-        text = f.read()
-    assert "RC_EXP_DIR_TABLE" not in text and "cast_ray_dda" not in text
+    for name in build.SOURCES + build.HEADERS:                              # every unit and header the shipped library is made of
+        with open(os.path.join(build.CSRC, name)) as f:
+            text = f.read()
+        assert "RC_EXP_DIR_TABLE" not in text and "cast_ray_dda" not in text, name
     lab = build.build_lab(verbose=False)
     assert not build.lab_needs_build() and build.library_build_id(lab) == build.source_hash(sources=build.LAB_SOURCES)
     import ctypes

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Sensitivity check of the parity tests to the scan's exact-count band (run on the GPU box): with the band shrunk
-# below the rounding bound (racecar_kernels.hip, cast_ray_rects) the corner-aimed test must fail; at the shipped
+# below the rounding bound (racecar_scan.h, ray_traverse) the corner-aimed test must fail; at the shipped
 # width (max(w, h) * 2^-21) it passes.
 for l2 in -40 -26 -24 -22 -21; do
   echo "== band log2 $l2"

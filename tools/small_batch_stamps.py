@@ -2,7 +2,7 @@
 """Where the scan's time goes at a SMALL batch (run on the GPU box): python tools/small_batch_stamps.py [--envs 4096] [--track columbia]
 
 At 65 536 cars the scan is throughput-bound (tools/scan_stamps.py); at 4 096 it is not: its 23 us are the same whether a car's
-17 rounds go to 1, 3 or 17 waves (racecar_abi.hip, the split's measurements).  This tool runs the instrumented scan
+17 rounds go to 1, 3 or 17 waves (racecar_abi.hip, set_launch_geometry: the split's measurements).  This tool runs the instrumented scan
 (`rc_debug_scan_stamps`) at a small batch for several splits and prints (the shader clocks of two CUs are not
 comparable - s_memtime is a per-CU counter -, so slots 6 / 7 hold the chip-wide 100 MHz clock at entry and flush): when waves ENTER
 relative to the first entry (the dispatcher's ramp), how long a wave lives and in which phase, when the last flush is issued and
