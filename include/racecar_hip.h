@@ -327,8 +327,8 @@ int rc_follow_the_gap_reference(rc_env *env, float dt, float *detail_dev);
  * `action`: obs_step from the previous latent and the previous RAW action, feature = [stoch, deter], actor mode;
  * models.py:61-87 RSSM.obs_step / img_step, :339-364 ActionDecoder 'tanh_normal' and actor_version "normalized") - the posterior
  * MEAN instead of a sample and tanh(mean) instead of the best of 100 draws, in the binary32 arithmetic of DESIGN.md §2 item 12
- * (tests/policy_spec.c is its CPU restatement; the device equals it bit for bit).  The sampled agent, the reward head and the
- * decoder are not part of it.
+ * (tests/policy_spec.c is its CPU restatement; the device equals it bit for bit).  rc_policy_set_sampling switches to the
+ * reference's own sampled modes; the reward head and the decoder are not part of it.
  *
  * rc_policy_weights: host pointers and shapes of the checkpoint's arrays in `tf.Module.variables` order (rssm.pkl: 13 arrays,
  * actor.pkl: 10, or 14 with the batch normalisation's four).  One-dimensional arrays have rows = 1. */
@@ -362,6 +362,36 @@ int rc_policy_act(rc_env *env, uint32_t slot_mask);
 /* The agent's state (models.py:61-87: the RSSM's stoch and deter; racing_dreamer.py:76: the previous action), zero-copy:
  * device float32 [n_cars, 232], readable and writable between calls. */
 int rc_policy_state(rc_env *env, void **dev_ptr, size_t *bytes);
+/* The sampled modes: the agent as the reference itself runs it (tests/policy_sample_spec.c is the CPU
+ * restatement, the device equals it bit for bit).
+ *   RC_POLICY_MODE_MEAN     posterior mean, tanh(mean): the deterministic mode above, the default.
+ *   RC_POLICY_MODE_DEPLOY   the deployed / evaluation agent (ros_agent/models/dreamer/racing_dreamer.py:61-80, dreamer/models.py:66-81
+ *                           with training=False, run_evaluation.py): the posterior is SAMPLED (RSSM.obs_step: stoch =
+ *                           Normal(mean, softplus(raw) + 0.1).sample()), the action is SampleDist.mode() - of
+ *                           RC_POLICY_MODE_SAMPLES tanh-normal draws the one with the highest log-probability
+ *                           (dreamer/tools.py:301-321), chosen per car - clipped to +-1.  expl_amount 0 = the reference's eval_noise off.
+ *   RC_POLICY_MODE_EXPLORE  the training-time collector (dreamer/models.py:75-79, 189-202, dream.py:96-99): the posterior sampled,
+ *                           ONE action draw actor(feat).sample(), then additive_gaussian exploration clip(Normal(action,
+ *                           expl_amount).sample(), -1, 1); the clipped action is the command and the next step's previous action.
+ * The draws are Philox4x32-10 keyed by `seed` and counted by (global env id, the env's episode counter, its agent step within the
+ * episode, slot and index): a function of those only - not of the shard (rc_config.first_env), the slot mask or the call history.
+ * Two rc_policy_act calls without a step in between draw the same numbers. */
+#define RC_POLICY_MODE_MEAN 0
+#define RC_POLICY_MODE_DEPLOY 1
+#define RC_POLICY_MODE_EXPLORE 2
+#define RC_POLICY_MODE_SAMPLES 100
+typedef struct rc_policy_sampling {
+    uint32_t struct_size;          /* = sizeof(rc_policy_sampling) */
+    int32_t mode;                  /* RC_POLICY_MODE_* */
+    uint64_t seed;
+    float expl_amount;             /* standard deviation of the additive exploration noise (dream.py:96-99: 0.3 while collecting), >= 0 */
+} rc_policy_sampling;
+/* rc_policy_set_sampling: the mode of the rc_policy_act calls that follow, until it is changed or the policy is unloaded;
+ * rc_policy_load resets it to RC_POLICY_MODE_MEAN.  s = NULL: RC_POLICY_MODE_MEAN.  RC_ERR_INVALID: wrong struct_size, unknown
+ * mode, expl_amount negative or not finite, no policy loaded.  Kernel of the sampled modes: rc_policy_sampled_kernel, timed
+ * under RC_K_POLICY.  rc_policy_get_sampling: what is installed. */
+int rc_policy_set_sampling(rc_env *env, const rc_policy_sampling *s);
+int rc_policy_get_sampling(rc_env *env, rc_policy_sampling *out);
 
 /* ---- Episode log: return, length, progress and time of every episode, kept on the device (opt-in; off = the launches of a step
  * are what they are without it) ---------------------------------------------------------------------------------------------------

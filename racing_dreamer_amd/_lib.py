@@ -78,6 +78,16 @@ class RcPolicyWeights(C.Structure):
     _fields_ = [("struct_size", C.c_uint32)] + [(k, RcPolicyArray) for k in POLICY_KEYS]
 
 
+class RcPolicySampling(C.Structure):
+    """rc_policy_sampling (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("seed", C.c_uint64), ("expl_amount", C.c_float)]
+
+
+POLICY_MODES = {"mean": 0, "deploy": 1, "explore": 2}          # RC_POLICY_MODE_*
+POLICY_MODE_SAMPLES = 100
+POLICY_EXPL_DEFAULT = {"mean": 0.0, "deploy": 0.0, "explore": 0.3}      # eval_noise off; dream.py:96-99 expl_amount
+
+
 def policy_weights(weights):
     """rc_policy_weights over a mapping of float32 arrays (or an .npz path).  Returns (struct, the arrays it points into -
     keep them alive until rc_policy_load has returned)."""
@@ -131,6 +141,8 @@ SYMBOLS = {
     "rc_policy_unload": (C.c_int, [C.c_void_p]),
     "rc_policy_act": (C.c_int, [C.c_void_p, C.c_uint32]),
     "rc_policy_state": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
+    "rc_policy_set_sampling": (C.c_int, [C.c_void_p, _P(RcPolicySampling)]),
+    "rc_policy_get_sampling": (C.c_int, [C.c_void_p, _P(RcPolicySampling)]),
     "rc_episode_log_enable": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "rc_episode_log_disable": (C.c_int, [C.c_void_p]),
     "rc_episode_log": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p), _P(C.c_size_t)]),

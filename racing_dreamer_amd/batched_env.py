@@ -588,11 +588,13 @@ class BatchedRaceEnv:
         del keep
         ptr, nb = C.c_void_p(), C.c_size_t()
         L.check(self._lib.rc_policy_state(self._h, C.byref(ptr), C.byref(nb)))
-        self._policy_array = _BorrowedDeviceArray(ptr.value, (self.n_cars, L.POLICY_STATE), self.device)
-        self._policy_state = torch.utils.dlpack.from_dlpack(self._policy_array)
+        # a second load keeps the first load's wrapper alive: torch reads the DLPack struct again when the tensor made from it
+        # is released, which may be after this call (a view the caller still holds)
+        self._policy_arrays = getattr(self, "_policy_arrays", []) + [_BorrowedDeviceArray(ptr.value, (self.n_cars, L.POLICY_STATE), self.device)]
+        self._policy_state = torch.utils.dlpack.from_dlpack(self._policy_arrays[-1])
 
     def policy_act(self, slots=None) -> torch.Tensor:
-        """One step of the loaded agent, deterministic mode, for every car (or the cars in the listed slots = car indices within
+        """One step of the loaded agent, in the mode of `set_policy_sampling` (deterministic by default), for every car (or the cars in the listed slots = car indices within
         an env, e.g. `slots=(1, 2, 3)`: trained opponents B-D next to a learner in slot A): reads `lidar` and `fresh` in place,
         fills and returns `action_in` in this env's action convention, so `step(None)` applies it."""
         mask = (1 << self.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
@@ -600,6 +602,26 @@ class BatchedRaceEnv:
         L.check(self._lib.rc_policy_act(self._h, C.c_uint32(mask)))
         self._exit()
         return self.views["action_in"]
+
+    def set_policy_sampling(self, mode: str = "mean", seed: int = 0, expl_amount: Optional[float] = None) -> None:
+        """How `policy_act` runs the loaded agent from now on (`rc_policy_set_sampling`; `load_policy` resets it to "mean"):
+        "mean" - posterior mean, tanh(mean), deterministic; "deploy" - the reference's deployed / evaluation agent: sampled
+        posterior, the most probable of 100 action draws (racing_dreamer.py:61-80, tools.py:301-321); "explore" - its
+        training-time collector: sampled posterior, one action draw, additive Gaussian noise of standard deviation
+        `expl_amount`, clipped (models.py:189-202).  `expl_amount=None`: 0 for "deploy", 0.3 for "explore".  The draws depend
+        on (seed, global env id, slot, episode, agent step) only."""
+        if mode not in L.POLICY_MODES:
+            raise ValueError(f"policy sampling mode must be one of {sorted(L.POLICY_MODES)}, got {mode!r}")
+        amount = L.POLICY_EXPL_DEFAULT[mode] if expl_amount is None else float(expl_amount)
+        s = L.RcPolicySampling(C.sizeof(L.RcPolicySampling), L.POLICY_MODES[mode], int(seed) & (2 ** 64 - 1), amount)
+        L.check(self._lib.rc_policy_set_sampling(self._h, C.byref(s)))
+
+    @property
+    def policy_sampling(self) -> dict:
+        """dict(mode, seed, expl_amount) as installed (`rc_policy_get_sampling`)."""
+        s = L.RcPolicySampling()
+        L.check(self._lib.rc_policy_get_sampling(self._h, C.byref(s)))
+        return dict(mode={v: k for k, v in L.POLICY_MODES.items()}[s.mode], seed=int(s.seed), expl_amount=float(s.expl_amount))
 
     @property
     def policy_state(self) -> torch.Tensor:
@@ -1005,6 +1027,15 @@ class MixedTrackEnv:
         mask = (1 << self.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
         self._fork_join(lambda p, blk: p._lib.rc_policy_act(p._h, C.c_uint32(mask)))
         return self.views["action_in"]
+
+    def set_policy_sampling(self, mode: str = "mean", seed: int = 0, expl_amount: Optional[float] = None) -> None:
+        """The same mode and seed on every block (BatchedRaceEnv.set_policy_sampling): the draws are keyed by global env ids."""
+        for p in self.parts:
+            p.set_policy_sampling(mode, seed, expl_amount)
+
+    @property
+    def policy_sampling(self) -> dict:
+        return self.parts[0].policy_sampling
 
     @property
     def policy_state(self) -> torch.Tensor:

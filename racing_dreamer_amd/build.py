@@ -112,6 +112,7 @@ CHECKED_KERNELS = (
     ("rc_raycast_ts_kernel", 8, True, "shipped"),               # (a track set: the same scan and render)
     ("rc_patch_ts_kernel", 8, False, "shipped"),
     ("rc_policy_kernel", None, False, "shipped"),               # (the Dreamer agent: 4 to 6 MFMA accumulator tiles per wave - a spill would sit in its k loops)
+    ("rc_policy_sampled_kernel", None, False, "shipped"),       # (its sampled modes: the same body, plus the draws)
 )
 NO_SPILL_KERNELS = tuple(k for k, _, _, _ in CHECKED_KERNELS)
 MIN_WAVES_PER_SIMD = {k: w for k, w, _, _ in CHECKED_KERNELS if w is not None}

@@ -193,6 +193,8 @@ struct rc_env {
     float *pol_mem = nullptr;
     float *pol_state = nullptr;
     RcPolicyDev pol{};
+    RcPolicySampleDev pol_s{};
+    rc_policy_sampling pol_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};      // rc_policy_set_sampling
     float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
     float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)
     void *order_mem = nullptr;         // RcStateDev::order + the sort's bucket counters (batches of RC_ORDER_MIN_CARS cars and more)

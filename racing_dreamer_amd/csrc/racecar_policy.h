@@ -1,4 +1,4 @@
-// The deterministic Dreamer agent on the device (racecar_policy.hip): what the C-ABI layer and the kernel share.
+// The Dreamer agent on the device (racecar_policy.hip), deterministic and sampled: what the C-ABI layer and the kernel share.
 // Not part of the public interface.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -16,6 +16,9 @@
 #define RC_POLICY_LD400 416
 #define RC_POLICY_LDGRU (3 * RC_POLICY_LD200)
 #define RC_POLICY_LDSMALL 32                                      // obs2 (30 mean columns), hout (2 mean columns)
+// The sampled modes read obs2 and hout from images of their own at ld 64: the mean columns in tile 0, the std columns at the
+// same offsets in tile 1, so that one wave holds mean and raw std of a (car, column) in matching accumulator registers.
+#define RC_POLICY_LDPAIR 64
 
 struct RcPolicyDev {
     const float *img1_w, *img1_b;            // [32][224], [224]
@@ -25,6 +28,13 @@ struct RcPolicyDev {
     const float *h_w[4], *h_b[4];            // [230][416], 3 x [400][416]; [416]
     const float *hout_w, *hout_b;            // [400][32], [32]         the 2 mean columns
     const float *hnorm;                      // [4][2] mean, sqrt(var + eps), gamma, beta of the 2 mean columns; null = plain actor
+};
+
+struct RcPolicySampleDev {                   // what the sampled modes read on top (behind RcPolicyCall's other fields: the
+                                             // deterministic kernel's arguments lie where they lay)
+    const float *obs2_w, *obs2_b;            // [200][64], [64]         mean | std columns
+    const float *hout_w, *hout_b;            // [400][64], [64]
+    const float *hnorm4;                     // [4][4] mean, sqrt(var + eps), gamma, beta of all four output columns; null = plain actor
 };
 
 struct RcPolicyCall {
@@ -38,7 +48,14 @@ struct RcPolicyCall {
     uint32_t slots;                          // slot of the mask's k-th set bit in byte k
     int32_t raw_actions;                     // rc_config.remap_actions: the env maps [-1, 1]^2 itself
     float lo0, lo1, hi0, hi1;                // else: postprocess_action's range
+    // the sampled modes only (rc_policy_set_sampling)
+    int32_t mode;                            // RC_POLICY_MODE_DEPLOY | RC_POLICY_MODE_EXPLORE
+    float expl_amount;
+    uint32_t seed_lo, seed_hi, first_env;
+    const uint32_t *episode;                 // [num_envs] the env's episode counter ...
+    const int32_t *agent_steps;              // ... and its agent steps within the episode, as the last step or reset left them
+    RcPolicySampleDev ws;
 };
 
 hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS limit (once per process and device is enough)
-hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);
+hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);      // c.mode: which kernel

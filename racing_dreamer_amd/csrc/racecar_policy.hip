@@ -1,7 +1,9 @@
 // rc_policy_act: one step of the reference's deployed Dreamer agent (ros_agent/models/dreamer/racing_dreamer.py:61-80 `action`;
 // models.py:61-87 RSSM.obs_step / img_step, :339-364 ActionDecoder) for every car, deterministic mode (posterior mean,
 // tanh(mean)), in the binary32 arithmetic of DESIGN.md §2 item 12: every dense layer is acc = bias, then acc = fmaf(x[k], W[k][j], acc)
-// for k ascending - which is what the f32-input MFMA computes from its C operand.
+// for k ascending - which is what the f32-input MFMA computes from its C operand.  The sampled modes (item 14: the posterior
+// sampled; the best of 100 tanh-normal draws, dreamer/tools.py:301-321, or one draw plus exploration noise, models.py:189-202)
+// are a second instantiation of the same body, rc_policy_sampled_kernel.
 //
 // One workgroup of four waves owns 32 cars = the rows of v_mfma_f32_32x32x2_f32 tiles and runs the whole network on them: the
 // activations stay in two [32][417] LDS buffers (X, Y), the weights are read from L2 straight into the B operand (lane l reads
@@ -24,6 +26,10 @@ constexpr int PD = 4;                          // k-steps (of 2) whose operands 
 constexpr int SCK = 120;                       // beams per staged piece of the scan (9 pieces)
 constexpr int N_BEAMS = 1080;
 constexpr size_t kLdsBytes = (size_t)2 * PM * XS * sizeof(float) + PM * sizeof(int);
+// the sampled modes keep per car, behind `cars`: 36 normals (30 of the posterior, 2 unused, the 4 of block 8), the draw's key
+// (global env, episode, agent step, slot) and the actor's distribution (mu 0, mu 1, sd 0, sd 1)
+constexpr int NS = 36;
+constexpr size_t kLdsBytesSampled = kLdsBytes + (size_t)PM * (NS + 4 + 4) * sizeof(float);
 
 // row q of the call -> car index (the mask's slots of env q / n_slots), -1 past the end
 __device__ __forceinline__ int pm_car(const RcPolicyCall &c, int q) {
@@ -87,6 +93,12 @@ __device__ __forceinline__ int pm_row(int reg, int half) { return (reg & 3) + 8 
 
 enum { PK_ELU = 0, PK_STOCH = 1, PK_ACTION = 2 };
 
+struct PmSampleLds {
+    float *normals;          // [32][NS]
+    uint32_t *key;           // [32][4]
+    float *dist;             // [32][4]
+};
+
 struct PmLayer {
     const float *a;          // LDS input [32][XS], first column of the layer's input
     int k;
@@ -131,16 +143,117 @@ __device__ __forceinline__ void pm_dense_tiles(const RcPolicyCall &c, const PmLa
     }
 }
 
-}  // namespace
+// The two layers whose std columns the sampled modes read (obs2, hout), one wave: mean columns in tile 0, std columns in tile 1
+// of an ld-64 image, so acc[0][r] and acc[1][r] are mean and raw std of the same (car, column).  PK_STOCH: stoch = mean + std n
+// -> the next layer's input and the state; PK_ACTION: the actor's mu and sd -> sm.dist.
+__device__ __forceinline__ void pm_dense_pair(const RcPolicyCall &c, const PmLayer &L, const int *cars, const PmSampleLds &sm, int lane) {
+    const int cc = lane & 31, half = lane >> 5;
+    const int col[2] = {0, 32};
+    pm_f32x16 acc[2];
+    pm_bias<2>(acc, L.b, col, cc);
+    pm_gemm<2>(acc, L.a + cc * XS + half, L.k / 2, L.w + (size_t)half * L.ld + cc, L.ld, col);
+    if (cc >= L.n) return;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int row = pm_row(r, half);
+        if (L.kind == PK_STOCH) {
+            const float sd = pm_softplus(acc[1][r]) + PM_STOCH_MIN_STD;
+            const float v = fmaf(sd, sm.normals[row * NS + cc], acc[0][r]);
+            L.d[row * XS + cc] = v;
+            const int car = cars[row];
+            if (car >= 0) c.state[(size_t)car * RC_POLICY_STATE + cc] = v;
+        } else {
+            float mu, sd;
+            pm_actor_dist(acc[0][r], acc[1][r], c.ws.hnorm4, cc, mu, sd);
+            sm.dist[4 * row + cc] = mu;
+            sm.dist[4 * row + 2 + cc] = sd;
+        }
+    }
+}
 
-__global__ __launch_bounds__(PT) void rc_policy_kernel(RcPolicyCall c) {
+// The action of the sampled modes from sm.dist: 8 lanes per car.  deploy: lane i of the 8 scores the candidates of blocks
+// i, i + 8, ... < 50 (two per block, ascending), the 8 are reduced to the highest score, the lowest index among equals; explore:
+// the one draw of block 8.  Then the exploration noise and the clip, and the command as PK_ACTION writes it.
+__device__ __forceinline__ void pm_sampled_action(const RcPolicyCall &c, const int *cars, const PmSampleLds &sm, int tid) {
+    const int row = tid >> 3, sub = tid & 7;
+    const int car = cars[row];
+    const uint32_t *key = sm.key + 4 * row;
+    const float mu0 = sm.dist[4 * row], mu1 = sm.dist[4 * row + 1], sd0 = sm.dist[4 * row + 2], sd1 = sm.dist[4 * row + 3];
+    float n0 = sm.normals[row * NS + 32], n1 = sm.normals[row * NS + 33];
+    if (c.mode == RC_POLICY_MODE_DEPLOY) {
+        float best = 0.0f;
+        int best_i = -1;
+#pragma unroll 1
+        for (int b = sub; b < PM_CANDIDATES / 2; b += 8) {
+            float n[4];
+            pm_normal_block(key[0], key[1], key[2], key[3], PM_BLOCK_CANDIDATES + (uint32_t)b, c.seed_lo, c.seed_hi, n);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float sc = pm_score_term(n[2 * h], fmaf(sd0, n[2 * h], mu0)) + pm_score_term(n[2 * h + 1], fmaf(sd1, n[2 * h + 1], mu1));
+                if (best_i < 0 || sc > best) { best = sc; best_i = 2 * b + h; }
+            }
+        }
+#pragma unroll
+        for (int m = 1; m < 8; m <<= 1) {
+            const float o = __shfl_xor(best, m);
+            const int oi = __shfl_xor(best_i, m);
+            if (o > best || (o == best && oi < best_i)) { best = o; best_i = oi; }
+        }
+        if (sub == 0) {
+            float n[4];
+            pm_normal_block(key[0], key[1], key[2], key[3], PM_BLOCK_CANDIDATES + (uint32_t)(best_i >> 1), c.seed_lo, c.seed_hi, n);
+            n0 = (best_i & 1) ? n[2] : n[0];
+            n1 = (best_i & 1) ? n[3] : n[1];
+        }
+    }
+    if (sub != 0 || car < 0) return;
+    const float a[2] = {pm_explore(pm_tanh(fmaf(sd0, n0, mu0)), c.expl_amount, sm.normals[row * NS + 34]),
+                        pm_explore(pm_tanh(fmaf(sd1, n1, mu1)), c.expl_amount, sm.normals[row * NS + 35])};
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        c.state[(size_t)car * RC_POLICY_STATE + RC_POLICY_STOCH + RC_POLICY_DETER + j] = a[j];
+        c.actions[2 * (size_t)car + j] = c.raw_actions ? a[j] : pm_postprocess(a[j], j ? c.lo1 : c.lo0, j ? c.hi1 : c.hi0);
+    }
+}
+
+template <bool SAMPLED>
+__device__ __forceinline__ void pm_policy(const RcPolicyCall &c) {
     extern __shared__ float pm_lds[];
     float *X = pm_lds, *Y = pm_lds + PM * XS;
     int *cars = (int *)(pm_lds + 2 * PM * XS);
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, cc = lane & 31, half = lane >> 5;
     const int row0 = blockIdx.x * PM;
+    PmSampleLds sm{};
 
     if (tid < PM) cars[tid] = pm_car(c, row0 + tid);
+    if constexpr (SAMPLED) {
+        // the car's key and its posterior normals: thread (row, block) = (tid / 8, tid % 8) draws block `block`, the thread of
+        // block 0 also block 8 (the single action sample and the exploration noise)
+        sm.normals = (float *)(cars + PM);
+        sm.key = (uint32_t *)(sm.normals + PM * NS);
+        sm.dist = (float *)(sm.key + 4 * PM);
+        const int row = tid >> 3, blk = tid & 7;
+        const int car = pm_car(c, row0 + row);
+        float n[4] = {0.0f, 0.0f, 0.0f, 0.0f}, m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        uint32_t key[4] = {0u, 0u, 0u, 0u};
+        if (car >= 0) {
+            const int e = car / c.cars_per_env;
+            key[0] = c.first_env + (uint32_t)e;
+            key[1] = c.episode[e];
+            key[2] = (uint32_t)c.agent_steps[e];
+            key[3] = (uint32_t)(car - e * c.cars_per_env);
+            pm_normal_block(key[0], key[1], key[2], key[3], (uint32_t)blk, c.seed_lo, c.seed_hi, n);
+            if (blk == 0) pm_normal_block(key[0], key[1], key[2], key[3], PM_BLOCK_ACTION, c.seed_lo, c.seed_hi, m);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            sm.normals[row * NS + 4 * blk + i] = n[i];
+            if (blk == 0) {
+                sm.normals[row * NS + 32 + i] = m[i];
+                sm.key[4 * row + i] = key[i];
+            }
+        }
+    }
     // the latent of the cars: Y[0, 200) = deter, Y[200, 232) = stoch | previous raw action; zero for a car whose observation opens
     // an episode (racing_dreamer.py:66-70: state None) and for rows past the end
     for (int idx = tid; idx < PM * RC_POLICY_STATE; idx += PT) {
@@ -170,7 +283,12 @@ __global__ __launch_bounds__(PT) void rc_policy_kernel(RcPolicyCall c) {
         }
         const int n_tiles = L.ld / 32;
         const int mine = wave < n_tiles ? (n_tiles - wave + 3) / 4 : 0;      // tiles wave, wave + 4, ...
-        if (mine == 1) pm_dense_tiles<1>(c, L, cars, wave, lane);
+        if (SAMPLED && (layer == 1 || layer == 6)) {
+            L.w = layer == 1 ? c.ws.obs2_w : c.ws.hout_w;
+            L.b = layer == 1 ? c.ws.obs2_b : c.ws.hout_b;
+            L.ld = RC_POLICY_LDPAIR;
+            if (wave == 0) pm_dense_pair(c, L, cars, sm, lane);
+        } else if (mine == 1) pm_dense_tiles<1>(c, L, cars, wave, lane);
         else if (mine == 2) pm_dense_tiles<2>(c, L, cars, wave, lane);
         else if (mine == 3) pm_dense_tiles<3>(c, L, cars, wave, lane);
         else if (mine == 4) pm_dense_tiles<4>(c, L, cars, wave, lane);
@@ -244,15 +362,24 @@ __global__ __launch_bounds__(PT) void rc_policy_kernel(RcPolicyCall c) {
         }
         __syncthreads();
     }
+    if constexpr (SAMPLED) pm_sampled_action(c, cars, sm, tid);
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(PT) void rc_policy_kernel(RcPolicyCall c) { pm_policy<false>(c); }
+__global__ __launch_bounds__(PT) void rc_policy_sampled_kernel(RcPolicyCall c) { pm_policy<true>(c); }
+
 hipError_t rck_policy_prepare() {
-    return hipFuncSetAttribute((const void *)rc_policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    const hipError_t e = hipFuncSetAttribute((const void *)rc_policy_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void *)rc_policy_sampled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesSampled);
 }
 
 hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s) {
     const unsigned blocks = (unsigned)((c.n_active + PM - 1) / PM);
-    hipExtLaunchKernelGGL(rc_policy_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytes, s, start, stop, 0u, c);
+    if (c.mode == RC_POLICY_MODE_MEAN) hipExtLaunchKernelGGL(rc_policy_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytes, s, start, stop, 0u, c);
+    else hipExtLaunchKernelGGL(rc_policy_sampled_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytesSampled, s, start, stop, 0u, c);
     return hipGetLastError();
 }
 
@@ -304,13 +431,14 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     if (n_norm != 0 && n_norm != 4) return fail(RC_ERR_INVALID, "rc_policy_load: %d of the four hnorm_* arrays given (all or none)", n_norm);
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
     // the padded device image (racecar_policy.h): offsets in floats
-    const size_t LD2 = RC_POLICY_LD200, LD4 = RC_POLICY_LD400, LDG = RC_POLICY_LDGRU, LDS = RC_POLICY_LDSMALL;
+    const size_t LD2 = RC_POLICY_LD200, LD4 = RC_POLICY_LD400, LDG = RC_POLICY_LDGRU, LDS = RC_POLICY_LDSMALL, LDP = RC_POLICY_LDPAIR;
     size_t at = 0;
     auto take = [&](size_t n) { const size_t o = at; at += (n + 63) / 64 * 64; return o; };
     const size_t o_img1 = take(32 * LD2), o_img1b = take(LD2), o_gk = take(200 * LDG), o_gr = take(200 * LDG), o_gb = take(2 * LDG),
                  o_obs1 = take(1280 * LD2), o_obs1b = take(LD2), o_obs2 = take(200 * LDS), o_obs2b = take(LDS),
                  o_h0 = take(230 * LD4), o_h1 = take(400 * LD4), o_h2 = take(400 * LD4), o_h3 = take(400 * LD4),
-                 o_hb = take(4 * LD4), o_hout = take(400 * LDS), o_houtb = take(LDS), o_norm = take(8);
+                 o_hb = take(4 * LD4), o_hout = take(400 * LDS), o_houtb = take(LDS), o_norm = take(8),
+                 o_obs2s = take(200 * LDP), o_obs2sb = take(LDP), o_houts = take(400 * LDP), o_houtsb = take(LDP), o_norm4 = take(16);
     std::vector<float> img(at, 0.0f);
     pol_pad(img, o_img1, w->img1_w.data, 32, 200, 1, 200, 200, (int)LD2);
     pol_pad(img, o_img1b, w->img1_b.data, 1, 200, 1, 200, 200, (int)LD2);
@@ -329,7 +457,18 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     }
     pol_pad(img, o_hout, w->hout_w.data, 400, 4, 1, 4, 2, (int)LDS);
     pol_pad(img, o_houtb, w->hout_b.data, 1, 4, 1, 4, 2, (int)LDS);
+    // the sampled modes' images: the mean columns in tile 0, the std columns in tile 1 (pol_pad: 2 groups of 30 / 2 columns)
+    pol_pad(img, o_obs2s, w->obs2_w.data, 200, 60, 2, RC_POLICY_STOCH, RC_POLICY_STOCH, 32);
+    pol_pad(img, o_obs2sb, w->obs2_b.data, 1, 60, 2, RC_POLICY_STOCH, RC_POLICY_STOCH, 32);
+    pol_pad(img, o_houts, w->hout_w.data, 400, 4, 2, 2, 2, 32);
+    pol_pad(img, o_houtsb, w->hout_b.data, 1, 4, 2, 2, 2, 32);
     if (n_norm) {
+        for (int j = 0; j < 4; ++j) {
+            img[o_norm4 + j] = w->hnorm_mean.data[j];
+            img[o_norm4 + 4 + j] = std::sqrt(w->hnorm_var.data[j] + 1e-3f);
+            img[o_norm4 + 8 + j] = w->hnorm_gamma.data[j];
+            img[o_norm4 + 12 + j] = w->hnorm_beta.data[j];
+        }
         for (int j = 0; j < 2; ++j) {
             img[o_norm + j] = w->hnorm_mean.data[j];
             img[o_norm + 2 + j] = std::sqrt(w->hnorm_var.data[j] + 1e-3f);        // binary32: Keras' epsilon, IEEE square root
@@ -352,6 +491,8 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     for (int i = 0; i < 4; ++i) { d.h_w[i] = m + o_h[i]; d.h_b[i] = m + o_hb + i * LD4; }
     d.hout_w = m + o_hout; d.hout_b = m + o_houtb;
     d.hnorm = n_norm ? m + o_norm : nullptr;
+    env->pol_s = RcPolicySampleDev{m + o_obs2s, m + o_obs2sb, m + o_houts, m + o_houtsb, n_norm ? m + o_norm4 : nullptr};
+    env->pol_sampling = rc_policy_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};
     return RC_OK;
 }
 
@@ -363,6 +504,32 @@ int rc_policy_unload(rc_env *env) {
     if (env->pol_state) (void)hipFree(env->pol_state);
     env->pol_mem = env->pol_state = nullptr;
     env->pol = RcPolicyDev{};
+    env->pol_s = RcPolicySampleDev{};
+    env->pol_sampling = rc_policy_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};
+    return RC_OK;
+}
+
+int rc_policy_set_sampling(rc_env *env, const rc_policy_sampling *sp) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_set_sampling: no policy loaded (rc_policy_load)");
+    rc_policy_sampling want{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};
+    if (sp) {
+        if (sp->struct_size != sizeof(rc_policy_sampling))
+            return fail(RC_ERR_INVALID, "rc_policy_sampling.struct_size %u != %zu", sp->struct_size, sizeof(rc_policy_sampling));
+        if (sp->mode != RC_POLICY_MODE_MEAN && sp->mode != RC_POLICY_MODE_DEPLOY && sp->mode != RC_POLICY_MODE_EXPLORE)
+            return fail(RC_ERR_INVALID, "rc_policy_set_sampling: unknown mode %d", sp->mode);
+        if (!(sp->expl_amount >= 0.0f) || std::isinf(sp->expl_amount))
+            return fail(RC_ERR_INVALID, "rc_policy_set_sampling: expl_amount %g is not a finite number >= 0", (double)sp->expl_amount);
+        want = *sp;
+    }
+    env->pol_sampling = want;
+    return RC_OK;
+}
+
+int rc_policy_get_sampling(rc_env *env, rc_policy_sampling *out) {
+    if (!env || !out) return fail(RC_ERR_INVALID, "NULL argument");
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_get_sampling: no policy loaded (rc_policy_load)");
+    *out = env->pol_sampling;
     return RC_OK;
 }
 
@@ -385,6 +552,13 @@ int rc_policy_act(rc_env *env, uint32_t slot_mask) {
         if ((slot_mask >> a) & 1u) c.slots |= (uint32_t)a << (8 * c.n_slots++);
     c.n_active = env->cfg.num_envs * c.n_slots;
     c.raw_actions = env->cfg.remap_actions != 0;
+    c.mode = env->pol_sampling.mode;
+    c.expl_amount = env->pol_sampling.expl_amount;
+    c.seed_lo = seed_lo(env->pol_sampling.seed); c.seed_hi = seed_hi(env->pol_sampling.seed);
+    c.first_env = env->params.first_env;
+    c.episode = env->params.st.episode;
+    c.agent_steps = env->params.st.agent_steps;
+    c.ws = env->pol_s;
     c.lo0 = env->cfg.action_low[0]; c.lo1 = env->cfg.action_low[1]; c.hi0 = env->cfg.action_high[0]; c.hi1 = env->cfg.action_high[1];
     KernelTimer t;
     int rc = t.begin(env, RC_K_POLICY);

@@ -3,6 +3,11 @@ same layers on the same device, and the closed loop policy_act + step(repeat) be
 
     python tools/policy_cost.py [--envs 65536] [--track austria] [--out profiles/policy_cost.json]
 
+    python tools/policy_cost.py --modes [--out profiles/policy_sample_cost.json]
+
+`--modes`: the sampled modes instead (rc_policy_set_sampling) - per-call time of `mean`, `deploy` and `explore` and their closed
+loops at repeat 4, all in this one process, with the target deploy <= 1.15 x mean reported as met or missed.
+
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
 windows; the torch baseline is timed with stream events around a window of calls (its dozen launches per call included - that is
 what it costs).  The baseline is a RATE baseline: torch.addmm sums in another order than the spec."""
@@ -120,6 +125,56 @@ def measure(n, args):
     return res
 
 
+def measure_modes(n, args):
+    """Per-call device time (RC_K_POLICY, both kernels are timed under it) and closed-loop rate of the three modes on one env."""
+    import torch
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    env = BatchedRaceEnv(args.track, n, 1, auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    res = {"cars": n}
+    with torch.cuda.stream(env.stream):
+        env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            env.step(None, repeat=4)
+        env.sync()
+        for mode in ("mean", "deploy", "explore"):
+            env.set_policy_sampling(mode, seed=1)
+            for k in range(5):
+                env.policy_act()
+            windows = []
+            for r in range(args.rounds):
+                env.reset_kernel_times()
+                env.set_profiling(True, kernels=[L.K_POLICY])
+                for k in range(args.calls):
+                    env.policy_act()
+                env.sync()
+                env.set_profiling(False)
+                windows.append(env.kernel_times()["rc_policy_kernel"]["avg_ms"])
+            res[f"{mode}_ms"] = round(statistics.median(windows), 4)
+            res[f"{mode}_windows_ms"] = [round(v, 4) for v in windows]
+        for mode in ("mean", "deploy", "explore"):
+            env.set_policy_sampling(mode, seed=1)
+            for k in range(10):
+                env.policy_act()
+                env.step(None, repeat=4)
+            env.sync()
+            t0 = time.perf_counter()
+            for k in range(args.loop_steps):
+                env.policy_act()
+                env.step(None, repeat=4)
+            env.sync()
+            dt = (time.perf_counter() - t0) / args.loop_steps
+            res[f"loop_{mode}_ms_per_agent_step"] = round(dt * 1e3, 4)
+            res[f"loop_{mode}_env_steps_per_s"] = round(n * 4 / dt)
+        res["deploy_over_mean"] = round(res["deploy_ms"] / res["mean_ms"], 4)
+        res["explore_over_mean"] = round(res["explore_ms"] / res["mean_ms"], 4)
+    env.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
@@ -130,8 +185,21 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--loop-steps", type=int, default=100)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--modes", action="store_true", help="measure the sampled modes (profiles/policy_sample_cost.json)")
     args = ap.parse_args()
     import torch
+    if args.modes:
+        out = {"tool": "tools/policy_cost.py --modes", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
+               "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle, "loop_repeat": 4,
+               "sizes": [measure_modes(n, args) for n in args.envs]}
+        last = out["sizes"][-1]
+        out["target_deploy_over_mean"] = 1.15
+        out["target_met_at_largest_size"] = bool(last["deploy_over_mean"] <= 1.15)
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     out = {"tool": "tools/policy_cost.py", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
            "macs_per_car": MACS_PER_CAR, "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle,
            "sizes": [measure(n, args) for n in args.envs]}
