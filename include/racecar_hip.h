@@ -328,7 +328,8 @@ int rc_follow_the_gap_reference(rc_env *env, float dt, float *detail_dev);
  * models.py:61-87 RSSM.obs_step / img_step, :339-364 ActionDecoder 'tanh_normal' and actor_version "normalized") - the posterior
  * MEAN instead of a sample and tanh(mean) instead of the best of 100 draws, in the binary32 arithmetic of DESIGN.md §2 item 12
  * (tests/policy_spec.c is its CPU restatement; the device equals it bit for bit).  rc_policy_set_sampling switches to the
- * reference's own sampled modes; the reward head and the decoder are not part of it.
+ * reference's own sampled modes; rc_policy_imagine (below) runs the prior and the reward head.  The observation decoder is not
+ * part of it.
  *
  * rc_policy_weights: host pointers and shapes of the checkpoint's arrays in `tf.Module.variables` order (rssm.pkl: 13 arrays,
  * actor.pkl: 10, or 14 with the batch normalisation's four).  One-dimensional arrays have rows = 1. */
@@ -337,8 +338,9 @@ typedef struct rc_policy_weights {
     uint32_t struct_size;          /* = sizeof(rc_policy_weights) */
     rc_policy_array gru_kernel, gru_recurrent, gru_bias;      /* [200, 600] x 2, [2, 600]: gates z, r, candidate; reset_after */
     rc_policy_array img1_w, img1_b;                            /* [32, 200], [200]    input [stoch 30, previous action 2]      */
-    rc_policy_array img2_w, img2_b, img3_w, img3_b;            /* the prior's layers: not read by the agent (data may be NULL;
-                                                                  checked when given: [200, 200], [200], [200, 60], [60])      */
+    rc_policy_array img2_w, img2_b, img3_w, img3_b;            /* the prior's layers: read by rc_policy_imagine only (data may be
+                                                                  NULL: the agent works, imagination is refused; checked when
+                                                                  given: [200, 200], [200], [200, 60], [60])                   */
     rc_policy_array obs1_w, obs1_b, obs2_w, obs2_b;            /* [1280, 200], [200], [200, 60], [60]   input [deter, scan]    */
     rc_policy_array h0_w, h0_b, h1_w, h1_b, h2_w, h2_b, h3_w, h3_b;   /* [230, 400], [400], 3 x ([400, 400], [400])            */
     rc_policy_array hout_w, hout_b;                            /* [400, 4], [4]                                                */
@@ -392,6 +394,50 @@ typedef struct rc_policy_sampling {
  * under RC_K_POLICY.  rc_policy_get_sampling: what is installed. */
 int rc_policy_set_sampling(rc_env *env, const rc_policy_sampling *s);
 int rc_policy_get_sampling(rc_env *env, rc_policy_sampling *out);
+
+/* Imagination: the world model rolled ahead from every car's stored latent, and its reward head (DESIGN.md §2 item 15;
+ * tests/policy_imagine_spec.c is the CPU restatement, the device equals it bit for bit).  For t = 0 .. horizon - 1: the action is
+ * the caller's actions_in[car, t] (open loop: ros_agent/models/dreamer/models.py:44-52 RSSM.imagine; raw, clamped to [-1, 1]) or
+ * the actor's on [stoch, deter] (closed loop: dreamer/models.py:213-224 _imagine_ahead); then the prior step img_step
+ * (models.py:72-84); feature[t] = [stoch', deter'], reward[t] = the reward head on it (models.py:301-318 DenseDecoder).
+ *   RC_POLICY_IMAGINE_MEAN     action tanh(mu), stoch' = the prior's mean: deterministic.
+ *   RC_POLICY_IMAGINE_SAMPLE   one tanh-normal action draw (the reference's actor(feat).sample(); no best of 100, no exploration
+ *                              noise) and stoch' ~ Normal(mean, softplus(raw) + 0.1), Philox4x32-10 keyed by `seed` and counted by
+ *                              (global env id, episode, agent step, slot, t, index): not by the shard, the mask or the call history.
+ * The "normalized" actor uses its moving statistics, as rc_policy_act does.  A pure function of the latent as rc_policy_act last
+ * left it (RC_F_FRESH is not looked at): the agent's state, RC_F_ACTION_IN, the arena and every counter stay as they are.
+ *
+ * rc_policy_heads: the reward head's arrays, host pointers as in rc_policy_weights.  rc_policy_load_heads checks the shapes first
+ * (RC_ERR_INVALID names the first that is wrong), needs a loaded policy and copies the arrays; h = NULL drops the head, and so do
+ * rc_policy_load and rc_policy_unload. */
+typedef struct rc_policy_heads {
+    uint32_t struct_size;          /* = sizeof(rc_policy_heads) */
+    rc_policy_array reward_h0_w, reward_h0_b;                  /* [230, 400], [400]   input [stoch, deter]                     */
+    rc_policy_array reward_h1_w, reward_h1_b;                  /* [400, 400], [400]                                            */
+    rc_policy_array reward_hout_w, reward_hout_b;              /* [400, 1], [1]                                                */
+} rc_policy_heads;
+int rc_policy_load_heads(rc_env *env, const rc_policy_heads *h);
+#define RC_POLICY_IMAGINE_MEAN 0
+#define RC_POLICY_IMAGINE_SAMPLE 1
+#define RC_POLICY_IMAGINE_MAX_HORIZON 64
+#define RC_POLICY_FEATURE 230      /* stoch 30 | deter 200 */
+typedef struct rc_policy_imagine_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_imagine_args) */
+    int32_t horizon;               /* H in [1, RC_POLICY_IMAGINE_MAX_HORIZON]; the reference's is 15 */
+    int32_t mode;                  /* RC_POLICY_IMAGINE_* */
+    uint32_t slot_mask;            /* bit a = slot a, as rc_policy_act's */
+    uint64_t seed;
+    const float *actions_in;       /* device float32 [n_cars, H, 2], or NULL: the actor's own actions */
+    float *reward;                 /* device float32 [n_cars, H], or NULL */
+    float *actions;                /* device float32 [n_cars, H, 2], or NULL: the actions taken (open loop: the clamped input) */
+    float *features;               /* device float32 [n_cars, H, 230], or NULL */
+    float *reward_start;           /* device float32 [n_cars], or NULL: the head on the starting feature */
+} rc_policy_imagine_args;
+/* rc_policy_imagine: one launch for the whole horizon, on the handle's stream.  Rows are indexed by car; rows of cars outside
+ * the mask are not touched.  RC_ERR_INVALID: wrong struct_size, no policy loaded, the policy loaded without img2 / img3,
+ * horizon outside [1, 64], unknown mode, empty mask or bits beyond cars_per_env, no output asked for, reward or reward_start
+ * asked for without a loaded head.  Kernels: rc_policy_imagine_kernel, rc_policy_imagine_sampled_kernel, timed under RC_K_POLICY. */
+int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *args);
 
 /* ---- Episode log: return, length, progress and time of every episode, kept on the device (opt-in; off = the launches of a step
  * are what they are without it) ---------------------------------------------------------------------------------------------------

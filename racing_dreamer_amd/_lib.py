@@ -88,29 +88,64 @@ POLICY_MODE_SAMPLES = 100
 POLICY_EXPL_DEFAULT = {"mean": 0.0, "deploy": 0.0, "explore": 0.3}      # eval_noise off; dream.py:96-99 expl_amount
 
 
-def policy_weights(weights):
-    """rc_policy_weights over a mapping of float32 arrays (or an .npz path).  Returns (struct, the arrays it points into -
-    keep them alive until rc_policy_load has returned)."""
+HEAD_KEYS = ("reward_h0_w", "reward_h0_b", "reward_h1_w", "reward_h1_b", "reward_hout_w", "reward_hout_b")
+POLICY_FEATURE = 230        # stoch 30 | deter 200
+IMAGINE_MODES = {"mean": 0, "sample": 1}                       # RC_POLICY_IMAGINE_*
+IMAGINE_MAX_HORIZON = 64
+
+
+class RcPolicyHeads(C.Structure):
+    """rc_policy_heads (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, RcPolicyArray) for k in HEAD_KEYS]
+
+
+class RcPolicyImagineArgs(C.Structure):
+    """rc_policy_imagine_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("horizon", C.c_int32), ("mode", C.c_int32), ("slot_mask", C.c_uint32), ("seed", C.c_uint64),
+                ("actions_in", C.c_void_p), ("reward", C.c_void_p), ("actions", C.c_void_p), ("features", C.c_void_p), ("reward_start", C.c_void_p)]
+
+
+def _fill_arrays(struct, weights, names, optional=()):
     import numpy as np
-    if isinstance(weights, (str, os.PathLike)):
-        weights = np.load(weights)
     keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
-    w = RcPolicyWeights()
-    w.struct_size = C.sizeof(RcPolicyWeights)
     keep = []
-    for k in POLICY_KEYS:
+    for k in names:
         if k not in keys:
-            if k in POLICY_OPTIONAL:
+            if k in optional:
                 continue
             raise KeyError(f"policy weights lack {k!r}")
         a = np.ascontiguousarray(weights[k], np.float32)
         if a.ndim not in (1, 2):
             raise ValueError(f"policy weights: {k} has {a.ndim} dimensions")
         keep.append(a)
-        arr = getattr(w, k)
+        arr = getattr(struct, k)
         arr.data = a.ctypes.data
         arr.rows, arr.cols = (1, a.shape[0]) if a.ndim == 1 else a.shape
-    return w, keep
+    return keep
+
+
+def policy_heads(weights):
+    """rc_policy_heads over a mapping that holds the reward_* arrays (or an .npz path), as policy_weights; None if it holds none."""
+    import numpy as np
+    if isinstance(weights, (str, os.PathLike)):
+        weights = np.load(weights)
+    keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
+    if not any(k.startswith("reward_") for k in keys):
+        return None
+    h = RcPolicyHeads()
+    h.struct_size = C.sizeof(RcPolicyHeads)
+    return h, _fill_arrays(h, weights, HEAD_KEYS)
+
+
+def policy_weights(weights):
+    """rc_policy_weights over a mapping of float32 arrays (or an .npz path).  Returns (struct, the arrays it points into -
+    keep them alive until rc_policy_load has returned)."""
+    import numpy as np
+    if isinstance(weights, (str, os.PathLike)):
+        weights = np.load(weights)
+    w = RcPolicyWeights()
+    w.struct_size = C.sizeof(RcPolicyWeights)
+    return w, _fill_arrays(w, weights, POLICY_KEYS, POLICY_OPTIONAL)
 
 
 # every symbol include/racecar_hip.h declares: name -> (restype, argtypes)
@@ -143,6 +178,8 @@ SYMBOLS = {
     "rc_policy_state": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t)]),
     "rc_policy_set_sampling": (C.c_int, [C.c_void_p, _P(RcPolicySampling)]),
     "rc_policy_get_sampling": (C.c_int, [C.c_void_p, _P(RcPolicySampling)]),
+    "rc_policy_load_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
+    "rc_policy_imagine": (C.c_int, [C.c_void_p, _P(RcPolicyImagineArgs)]),
     "rc_episode_log_enable": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "rc_episode_log_disable": (C.c_int, [C.c_void_p]),
     "rc_episode_log": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p), _P(C.c_size_t)]),

@@ -108,6 +108,40 @@ def _ensure_lab() -> None:
         build.build_lab(verbose=False)
 
 
+def _imagine_setup(env, horizon, mode, seed, actions, slots, features, start_reward, out):
+    """policy_imagine's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
+    rc_policy_imagine_args field - one row per car -, the dict to return)."""
+    if mode not in L.IMAGINE_MODES:
+        raise ValueError(f"imagination mode must be one of {sorted(L.IMAGINE_MODES)}, got {mode!r}")
+    h, n = int(horizon), env.n_cars
+    if not 1 <= h <= L.IMAGINE_MAX_HORIZON:
+        raise ValueError(f"horizon must be in [1, {L.IMAGINE_MAX_HORIZON}], got {horizon}")
+    if start_reward and not env.policy_has_reward_head:
+        raise L.RacecarHipError("start_reward needs a checkpoint with a reward head (reward_* arrays)")
+    shapes = {"action": (n, h, 2)}
+    if env.policy_has_reward_head:
+        shapes["reward"] = (n, h)
+    if features:
+        shapes["feature"] = (n, h, L.POLICY_FEATURE)
+    if start_reward:
+        shapes["reward_start"] = (n,)
+    result = {}
+    for name, shape in shapes.items():
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = (torch.empty if slots is None else torch.zeros)(shape, dtype=torch.float32, device=env.device)
+        elif t.shape != shape or t.dtype != torch.float32 or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of shape {shape} on {env.device}")
+        result[name] = t
+    if actions is not None:
+        actions = actions.to(env.device, torch.float32).reshape(n, h, 2).contiguous()
+    args = dict(horizon=h, mode=L.IMAGINE_MODES[mode], seed=int(seed) & (2 ** 64 - 1),
+                mask=(1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots}))
+    tensors = dict(actions_in=actions, reward=result.get("reward"), actions=result["action"], features=result.get("feature"),
+                   reward_start=result.get("reward_start"))
+    return args, tensors, result
+
+
 class BatchedRaceEnv:
     def __init__(self, track: Union[str, Track], num_envs: int, cars_per_env: int = 1, obs_type: str = "lidar",
                  action_repeat: int = 1, seed: int = 0, device: int = 0, first_env: int = 0,
@@ -592,6 +626,42 @@ class BatchedRaceEnv:
         # is released, which may be after this call (a view the caller still holds)
         self._policy_arrays = getattr(self, "_policy_arrays", []) + [_BorrowedDeviceArray(ptr.value, (self.n_cars, L.POLICY_STATE), self.device)]
         self._policy_state = torch.utils.dlpack.from_dlpack(self._policy_arrays[-1])
+        self._policy_has_head = False                       # (rc_policy_load drops a head loaded before)
+        heads = L.policy_heads(weights)
+        if heads is not None:
+            L.check(self._lib.rc_policy_load_heads(self._h, C.byref(heads[0])))
+            self._policy_has_head = True
+
+    @property
+    def policy_has_reward_head(self) -> bool:
+        """Whether the loaded checkpoint brought a reward head (`reward_*` arrays): `policy_imagine` then returns rewards."""
+        return bool(getattr(self, "_policy_has_head", False))
+
+    def _imagine(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_imagine on this handle, reading and writing rows [lo, hi) of the tensors (one row per car)."""
+        a = L.RcPolicyImagineArgs(C.sizeof(L.RcPolicyImagineArgs), args["horizon"], args["mode"], args["mask"], args["seed"])
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else t[lo:hi].data_ptr())
+        return self._lib.rc_policy_imagine(self._h, C.byref(a))
+
+    def policy_imagine(self, horizon: int = 15, mode: str = "mean", seed: int = 0, actions: Optional[torch.Tensor] = None, slots=None,
+                       features: bool = False, start_reward: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """Roll the world model `horizon` steps ahead from every car's latent as `policy_act` last left it (`rc_policy_imagine`,
+        one launch): under the actor's own actions (the reference's `_imagine_ahead`), or under `actions` float32
+        [n_cars, horizon, 2] raw in [-1, 1] (`RSSM.imagine`, open loop; clamped).  mode "mean": tanh of the actor's mean and the
+        prior's mean; "sample": one tanh-normal action draw and a sampled prior, a function of (seed, global env id, slot,
+        episode, agent step, t) only.  Returns device tensors: `action` [n_cars, horizon, 2], `reward` [n_cars, horizon] (when
+        the checkpoint has a reward head), `feature` [n_cars, horizon, 230] = stoch | deter (features=True), `reward_start`
+        [n_cars] = the head on the starting latent (start_reward=True).  Nothing else changes: not the agent's state, not
+        `action_in`.  With `slots`, rows of the other cars are zero - or what `out` (tensors to write into, by the same names)
+        held."""
+        args, tensors, result = _imagine_setup(self, horizon, mode, seed, actions, slots, features, start_reward, out)
+        self._enter()
+        try:
+            L.check(self._imagine(args, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
 
     def policy_act(self, slots=None) -> torch.Tensor:
         """One step of the loaded agent, in the mode of `set_policy_sampling` (deterministic by default), for every car (or the cars in the listed slots = car indices within
@@ -633,6 +703,7 @@ class BatchedRaceEnv:
 
     def unload_policy(self) -> None:
         self._policy_state = None
+        self._policy_has_head = False
         L.check(self._lib.rc_policy_unload(self._h))
 
     # ------------------------------------------------------------------ episode log (include/racecar_hip.h, rc_episode_log_*)
@@ -1027,6 +1098,18 @@ class MixedTrackEnv:
         mask = (1 << self.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
         self._fork_join(lambda p, blk: p._lib.rc_policy_act(p._h, C.c_uint32(mask)))
         return self.views["action_in"]
+
+    @property
+    def policy_has_reward_head(self) -> bool:
+        return self.parts[0].policy_has_reward_head
+
+    def policy_imagine(self, horizon: int = 15, mode: str = "mean", seed: int = 0, actions: Optional[torch.Tensor] = None, slots=None,
+                       features: bool = False, start_reward: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_imagine over all blocks: each block writes its cars' rows of one tensor per output."""
+        args, tensors, result = _imagine_setup(self, horizon, mode, seed, actions, slots, features, start_reward, out)
+        k = self.cars_per_env
+        self._fork_join(lambda p, blk: p._imagine(args, tensors, blk[0] * k, blk[1] * k))
+        return result
 
     def set_policy_sampling(self, mode: str = "mean", seed: int = 0, expl_amount: Optional[float] = None) -> None:
         """The same mode and seed on every block (BatchedRaceEnv.set_policy_sampling): the draws are keyed by global env ids."""

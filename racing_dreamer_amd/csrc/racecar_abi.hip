@@ -596,8 +596,7 @@ void rc_destroy(rc_env *env) {
     if (env->own_arena && env->arena) (void)hipFree(env->arena);
     if (env->state_mem) (void)hipFree(env->state_mem);
     if (env->ftg_prev) (void)hipFree(env->ftg_prev);
-    if (env->pol_mem) (void)hipFree(env->pol_mem);
-    if (env->pol_state) (void)hipFree(env->pol_state);
+    policy_release(env);
     if (env->vp_mem) (void)hipFree(env->vp_mem);
     if (env->exact_mem) (void)hipFree(env->exact_mem);
     if (env->order_mem) (void)hipFree(env->order_mem);

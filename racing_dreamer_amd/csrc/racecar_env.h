@@ -194,6 +194,8 @@ struct rc_env {
     float *pol_state = nullptr;
     RcPolicyDev pol{};
     RcPolicySampleDev pol_s{};
+    RcImagineDev pol_i{};              // rc_policy_imagine: img2 / img3 (in pol_mem, when rc_policy_load was given them) and the reward head
+    float *pol_heads_mem = nullptr;    // rc_policy_load_heads
     rc_policy_sampling pol_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};      // rc_policy_set_sampling
     float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
     float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)
@@ -268,3 +270,4 @@ struct KernelTimer {
 void episode_bind(rc_env *env);     // racecar_episode.hip
 int episode_step(rc_env *env);
 void gather_release(rc_env *env);   // racecar_gather.hip: the peer-copy transport, the communicator and its stream
+void policy_release(rc_env *env);   // racecar_policy.hip: the agent's weights and state, the prior's layers and the reward head

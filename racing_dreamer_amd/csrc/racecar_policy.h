@@ -57,5 +57,30 @@ struct RcPolicyCall {
     RcPolicySampleDev ws;
 };
 
+// Imagination (racecar_imagine.hip): the prior's second half and the reward head, packed like the rest
+struct RcImagineDev {
+    const float *img2_w, *img2_b;            // [200][224], [224]
+    const float *img3_w, *img3_b;            // [200][64], [64]         mean | std columns (mode `mean` reads tile 0 only); null = not loaded
+    const float *rh_w[2], *rh_b[2];          // reward head [230][416], [400][416]; [416]; null = no heads loaded
+    const float *rout_w, *rout_b;            // [400][32], [32]         its one output column
+};
+
+struct RcImagineCall {
+    RcPolicyDev w;
+    RcPolicySampleDev ws;
+    RcImagineDev wi;
+    const float *state;                      // [n_cars][RC_POLICY_STATE], read only
+    const uint32_t *episode;                 // [num_envs]: the draw's key, as rc_policy_act reads it
+    const int32_t *agent_steps;
+    uint32_t seed_lo, seed_hi, first_env;
+    int32_t n_active, cars_per_env, n_slots;
+    uint32_t slots;
+    int32_t horizon, sample;
+    const float *actions_in;                 // [n_cars][H][2] or null: the actor's own
+    float *reward, *actions, *features, *reward_start;      // [n_cars][H], [n_cars][H][2], [n_cars][H][230], [n_cars]; any may be null
+};
+
 hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS limit (once per process and device is enough)
 hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);      // c.mode: which kernel
+hipError_t rck_imagine_prepare();
+hipError_t rck_launch_imagine(const RcImagineCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel

@@ -13,16 +13,11 @@
 // arithmetic behind the choice (M = 32 cars per pass over the 4.4 MB of weights) and the measured cost.
 #include "racecar_env.h"
 #include "racecar_policy_math.h"
+#include "racecar_policy_tiles.h"
 #include <hip/hip_ext.h>
-
-typedef float pm_f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 
-constexpr int PT = 256;                        // threads per workgroup
-constexpr int PM = RC_POLICY_TILE;             // cars per workgroup
-constexpr int XS = 417;                        // row stride of X and Y [floats]
-constexpr int PD = 4;                          // k-steps (of 2) whose operands are requested one block ahead
 constexpr int SCK = 120;                       // beams per staged piece of the scan (9 pieces)
 constexpr int N_BEAMS = 1080;
 constexpr size_t kLdsBytes = (size_t)2 * PM * XS * sizeof(float) + PM * sizeof(int);
@@ -37,59 +32,6 @@ __device__ __forceinline__ int pm_car(const RcPolicyCall &c, int q) {
     const int e = q / c.n_slots, k = q - e * c.n_slots;
     return e * c.cars_per_env + (int)((c.slots >> (8 * k)) & 0xffu);
 }
-
-// acc[t] += A[32 x 2 ksteps] W[2 ksteps x 32 columns at col[t]], k ascending.  a = &A[lane & 31][lane >> 5] (LDS),
-// w = &W[lane >> 5][lane & 31] (global).  The operands of the next PD k-steps are requested before this block's MFMAs issue;
-// past the end the last step is requested again (a valid address) and not used.
-template <int TN>
-__device__ __forceinline__ void pm_gemm(pm_f32x16 (&acc)[TN], const float *a, int ksteps, const float *__restrict__ w, int ld,
-                                        const int (&col)[TN]) {
-    float ac[PD], bc[PD][TN], an[PD], bn[PD][TN];
-#pragma unroll
-    for (int u = 0; u < PD; ++u) {
-        const int s = u < ksteps ? u : ksteps - 1;
-        ac[u] = a[2 * s];
-#pragma unroll
-        for (int t = 0; t < TN; ++t) bc[u][t] = w[(size_t)(2 * s) * ld + col[t]];
-    }
-#pragma unroll 1
-    for (int s0 = 0; s0 < ksteps; s0 += PD) {
-#pragma unroll
-        for (int u = 0; u < PD; ++u) {
-            int s = s0 + PD + u;
-            s = s < ksteps ? s : ksteps - 1;
-            an[u] = a[2 * s];
-#pragma unroll
-            for (int t = 0; t < TN; ++t) bn[u][t] = w[(size_t)(2 * s) * ld + col[t]];
-        }
-#pragma unroll
-        for (int u = 0; u < PD; ++u) {
-            if (s0 + u < ksteps) {
-#pragma unroll
-                for (int t = 0; t < TN; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(ac[u], bc[u][t], acc[t], 0, 0, 0);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < PD; ++u) {
-            ac[u] = an[u];
-#pragma unroll
-            for (int t = 0; t < TN; ++t) bc[u][t] = bn[u][t];
-        }
-    }
-}
-
-template <int TN>
-__device__ __forceinline__ void pm_bias(pm_f32x16 (&acc)[TN], const float *__restrict__ b, const int (&col)[TN], int c) {
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const float v = b[col[t] + c];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[t][r] = v;
-    }
-}
-
-// C/D map of the 32x32 tile: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ int pm_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
 
 enum { PK_ELU = 0, PK_STOCH = 1, PK_ACTION = 2 };
 
@@ -411,7 +353,40 @@ void pol_pad(std::vector<float> &dst, size_t at, const float *src, int rows, int
         for (int g = 0; g < gates; ++g)
             for (int j = 0; j < take; ++j) dst[at + (size_t)k * gates * ld + (size_t)g * ld + j] = src[(size_t)k * n_src + g * group + j];
 }
+
+// the reward head's memory and pointers go (rc_policy_load_heads(NULL), a new rc_policy_load); the prior's layers stay
+int pol_drop_heads(rc_env *env) {
+    if (env->pol_heads_mem) {
+        HIP_TRY(hipSetDevice(env->cfg.device));
+        HIP_TRY(hipStreamSynchronize(env->stream));
+        (void)hipFree(env->pol_heads_mem);
+        env->pol_heads_mem = nullptr;
+    }
+    env->pol_i.rh_w[0] = env->pol_i.rh_w[1] = env->pol_i.rh_b[0] = env->pol_i.rh_b[1] = env->pol_i.rout_w = env->pol_i.rout_b = nullptr;
+    return RC_OK;
+}
+
+struct HeadShape { const char *name; const rc_policy_array rc_policy_heads::*arr; int rows, cols; };
+const HeadShape kHeadShapes[] = {
+    {"reward_h0_w", &rc_policy_heads::reward_h0_w, 230, 400}, {"reward_h0_b", &rc_policy_heads::reward_h0_b, 1, 400},
+    {"reward_h1_w", &rc_policy_heads::reward_h1_w, 400, 400}, {"reward_h1_b", &rc_policy_heads::reward_h1_b, 1, 400},
+    {"reward_hout_w", &rc_policy_heads::reward_hout_w, 400, 1}, {"reward_hout_b", &rc_policy_heads::reward_hout_b, 1, 1},
+};
 }  // namespace
+}  // extern "C"
+
+// rc_policy_unload and rc_destroy; the caller has synchronised the stream
+void policy_release(rc_env *env) {
+    (void)pol_drop_heads(env);
+    if (env->pol_mem) (void)hipFree(env->pol_mem);
+    if (env->pol_state) (void)hipFree(env->pol_state);
+    env->pol_mem = env->pol_state = nullptr;
+    env->pol = RcPolicyDev{};
+    env->pol_s = RcPolicySampleDev{};
+    env->pol_i = RcImagineDev{};
+}
+
+extern "C" {
 
 int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     if (!w) return fail(RC_ERR_INVALID, "rc_policy_weights is NULL");
@@ -438,7 +413,9 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
                  o_obs1 = take(1280 * LD2), o_obs1b = take(LD2), o_obs2 = take(200 * LDS), o_obs2b = take(LDS),
                  o_h0 = take(230 * LD4), o_h1 = take(400 * LD4), o_h2 = take(400 * LD4), o_h3 = take(400 * LD4),
                  o_hb = take(4 * LD4), o_hout = take(400 * LDS), o_houtb = take(LDS), o_norm = take(8),
-                 o_obs2s = take(200 * LDP), o_obs2sb = take(LDP), o_houts = take(400 * LDP), o_houtsb = take(LDP), o_norm4 = take(16);
+                 o_obs2s = take(200 * LDP), o_obs2sb = take(LDP), o_houts = take(400 * LDP), o_houtsb = take(LDP), o_norm4 = take(16),
+                 o_img2 = take(200 * LD2), o_img2b = take(LD2), o_img3 = take(200 * LDP), o_img3b = take(LDP);
+    const bool prior = w->img2_w.data && w->img2_b.data && w->img3_w.data && w->img3_b.data;      // rc_policy_imagine's layers
     std::vector<float> img(at, 0.0f);
     pol_pad(img, o_img1, w->img1_w.data, 32, 200, 1, 200, 200, (int)LD2);
     pol_pad(img, o_img1b, w->img1_b.data, 1, 200, 1, 200, 200, (int)LD2);
@@ -462,6 +439,12 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     pol_pad(img, o_obs2sb, w->obs2_b.data, 1, 60, 2, RC_POLICY_STOCH, RC_POLICY_STOCH, 32);
     pol_pad(img, o_houts, w->hout_w.data, 400, 4, 2, 2, 2, 32);
     pol_pad(img, o_houtsb, w->hout_b.data, 1, 4, 2, 2, 2, 32);
+    if (prior) {
+        pol_pad(img, o_img2, w->img2_w.data, 200, 200, 1, 200, 200, (int)LD2);
+        pol_pad(img, o_img2b, w->img2_b.data, 1, 200, 1, 200, 200, (int)LD2);
+        pol_pad(img, o_img3, w->img3_w.data, 200, 60, 2, RC_POLICY_STOCH, RC_POLICY_STOCH, 32);      // mean | std, as obs2's
+        pol_pad(img, o_img3b, w->img3_b.data, 1, 60, 2, RC_POLICY_STOCH, RC_POLICY_STOCH, 32);
+    }
     if (n_norm) {
         for (int j = 0; j < 4; ++j) {
             img[o_norm4 + j] = w->hnorm_mean.data[j];
@@ -478,6 +461,9 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     }
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(rck_policy_prepare());
+    HIP_TRY(rck_imagine_prepare());
+    int rc = pol_drop_heads(env);
+    if (rc) return rc;
     if (!env->pol_mem) HIP_TRY(hipMalloc((void **)&env->pol_mem, at * sizeof(float)));
     const size_t state_bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
     if (!env->pol_state) HIP_TRY(hipMalloc((void **)&env->pol_state, state_bytes));
@@ -492,6 +478,8 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     d.hout_w = m + o_hout; d.hout_b = m + o_houtb;
     d.hnorm = n_norm ? m + o_norm : nullptr;
     env->pol_s = RcPolicySampleDev{m + o_obs2s, m + o_obs2sb, m + o_houts, m + o_houtsb, n_norm ? m + o_norm4 : nullptr};
+    env->pol_i = RcImagineDev{};
+    if (prior) { env->pol_i.img2_w = m + o_img2; env->pol_i.img2_b = m + o_img2b; env->pol_i.img3_w = m + o_img3; env->pol_i.img3_b = m + o_img3b; }
     env->pol_sampling = rc_policy_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};
     return RC_OK;
 }
@@ -500,11 +488,7 @@ int rc_policy_unload(rc_env *env) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(hipStreamSynchronize(env->stream));
-    if (env->pol_mem) (void)hipFree(env->pol_mem);
-    if (env->pol_state) (void)hipFree(env->pol_state);
-    env->pol_mem = env->pol_state = nullptr;
-    env->pol = RcPolicyDev{};
-    env->pol_s = RcPolicySampleDev{};
+    policy_release(env);
     env->pol_sampling = rc_policy_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};
     return RC_OK;
 }
@@ -575,6 +559,84 @@ int rc_policy_state(rc_env *env, void **dev_ptr, size_t *bytes) {
     *dev_ptr = env->pol_state;
     *bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
     return RC_OK;
+}
+
+int rc_policy_load_heads(rc_env *env, const rc_policy_heads *h) {
+    if (!h) {
+        if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+        return pol_drop_heads(env);
+    }
+    if (h->struct_size != sizeof(rc_policy_heads))
+        return fail(RC_ERR_INVALID, "rc_policy_heads.struct_size %u != %zu", h->struct_size, sizeof(rc_policy_heads));
+    for (const HeadShape &sh : kHeadShapes) {
+        const rc_policy_array &a = h->*(sh.arr);
+        if (!a.data) return fail(RC_ERR_INVALID, "rc_policy_load_heads: %s is missing", sh.name);
+        if (a.rows != sh.rows || a.cols != sh.cols)
+            return fail(RC_ERR_INVALID, "rc_policy_load_heads: %s has shape [%d, %d], the reward head's is [%d, %d]", sh.name, a.rows, a.cols, sh.rows, sh.cols);
+    }
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_load_heads: no policy loaded (rc_policy_load)");
+    const size_t LD4 = RC_POLICY_LD400, LDS = RC_POLICY_LDSMALL;
+    size_t at = 0;
+    auto take = [&](size_t n) { const size_t o = at; at += (n + 63) / 64 * 64; return o; };
+    const size_t o_h0 = take(230 * LD4), o_h1 = take(400 * LD4), o_hb = take(2 * LD4), o_out = take(400 * LDS), o_outb = take(LDS);
+    std::vector<float> img(at, 0.0f);
+    pol_pad(img, o_h0, h->reward_h0_w.data, 230, 400, 1, 400, 400, (int)LD4);
+    pol_pad(img, o_h1, h->reward_h1_w.data, 400, 400, 1, 400, 400, (int)LD4);
+    pol_pad(img, o_hb, h->reward_h0_b.data, 1, 400, 1, 400, 400, (int)LD4);
+    pol_pad(img, o_hb + LD4, h->reward_h1_b.data, 1, 400, 1, 400, 400, (int)LD4);
+    pol_pad(img, o_out, h->reward_hout_w.data, 400, 1, 1, 1, 1, (int)LDS);
+    pol_pad(img, o_outb, h->reward_hout_b.data, 1, 1, 1, 1, 1, (int)LDS);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    if (!env->pol_heads_mem) HIP_TRY(hipMalloc((void **)&env->pol_heads_mem, at * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(env->pol_heads_mem, img.data(), at * sizeof(float), hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
+    const float *m = env->pol_heads_mem;
+    RcImagineDev &d = env->pol_i;
+    d.rh_w[0] = m + o_h0; d.rh_w[1] = m + o_h1; d.rh_b[0] = m + o_hb; d.rh_b[1] = m + o_hb + LD4; d.rout_w = m + o_out; d.rout_b = m + o_outb;
+    return RC_OK;
+}
+
+int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_imagine_args))
+        return fail(RC_ERR_INVALID, "rc_policy_imagine_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_imagine_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_imagine: no policy loaded (rc_policy_load)");
+    if (!env->pol_i.img3_w) return fail(RC_ERR_INVALID, "rc_policy_imagine: the policy was loaded without the prior's layers img2 / img3");
+    if (a->horizon < 1 || a->horizon > RC_POLICY_IMAGINE_MAX_HORIZON)
+        return fail(RC_ERR_INVALID, "rc_policy_imagine: horizon %d is outside [1, %d]", a->horizon, RC_POLICY_IMAGINE_MAX_HORIZON);
+    if (a->mode != RC_POLICY_IMAGINE_MEAN && a->mode != RC_POLICY_IMAGINE_SAMPLE) return fail(RC_ERR_INVALID, "rc_policy_imagine: unknown mode %d", a->mode);
+    if (a->slot_mask == 0) return fail(RC_ERR_INVALID, "rc_policy_imagine: the slot mask is empty");
+    if (a->slot_mask >> env->cfg.cars_per_env)
+        return fail(RC_ERR_INVALID, "rc_policy_imagine: slot mask 0x%x names slots beyond cars_per_env = %d", a->slot_mask, env->cfg.cars_per_env);
+    if (!a->reward && !a->actions && !a->features && !a->reward_start) return fail(RC_ERR_INVALID, "rc_policy_imagine: no output asked for");
+    if ((a->reward || a->reward_start) && !env->pol_i.rout_w)
+        return fail(RC_ERR_INVALID, "rc_policy_imagine: a reward is asked for and no reward head is loaded (rc_policy_load_heads)");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    RcImagineCall c{};
+    c.w = env->pol;
+    c.ws = env->pol_s;
+    c.wi = env->pol_i;
+    c.state = env->pol_state;
+    c.episode = env->params.st.episode;
+    c.agent_steps = env->params.st.agent_steps;
+    c.seed_lo = seed_lo(a->seed); c.seed_hi = seed_hi(a->seed);
+    c.first_env = env->params.first_env;
+    c.cars_per_env = env->cfg.cars_per_env;
+    for (int s = 0; s < env->cfg.cars_per_env; ++s)
+        if ((a->slot_mask >> s) & 1u) c.slots |= (uint32_t)s << (8 * c.n_slots++);
+    c.n_active = env->cfg.num_envs * c.n_slots;
+    c.horizon = a->horizon;
+    c.sample = a->mode == RC_POLICY_IMAGINE_SAMPLE;
+    c.actions_in = a->actions_in;
+    c.reward = a->reward; c.actions = a->actions; c.features = a->features; c.reward_start = a->reward_start;
+    KernelTimer t;
+    int rc = t.begin(env, RC_K_POLICY);
+    if (rc) return rc;
+    hipEvent_t ea = nullptr, eb = nullptr;
+    rck_take_launch_events(&ea, &eb);
+    HIP_TRY(rck_launch_imagine(c, ea, eb, env->stream));
+    return t.end();
 }
 
 }  // extern "C"

@@ -193,3 +193,21 @@ __device__ __forceinline__ void pm_actor_dist(float out_mean, float out_std, con
         sd = pm_softplus(out_std + PM_RAW_INIT_STD) + PM_ACTION_MIN_STD;
     }
 }
+
+// ---- imagination: tests/policy_imagine_spec.c restates what follows
+#define PM_IMAGINE_TAG 5u                  // Philox counter word 3, bits 24-31
+#define PM_IMAGINE_BLOCK_ACTION 8u         // block 8 of imagined step t: words 0-1 the action draw; blocks 0-7: the prior's 30 normals
+
+// the four normals of block `block` of imagined step t of a car's rollout
+__device__ __forceinline__ void pm_imagine_normal_block(uint32_t env, uint32_t episode, uint32_t agent_step, uint32_t slot, uint32_t t,
+                                                        uint32_t block, uint32_t seed_lo, uint32_t seed_hi, float (&n)[4]) {
+    const rcd::u32x4 r = rcd::philox4x32(env, episode, agent_step, block | (slot << 8) | (t << 12) | (PM_IMAGINE_TAG << 24), seed_lo, seed_hi);
+    pm_normal_pair(r.x, r.y, n[0], n[1]);
+    pm_normal_pair(r.z, r.w, n[2], n[3]);
+}
+
+// an action given from outside: clamped to [-1, 1] as pm_postprocess clamps
+__device__ __forceinline__ float pm_clamp_action(float a) {
+    a = a > -1.0f ? a : -1.0f;
+    return a < 1.0f ? a : 1.0f;
+}

@@ -8,6 +8,12 @@ same layers on the same device, and the closed loop policy_act + step(repeat) be
 `--modes`: the sampled modes instead (rc_policy_set_sampling) - per-call time of `mean`, `deploy` and `explore` and their closed
 loops at repeat 4, all in this one process, with the target deploy <= 1.15 x mean reported as met or missed.
 
+    python tools/policy_cost.py --imagine [--out profiles/policy_imagine_cost.json]
+
+`--imagine`: imagination (rc_policy_imagine) at H = 15 - `mean`, `sample` and open loop, with the reward only and with all outputs -
+beside `policy_act` (`mean`) of the same run, with the target: time per imagined step <= (padded MACs of an imagined step / padded
+MACs of an agent step) x the agent's call + 5 %, reported as met or missed.
+
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
 windows; the torch baseline is timed with stream events around a window of calls (its dozen launches per call included - that is
 what it costs).  The baseline is a RATE baseline: torch.addmm sums in another order than the spec."""
@@ -175,6 +181,127 @@ def measure_modes(n, args):
     return res
 
 
+def _packed_ld():
+    """The leading dimensions the weight packer pads to (RC_POLICY_LD* of racing_dreamer_amd/csrc/racecar_policy.h): the columns a
+    layer's MFMA tiles cover, so the MACs the kernels issue follow the packing and not a copy of it."""
+    import re
+    with open(os.path.join(ROOT, "racing_dreamer_amd", "csrc", "racecar_policy.h")) as f:
+        ld = {k: int(v) for k, v in re.findall(r"#define RC_POLICY_(LD\w+) (\d+)\b", f.read())}
+    assert set(ld) >= {"LD200", "LD400", "LDSMALL", "LDPAIR"}, ld
+    return ld
+
+
+# MACs as the kernels issue them: a layer of K rows costs K x (the packed width its tiles cover)
+_LD = _packed_ld()
+PADDED_ACTOR = 230 * _LD["LD400"] + 3 * 400 * _LD["LD400"] + 400 * _LD["LDSMALL"]
+PADDED_GRU = 32 * _LD["LD200"] + 2 * 200 * 3 * _LD["LD200"]
+PADDED_AGENT_STEP = PADDED_GRU + 1280 * _LD["LD200"] + 200 * _LD["LDSMALL"] + PADDED_ACTOR
+PADDED_HEAD = 230 * _LD["LD400"] + 400 * _LD["LD400"] + 400 * _LD["LDSMALL"]
+# mode mean, closed loop, reward: img3 is packed at LDPAIR (mean | std) and mode mean issues its mean tile only
+PADDED_IMAGINED_STEP = PADDED_ACTOR + PADDED_GRU + 200 * _LD["LD200"] + 200 * (_LD["LDPAIR"] // 2) + PADDED_HEAD
+# mode sample also issues the std tiles of img3 and of the actor's hout (not in the target's ratio, which is for `mean`)
+PADDED_IMAGINED_STEP_SAMPLE = PADDED_IMAGINED_STEP + 200 * (_LD["LDPAIR"] // 2) + 400 * (_LD["LDPAIR"] - _LD["LDSMALL"])
+MACS_IMAGINED_STEP = 230 * 400 + 3 * 400 * 400 + 400 * 2 + 32 * 200 + 2 * 200 * 600 + 200 * 200 + 200 * 30 + 230 * 400 + 400 * 400 + 400
+
+
+class TorchImagine(TorchAgent):
+    """H imagined steps (mode mean, closed loop, reward) in plain fp32 torch."""
+
+    def imagine(self, state, horizon):
+        import torch
+        import torch.nn.functional as F
+        w = self.w
+        stoch, deter = state[:, :30], state[:, 30:230]
+        rewards = []
+        for t in range(horizon):
+            h = torch.cat([stoch, deter], 1)
+            for i in range(4):
+                h = F.elu(torch.addmm(w[f"h{i}_b"], h, w[f"h{i}_w"]))
+            action = torch.tanh(5.0 * torch.tanh(torch.addmm(self.hout_b, h, self.hout_w) / 5.0))
+            x = F.elu(torch.addmm(w["img1_b"], torch.cat([stoch, action], 1), w["img1_w"]))
+            mx, mh = torch.addmm(w["gru_bias"][0], x, w["gru_kernel"]), torch.addmm(w["gru_bias"][1], deter, w["gru_recurrent"])
+            z, r = torch.sigmoid(mx[:, :200] + mh[:, :200]), torch.sigmoid(mx[:, 200:400] + mh[:, 200:400])
+            deter = z * deter + (1.0 - z) * torch.tanh(mx[:, 400:] + r * mh[:, 400:])
+            x = F.elu(torch.addmm(w["img2_b"], deter, w["img2_w"]))
+            stoch = torch.addmm(w["img3_b"][:30], x, w["img3_w"][:, :30])
+            h = torch.cat([stoch, deter], 1)
+            for i in range(2):
+                h = F.elu(torch.addmm(w[f"reward_h{i}_b"], h, w[f"reward_h{i}_w"]))
+            rewards.append(torch.addmm(w["reward_hout_b"], h, w["reward_hout_w"]))
+        return torch.cat(rewards, 1)
+
+
+def measure_imagine(n, args):
+    """Per-call device time (RC_K_POLICY) of policy_act (`mean`) and of rc_policy_imagine at H = args.horizon in six variants."""
+    import torch
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    env = BatchedRaceEnv(args.track, n, 1, auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    h = args.horizon
+    res = {"cars": n, "horizon": h}
+
+    def timed(call):
+        for k in range(3):
+            call()
+        windows = []
+        for r in range(args.rounds):
+            env.reset_kernel_times()
+            env.set_profiling(True, kernels=[L.K_POLICY])
+            for k in range(args.calls):
+                call()
+            env.sync()
+            env.set_profiling(False)
+            windows.append(env.kernel_times()["rc_policy_kernel"]["avg_ms"])
+        return statistics.median(windows), [round(v, 4) for v in windows]
+
+    with torch.cuda.stream(env.stream):
+        env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            env.step(None, repeat=4)
+        env.sync()
+        act_ms, act_windows = timed(env.policy_act)
+        res["policy_act_mean_ms"], res["policy_act_mean_windows_ms"] = round(act_ms, 4), act_windows
+        bufs = dict(reward=torch.empty((n, h), device=env.device), actions=torch.empty((n, h, 2), device=env.device),
+                    features=torch.empty((n, h, 230), device=env.device), reward_start=torch.empty(n, device=env.device))
+        given = (torch.rand((n, h, 2), device=env.device) * 2.0 - 1.0).contiguous()
+        limit = PADDED_IMAGINED_STEP / PADDED_AGENT_STEP * act_ms * 1.05
+        res["target_ms_per_imagined_step"] = round(limit, 4)
+        for variant, mode, open_loop in (("mean", "mean", False), ("sample", "sample", False), ("open_loop", "mean", True)):
+            for outputs in ("reward", "all"):
+                tensors = dict(actions_in=given if open_loop else None, reward=bufs["reward"], actions=None, features=None, reward_start=None)
+                if outputs == "all":
+                    tensors.update(actions=bufs["actions"], features=bufs["features"], reward_start=bufs["reward_start"])
+                a = dict(horizon=h, mode=L.IMAGINE_MODES[mode], seed=1, mask=1)
+                ms, windows = timed(lambda: L.check(env._imagine(a, tensors, 0, n)))
+                macs = MACS_IMAGINED_STEP - (230 * 400 + 3 * 400 * 400 + 400 * 2 if open_loop else 0)
+                res[f"{variant}_{outputs}"] = {"ms_per_call": round(ms, 4), "windows_ms": windows, "ms_per_imagined_step": round(ms / h, 4),
+                                               "tflops": round(2 * macs * n * h / (ms * 1e-3) / 1e12, 2),
+                                               "step_over_policy_act": round(ms / h / act_ms, 4)}
+        res["target_met"] = bool(res["mean_reward"]["ms_per_imagined_step"] <= limit)
+        res["mean_step_over_target"] = round(res["mean_reward"]["ms_per_imagined_step"] / limit, 4)
+        # ---- the torch baseline of the same layers (mode mean, closed loop, reward)
+        agent = TorchImagine(weights, env.device)
+        state = env.policy_state.clone()
+        for k in range(2):
+            agent.imagine(state, h)
+        windows = []
+        for r in range(args.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k in range(max(1, args.calls // 4)):
+                agent.imagine(state, h)
+            e1.record()
+            e1.synchronize()
+            windows.append(e0.elapsed_time(e1) / max(1, args.calls // 4))
+        res["torch_fp32_ms_per_call"] = round(statistics.median(windows), 4)
+        res["hip_over_torch"] = round(res["mean_reward"]["ms_per_call"] / res["torch_fp32_ms_per_call"], 3)
+    env.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
@@ -186,8 +313,26 @@ def main():
     ap.add_argument("--loop-steps", type=int, default=100)
     ap.add_argument("--out", default=None)
     ap.add_argument("--modes", action="store_true", help="measure the sampled modes (profiles/policy_sample_cost.json)")
+    ap.add_argument("--imagine", action="store_true", help="measure imagination (profiles/policy_imagine_cost.json)")
+    ap.add_argument("--horizon", type=int, default=15)
     args = ap.parse_args()
     import torch
+    if args.imagine:
+        out = {"tool": "tools/policy_cost.py --imagine", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
+               "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle,
+               "macs_per_imagined_step": MACS_IMAGINED_STEP, "macs_per_agent_step": MACS_PER_CAR,
+               "padded_macs_per_imagined_step": PADDED_IMAGINED_STEP, "padded_macs_per_agent_step": PADDED_AGENT_STEP,
+               "padded_ratio": round(PADDED_IMAGINED_STEP / PADDED_AGENT_STEP, 4), "spread_allowance": 1.05,
+               "padded_macs_per_imagined_step_sample": PADDED_IMAGINED_STEP_SAMPLE,
+               "note": "padded MACs follow RC_POLICY_LD* of racecar_policy.h; the ratio and the target are for mode mean, closed loop, "
+                       "reward only - mode sample's extra std tiles (img3, hout) are in padded_macs_per_imagined_step_sample only",
+               "sizes": [measure_imagine(n, args) for n in args.envs]}
+        out["target_met_at_largest_size"] = out["sizes"][-1]["target_met"]
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.modes:
         out = {"tool": "tools/policy_cost.py --modes", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
                "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle, "loop_repeat": 4,
