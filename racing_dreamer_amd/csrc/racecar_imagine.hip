@@ -23,15 +23,8 @@ namespace {
 constexpr int ZS = 233;                        // row stride of Z (41 mod 64, odd: the 32 rows on 32 banks)
 constexpr int Z_STOCH = RC_POLICY_DETER, Z_ACTION = RC_POLICY_DETER + RC_POLICY_STOCH;
 constexpr int FEAT = RC_POLICY_STOCH + RC_POLICY_DETER;
-constexpr int NI = 36;                         // the sampled mode's normals per car and step: 32 of the prior (30 used), block 8's 4
 constexpr size_t kLdsBytes = (size_t)(2 * PM * XS + PM * ZS) * sizeof(float) + PM * sizeof(int);
-constexpr size_t kLdsBytesSampled = kLdsBytes + (size_t)PM * (NI + 4) * sizeof(float);      // + normals and the draw's key
-
-__device__ __forceinline__ int im_car(const RcImagineCall &c, int q) {
-    if (q >= c.n_active) return -1;
-    const int e = q / c.n_slots, k = q - e * c.n_slots;
-    return e * c.cars_per_env + (int)((c.slots >> (8 * k)) & 0xffu);
-}
+constexpr size_t kLdsBytesSampled = kLdsBytes + (size_t)PM * (PN + 4) * sizeof(float);      // + a step's normals and the draw's key
 
 enum { IK_ELU = 0, IK_STOCH = 1, IK_ACTION = 2, IK_REWARD = 3 };
 
@@ -65,11 +58,11 @@ __device__ __forceinline__ void im_dense(const RcImagineCall &c, const ImLayer &
             const int row = pm_row(r, half);
             float v;
             if (L.kind == IK_STOCH) {
-                v = fmaf(pm_softplus(acc[1][r]) + PM_STOCH_MIN_STD, normals[row * NI + cc], acc[0][r]);
+                v = fmaf(pm_softplus(acc[1][r]) + PM_STOCH_MIN_STD, normals[row * PN + cc], acc[0][r]);
             } else {
                 float mu, sd;
                 pm_actor_dist(acc[0][r], acc[1][r], c.ws.hnorm4, cc, mu, sd);
-                v = pm_tanh(fmaf(sd, normals[row * NI + 32 + cc], mu));
+                v = pm_tanh(fmaf(sd, normals[row * PN + 32 + cc], mu));
                 const int car = cars[row];
                 if (car >= 0 && c.actions) c.actions[((size_t)car * c.horizon + t) * 2 + cc] = v;
             }
@@ -110,34 +103,29 @@ __device__ __forceinline__ void im_imagine(const RcImagineCall &c) {
     extern __shared__ float im_lds[];
     float *X = im_lds, *Y = im_lds + PM * XS, *Z = im_lds + 2 * PM * XS;
     int *cars = (int *)(Z + PM * ZS);
-    float *normals = (float *)(cars + PM);                   // [32][NI]   (sampled only)
-    uint32_t *key = (uint32_t *)(normals + PM * NI);         // [32][4]    global env, episode, agent step, slot
+    float *normals = (float *)(cars + PM);                   // [32][PN]   (sampled only)
+    uint32_t *key = (uint32_t *)(normals + PM * PN);         // [32][4]    global env, episode, agent step, slot
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, cc = lane & 31, half = lane >> 5;
     const int row0 = blockIdx.x * PM;
 
     if (tid < PM) {
-        const int car = im_car(c, row0 + tid);
+        const int car = pm_car(c.rows, row0 + tid);
         cars[tid] = car;
         if constexpr (SAMPLED) {
             uint32_t k[4] = {0u, 0u, 0u, 0u};
             if (car >= 0) {
-                const int e = car / c.cars_per_env;
-                k[0] = c.first_env + (uint32_t)e;
-                k[1] = c.episode[e];
-                k[2] = (uint32_t)c.agent_steps[e];
-                k[3] = (uint32_t)(car - e * c.cars_per_env);
+                const int e = car / c.rows.cars_per_env;
+                k[0] = c.rows.first_env + (uint32_t)e;
+                k[1] = c.rows.episode[e];
+                k[2] = (uint32_t)c.rows.agent_steps[e];
+                k[3] = (uint32_t)(car - e * c.rows.cars_per_env);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) key[4 * tid + i] = k[i];
         }
     }
-    // the latent as rc_policy_act left it (`fresh` is not looked at); zero rows past the end
-    for (int idx = tid; idx < PM * RC_POLICY_STATE; idx += PT) {
-        const int row = idx / RC_POLICY_STATE, j = idx - row * RC_POLICY_STATE;
-        const int car = im_car(c, row0 + row);
-        const float v = car >= 0 && j < FEAT ? c.state[(size_t)car * RC_POLICY_STATE + j] : 0.0f;
-        Z[row * ZS + (j < RC_POLICY_STOCH ? Z_STOCH + j : (j < FEAT ? j - RC_POLICY_STOCH : j))] = v;
-    }
+    // the latent as rc_policy_act left it (`fresh` is not looked at, the previous action not read); zero rows past the end
+    pm_load_latent(c.rows, c.state, Z, ZS, row0, tid, [](int, int j) { return j < FEAT; });
     __syncthreads();
 
     const bool open_loop = c.actions_in != nullptr, head = c.reward != nullptr;
@@ -150,13 +138,13 @@ __device__ __forceinline__ void im_imagine(const RcImagineCall &c) {
                 const uint32_t *k = key + 4 * row;
                 float n[4] = {0.0f, 0.0f, 0.0f, 0.0f}, m[4] = {0.0f, 0.0f, 0.0f, 0.0f};
                 if (cars[row] >= 0) {
-                    pm_imagine_normal_block(k[0], k[1], k[2], k[3], (uint32_t)t, (uint32_t)blk, c.seed_lo, c.seed_hi, n);
-                    if (blk == 0 && !open_loop) pm_imagine_normal_block(k[0], k[1], k[2], k[3], (uint32_t)t, PM_IMAGINE_BLOCK_ACTION, c.seed_lo, c.seed_hi, m);
+                    pm_imagine_normal_block(k[0], k[1], k[2], k[3], (uint32_t)t, (uint32_t)blk, c.rows.seed_lo, c.rows.seed_hi, n);
+                    if (blk == 0 && !open_loop) pm_imagine_normal_block(k[0], k[1], k[2], k[3], (uint32_t)t, PM_BLOCK_ACTION, c.rows.seed_lo, c.rows.seed_hi, m);
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    normals[row * NI + 4 * blk + i] = n[i];
-                    if (blk == 0) normals[row * NI + 32 + i] = m[i];
+                    normals[row * PN + 4 * blk + i] = n[i];
+                    if (blk == 0) normals[row * PN + 32 + i] = m[i];
                 }
             }
             if (open_loop && tid < 2 * PM) {
@@ -245,7 +233,7 @@ hipError_t rck_imagine_prepare() {
 }
 
 hipError_t rck_launch_imagine(const RcImagineCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s) {
-    const unsigned blocks = (unsigned)((c.n_active + PM - 1) / PM);
+    const unsigned blocks = (unsigned)((c.rows.n_active + PM - 1) / PM);
     if (!c.sample) hipExtLaunchKernelGGL(rc_policy_imagine_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytes, s, start, stop, 0u, c);
     else hipExtLaunchKernelGGL(rc_policy_imagine_sampled_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytesSampled, s, start, stop, 0u, c);
     return hipGetLastError();

@@ -30,11 +30,21 @@ struct RcPolicyDev {
     const float *hnorm;                      // [4][2] mean, sqrt(var + eps), gamma, beta of the 2 mean columns; null = plain actor
 };
 
-struct RcPolicySampleDev {                   // what the sampled modes read on top (behind RcPolicyCall's other fields: the
-                                             // deterministic kernel's arguments lie where they lay)
+struct RcPolicySampleDev {                   // what the sampled modes read on top
     const float *obs2_w, *obs2_b;            // [200][64], [64]         mean | std columns
     const float *hout_w, *hout_b;            // [400][64], [64]
     const float *hnorm4;                     // [4][4] mean, sqrt(var + eps), gamma, beta of all four output columns; null = plain actor
+};
+
+// The rows of a call and the key of their draws: row q is the car of env q / n_slots in the mask's (q % n_slots)-th slot; a car's
+// draws are keyed by (first_env + env, episode, agent_steps, slot) under the seed ("random stream")
+struct RcPolicyRows {
+    int32_t n_active;                        // num_envs x (slots in the mask): the rows of this call
+    int32_t cars_per_env, n_slots;
+    uint32_t slots;                          // slot of the mask's k-th set bit in byte k
+    uint32_t seed_lo, seed_hi, first_env;
+    const uint32_t *episode;                 // [num_envs] the env's episode counter ...
+    const int32_t *agent_steps;              // ... and its agent steps within the episode, as the last step or reset left them
 };
 
 struct RcPolicyCall {
@@ -43,17 +53,12 @@ struct RcPolicyCall {
     const uint8_t *fresh;                    // [n_cars]
     float *state;                            // [n_cars][RC_POLICY_STATE]
     float *actions;                          // [n_cars][2] RC_F_ACTION_IN
-    int32_t n_active;                        // num_envs x (slots in the mask): the rows of this call
-    int32_t cars_per_env, n_slots;
-    uint32_t slots;                          // slot of the mask's k-th set bit in byte k
+    RcPolicyRows rows;                       // (the seed and the counters: the sampled modes only)
     int32_t raw_actions;                     // rc_config.remap_actions: the env maps [-1, 1]^2 itself
     float lo0, lo1, hi0, hi1;                // else: postprocess_action's range
     // the sampled modes only (rc_policy_set_sampling)
     int32_t mode;                            // RC_POLICY_MODE_DEPLOY | RC_POLICY_MODE_EXPLORE
     float expl_amount;
-    uint32_t seed_lo, seed_hi, first_env;
-    const uint32_t *episode;                 // [num_envs] the env's episode counter ...
-    const int32_t *agent_steps;              // ... and its agent steps within the episode, as the last step or reset left them
     RcPolicySampleDev ws;
 };
 
@@ -70,11 +75,7 @@ struct RcImagineCall {
     RcPolicySampleDev ws;
     RcImagineDev wi;
     const float *state;                      // [n_cars][RC_POLICY_STATE], read only
-    const uint32_t *episode;                 // [num_envs]: the draw's key, as rc_policy_act reads it
-    const int32_t *agent_steps;
-    uint32_t seed_lo, seed_hi, first_env;
-    int32_t n_active, cars_per_env, n_slots;
-    uint32_t slots;
+    RcPolicyRows rows;                       // (the draw's key: as rc_policy_act reads it)
     int32_t horizon, sample;
     const float *actions_in;                 // [n_cars][H][2] or null: the actor's own
     float *reward, *actions, *features, *reward_start;      // [n_cars][H], [n_cars][H][2], [n_cars][H][230], [n_cars]; any may be null

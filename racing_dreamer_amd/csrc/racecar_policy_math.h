@@ -84,11 +84,15 @@ __device__ __forceinline__ float pm_action_normalized(float out, float mean, flo
     return pm_tanh((out - mean) / sd * gamma + beta);
 }
 
+// the clip to [-1, 1] of postprocess_action, and of an action given to imagination from outside
+__device__ __forceinline__ float pm_clamp_action(float a) {
+    a = a > -1.0f ? a : -1.0f;
+    return a < 1.0f ? a : 1.0f;
+}
+
 // postprocess_action (racing_dreamer.py:53-59) = ReduceActionSpace (dreamer/wrappers.py:128-130), as the dynamics kernel writes it
 __device__ __forceinline__ float pm_postprocess(float a, float lo, float hi) {
-    a = a > -1.0f ? a : -1.0f;
-    a = a < 1.0f ? a : 1.0f;
-    return ((a + 1.0f) * 0.5f) * (hi - lo) + lo;
+    return ((pm_clamp_action(a) + 1.0f) * 0.5f) * (hi - lo) + lo;
 }
 
 // ---- the sampled modes: tests/policy_sample_spec.c restates what follows
@@ -109,7 +113,7 @@ __device__ __forceinline__ float pm_postprocess(float a, float lo, float hi) {
 #define PM_TWO_PI 0x1.921fb6p+2f
 #define PM_2P24_INV 0x1p-24f
 #define PM_SAMPLE_TAG 4u                   // Philox counter word 3, bits 24-31 (spawn 0, DR 2, track draw 3)
-#define PM_BLOCK_ACTION 8u                 // block 8: words 0-1 the single action sample, words 2-3 the exploration noise
+#define PM_BLOCK_ACTION 8u                 // block 8: words 0-1 the single action sample, words 2-3 the exploration noise (imagination: words 0-1 step t's action draw)
 #define PM_BLOCK_CANDIDATES 16u            // blocks 16 + i, i < 50: candidates 2 i and 2 i + 1 of the best of 100
 #define PM_CANDIDATES 100
 
@@ -160,12 +164,18 @@ __device__ __forceinline__ void pm_normal_pair(uint32_t w0, uint32_t w1, float &
     n1 = r * sn;
 }
 
+// the four normals of the Philox block whose counter is (env, episode, agent step, word): the two streams below
+__device__ __forceinline__ void pm_normal_word(uint32_t env, uint32_t episode, uint32_t agent_step, uint32_t word, uint32_t seed_lo,
+                                               uint32_t seed_hi, float (&n)[4]) {
+    const rcd::u32x4 r = rcd::philox4x32(env, episode, agent_step, word, seed_lo, seed_hi);
+    pm_normal_pair(r.x, r.y, n[0], n[1]);
+    pm_normal_pair(r.z, r.w, n[2], n[3]);
+}
+
 // the four normals of block `block` of a car's draw ("random stream")
 __device__ __forceinline__ void pm_normal_block(uint32_t env, uint32_t episode, uint32_t agent_step, uint32_t slot, uint32_t block,
                                                 uint32_t seed_lo, uint32_t seed_hi, float (&n)[4]) {
-    const rcd::u32x4 r = rcd::philox4x32(env, episode, agent_step, block | (slot << 8) | (PM_SAMPLE_TAG << 24), seed_lo, seed_hi);
-    pm_normal_pair(r.x, r.y, n[0], n[1]);
-    pm_normal_pair(r.z, r.w, n[2], n[3]);
+    pm_normal_word(env, episode, agent_step, block | (slot << 8) | (PM_SAMPLE_TAG << 24), seed_lo, seed_hi, n);
 }
 
 // one action dimension's term of a candidate's score: the tanh-normal log-density at the pre-tanh u = mu + sd n without the
@@ -196,18 +206,9 @@ __device__ __forceinline__ void pm_actor_dist(float out_mean, float out_std, con
 
 // ---- imagination: tests/policy_imagine_spec.c restates what follows
 #define PM_IMAGINE_TAG 5u                  // Philox counter word 3, bits 24-31
-#define PM_IMAGINE_BLOCK_ACTION 8u         // block 8 of imagined step t: words 0-1 the action draw; blocks 0-7: the prior's 30 normals
 
-// the four normals of block `block` of imagined step t of a car's rollout
+// the four normals of block `block` of imagined step t of a car's rollout: blocks 0-7 the prior's 30 normals, PM_BLOCK_ACTION the action draw
 __device__ __forceinline__ void pm_imagine_normal_block(uint32_t env, uint32_t episode, uint32_t agent_step, uint32_t slot, uint32_t t,
                                                         uint32_t block, uint32_t seed_lo, uint32_t seed_hi, float (&n)[4]) {
-    const rcd::u32x4 r = rcd::philox4x32(env, episode, agent_step, block | (slot << 8) | (t << 12) | (PM_IMAGINE_TAG << 24), seed_lo, seed_hi);
-    pm_normal_pair(r.x, r.y, n[0], n[1]);
-    pm_normal_pair(r.z, r.w, n[2], n[3]);
-}
-
-// an action given from outside: clamped to [-1, 1] as pm_postprocess clamps
-__device__ __forceinline__ float pm_clamp_action(float a) {
-    a = a > -1.0f ? a : -1.0f;
-    return a < 1.0f ? a : 1.0f;
+    pm_normal_word(env, episode, agent_step, block | (slot << 8) | (t << 12) | (PM_IMAGINE_TAG << 24), seed_lo, seed_hi, n);
 }

@@ -1,8 +1,11 @@
 // The MFMA machinery the Dreamer kernels share (racecar_policy.hip: the agent; racecar_imagine.hip: imagination): one workgroup of
 // four waves owns 32 cars = the rows of v_mfma_f32_32x32x2_f32 tiles; activations lie in LDS rows of an odd stride, weights are
-// read from L2 straight into the B operand.  Not part of the public interface.
+// read from L2 straight into the B operand.  Below the k loop (pm_gemm): the row-to-car map of a call and the packing of the
+// stored latent into LDS.  The dense wrappers, the tile ladder and the GRU loop are each kernel's own (DESIGN.md §4 says why).
+// Not part of the public interface.
 #pragma once
 #include "racecar_policy.h"
+#include "racecar_policy_math.h"
 
 typedef float pm_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -12,6 +15,7 @@ constexpr int PT = 256;                        // threads per workgroup
 constexpr int PM = RC_POLICY_TILE;             // cars per workgroup
 constexpr int XS = 417;                        // row stride of X and Y [floats]
 constexpr int PD = 4;                          // k-steps (of 2) whose operands are requested one block ahead
+constexpr int PN = 36;                         // normals per car and draw: blocks 0-7 (the 30 of stoch, 2 unused), the 4 of block 8
 
 // acc[t] += A[32 x 2 ksteps] W[2 ksteps x 32 columns at col[t]], k ascending.  a = &A[lane & 31][lane >> 5] (LDS),
 // w = &W[lane >> 5][lane & 31] (global).  The operands of the next PD k-steps are requested before this block's MFMAs issue;
@@ -65,5 +69,28 @@ __device__ __forceinline__ void pm_bias(pm_f32x16 (&acc)[TN], const float *__res
 
 // C/D map of the 32x32 tile: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
 __device__ __forceinline__ int pm_row(int reg, int half) { return (reg & 3) + 8 * (reg >> 2) + 4 * half; }
+
+// row q of the call -> car index (the mask's slots of env q / n_slots), -1 past the end
+__device__ __forceinline__ int pm_car(const RcPolicyRows &c, int q) {
+    if (q >= c.n_active) return -1;
+    const int e = q / c.n_slots, k = q - e * c.n_slots;
+    return e * c.cars_per_env + (int)((c.slots >> (8 * k)) & 0xffu);
+}
+
+// The stored latent of the workgroup's rows into LDS, dst rows ds apart: deter at [0, 200), stoch at [200, 230), the previous raw
+// action at [230, 232); zero for rows past the end and wherever keep(car, column of the state) says no
+template <class Keep>
+__device__ __forceinline__ void pm_load_latent(const RcPolicyRows &c, const float *state, float *dst, int ds, int row0, int tid, Keep &&keep) {
+    for (int idx = tid; idx < PM * RC_POLICY_STATE; idx += PT) {
+        const int row = idx / RC_POLICY_STATE, j = idx - row * RC_POLICY_STATE;
+        const int car = pm_car(c, row0 + row);
+        const float v = car >= 0 && keep(car, j) ? state[(size_t)car * RC_POLICY_STATE + j] : 0.0f;
+        int at;
+        if (j < RC_POLICY_STOCH) at = RC_POLICY_DETER + j;
+        else if (j < RC_POLICY_STOCH + RC_POLICY_DETER) at = j - RC_POLICY_STOCH;
+        else at = j;                                                // (the action's 2 columns follow stoch's 30)
+        dst[row * ds + at] = v;
+    }
+}
 
 }  // namespace

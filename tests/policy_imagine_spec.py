@@ -3,10 +3,7 @@ which includes policy_sample_spec.c and policy_spec.c), built and loaded the way
 `imagine` takes the packed latents [n, 232] and the draws' keys - (global env, episode, agent step, slot) per car - and returns
 what the device call returns, plus the normals it drew."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -31,21 +28,7 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    cc = os.environ.get("CC", "cc")
-    flags = ps.CFLAGS + ps._hardware_fma_flags(cc)
-    h = hashlib.sha256()
-    for path in (SRC, pss.SRC, ps.SRC):
-        with open(path, "rb") as f:
-            h.update(f.read())
-    tag = hashlib.sha256(h.digest() + " ".join(flags).encode()).hexdigest()[:16]
-    os.makedirs(ps.BUILD_DIR, exist_ok=True)
-    so = os.path.join(ps.BUILD_DIR, f"policy_imagine_spec_{tag}.so")
-    if not os.path.exists(so):
-        fd, tmp = tempfile.mkstemp(suffix=".so", dir=ps.BUILD_DIR)
-        os.close(fd)
-        subprocess.run([cc, *flags, SRC, "-o", tmp, "-lm"], check=True)
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    lib = ps.build_and_load("policy_imagine_spec", [SRC, pss.SRC, ps.SRC])
     lib.pis_imagine.restype = None
     lib.pis_imagine.argtypes = [C.POINTER(ps._Weights), C.POINTER(_Heads), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int] + [C.c_void_p] * 8
     lib.pis_normals.restype = None

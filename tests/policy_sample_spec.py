@@ -3,10 +3,7 @@ which includes policy_spec.c), built and loaded the way policy_spec.py builds Po
 (global env, episode, agent step, slot) per car - and can return the normals it drew, the winning candidate and the actor's
 distribution; `EpisodeClock` keeps the two counters the device reads for an env that is driven with auto-reset."""
 import ctypes as C
-import hashlib
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
@@ -25,21 +22,7 @@ def load():
     global _lib
     if _lib is not None:
         return _lib
-    cc = os.environ.get("CC", "cc")
-    flags = ps.CFLAGS + ps._hardware_fma_flags(cc)
-    h = hashlib.sha256()
-    for path in (SRC, ps.SRC):
-        with open(path, "rb") as f:
-            h.update(f.read())
-    tag = hashlib.sha256(h.digest() + " ".join(flags).encode()).hexdigest()[:16]
-    os.makedirs(ps.BUILD_DIR, exist_ok=True)
-    so = os.path.join(ps.BUILD_DIR, f"policy_sample_spec_{tag}.so")
-    if not os.path.exists(so):
-        fd, tmp = tempfile.mkstemp(suffix=".so", dir=ps.BUILD_DIR)
-        os.close(fd)
-        subprocess.run([cc, *flags, SRC, "-o", tmp, "-lm"], check=True)
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    lib = ps.build_and_load("policy_sample_spec", [SRC, ps.SRC])
     lib.pss_act.restype = None
     lib.pss_act.argtypes = [C.POINTER(ps._Weights), C.c_int, C.c_uint32, C.c_uint32, C.c_float, C.c_int] + [C.c_void_p] * 8
     lib.pss_map.restype = None

@@ -39,22 +39,33 @@ def _hardware_fma_flags(cc):
     return ["-mfma"] if r.returncode == 0 else []
 
 
+def build_and_load(name, sources):
+    """Compile sources[0] - the others are the files it includes: they enter the hash only - into _build/<name>_<hash of the
+    sources and flags>.so unless it is there, and load it."""
+    cc = os.environ.get("CC", "cc")
+    flags = CFLAGS + _hardware_fma_flags(cc)
+    blobs = []
+    for path in sources:
+        with open(path, "rb") as f:
+            blobs.append(f.read())
+    # (the names the libraries have had: one source is hashed with the flags directly, several through a hash of their own)
+    body = blobs[0] if len(blobs) == 1 else hashlib.sha256(b"".join(blobs)).digest()
+    tag = hashlib.sha256(body + " ".join(flags).encode()).hexdigest()[:16]
+    os.makedirs(BUILD_DIR, exist_ok=True)
+    so = os.path.join(BUILD_DIR, f"{name}_{tag}.so")
+    if not os.path.exists(so):
+        fd, tmp = tempfile.mkstemp(suffix=".so", dir=BUILD_DIR)
+        os.close(fd)
+        subprocess.run([cc, *flags, sources[0], "-o", tmp, "-lm"], check=True)
+        os.replace(tmp, so)
+    return C.CDLL(so)
+
+
 def load():
     global _lib
     if _lib is not None:
         return _lib
-    cc = os.environ.get("CC", "cc")
-    flags = CFLAGS + _hardware_fma_flags(cc)
-    with open(SRC, "rb") as f:
-        tag = hashlib.sha256(f.read() + " ".join(flags).encode()).hexdigest()[:16]
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    so = os.path.join(BUILD_DIR, f"policy_spec_{tag}.so")
-    if not os.path.exists(so):
-        fd, tmp = tempfile.mkstemp(suffix=".so", dir=BUILD_DIR)
-        os.close(fd)
-        subprocess.run([cc, *flags, SRC, "-o", tmp, "-lm"], check=True)
-        os.replace(tmp, so)
-    lib = C.CDLL(so)
+    lib = build_and_load("policy_spec", [SRC])
     lib.ps_act.restype = None
     lib.ps_act.argtypes = [C.POINTER(_Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ps_map.restype = None

@@ -58,22 +58,26 @@ def test_one_call_is_the_spec_bit_for_bit(name, remap):
         env.close()
 
 
-@pytest.mark.parametrize("mode", MODES)
-def test_open_loop_follows_the_given_actions(mode):
-    """Actions given from outside, a third of them beyond +-1: the outputs equal the spec's, `action` echoes the clamped input."""
+@pytest.mark.parametrize("mode, name, h, start", [pytest.param(mode, *case, id=mode + tag) for tag, case in
+                                                  (("", ("austria", 5, True)), ("-no-head", ("treitlstrasse_20210220", 2, False))) for mode in MODES])
+def test_open_loop_follows_the_given_actions(mode, name, h, start):
+    """Actions given from outside, a third of them beyond +-1: the outputs equal the spec's, `action` echoes the clamped input.
+    Also on the normalized checkpoint, which has no reward head, without the starting reward: the prior's three layers alone."""
     import torch
     from racing_dreamer_amd.batched_env import BatchedRaceEnv
-    n, h = 33, 5
+    n = 33
     _, state, _ = _recorded_inputs(n, seed=3)
     env = BatchedRaceEnv("austria", n, 1, auto_reset=True, remap_actions=True)
     env.reset(mode="random", seed=1)
-    env.load_policy(weights("austria"))
+    env.load_policy(weights(name))
+    assert env.policy_has_reward_head == start
     env.policy_state.copy_(torch.from_numpy(state))
     clock = EpisodeClock(n)
     clock.reset()
     acts = np.random.default_rng(2).uniform(-1.5, 1.5, (n, h, 2)).astype(np.float32)
-    got = _cpu(env.policy_imagine(h, mode, seed=5, actions=torch.from_numpy(acts), features=True, start_reward=True))
-    _same(got, PolicyImagineSpec(weights("austria")).imagine(state, clock.keys(), h, mode, seed=5, actions=acts), mode)
+    got = _cpu(env.policy_imagine(h, mode, seed=5, actions=torch.from_numpy(acts), features=True, start_reward=start))
+    assert set(got) == {"action", "feature"} | ({"reward", "reward_start"} if start else set())
+    _same(got, PolicyImagineSpec(weights(name)).imagine(state, clock.keys(), h, mode, seed=5, actions=acts), (name, mode))
     assert np.array_equal(got["action"], np.clip(acts, -1.0, 1.0)) and np.abs(acts).max() > 1.0
     env.close()
 
