@@ -246,6 +246,22 @@ __device__ __forceinline__ unsigned first_trip_entry(uint32_t lds_line, float dy
     typedef const __attribute__((address_space(3))) uint16_t *lds_u16_ptr;
     return *(lds_u16_ptr)(uintptr_t)(lds_line + addr);
 }
+// The same, and the LDS address of the ray's quadrant record in the wave's frame table (scan_car: 32 bytes per quadrant
+// q = 2 (dy < 0) + (dx < 0) behind the first-trip line): q32 = 32 q is what both addresses are made of, the line's
+// quadrant offset being 2 RC_FIRST_BINS q = 4 q32 bytes.
+__device__ __forceinline__ unsigned first_trip_entry_frame(uint32_t lds_line, uint32_t frame_base, float dy, float idx, int nx, int ny, uint32_t &frame_addr) {
+    static_assert(2u * RC_FIRST_BINS == 4u * 32u, "a quadrant of the first-trip line is four frame records long");
+    float slope;
+    asm("v_mul_f32_e64 %0, |%1|, |%2|" : "=v"(slope) : "v"(dy), "v"(idx));
+    const unsigned bin = med3_u32(__float_as_uint(slope) >> RC_FIRST_SHIFT, RC_FIRST_BIAS, RC_FIRST_BIAS + RC_FIRST_BINS - 1);
+    unsigned q32, w, addr;
+    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(q32) : "v"(ny), "v"(64u), "v"((unsigned)nx & 32u));
+    asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(w) : "v"(q32), "v"(bin));          // bin + 2 q32: twice that = 2 bin + 128 q
+    asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(addr) : "v"(w), "v"(lds_line));
+    frame_addr = q32 + frame_base;
+    typedef const __attribute__((address_space(3))) uint16_t *lds_u16_ptr;
+    return *(lds_u16_ptr)(uintptr_t)addr;
+}
 
 // ---- The traversal (variants 6 and 7), in the mirrored frame with cell indices as float bits (see above) ----------
 constexpr float kCellMagic = 12582912.0f;               // 1.5 * 2^23
@@ -306,20 +322,32 @@ struct NothingBetween { __device__ __forceinline__ void operator()() const {} };
 // grid is ringed by them.  The bound costs 4 % of the scan, so it is compiled into the builds that run when that proof
 // does not cover the run: the validation scan of rc_load_track, any run with a validation band or RC_DBG_SCAN_BOUNDED,
 // and the per-ray variant 6.
-template <bool FROM_PLANE, class Between = NothingBetween, bool GUARD = true>
+// FRAME_LDS: the ray's frame (below) is read from the wave's frame table at LDS address frame_addr instead of computed.
+template <bool FROM_PLANE, class Between = NothingBetween, bool GUARD = true, bool FRAME_LDS = false>
 __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackDev &t, const TravConst &k, float gx, float gy,
                                               float dx, float dy, float idx, float idy, int nx, int ny, int ix, int iy,
                                               unsigned v, bool in_grid, int *wave_trips = nullptr, int *wave_exact = nullptr,
-                                              Between between = Between(), int *overrun = nullptr) {
+                                              Between between = Between(), int *overrun = nullptr, uint32_t frame_addr = 0) {
     const int pitch2 = t.cell_pitch * 2;
     const char *qb = reinterpret_cast<const char *>(qr);
     // mirrored origin, the origin of the position estimate, the start cell (i~ = ~i on a mirrored axis) and the part of
     // the table address that depends on the quadrant only
-    const float gmx = __uint_as_float(__float_as_uint(gx) ^ ((uint32_t)nx & 0x80000000u));
-    const float gmy = __uint_as_float(__float_as_uint(gy) ^ ((uint32_t)ny & 0x80000000u));
-    const float hx = gmx + k.band_mh, hy = gmy + k.band_mh;
-    uint32_t Tx = (uint32_t)(ix ^ nx) + kCellMagicBits, Ty = (uint32_t)(iy ^ ny) + kCellMagicBits;
-    uint32_t qoff = (((uint32_t)nx & k.kx) + ((uint32_t)ny & k.ky)) + k.c00;
+    float gmx, gmy, hx, hy;
+    uint32_t Tx, Ty, qoff;
+    if (FRAME_LDS) {
+        // all seven depend on the car and the ray's QUADRANT only: the wave computed the four records once (scan_car) and
+        // every ray reads its own - two 16-byte LDS reads instead of nine vector instructions per ray
+        typedef const __attribute__((address_space(3))) v4u *lds_v4u_cptr;
+        const v4u a = *(lds_v4u_cptr)(uintptr_t)frame_addr, b = *(lds_v4u_cptr)(uintptr_t)(frame_addr + 16u);
+        gmx = __uint_as_float(a.x); gmy = __uint_as_float(a.y); hx = __uint_as_float(a.z); hy = __uint_as_float(a.w);
+        Tx = b.x; Ty = b.y; qoff = b.z;
+    } else {
+        gmx = __uint_as_float(__float_as_uint(gx) ^ ((uint32_t)nx & 0x80000000u));
+        gmy = __uint_as_float(__float_as_uint(gy) ^ ((uint32_t)ny & 0x80000000u));
+        hx = gmx + k.band_mh; hy = gmy + k.band_mh;
+        Tx = (uint32_t)(ix ^ nx) + kCellMagicBits; Ty = (uint32_t)(iy ^ ny) + kCellMagicBits;
+        qoff = (((uint32_t)nx & k.kx) + ((uint32_t)ny & k.ky)) + k.c00;
+    }
     asm("" : "+v"(qoff));                                                 // one value: keep it out of the loop's address math
     if (FROM_PLANE) {
         v = 0;
@@ -440,7 +468,10 @@ __device__ __forceinline__ uint32_t quantise_pair(float a, float b, float off, f
 }
 
 constexpr unsigned kCarRowBytes = ((RC_N_BEAMS + 63) / 64) * 64 * 4;   // LDS per wave of rc_raycast_car_kernel: its car's ranges ...
-constexpr unsigned kCarLdsBytes = kCarRowBytes + 2 * RC_FIRST_PLANES;  // ... and the start cell's line of the first-trip table
+constexpr unsigned kCarFrameBytes = 4 * 32;                            // ... the four quadrant records of the traversal's frame ...
+constexpr unsigned kCarLdsBytes = kCarRowBytes + 2 * RC_FIRST_PLANES + kCarFrameBytes;  // ... and the start cell's line of the first-trip table
+// (8 waves per SIMD = 32 per CU x 4 992 bytes = 156 KB of the CU's 160 KB: the LDS still lets the scan's occupancy stand)
+static_assert(32u * kCarLdsBytes <= 160u * 1024u, "the scan's LDS must leave room for 8 waves per SIMD");
 
 // STAMPS: the instrumented build (rc_debug_scan_stamps): RC_STAMP_SLOTS uint64 per wave.  Shader-clock values (s_memtime: a
 // per-CU counter, comparable within a wave only) at fixed points of the wave's life - slot 0 entry, 1 car state arrived,
@@ -557,6 +588,25 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
     const TravConst kc = trav_const(t);
     const TravConst k = {pin_vgpr(kc.band_mh), pin_vgpr(kc.res), pin_vgpr(kc.kx), pin_vgpr(kc.ky), pin_vgpr(kc.c00)};
     const int ixv = pin_vgpr(ix), iyv = pin_vgpr(iy);
+    // The frame table: what ray_traverse needs of the ray's frame - mirrored origin, origin of the position estimate, start cell,
+    // the quadrant's part of the table address - depends on the car and the ray's QUADRANT only, so lane q < 4 writes quadrant
+    // q's record (the very expressions ray_traverse evaluates per ray otherwise: the bits are the same) and every ray reads its
+    // own with two 16-byte LDS reads: 7 vector instructions per round and 4 registers less.
+    const uint32_t lds_frame = lds_first + 2u * RC_FIRST_PLANES;
+    if (lane < 4u) {
+        const int qnx = (lane & 1u) ? -1 : 0, qny = (lane & 2u) ? -1 : 0;
+        const float qgmx = __uint_as_float(__float_as_uint(gx) ^ ((uint32_t)qnx & 0x80000000u));
+        const float qgmy = __uint_as_float(__float_as_uint(gy) ^ ((uint32_t)qny & 0x80000000u));
+        const float qhx = qgmx + kc.band_mh, qhy = qgmy + kc.band_mh;
+        const uint32_t qTx = (uint32_t)(ix ^ qnx) + kCellMagicBits, qTy = (uint32_t)(iy ^ qny) + kCellMagicBits;
+        const uint32_t qq = (((uint32_t)qnx & kc.kx) + ((uint32_t)qny & kc.ky)) + kc.c00;
+        typedef __attribute__((address_space(3))) v4u *lds_v4u_wptr;
+        const v4u fa = {__float_as_uint(qgmx), __float_as_uint(qgmy), __float_as_uint(qhx), __float_as_uint(qhy)};
+        const v4u fb = {qTx, qTy, qq, 0u};
+        *(lds_v4u_wptr)(uintptr_t)(lds_frame + 32u * lane) = fa;
+        *(lds_v4u_wptr)(uintptr_t)(lds_frame + 32u * lane + 16u) = fb;
+    }
+    const uint32_t frame_base = pin_vgpr(lds_frame);
     constexpr int kRounds = (RC_N_BEAMS + 63) / 64;
     // (per-round steps live in vector registers: a full-rate add that reads a scalar register issues at half rate)
     const unsigned bstep = pin_vgpr(512u * (unsigned)split), ostep = pin_vgpr(256u * (unsigned)split);
@@ -570,7 +620,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
     // and first-trip entry are already computed / in flight (and round r + 2's beam pair is being fetched), so no
     // round starts by waiting for its start entry.  Two register sets take turns (the loop body holds two rounds), so
     // nothing is copied between them.
-    struct Ray { float dx, dy, idx, idy; int nx, ny; unsigned v; };
+    struct Ray { float dx, dy, idx, idy; int nx, ny; unsigned v; uint32_t fa; };   // fa: LDS address of the ray's frame record
     // (dx, dy) = (ct cb - st sb, ct sb + st cb), one rounding per operator: four products, a subtract and an add - plain
     // full-rate instructions (the packed forms issue at half rate and need their operands swizzled into pairs)
     auto prepare = [&](float2 b, Ray &r) {
@@ -578,7 +628,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         r.dy = ct * b.y + st * b.x;
         ray_reciprocals(r.dx, r.dy, r.idx, r.idy);
         r.nx = sign_mask(r.dx); r.ny = sign_mask(r.dy);
-        r.v = first_trip_entry(first_line, r.dy, r.idx, r.nx, r.ny);
+        r.v = first_trip_entry_frame(first_line, frame_base, r.dy, r.idx, r.nx, r.ny, r.fa);
     };
     // one round: prepare `nxt` for round + split, traverse `cur`, store.  false: this lane has no beam in the round
     auto stage = [&](int round, const Ray &cur, Ray &nxt) -> bool {
@@ -599,14 +649,14 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         };
         float rng;
         if (OVERLAP) {
-            rng = ray_traverse<false, decltype(prepare_next), GUARD>(t.quad_rect, t, k, gx, gy, cur.dx, cur.dy, cur.idx, cur.idy, cur.nx, cur.ny, ixv, iyv, cur.v, true,
-                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, prepare_next, GUARD ? &overrun : nullptr);
+            rng = ray_traverse<false, decltype(prepare_next), GUARD, true>(t.quad_rect, t, k, gx, gy, cur.dx, cur.dy, cur.idx, cur.idy, cur.nx, cur.ny, ixv, iyv, cur.v, true,
+                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, prepare_next, GUARD ? &overrun : nullptr, cur.fa);
         } else {
             prepare_next();
             if (STAMPS) asm volatile("" :: "v"(nxt.idx), "v"(nxt.idy));
             phase(t_prep);
-            rng = ray_traverse<false, NothingBetween, GUARD>(t.quad_rect, t, k, gx, gy, cur.dx, cur.dy, cur.idx, cur.idy, cur.nx, cur.ny, ixv, iyv, cur.v, true,
-                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, NothingBetween(), GUARD ? &overrun : nullptr);
+            rng = ray_traverse<false, NothingBetween, GUARD, true>(t.quad_rect, t, k, gx, gy, cur.dx, cur.dy, cur.idx, cur.idy, cur.nx, cur.ny, ixv, iyv, cur.v, true,
+                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, NothingBetween(), GUARD ? &overrun : nullptr, cur.fa);
         }
         if (STAMPS) asm volatile("" :: "v"(rng));
         phase(t_trav);
