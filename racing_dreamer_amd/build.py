@@ -53,8 +53,8 @@ def source_hash(csrc: str = CSRC, flags=None, sources=None) -> str:
 
 
 def headers_hash(csrc: str = CSRC) -> str:
-    """sha256 over the CONTENT of the headers alone: what the shipped library and the lab library must have in common (RcParams
-    and RcLaunchInfo cross between them by pointer).  Compiled into both as -DRC_HEADERS_ID; the loader compares."""
+    """sha256 over the CONTENT of the headers alone: what the shipped library and the lab library must have in common (RcParams,
+    RcLaunchInfo and RcLabTables cross between them by pointer).  Compiled into both as -DRC_HEADERS_ID; the loader compares."""
     import hashlib
     h = hashlib.sha256()
     for name in HEADERS:

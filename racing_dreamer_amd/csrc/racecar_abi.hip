@@ -88,7 +88,10 @@ void set_launch_geometry(rc_env *env) {
         return (int)std::min<long long>((items + threads - 1) / threads, (long long)li.n_cu * wg_per_cu);
     };
     const long long rays = (long long)env->n_cars * RC_N_BEAMS;
-    li.ray_blocks = blocks_for(li.raycast_variant >= 4 ? (size_t)1 : li.raycast_variant == 3 ? li.lds_bytes_packed : (li.raycast_variant != 0 ? li.lds_bytes_skip : li.lds_bytes), rays, li.ray_threads);
+    // (variants 1-3 stage the lab's tables in LDS: their sizes follow from the grid's shape, built or not)
+    const RcTrackDev &t = env->params.trk;
+    const RcLabTables lg = li.raycast_variant >= 1 && li.raycast_variant <= 3 ? rc_lab_geometry(t.h, t.w, t.pitch) : RcLabTables{};
+    li.ray_blocks = blocks_for(li.raycast_variant >= 4 ? (size_t)1 : li.raycast_variant == 3 ? lg.lds_bytes_packed : (li.raycast_variant != 0 ? lg.lds_bytes_skip : li.lds_bytes), rays, li.ray_threads);
     li.patch_variant = env->dbg[RC_DBG_PATCH_VARIANT];
     // tuning knobs for experiments (rc_debug_set; all zero in production): workgroup size / workgroups per CU of the LDS-free scan
     if (li.raycast_variant == 7) {
@@ -263,7 +266,7 @@ int observe(rc_env *env) {
         if ((rc = ts_sync_table(env))) return rc;
         HIP_TRY(rck_launch_ts_list(env->params, env->stream));
     }
-    TIMED(env, RC_K_RAYCAST, ts ? rck_launch_ts_raycast(env->params, env->launch, env->stream) : rck_launch_raycast(env->params, env->launch, env->stream));
+    TIMED(env, RC_K_RAYCAST, ts ? rck_launch_ts_raycast(env->params, env->launch, env->stream) : rck_launch_raycast(env->params, env->launch, &env->track->lab, env->stream));
     env->last_scan_rows = env->params.out.lidar;
     if ((rc = render_patches(env))) return rc;
     if (env->compact_slab)      // the scan has written the uint16 rows; the 76 B/car summary follows them
@@ -671,147 +674,100 @@ int rc_set_source_frame(rc_env *env, int32_t full_height, int32_t row_top, int32
     return RC_OK;
 }
 
-int rc_load_track(rc_env *env, const uint32_t *occ_words, const uint32_t *drivable_words, const float *progress,
-                  int32_t h, int32_t w, int32_t pitch, float resolution, float origin_x, float origin_y,
-                  const float *centerline, int32_t n_centerline) {
+}  // extern "C"
+
+namespace {
+// ---- rc_load_track, step by step
+struct TrackSource {             // the caller's arrays
+    const uint32_t *occ_words, *drivable_words;
+    const float *progress;
+    int32_t h, w, pitch;
+    float resolution, origin_x, origin_y;
+    const float *centerline;
+    int32_t n_centerline;
+    size_t nwords() const { return (size_t)h * pitch; }
+};
+struct TrackKey { uint64_t key = 0xcbf29ce484222325ull, sum2 = 0; };
+struct TrackHostTables {         // what the host prepares for the upload
+    size_t bm_bytes = 0;
+    std::vector<uint32_t> ray, drv;
+    std::vector<float> beams, foot;
+};
+
+int check_track_source(const rc_env *env, const TrackSource &src) {
+    const int32_t h = src.h, w = src.w, pitch = src.pitch;
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (!occ_words || !drivable_words || !progress || !centerline) return fail(RC_ERR_INVALID, "NULL track array");
+    if (!src.occ_words || !src.drivable_words || !src.progress || !src.centerline) return fail(RC_ERR_INVALID, "NULL track array");
     if (h < 3 || w < 3 || pitch * 32 < w) return fail(RC_ERR_INVALID, "bad track shape h=%d w=%d pitch=%d", h, w, pitch);
-    if (n_centerline < 1) return fail(RC_ERR_INVALID, "centerline table is empty");
-    if (!(resolution > 0.f)) return fail(RC_ERR_INVALID, "resolution must be > 0");
+    if (src.n_centerline < 1) return fail(RC_ERR_INVALID, "centerline table is empty");
+    if (!(src.resolution > 0.f)) return fail(RC_ERR_INVALID, "resolution must be > 0");
     // the skipping traversals place a ray inside a free rectangle with fp32 arithmetic on cell coordinates and fall
     // back to exact comparisons within max(w, h) * 2^-21 cell of a boundary (RcTrackDev::band, derived in
     // racecar_kernels.hip); 4096 keeps that zone below 2e-3 cell and every index within the 24-bit multiplies
     if (h > 4096 || w > 4096) return fail(RC_ERR_INVALID, "grids larger than 4096 cells per side are not supported (h=%d w=%d)", h, w);
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    const size_t nwords = (size_t)h * pitch;
-    // the same track already on this device (another handle of the process loaded it)?
-    uint64_t key = 0xcbf29ce484222325ull, sum2 = 0;
-    {
-        const int32_t dims[4] = {h, w, pitch, n_centerline};
-        const float geo[3] = {resolution, origin_x, origin_y};
-        key = fnv1a(key, dims, sizeof(dims));
-        key = fnv1a(key, geo, sizeof(geo));
-        key = fnv1a(key, occ_words, nwords * 4);
-        key = fnv1a(key, drivable_words, nwords * 4);
-        key = fnv1a(key, progress, (size_t)h * w * 4);
-        key = fnv1a(key, centerline, (size_t)n_centerline * 16);
-        sum2 = wordsum(wordsum(wordsum(wordsum(0, occ_words, nwords * 4), drivable_words, nwords * 4), progress, (size_t)h * w * 4),
-                       centerline, (size_t)n_centerline * 16);
-    }
-    std::lock_guard<std::mutex> track_lock(g_track_mutex);
-    auto finish_load = [&](const std::shared_ptr<TrackTables> &tt) {
-        env->track = tt;
-        env->params.trk = tt->t;
-        set_band(env);
-        RcLaunchInfo &li = env->launch;
-        li.lds_bytes = tt->lds_bytes;
-        li.lds_bytes_skip = tt->lds_bytes_skip;
-        li.lds_bytes_packed = tt->lds_bytes_packed;
-        li.raycast_variant = 7;         // per-cell, per-quadrant free rectangles, one wave per car
-        li.car_threads = 64;
-        li.car_split = 1;
-        li.ray_threads = 1024;
-        env->has_track = true;
-        set_launch_geometry(env);
-        env->was_reset = false;
-    };
+    return RC_OK;
+}
+
+TrackKey content_key(const TrackSource &src) {
+    const int32_t h = src.h, w = src.w, n_centerline = src.n_centerline;
+    const size_t nwords = src.nwords();
+    TrackKey k;
+    const int32_t dims[4] = {h, w, src.pitch, n_centerline};
+    const float geo[3] = {src.resolution, src.origin_x, src.origin_y};
+    k.key = fnv1a(k.key, dims, sizeof(dims));
+    k.key = fnv1a(k.key, geo, sizeof(geo));
+    k.key = fnv1a(k.key, src.occ_words, nwords * 4);
+    k.key = fnv1a(k.key, src.drivable_words, nwords * 4);
+    k.key = fnv1a(k.key, src.progress, (size_t)h * w * 4);
+    k.key = fnv1a(k.key, src.centerline, (size_t)n_centerline * 16);
+    k.sum2 = wordsum(wordsum(wordsum(wordsum(0, src.occ_words, nwords * 4), src.drivable_words, nwords * 4), src.progress, (size_t)h * w * 4),
+                     src.centerline, (size_t)n_centerline * 16);
+    return k;
+}
+
+// the same track already on this device (another handle of the process loaded it)?  Null if not.  (g_track_mutex is held)
+std::shared_ptr<TrackTables> cached_track(int device, const TrackSource &src, const TrackKey &k) {
     for (auto it = g_track_cache.begin(); it != g_track_cache.end();)       // entries whose tables are gone
         it = it->second.expired() ? g_track_cache.erase(it) : std::next(it);
-    {
-        auto it = g_track_cache.find({env->cfg.device, key});
-        if (it != g_track_cache.end()) {
-            std::shared_ptr<TrackTables> tt = it->second.lock();
-            const bool same = tt && tt->h == h && tt->w == w && tt->pitch == pitch && tt->n_centerline == n_centerline &&
-                              tt->res == resolution && tt->ox == origin_x && tt->oy == origin_y && tt->sum2 == sum2;
-            if (same) {
-                HIP_TRY(hipStreamSynchronize(env->stream));       // nothing of this handle still reads its old track
-                finish_load(tt);
-                return RC_OK;
-            }
-            // (a different track under the same 64-bit key: build its tables; the map keeps the newer one)
-        }
-    }
-    const size_t bm_bytes = align_up(nwords * 4 + 4, 64);   // at least one all-zero word behind the bitmap (rc_patch_car_kernel)
-    // The lidar_occupancy render and the scan's early forms (variants 0-3) keep the whole bitmap in the 160 KiB LDS;
-    // the default scan does not, so a larger map is fine as long as the patch is not asked for.
-    const bool fits_lds = bm_bytes <= 160 * 1024;
-    if (!fits_lds && env->params.render_patch)
-        return fail(RC_ERR_INVALID, "track bitmap %zu B does not fit the 160 KiB LDS (needed for obs_type lidar_occupancy)", bm_bytes);
+    auto it = g_track_cache.find({device, k.key});
+    if (it == g_track_cache.end()) return nullptr;
+    std::shared_ptr<TrackTables> tt = it->second.lock();
+    const bool same = tt && tt->h == src.h && tt->w == src.w && tt->pitch == src.pitch && tt->n_centerline == src.n_centerline &&
+                      tt->res == src.resolution && tt->ox == src.origin_x && tt->oy == src.origin_y && tt->sum2 == k.sum2;
+    // (not the same: a different track under the same 64-bit key - build its tables; the map keeps the newer one)
+    return same ? tt : nullptr;
+}
+
+// the ringed bitmaps (ht.bm_bytes each) and the beam and footprint tables
+int make_host_tables(const TrackSource &src, TrackHostTables &ht) {
+    const int32_t h = src.h, w = src.w, pitch = src.pitch;
+    const size_t nwords = src.nwords();
     // occupancy with the sentinel ring set
-    std::vector<uint32_t> ray(bm_bytes / 4, 0u), drv(bm_bytes / 4, 0u);
-    std::memcpy(ray.data(), occ_words, nwords * 4);
-    std::memcpy(drv.data(), drivable_words, nwords * 4);
+    std::vector<uint32_t> &ray = ht.ray, &drv = ht.drv;
+    ray.assign(ht.bm_bytes / 4, 0u);
+    drv.assign(ht.bm_bytes / 4, 0u);
+    std::memcpy(ray.data(), src.occ_words, nwords * 4);
+    std::memcpy(drv.data(), src.drivable_words, nwords * 4);
     auto setbit = [&](int ix, int iy) { ray[(size_t)iy * pitch + (ix >> 5)] |= 1u << (ix & 31); };
     // ... and the drivable bitmap's outermost ring cleared: the lidar_occupancy render clamps out-of-grid taps onto it
     // (env spec: "the outermost ring of cells is not drivable"; every compiled track keeps a 16-cell margin anyway)
     auto clrbit = [&](int ix, int iy) { drv[(size_t)iy * pitch + (ix >> 5)] &= ~(1u << (ix & 31)); };
     for (int ix = 0; ix < w; ++ix) { setbit(ix, 0); setbit(ix, h - 1); clrbit(ix, 0); clrbit(ix, h - 1); }
     for (int iy = 0; iy < h; ++iy) { setbit(0, iy); setbit(w - 1, iy); clrbit(0, iy); clrbit(w - 1, iy); }
-    std::vector<float> beams(((RC_N_BEAMS + 63) / 64) * 64 * 2, 0.0f), foot(RCS_N_FOOTPRINT * 2);   // beams padded to whole waves
-    make_tables(beams.data(), foot.data());
+    ht.beams.assign(((RC_N_BEAMS + 63) / 64) * 64 * 2, 0.0f);   // beams padded to whole waves
+    ht.foot.assign(RCS_N_FOOTPRINT * 2, 0.0f);
+    make_tables(ht.beams.data(), ht.foot.data());
     // the one-wave-per-car scan relies on no beam being exactly axis-parallel in the sensor frame (racecar_kernels.hip)
     for (int i = 0; i < 2 * RC_N_BEAMS; ++i)
-        if (!(std::fabs(beams[i]) >= 1e-4f)) return fail(RC_ERR_INVALID, "beam table holds a zero component");
-    // Free-block table for the skipping traversal: exact chessboard distance transform of the stop cells
-    // (two raster passes), then the minimum over each block.  A block value v >= 1 certifies that every
-    // cell within Chebyshev distance v - 1 of any cell of the block is free.
-    std::vector<int32_t> dist((size_t)h * w);
-    for (int iy = 0; iy < h; ++iy)
-        for (int ix = 0; ix < w; ++ix)
-            dist[(size_t)iy * w + ix] = ((ray[(size_t)iy * pitch + (ix >> 5)] >> (ix & 31)) & 1u) ? 0 : (1 << 20);
-    auto relax = [&](int iy, int ix, int oy, int ox) {
-        const int y = iy + oy, x = ix + ox;
-        if (y < 0 || y >= h || x < 0 || x >= w) return;
-        int32_t &d = dist[(size_t)iy * w + ix];
-        const int32_t c = dist[(size_t)y * w + x] + 1;
-        if (c < d) d = c;
-    };
-    for (int iy = 0; iy < h; ++iy)
-        for (int ix = 0; ix < w; ++ix) { relax(iy, ix, -1, -1); relax(iy, ix, -1, 0); relax(iy, ix, -1, 1); relax(iy, ix, 0, -1); }
-    for (int iy = h - 1; iy >= 0; --iy)
-        for (int ix = w - 1; ix >= 0; --ix) { relax(iy, ix, 1, 1); relax(iy, ix, 1, 0); relax(iy, ix, 1, -1); relax(iy, ix, 0, 1); }
-    int blk_shift = 2;
-    auto blk_dim = [&](int n) { return (n + (1 << blk_shift) - 1) >> blk_shift; };
-    if (bm_bytes + align_up((size_t)blk_dim(h) * blk_dim(w), 64) > 160 * 1024) blk_shift = 3;
-    const int blk_w = blk_dim(w), blk_h = blk_dim(h), bs = 1 << blk_shift;
-    const size_t blk_bytes = align_up((size_t)blk_w * blk_h, 64);
-    std::vector<uint8_t> blocks(blk_bytes, 0);
-    for (int by = 0; by < blk_h; ++by)
-        for (int bx = 0; bx < blk_w; ++bx) {
-            int32_t m = 255;
-            for (int oy = 0; oy < bs; ++oy)
-                for (int ox = 0; ox < bs; ++ox) {
-                    const int y = by * bs + oy, x = bx * bs + ox;
-                    const int32_t d = (y < h && x < w) ? dist[(size_t)y * w + x] : 0;
-                    if (d < m) m = d;
-                }
-            blocks[(size_t)by * blk_w + bx] = (uint8_t)m;
-        }
-    // packed table for variant 3: one uint32 per 4x4 block = [value << 16 | 16 occupancy bits]
-    const int pk_w = (w + 3) >> 2, pk_h = (h + 3) >> 2;
-    const size_t packed_bytes = align_up((size_t)pk_w * pk_h * 4, 64);
-    std::vector<uint32_t> packed(packed_bytes / 4, 0u);
-    for (int by = 0; by < pk_h; ++by)
-        for (int bx = 0; bx < pk_w; ++bx) {
-            uint32_t occ16 = 0;
-            int32_t m = 255;
-            for (int oy = 0; oy < 4; ++oy)
-                for (int ox = 0; ox < 4; ++ox) {
-                    const int y = by * 4 + oy, x = bx * 4 + ox;
-                    const bool in = y < h && x < w;
-                    const int32_t d = in ? dist[(size_t)y * w + x] : 0;
-                    if (d < m) m = d;
-                    if (!in || d == 0) occ16 |= 1u << (oy * 4 + ox);
-                }
-            packed[(size_t)by * pk_w + bx] = ((uint32_t)m << 16) | occ16;
-        }
-    // per-cell table for variant 5
+        if (!(std::fabs(ht.beams[i]) >= 1e-4f)) return fail(RC_ERR_INVALID, "beam table holds a zero component");
+    return RC_OK;
+}
+
+// one allocation for all of the track's tables; the arrays uploaded, the device-built tables' places reserved
+int upload_track(const TrackSource &src, const TrackHostTables &ht, TrackTables *tt) {
+    const int32_t h = src.h, w = src.w, n_centerline = src.n_centerline;
+    const size_t bm_bytes = ht.bm_bytes;
     const int cell_pitch = (w + 3) & ~3;
-    const size_t cell_bytes = align_up((size_t)cell_pitch * h, 64);
-    std::vector<uint8_t> cells(cell_bytes, 0);
-    for (int iy = 0; iy < h; ++iy)
-        for (int ix = 0; ix < w; ++ix) cells[(size_t)iy * cell_pitch + ix] = (uint8_t)std::min<int32_t>(dist[(size_t)iy * w + ix], 255);
     // per-cell, per-quadrant free rectangles for variant 6.  A ray in cell (ix, iy) heading into quadrant
     // (sx, sy) only ever visits cells with (x - ix) * sx >= 0 and (y - iy) * sy >= 0, so the certificate can be a
     // rectangle with the current cell at its corner: it reaches as far as the walls AHEAD allow, where the
@@ -830,9 +786,106 @@ int rc_load_track(rc_env *env, const uint32_t *occ_words, const uint32_t *drivab
     const size_t first_bytes = align_up((size_t)cell_pitch * h * RC_FIRST_PLANES * 2, 64);
     const size_t prog_bytes = align_up((size_t)h * w * 4, 64);
     const size_t cl_bytes = align_up((size_t)n_centerline * 16, 64);
-    const size_t beam_bytes = align_up(beams.size() * 4, 64), foot_bytes = align_up(foot.size() * 4, 64);
+    const size_t beam_bytes = align_up(ht.beams.size() * 4, 64), foot_bytes = align_up(ht.foot.size() * 4, 64);
     const size_t spawn_bytes = align_up((size_t)n_centerline * 32, 64);
-    const size_t total = 2 * bm_bytes + prog_bytes + cl_bytes + spawn_bytes + beam_bytes + foot_bytes + blk_bytes + packed_bytes + cell_bytes + 4 * quad_plane_bytes + first_bytes;
+    const size_t total = 2 * bm_bytes + prog_bytes + cl_bytes + spawn_bytes + beam_bytes + foot_bytes + 4 * quad_plane_bytes + first_bytes;
+    HIP_TRY(hipMalloc(&tt->mem, total));
+    char *m = (char *)tt->mem;
+    RcTrackDev &t = tt->t;
+    HIP_TRY(hipMemcpy(m, ht.ray.data(), bm_bytes, hipMemcpyHostToDevice)); t.ray_words = (const uint32_t *)m; m += bm_bytes;
+    HIP_TRY(hipMemcpy(m, ht.drv.data(), bm_bytes, hipMemcpyHostToDevice)); t.drv_words = (const uint32_t *)m; m += bm_bytes;
+    HIP_TRY(hipMemcpy(m, src.progress, (size_t)h * w * 4, hipMemcpyHostToDevice)); t.progress = (const float *)m; m += prog_bytes;
+    HIP_TRY(hipMemcpy(m, src.centerline, (size_t)n_centerline * 16, hipMemcpyHostToDevice)); t.centerline = (const float *)m; m += cl_bytes;
+    t.spawn = (const float4 *)m; m += spawn_bytes;            // filled on the device (build_device_tables)
+    HIP_TRY(hipMemcpy(m, ht.beams.data(), ht.beams.size() * 4, hipMemcpyHostToDevice)); t.beams = (const float *)m; m += beam_bytes;
+    HIP_TRY(hipMemcpy(m, ht.foot.data(), ht.foot.size() * 4, hipMemcpyHostToDevice)); t.footprint = (const float *)m; m += foot_bytes;
+    t.cell_pitch = cell_pitch;
+    t.quad_rect = (const uint16_t *)m; m += 4 * quad_plane_bytes;      // filled on the device
+    t.quad_plane_bytes = (int32_t)quad_plane_bytes;
+    t.first_rect = (const uint16_t *)m; m += first_bytes;      // filled on the device
+    t.h = h; t.w = w; t.pitch = src.pitch; t.n_centerline = n_centerline;
+    t.org_x = src.origin_x; t.org_y = src.origin_y; t.res = src.resolution;
+    t.inv_res = 1.0f / src.resolution;
+    t.tmax = RCS_MAX_RANGE * t.inv_res;
+    t.band = t.band_mh = t.band2 = 0.0f;                   // per handle: set_band
+    return RC_OK;
+}
+
+// The dynamic-LDS ceiling of this library's kernels that keep a bitmap image in LDS (the render; variant 0 of the lab reads
+// lds_bytes too, and looks after its own ceiling).  It is a property of the kernel functions, not of a handle: only ever raise
+// it, or a small track loaded after a large one would make the large one's launches fail.
+int raise_lds_ceiling(int device, const TrackTables &tt) {
+    static std::map<int, size_t> lds_limit;
+    size_t &lim = lds_limit[device];
+    const size_t need = std::min<size_t>(160 * 1024, std::max(tt.lds_bytes, rc_patch_padded_bytes(tt.h, tt.w)));
+    if (need > lim || lim == 0) {
+        HIP_TRY(rck_set_lds_limits(std::max(need, lim)));
+        lim = std::max(need, lim);
+    }
+    return RC_OK;
+}
+
+// the three tables built on the device from what was uploaded: quadrant planes, first-trip table, spawn table
+int build_device_tables(const RcTrackDev &t, hipStream_t stream) {
+    HIP_TRY(rck_build_quad_planes(t, (uint16_t *)t.quad_rect, stream));
+    HIP_TRY(rck_build_first_table(t, (uint16_t *)t.first_rect, stream));
+    HIP_TRY(rck_build_spawn_table(t, (float4 *)t.spawn, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RC_OK;
+}
+
+// the new tables under the bounded scan, from every cell a sensor can stand in: a table that sends a ray in circles
+// fails HERE, with a message, and not as a hung wave in the unbounded production loop
+int validate_track(const RcTrackDev &t, hipStream_t stream) {
+    unsigned long long n_scans = 0;
+    unsigned n_overruns = 0;
+    HIP_TRY(rck_validate_tables(t, std::ldexp((float)(std::max(t.w, t.h) + 2), -21), stream, &n_scans, &n_overruns));
+    if (n_overruns != 0)
+        return fail(RC_ERR_INVALID, "track tables failed validation: %u of %llu validation scans used up their trip budget", n_overruns, n_scans);
+    return RC_OK;
+}
+
+// the handle takes the track: the default scan, its launch geometry, no reset yet
+void publish_track(rc_env *env, const std::shared_ptr<TrackTables> &tt) {
+    env->track = tt;
+    env->params.trk = tt->t;
+    set_band(env);
+    RcLaunchInfo &li = env->launch;
+    li.lds_bytes = tt->lds_bytes;
+    li.raycast_variant = 7;         // per-cell, per-quadrant free rectangles, one wave per car
+    li.car_threads = 64;
+    li.car_split = 1;
+    li.ray_threads = 1024;
+    env->has_track = true;
+    set_launch_geometry(env);
+    env->was_reset = false;
+}
+}  // namespace
+
+extern "C" {
+
+int rc_load_track(rc_env *env, const uint32_t *occ_words, const uint32_t *drivable_words, const float *progress,
+                  int32_t h, int32_t w, int32_t pitch, float resolution, float origin_x, float origin_y,
+                  const float *centerline, int32_t n_centerline) {
+    const TrackSource src = {occ_words, drivable_words, progress, h, w, pitch, resolution, origin_x, origin_y, centerline, n_centerline};
+    int rc = check_track_source(env, src);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    const TrackKey key = content_key(src);
+    std::lock_guard<std::mutex> track_lock(g_track_mutex);
+    if (std::shared_ptr<TrackTables> hit = cached_track(env->cfg.device, src, key)) {
+        HIP_TRY(hipStreamSynchronize(env->stream));       // nothing of this handle still reads its old track
+        publish_track(env, hit);
+        return RC_OK;
+    }
+    TrackHostTables ht;
+    ht.bm_bytes = align_up(src.nwords() * 4 + 4, 64);   // at least one all-zero word behind the bitmap (rc_patch_car_kernel)
+    // The lidar_occupancy render and the scan's early forms (variants 0-3) keep the whole bitmap in the 160 KiB LDS;
+    // the default scan does not, so a larger map is fine as long as the patch is not asked for.
+    const bool fits_lds = ht.bm_bytes <= 160 * 1024;
+    if (!fits_lds && env->params.render_patch)
+        return fail(RC_ERR_INVALID, "track bitmap %zu B does not fit the 160 KiB LDS (needed for obs_type lidar_occupancy)", ht.bm_bytes);
+    if ((rc = make_host_tables(src, ht))) return rc;
     HIP_TRY(hipStreamSynchronize(env->stream));
     // from here on the handle has NO track until the new one is complete: a failure below (allocation, upload, validation)
     // must not leave it launching on the tables it has just given up
@@ -843,61 +896,14 @@ int rc_load_track(rc_env *env, const uint32_t *occ_words, const uint32_t *drivab
     std::shared_ptr<TrackTables> tt = std::make_shared<TrackTables>();
     tt->device = env->cfg.device;
     tt->h = h; tt->w = w; tt->pitch = pitch; tt->n_centerline = n_centerline;
-    tt->res = resolution; tt->ox = origin_x; tt->oy = origin_y; tt->sum2 = sum2;
-    HIP_TRY(hipMalloc(&tt->mem, total));
-    char *m = (char *)tt->mem;
-    RcTrackDev &t = tt->t;
-    HIP_TRY(hipMemcpy(m, ray.data(), bm_bytes, hipMemcpyHostToDevice)); t.ray_words = (const uint32_t *)m; m += bm_bytes;
-    HIP_TRY(hipMemcpy(m, drv.data(), bm_bytes, hipMemcpyHostToDevice)); t.drv_words = (const uint32_t *)m; m += bm_bytes;
-    HIP_TRY(hipMemcpy(m, progress, (size_t)h * w * 4, hipMemcpyHostToDevice)); t.progress = (const float *)m; m += prog_bytes;
-    HIP_TRY(hipMemcpy(m, centerline, (size_t)n_centerline * 16, hipMemcpyHostToDevice)); t.centerline = (const float *)m; m += cl_bytes;
-    t.spawn = (const float4 *)m; m += spawn_bytes;            // filled below, on the device
-    HIP_TRY(hipMemcpy(m, beams.data(), beams.size() * 4, hipMemcpyHostToDevice)); t.beams = (const float *)m; m += beam_bytes;
-    HIP_TRY(hipMemcpy(m, foot.data(), foot.size() * 4, hipMemcpyHostToDevice)); t.footprint = (const float *)m; m += foot_bytes;
-    HIP_TRY(hipMemcpy(m, blocks.data(), blk_bytes, hipMemcpyHostToDevice)); t.free_blocks = (const uint8_t *)m; m += blk_bytes;
-    t.blk_w = blk_w; t.blk_h = blk_h; t.blk_shift = blk_shift; t.blk_bytes = (int32_t)blk_bytes;
-    HIP_TRY(hipMemcpy(m, packed.data(), packed_bytes, hipMemcpyHostToDevice)); t.packed_blocks = (const uint32_t *)m; m += packed_bytes;
-    t.packed_bytes = (int32_t)packed_bytes;
-    t.packed_w = pk_w;
-    HIP_TRY(hipMemcpy(m, cells.data(), cell_bytes, hipMemcpyHostToDevice)); t.cell_dist = (const uint8_t *)m; m += cell_bytes;
-    t.cell_pitch = cell_pitch;
-    t.quad_rect = (const uint16_t *)m; m += 4 * quad_plane_bytes;      // filled below, on the device
-    t.quad_plane_bytes = (int32_t)quad_plane_bytes;
-    t.first_rect = (const uint16_t *)m; m += first_bytes;      // filled below, on the device
-    t.h = h; t.w = w; t.pitch = pitch; t.n_centerline = n_centerline;
-    t.org_x = origin_x; t.org_y = origin_y; t.res = resolution;
-    t.inv_res = 1.0f / resolution;
-    t.tmax = RCS_MAX_RANGE * t.inv_res;
-    t.band = t.band_mh = t.band2 = 0.0f;                   // per handle: set_band
-    // launch geometry: persistent workgroups, the whole bitmap resident in each workgroup's LDS
-    tt->lds_bytes = fits_lds ? bm_bytes : 0;
-    tt->lds_bytes_skip = bm_bytes + blk_bytes <= 160 * 1024 ? bm_bytes + blk_bytes : 0;
-    tt->lds_bytes_packed = (blk_shift == 2 && packed_bytes <= 160 * 1024) ? packed_bytes : 0;
-    {   // the dynamic-LDS ceiling is a property of the kernel functions, not of a handle: only ever raise it, or a
-        // small track loaded after a large one would make the large one's launches fail
-        static std::map<int, size_t> lds_limit;
-        size_t &lim = lds_limit[env->cfg.device];
-        const size_t need = std::min<size_t>(160 * 1024, std::max(std::max(std::max(tt->lds_bytes, tt->lds_bytes_skip), tt->lds_bytes_packed),
-                                                                  rc_patch_padded_bytes(h, w)));
-        if (need > lim || lim == 0) {
-            HIP_TRY(rck_set_lds_limits(std::max(need, lim)));
-            lim = std::max(need, lim);
-        }
-    }
-    HIP_TRY(rck_build_quad_planes(t, (uint16_t *)t.quad_rect, env->stream));
-    HIP_TRY(rck_build_first_table(t, (uint16_t *)t.first_rect, env->stream));
-    HIP_TRY(rck_build_spawn_table(t, (float4 *)t.spawn, env->stream));
-    HIP_TRY(hipStreamSynchronize(env->stream));
-    {   // the new tables under the bounded scan, from every cell a sensor can stand in: a table that sends a ray in circles
-        // fails HERE, with a message, and not as a hung wave in the unbounded production loop
-        unsigned long long n_scans = 0;
-        unsigned n_overruns = 0;
-        HIP_TRY(rck_validate_tables(t, std::ldexp((float)(std::max(w, h) + 2), -21), env->stream, &n_scans, &n_overruns));
-        if (n_overruns != 0)
-            return fail(RC_ERR_INVALID, "track tables failed validation: %u of %llu validation scans used up their trip budget", n_overruns, n_scans);
-    }
-    g_track_cache[{env->cfg.device, key}] = tt;
-    finish_load(tt);
+    tt->res = resolution; tt->ox = origin_x; tt->oy = origin_y; tt->sum2 = key.sum2;
+    tt->lds_bytes = fits_lds ? ht.bm_bytes : 0;            // launch geometry: persistent workgroups, the whole bitmap resident in each workgroup's LDS
+    if ((rc = upload_track(src, ht, tt.get()))) return rc;
+    if ((rc = raise_lds_ceiling(env->cfg.device, *tt))) return rc;
+    if ((rc = build_device_tables(tt->t, env->stream))) return rc;
+    if ((rc = validate_track(tt->t, env->stream))) return rc;
+    g_track_cache[{env->cfg.device, key.key}] = tt;
+    publish_track(env, tt);
     return RC_OK;
 }
 
@@ -1439,15 +1445,26 @@ int rc_set_raycast_variant(rc_env *env, int32_t variant) {
     if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called first");
     if (variant == 0 && env->launch.lds_bytes == 0)
         return fail(RC_ERR_INVALID, "variant 0 needs the bitmap in the 160 KiB LDS; this track is too large");
-    if (variant == 3 && env->launch.lds_bytes_packed == 0)
+    const RcTrackDev &t = env->params.trk;
+    const RcLabTables lg = rc_lab_geometry(t.h, t.w, t.pitch);
+    if (variant == 3 && lg.lds_bytes_packed == 0)
         return fail(RC_ERR_INVALID, "variant 3 needs the packed 4x4 block table in the 160 KiB LDS; this track is too large");
-    if ((variant == 1 || variant == 2) && env->launch.lds_bytes_skip == 0)
+    if ((variant == 1 || variant == 2) && lg.lds_bytes_skip == 0)
         return fail(RC_ERR_INVALID, "variants 1/2 need bitmap + free-block table in the 160 KiB LDS; this track is too large");
     if (variant != 7 && env->compact_slab)
         return fail(RC_ERR_INVALID, "the uint16 LiDAR copy (rc_set_compact_slab) is written by variant 7 only");
     if (variant != 7) {
         const char *why = rck_lab_unavailable();                   // variants 0-6 live in the lab library (racecar_lab.hip)
         if (why != nullptr) return fail(RC_ERR_INVALID, "%s", why);
+    }
+    // Variants 1-5 read tables that the lab builds, once per track, on the first such request; the handles that share the
+    // track share them.  Variants 0, 6 and 7 and the stamps build read none, and build none.
+    if (variant >= 1 && variant <= 5) {
+        std::lock_guard<std::mutex> track_lock(g_track_mutex);
+        if (env->track->lab.free_blocks == nullptr) {
+            HIP_TRY(hipSetDevice(env->cfg.device));
+            HIP_TRY(rck_lab_build_tables(env->track->t, &env->track->lab));
+        }
     }
     env->launch.raycast_variant = variant;
     set_launch_geometry(env);

@@ -91,12 +91,13 @@ struct TrackTables {
     float res = 0.f, ox = 0.f, oy = 0.f;
     uint64_t sum2 = 0;
     RcTrackDev t{};
-    size_t lds_bytes = 0, lds_bytes_skip = 0, lds_bytes_packed = 0;
+    size_t lds_bytes = 0;
+    RcLabTables lab{};       // scan variants 1-5: built by the lab library on first request (rc_set_raycast_variant, under the track
+                             // mutex), shared by the handles of this track like `mem`, freed here - no call into the lab
     ~TrackTables() {
-        if (mem) {
-            (void)hipSetDevice(device);
-            (void)hipFree(mem);
-        }
+        if (mem || lab.free_blocks) (void)hipSetDevice(device);
+        if (mem) (void)hipFree(mem);
+        if (lab.free_blocks) (void)hipFree(const_cast<uint8_t *>(lab.free_blocks));
     }
 };
 

@@ -25,10 +25,7 @@ struct RcTrackDev {
                                  // everything a reset needs from a spawn index in one 32-byte gather (built on the device)
     const float *beams;          // [1080][2] = cos, sin of the beam angle in the sensor frame
     const float *footprint;      // [34][2] body-frame perimeter points
-    const uint8_t *free_blocks;  // [blk_h][blk_w]: per (1<<blk_shift)^2-cell block, min over its cells of the
-                                 // Chebyshev distance to the nearest occupied/ring cell (0 = block not free)
-    const uint8_t *cell_dist;    // [h][cell_pitch]: per cell, chessboard distance to the nearest stop cell (0 = stop, capped 255)
-    int32_t cell_pitch;
+    int32_t cell_pitch;          // cells per row of the per-cell tables below
     const uint16_t *quad_rect;   // [4][h][cell_pitch]: per direction quadrant q = (dy < 0) * 2 + (dx < 0) and cell, a free
                                  // rectangle with that cell at its corner, extending towards the quadrant:
                                  // width | height << 8 in cells (1..255 each), 0 = wall, 0x0100 = sentinel ring.
@@ -36,14 +33,44 @@ struct RcTrackDev {
                                  // every ray walks its plane towards increasing addresses (racecar_kernels.hip)
     int32_t quad_plane_bytes;    // bytes per quadrant plane
     const uint16_t *first_rect;  // [h][cell_pitch][RC_FIRST_PLANES]: first-trip rectangles by quadrant and slope bin (variant 7)
-    const uint32_t *packed_blocks; // [blk_h][blk_w] for 4x4 blocks: bits 0-15 occupancy of the block's cells
-                                 // (bit (iy&3)*4 + (ix&3), sentinel ring included), bits 16-23 the value above
-    int32_t blk_w, blk_h, blk_shift, blk_bytes, packed_bytes, packed_w;   // packed_w: uint32 per packed row
     int32_t h, w, pitch, n_centerline;
     float org_x, org_y, res, inv_res, tmax;
     float band, band_mh, band2;  // scan variants 6/7: half-width of the zone around a cell boundary in which the other-axis cell
                                  // is counted exactly = (max(w, h) + 2) * 2^-21 cells; band - 0.5; 2 * band
 };
+
+// The tables of the lab library's scan variants 1-5 (racecar_lab.hip).  The shipped kernels read none of them: the lab builds
+// them from a track's ringed bitmap into ONE device block the first time a handle of that track asks for such a variant
+// (rclab_build_tables), the track's TrackTables owns the block, and it reaches the lab's kernels as an argument of their own.
+struct RcLabTables {
+    const uint8_t *free_blocks;  // [blk_h][blk_w]: per (1<<blk_shift)^2-cell block, min over its cells of the
+                                 // Chebyshev distance to the nearest occupied/ring cell (0 = block not free).
+                                 // Null: not built.  Also the start of the block (what hipFree takes)
+    const uint32_t *packed_blocks; // [blk_h][blk_w] for 4x4 blocks: bits 0-15 occupancy of the block's cells
+                                 // (bit (iy&3)*4 + (ix&3), sentinel ring included), bits 16-23 the value above
+    const uint8_t *cell_dist;    // [h][cell_pitch]: per cell, chessboard distance to the nearest stop cell (0 = stop, capped 255)
+    int32_t blk_w, blk_h, blk_shift, blk_bytes, packed_bytes, packed_w;   // packed_w: uint32 per packed row
+    size_t lds_bytes_skip;       // bitmap + free-block table (raycast variants 1, 2); 0 if it does not fit
+    size_t lds_bytes_packed;     // packed block table only (raycast variant 3); 0 if it does not fit / blocks are 8x8
+};
+// The geometry and the LDS sizes of those tables (pointers null): a function of the grid's shape alone, so the shipped library
+// can refuse a variant whose tables do not fit the 160 KiB LDS, and size its launch, without building anything.  Blocks are
+// 4x4 cells unless bitmap + block table only fit with 8x8.
+static inline RcLabTables rc_lab_geometry(int h, int w, int pitch) {
+    const auto up64 = [](size_t v) { return (v + 63) / 64 * 64; };
+    const size_t lds_max = 160 * 1024, bm_bytes = up64((size_t)h * pitch * 4 + 4);
+    RcLabTables g{};
+    g.blk_shift = 2;
+    auto blk_dim = [&](int n) { return (n + (1 << g.blk_shift) - 1) >> g.blk_shift; };
+    if (bm_bytes + up64((size_t)blk_dim(h) * blk_dim(w)) > lds_max) g.blk_shift = 3;
+    g.blk_w = blk_dim(w); g.blk_h = blk_dim(h);
+    g.blk_bytes = (int32_t)up64((size_t)g.blk_w * g.blk_h);
+    g.packed_w = (w + 3) >> 2;
+    g.packed_bytes = (int32_t)up64((size_t)g.packed_w * ((h + 3) >> 2) * 4);
+    g.lds_bytes_skip = bm_bytes + g.blk_bytes <= lds_max ? bm_bytes + g.blk_bytes : 0;
+    g.lds_bytes_packed = (g.blk_shift == 2 && (size_t)g.packed_bytes <= lds_max) ? (size_t)g.packed_bytes : 0;
+    return g;
+}
 
 struct RcStateDev {              // persistent per-car / per-env simulator state (SoA)
     float *x, *y, *theta, *ct, *st, *v, *delta, *omega, *accel, *progress;
@@ -158,8 +185,6 @@ struct RcLaunchInfo {            // per-handle launch geometry decided at rc_loa
     int32_t scan_stamp_waves;
     int32_t patch_variant;       // experiment bits of the lidar_occupancy render (rc_debug_set): 2 = plain instead of non-temporal stores
     size_t lds_bytes;            // occupancy bitmap (also the patch kernel's drivable bitmap)
-    size_t lds_bytes_skip;       // bitmap + free-block table (raycast variants 1, 2); 0 if it does not fit
-    size_t lds_bytes_packed;     // packed block table only (raycast variant 3); 0 if it does not fit / blocks are 8x8
     int32_t raycast_variant;     // 0 plain, 1 skipping, 2 skipping tuned, 3 tuned + packed table in LDS,
                                  // 4 packed table read from global memory, 5 per-cell distance table from global memory,
                                  // 6 per-cell, per-quadrant free rectangles from global memory, 7 the same with one wave per car
@@ -211,8 +236,9 @@ inline void launch(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t s, A
     hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, s, a, b, 0u, args...);
 }
 hipError_t rck_set_lds_limits(size_t lds_bytes);
-const char *rck_lab_abi_string();   // sizes of RcParams / RcLaunchInfo + the hash of the headers: what a lab library must have been built against
+const char *rck_lab_abi_string();   // sizes of RcParams / RcLaunchInfo / RcLabTables + the hash of the headers: what a lab library must have been built against
 const char *rck_lab_unavailable();   // nullptr if the lab library (scan variants 0-6, stamps build: racecar_lab.hip) can be used, else why not
+hipError_t rck_lab_build_tables(const RcTrackDev &t, RcLabTables *out);   // the lab's builder on the current device (synchronous); needs ray_words, h, w, pitch, cell_pitch
 hipError_t rck_build_quad_planes(const RcTrackDev &t, uint16_t *quad_rect_dev, hipStream_t s);   // needs ray_words, h, w, pitch, cell_pitch, quad_plane_bytes
 hipError_t rck_build_first_table(const RcTrackDev &t, uint16_t *first_rect_dev, hipStream_t s);   // needs ray_words, h, w, pitch, cell_pitch
 hipError_t rck_validate_tables(const RcTrackDev &t, float band, hipStream_t s, unsigned long long *n_scans, unsigned *n_overruns);   // bounded scan from every free cell
@@ -221,7 +247,7 @@ struct RcRandomActions { int32_t on; uint32_t seed_lo, seed_hi, step; };   // on
 hipError_t rck_launch_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s);
 hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s);
 hipError_t rck_launch_set_pose(const RcParams &p, const float *xyyaw_dev, hipStream_t s);
-hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
+hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, const RcLabTables *lab, hipStream_t s);   // lab: the track's block for variants 1-5, else unused
 hipError_t rck_launch_patch(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
 // track set (rc_set_track_set): the track-major car list, the scan and the render (the dynamics and the reset above go by RcParams::ts_n)
 hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s);

@@ -1248,20 +1248,19 @@ hipError_t rck_sort_cars(const float *progress_dev, int n_cars, uint32_t *counts
 #endif
 const char *rck_lab_abi_string() {
     static const std::string s = "RcParams " + std::to_string(sizeof(RcParams)) + " RcLaunchInfo " + std::to_string(sizeof(RcLaunchInfo)) +
-                                 " headers " RC_HEADERS_ID;
+                                 " RcLabTables " + std::to_string(sizeof(RcLabTables)) + " headers " RC_HEADERS_ID;
     return s.c_str();
 }
 
 namespace {
 struct Lab {
     void *handle = nullptr;
-    int (*launch_raycast)(const RcParams *, const RcLaunchInfo *, hipStream_t, hipEvent_t, hipEvent_t) = nullptr;
-    int (*set_lds_limits)(size_t) = nullptr;
+    int (*launch_raycast)(const RcParams *, const RcLaunchInfo *, const RcLabTables *, hipStream_t, hipEvent_t, hipEvent_t) = nullptr;
+    int (*build_tables)(const RcTrackDev *, RcLabTables *) = nullptr;
     std::string why;                 // why it is not available
 };
 std::mutex g_lab_mutex;
 Lab g_lab;
-size_t g_lds_limit = 0;              // what rck_set_lds_limits was last called with (the lab's kernels get the same)
 
 // A snapshot BY VALUE, taken under the lock (a reference to g_lab read after the lock was dropped raced with another
 // thread inside lab() clearing `why` and assigning the function pointers).
@@ -1270,7 +1269,7 @@ Lab lab() {
     if (g_lab.handle != nullptr) return g_lab;
     g_lab.why.clear();               // (not loaded yet: look again - it may have been built since the last request)
     g_lab.launch_raycast = nullptr;
-    g_lab.set_lds_limits = nullptr;
+    g_lab.build_tables = nullptr;
     Dl_info info;
     std::string dir = ".";
     if (dladdr(reinterpret_cast<const void *>(&rck_set_launch_events), &info) != 0 && info.dli_fname != nullptr) {
@@ -1290,11 +1289,11 @@ Lab lab() {
     auto refuse = [&](const std::string &why) {
         g_lab.why = why;
         g_lab.launch_raycast = nullptr;
-        g_lab.set_lds_limits = nullptr;
+        g_lab.build_tables = nullptr;
         dlclose(h);
         return g_lab;
     };
-    // RcParams and RcLaunchInfo cross this boundary by pointer: a lab built against other headers reads them wrongly - wrong scans
+    // RcParams, RcLaunchInfo and RcLabTables cross this boundary by pointer: a lab built against other headers reads them wrongly - wrong scans
     // or a GPU fault, no error.  The lab says what it was built against; anything else is refused.
     auto abi = reinterpret_cast<const char *(*)(void)>(dlsym(h, "rclab_abi"));
     const std::string want = rck_lab_abi_string();
@@ -1302,10 +1301,9 @@ Lab lab() {
         return refuse(path + " was built against other headers (it says \"" + std::string(abi != nullptr ? abi() : "nothing: no rclab_abi") +
                       "\", this library needs \"" + want + "\"); rebuild it with `python -m racing_dreamer_amd.build --lab`");
     g_lab.launch_raycast = reinterpret_cast<decltype(g_lab.launch_raycast)>(dlsym(h, "rclab_launch_raycast"));
-    g_lab.set_lds_limits = reinterpret_cast<decltype(g_lab.set_lds_limits)>(dlsym(h, "rclab_set_lds_limits"));
-    if (g_lab.launch_raycast == nullptr || g_lab.set_lds_limits == nullptr)
-        return refuse(path + " does not export rclab_launch_raycast / rclab_set_lds_limits");
-    if (g_lds_limit != 0 && g_lab.set_lds_limits(g_lds_limit) != (int)hipSuccess) return refuse(path + ": rclab_set_lds_limits failed");
+    g_lab.build_tables = reinterpret_cast<decltype(g_lab.build_tables)>(dlsym(h, "rclab_build_tables"));
+    if (g_lab.launch_raycast == nullptr || g_lab.build_tables == nullptr)
+        return refuse(path + " does not export rclab_launch_raycast / rclab_build_tables");
     g_lab.handle = h;
     return g_lab;
 }
@@ -1318,6 +1316,13 @@ const char *rck_lab_unavailable() {
     if (l.handle != nullptr) return nullptr;
     reason = l.why;
     return reason.c_str();
+}
+
+// The tables of scan variants 1-5 for track `t`, built by the lab on the current device (rc_set_raycast_variant).
+hipError_t rck_lab_build_tables(const RcTrackDev &t, RcLabTables *out) {
+    const Lab l = lab();
+    if (l.handle == nullptr) return hipErrorSharedObjectInitFailed;          // (rc_set_raycast_variant refuses before it comes to this)
+    return (hipError_t)l.build_tables(&t, out);
 }
 
 // Run-time (cars per env, flag) -> template arguments: f gets a std::integral_constant / std::bool_constant and names the
@@ -1368,13 +1373,7 @@ hipError_t rck_set_lds_limits(size_t lds_bytes) {
         with_cars(cars, [&](auto a) {
             for (const ScanChoice &c : kScanChoices) no_static_lds(reinterpret_cast<const void *>(scan_kernel<decltype(a)::value>(c)));
         });
-    if (e != hipSuccess) return e;
-    {
-        std::lock_guard<std::mutex> lock(g_lab_mutex);
-        g_lds_limit = lds_bytes > g_lds_limit ? lds_bytes : g_lds_limit;
-        if (g_lab.handle != nullptr && g_lab.set_lds_limits(g_lds_limit) != (int)hipSuccess) return hipErrorInvalidValue;
-    }
-    return hipSuccess;
+    return e;
 }
 
 // The dynamics of one handle: by the env's track with a track set, with the vehicle parameters per car while vp_mode is on.
@@ -1426,7 +1425,7 @@ hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStrea
     return hipGetLastError();
 }
 
-hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s) {
+hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, const RcLabTables *lab_tables, hipStream_t s) {
     const bool stamps = li.scan_stamps != nullptr && p.cars_per_env == 1;
     if (li.raycast_variant != 7 || stamps) {
         // a lab kernel (superseded variant or the instrumented build): racecar_lab.hip, loaded on first use
@@ -1434,7 +1433,7 @@ hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, hipStre
         if (l.handle == nullptr) return hipErrorSharedObjectInitFailed;      // (rc_set_raycast_variant / rc_debug_scan_stamps refuse before it comes to this)
         hipEvent_t a, b;
         rck_take_launch_events(&a, &b);
-        return (hipError_t)l.launch_raycast(&p, &li, s, a, b);
+        return (hipError_t)l.launch_raycast(&p, &li, lab_tables, s, a, b);
     }
     const int threads = li.car_threads, per = threads / 64;                     // waves per workgroup
     const long long waves = (long long)p.n_cars * li.car_split;

@@ -10,11 +10,30 @@
 //   rclab_cohabit_kernel            a co-tenant of chosen size for the scan (tools/cohabit_sweep.py: what a collective beside it costs)
 //
 // Numerics as in racecar_kernels.hip: one IEEE operation per written operator (-ffp-contract=off).
+#include <algorithm>
+#include <map>
+#include <mutex>
 #include <string>
+#include <vector>
 
 #include "racecar_scan.h"
 
 namespace {
+
+// Selections without v_cndmask, for the tuned variants below (only they use them)
+__device__ __forceinline__ int nonzero_mask(int a) {           // -1 if a != 0 (0 <= a < 2^31), else 0
+    int r;
+    asm("v_sub_u32 %0, 0, %1\n\tv_ashrrev_i32 %0, 31, %0" : "=v"(r) : "v"(a));
+    return r;
+}
+__device__ __forceinline__ int bfi(int mask, int a, int b) {   // (mask & a) | (~mask & b)
+    int r;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float bfi(int mask, float a, float b) {
+    return __int_as_float(bfi(mask, __float_as_int(a), __float_as_int(b)));
+}
 
 // Exact grid traversal (H3).  Cell boundaries are derived from the integer cell index at every
 // step (t = (boundary - origin) * 1/d), so the visited cell sequence and the returned range do
@@ -67,7 +86,7 @@ __device__ __forceinline__ float cast_ray_dda(const uint32_t *bits, const RcTrac
 // comparisons, so the visited-cell sequence outside free rectangles, the hit cell and the returned range
 // are bit-identical to cast_ray_dda (checked against the CPU oracle in tests/test_gpu_parity.py).
 // With v == 0 the rectangle is the current cell and the iteration is exactly one traversal step.
-__device__ __forceinline__ float cast_ray_skip(const uint32_t *bits, const uint8_t *blk, const RcTrackDev &t,
+__device__ __forceinline__ float cast_ray_skip(const uint32_t *bits, const uint8_t *blk, const RcTrackDev &t, const RcLabTables &lt,
                                                float gx, float gy, float dx, float dy) {
     int ix = (int)floorf(gx), iy = (int)floorf(gy);
     if ((unsigned)ix >= (unsigned)t.w || (unsigned)iy >= (unsigned)t.h) return 0.0f;
@@ -77,10 +96,10 @@ __device__ __forceinline__ float cast_ray_skip(const uint32_t *bits, const uint8
     const float idy = hy ? 1.0f / dy : 0.0f;
     const int sx = px ? 1 : -1, sy = py ? 1 : -1;
     const float sxf = (float)sx, syf = (float)sy;
-    const int shift = t.blk_shift, bs = 1 << shift, bmask = ~(bs - 1);
+    const int shift = lt.blk_shift, bs = 1 << shift, bmask = ~(bs - 1);
     const int wm1 = t.w - 1, hm1 = t.h - 1;
     for (int it = 0; it < 4096; ++it) {          // a ray crosses < 430 cells; the cap only bounds a logic error
-        const int v = blk[(iy >> shift) * t.blk_w + (ix >> shift)];
+        const int v = blk[(iy >> shift) * lt.blk_w + (ix >> shift)];
         const int r = v - 1;
         const int x0 = v ? (ix & bmask) - r : ix, x1 = v ? (ix & bmask) + bs + r : ix + 1;
         const int y0 = v ? (iy & bmask) - r : iy, y1 = v ? (iy & bmask) + bs + r : iy + 1;
@@ -156,7 +175,7 @@ __device__ __forceinline__ int exact_other_cell(int on_est, int oi, int opi, flo
     return oi + __mul24(m0 + c0 + c1, os);
 }
 
-__device__ __forceinline__ float cast_ray_fast(const uint32_t *bits, const uint8_t *blk, const RcTrackDev &t,
+__device__ __forceinline__ float cast_ray_fast(const uint32_t *bits, const uint8_t *blk, const RcTrackDev &t, const RcLabTables &lt,
                                                float gx, float gy, float dx, float dy) {
     int ix = (int)floorf(gx), iy = (int)floorf(gy);
     bool alive = (unsigned)ix < (unsigned)t.w && (unsigned)iy < (unsigned)t.h;
@@ -168,9 +187,9 @@ __device__ __forceinline__ float cast_ray_fast(const uint32_t *bits, const uint8
     int nx = pxi - 1, ny = pyi - 1;                                       // -1 for a negative direction
     asm("" : "+v"(nx));                                                   // see cast_ray_packed
     asm("" : "+v"(ny));
-    const int shift = t.blk_shift, bs = 1 << shift, bmask = ~(bs - 1);
+    const int shift = lt.blk_shift, bs = 1 << shift, bmask = ~(bs - 1);
     const int cx = (pxi << shift) - nx, cy = (pyi << shift) - ny;
-    const int blk_w = t.blk_w, pitch = t.pitch;
+    const int blk_w = lt.blk_w, pitch = t.pitch;
     const float tmax = t.tmax;
     float tt = 0.0f;
     int v = 0;
@@ -213,11 +232,11 @@ __device__ __forceinline__ float cast_ray_fast(const uint32_t *bits, const uint8
 // value (bits 16-23) and the occupancy of its 16 cells (bits 0-15), so an iteration is one LDS read and the
 // cell test is branch-free: a certified block has no occupancy bits, hence `(word >> cell) & 1` is the hit
 // flag for every block.  The row-major bitmap is not needed by the scan at all (LDS: 4 B per 16 cells).
-__device__ __forceinline__ float cast_ray_packed(const uint32_t *pk, const RcTrackDev &t, float gx, float gy,
+__device__ __forceinline__ float cast_ray_packed(const uint32_t *pk, const RcTrackDev &t, const RcLabTables &lt, float gx, float gy,
                                                  float dx, float dy) {
     int ix = (int)floorf(gx), iy = (int)floorf(gy);
     bool alive = (unsigned)ix < (unsigned)t.w && (unsigned)iy < (unsigned)t.h;
-    const int row_bytes = t.packed_w * 4;
+    const int row_bytes = lt.packed_w * 4;
     const char *pkb = reinterpret_cast<const char *>(pk);
     uint32_t word = 0;
     if (alive) {
@@ -336,7 +355,7 @@ __device__ __forceinline__ float cast_ray_rects(const uint16_t *qr, const RcTrac
 }
 
 template <int A, int VARIANT>
-__global__ __launch_bounds__(1024) void rc_raycast_kernel(RcParams p, int total_rays) {
+__global__ __launch_bounds__(1024) void rc_raycast_kernel(RcParams p, RcLabTables lt, int total_rays) {
     extern __shared__ uint32_t lds_words[];
     const RcTrackDev &t = p.trk;
     const int nwords = t.h * t.pitch;
@@ -344,12 +363,12 @@ __global__ __launch_bounds__(1024) void rc_raycast_kernel(RcParams p, int total_
     if (VARIANT >= 4) {
         // tables read from global memory (L2 / L1): no LDS, any map size
     } else if (VARIANT == 3) {
-        stage_bitmap(lds_words, t.packed_blocks, t.packed_bytes >> 2);
+        stage_bitmap(lds_words, lt.packed_blocks, lt.packed_bytes >> 2);
     } else {
         if (VARIANT != 0) {
             uint4 *d4 = reinterpret_cast<uint4 *>(lds_words + ((nwords + 15) & ~15));
-            const uint4 *s4 = reinterpret_cast<const uint4 *>(t.free_blocks);
-            for (int i = threadIdx.x; i < (t.blk_bytes >> 4); i += blockDim.x) d4[i] = s4[i];
+            const uint4 *s4 = reinterpret_cast<const uint4 *>(lt.free_blocks);
+            for (int i = threadIdx.x; i < (lt.blk_bytes >> 4); i += blockDim.x) d4[i] = s4[i];
         }
         stage_bitmap(lds_words, t.ray_words, nwords);
     }
@@ -367,11 +386,11 @@ __global__ __launch_bounds__(1024) void rc_raycast_kernel(RcParams p, int total_
         const float gx = (lx - t.org_x) * t.inv_res;
         const float gy = (ly - t.org_y) * t.inv_res;
         float rng = VARIANT == 6   ? cast_ray_rects(t.quad_rect, t, gx, gy, dx, dy, (int)floorf(gx), (int)floorf(gy))
-                    : VARIANT == 5 ? cast_ray_cells(t.cell_dist, t, gx, gy, dx, dy)
-                    : VARIANT == 4 ? cast_ray_packed(t.packed_blocks, t, gx, gy, dx, dy)
-                    : VARIANT == 3 ? cast_ray_packed(lds_words, t, gx, gy, dx, dy)
-                    : VARIANT == 2 ? cast_ray_fast(lds_words, lds_blk, t, gx, gy, dx, dy)
-                    : VARIANT == 1 ? cast_ray_skip(lds_words, lds_blk, t, gx, gy, dx, dy)
+                    : VARIANT == 5 ? cast_ray_cells(lt.cell_dist, t, gx, gy, dx, dy)
+                    : VARIANT == 4 ? cast_ray_packed(lt.packed_blocks, t, lt, gx, gy, dx, dy)
+                    : VARIANT == 3 ? cast_ray_packed(lds_words, t, lt, gx, gy, dx, dy)
+                    : VARIANT == 2 ? cast_ray_fast(lds_words, lds_blk, t, lt, gx, gy, dx, dy)
+                    : VARIANT == 1 ? cast_ray_skip(lds_words, lds_blk, t, lt, gx, gy, dx, dy)
                                    : cast_ray_dda(lds_words, t, gx, gy, dx, dy);
         if (A > 1) {
             const unsigned env = car / A;
@@ -458,25 +477,35 @@ const char *rclab_build_id(void) { return "RC_BUILD_ID=" RC_BUILD_ID; }
 #endif
 const char *rclab_abi(void) {
     static const std::string s = "RcParams " + std::to_string(sizeof(RcParams)) + " RcLaunchInfo " + std::to_string(sizeof(RcLaunchInfo)) +
-                                 " headers " RC_HEADERS_ID;
+                                 " RcLabTables " + std::to_string(sizeof(RcLabTables)) + " headers " RC_HEADERS_ID;
     return s.c_str();
 }
 
-// Dynamic LDS of the variants that stage tables there, and the check that the stamps kernel - which addresses its dynamic
-// LDS from 0 like the shipped scan - has no static LDS.
-int rclab_set_lds_limits(size_t lds_bytes) {
-    hipError_t e;
+// Dynamic LDS of the variants that stage tables there: the ceiling is a property of the kernel functions, so it is raised per
+// device and never lowered (a small track after a large one must not make the large one's launches fail).  The first call on a
+// device also checks that the stamps kernel - which addresses its dynamic LDS from 0 like the shipped scan - has no static LDS.
+static hipError_t raise_lds_limit(size_t lds_bytes) {
+    static std::mutex mutex;
+    static std::map<int, size_t> limit;
+    int device = 0;
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess) return e;
+    lds_bytes = std::max<size_t>(lds_bytes, 64 * 1024);     // (what a kernel may use without asking)
+    std::lock_guard<std::mutex> lock(mutex);
+    const auto it = limit.find(device);
+    if (it != limit.end() && lds_bytes <= it->second) return hipSuccess;
     const int b = (int)lds_bytes;
-#define SET(k) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b); if (e != hipSuccess) return (int)e;
+#define SET(k) e = hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, b); if (e != hipSuccess) return e;
 #define SET_V(v) SET((rc_raycast_kernel<1, v>)) SET((rc_raycast_kernel<2, v>)) SET((rc_raycast_kernel<3, v>)) SET((rc_raycast_kernel<4, v>))
     SET_V(0) SET_V(1) SET_V(2) SET_V(3) SET_V(4) SET_V(5) SET_V(6)
 #undef SET_V
 #undef SET
     hipFuncAttributes fa;
     e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(rc_raycast_car_stamps_kernel));
-    if (e != hipSuccess) return (int)e;
-    if (fa.sharedSizeBytes != 0) return (int)hipErrorInvalidValue;
-    return (int)hipSuccess;
+    if (e != hipSuccess) return e;
+    if (fa.sharedSizeBytes != 0) return hipErrorInvalidValue;
+    limit[device] = lds_bytes;
+    return hipSuccess;
 }
 
 // The co-tenant kernel on `s`: workgroups x threads, resident for `microseconds` (at most 100 000); copied_dev (device, may be
@@ -490,32 +519,120 @@ int rclab_launch_cohabit(hipStream_t s, int workgroups, int threads, unsigned mi
     return (int)hipGetLastError();
 }
 
+// The tables of scan variants 1-5 for track `t` on the current device, from its ringed occupancy bitmap (read back from
+// t.ray_words: the sentinel ring is in it) - one device block, returned in *out.  Synchronous.  The caller owns the block and
+// frees it with hipFree(out->free_blocks).
+int rclab_build_tables(const RcTrackDev *tp, RcLabTables *out) {
+    const RcTrackDev &t = *tp;
+    const int h = t.h, w = t.w, pitch = t.pitch;
+    std::vector<uint32_t> ray((size_t)h * pitch);
+    hipError_t e = hipMemcpy(ray.data(), t.ray_words, ray.size() * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return (int)e;
+    auto align_up = [](size_t v, size_t a) { return (v + a - 1) / a * a; };
+    // Free-block table for the skipping traversal: exact chessboard distance transform of the stop cells
+    // (two raster passes), then the minimum over each block.  A block value v >= 1 certifies that every
+    // cell within Chebyshev distance v - 1 of any cell of the block is free.
+    std::vector<int32_t> dist((size_t)h * w);
+    for (int iy = 0; iy < h; ++iy)
+        for (int ix = 0; ix < w; ++ix)
+            dist[(size_t)iy * w + ix] = ((ray[(size_t)iy * pitch + (ix >> 5)] >> (ix & 31)) & 1u) ? 0 : (1 << 20);
+    auto relax = [&](int iy, int ix, int oy, int ox) {
+        const int y = iy + oy, x = ix + ox;
+        if (y < 0 || y >= h || x < 0 || x >= w) return;
+        int32_t &d = dist[(size_t)iy * w + ix];
+        const int32_t c = dist[(size_t)y * w + x] + 1;
+        if (c < d) d = c;
+    };
+    for (int iy = 0; iy < h; ++iy)
+        for (int ix = 0; ix < w; ++ix) { relax(iy, ix, -1, -1); relax(iy, ix, -1, 0); relax(iy, ix, -1, 1); relax(iy, ix, 0, -1); }
+    for (int iy = h - 1; iy >= 0; --iy)
+        for (int ix = w - 1; ix >= 0; --ix) { relax(iy, ix, 1, 1); relax(iy, ix, 1, 0); relax(iy, ix, 1, -1); relax(iy, ix, 0, 1); }
+    RcLabTables lt = rc_lab_geometry(h, w, pitch);         // block size (4x4, or 8x8 where only that fits the LDS), table sizes
+    const int blk_w = lt.blk_w, blk_h = lt.blk_h, bs = 1 << lt.blk_shift;
+    const size_t blk_bytes = (size_t)lt.blk_bytes;
+    std::vector<uint8_t> blocks(blk_bytes, 0);
+    for (int by = 0; by < blk_h; ++by)
+        for (int bx = 0; bx < blk_w; ++bx) {
+            int32_t m = 255;
+            for (int oy = 0; oy < bs; ++oy)
+                for (int ox = 0; ox < bs; ++ox) {
+                    const int y = by * bs + oy, x = bx * bs + ox;
+                    const int32_t d = (y < h && x < w) ? dist[(size_t)y * w + x] : 0;
+                    if (d < m) m = d;
+                }
+            blocks[(size_t)by * blk_w + bx] = (uint8_t)m;
+        }
+    // packed table for variant 3: one uint32 per 4x4 block = [value << 16 | 16 occupancy bits]
+    const int pk_w = (w + 3) >> 2, pk_h = (h + 3) >> 2;
+    const size_t packed_bytes = (size_t)lt.packed_bytes;
+    std::vector<uint32_t> packed(packed_bytes / 4, 0u);
+    for (int by = 0; by < pk_h; ++by)
+        for (int bx = 0; bx < pk_w; ++bx) {
+            uint32_t occ16 = 0;
+            int32_t m = 255;
+            for (int oy = 0; oy < 4; ++oy)
+                for (int ox = 0; ox < 4; ++ox) {
+                    const int y = by * 4 + oy, x = bx * 4 + ox;
+                    const bool in = y < h && x < w;
+                    const int32_t d = in ? dist[(size_t)y * w + x] : 0;
+                    if (d < m) m = d;
+                    if (!in || d == 0) occ16 |= 1u << (oy * 4 + ox);
+                }
+            packed[(size_t)by * pk_w + bx] = ((uint32_t)m << 16) | occ16;
+        }
+    // per-cell table for variant 5
+    const int cell_pitch = t.cell_pitch;
+    const size_t cell_bytes = align_up((size_t)cell_pitch * h, 64);
+    std::vector<uint8_t> cells(cell_bytes, 0);
+    for (int iy = 0; iy < h; ++iy)
+        for (int ix = 0; ix < w; ++ix) cells[(size_t)iy * cell_pitch + ix] = (uint8_t)std::min<int32_t>(dist[(size_t)iy * w + ix], 255);
+    char *m = nullptr;
+    if ((e = hipMalloc((void **)&m, blk_bytes + packed_bytes + cell_bytes)) != hipSuccess) return (int)e;
+    e = hipMemcpy(m, blocks.data(), blk_bytes, hipMemcpyHostToDevice); lt.free_blocks = (const uint8_t *)m;
+    if (e == hipSuccess) e = hipMemcpy(m + blk_bytes, packed.data(), packed_bytes, hipMemcpyHostToDevice); lt.packed_blocks = (const uint32_t *)(m + blk_bytes);
+    if (e == hipSuccess) e = hipMemcpy(m + blk_bytes + packed_bytes, cells.data(), cell_bytes, hipMemcpyHostToDevice); lt.cell_dist = (const uint8_t *)(m + blk_bytes + packed_bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(m);
+        return (int)e;
+    }
+    *out = lt;
+    return (int)hipSuccess;
+}
+
 // One scan launch of a lab kernel on `s`: what rck_launch_raycast (racecar_kernels.hip) hands over when the handle's variant is
-// not 7 or its stamps buffer is set.  ev_start / ev_stop: the launch-attached timer of the caller, or null.
-int rclab_launch_raycast(const RcParams *pp, const RcLaunchInfo *lp, hipStream_t s, hipEvent_t ev_start, hipEvent_t ev_stop) {
+// not 7 or its stamps buffer is set.  tables: the track's block for variants 1-5 (rclab_build_tables), not read otherwise and
+// then null.  ev_start / ev_stop: the launch-attached timer of the caller, or null.
+int rclab_launch_raycast(const RcParams *pp, const RcLaunchInfo *lp, const RcLabTables *tables, hipStream_t s, hipEvent_t ev_start,
+                         hipEvent_t ev_stop) {
     const RcParams &p = *pp;
     const RcLaunchInfo &li = *lp;
-    const int total = p.n_cars * RC_N_BEAMS;
-    if (li.raycast_variant == 7) {
+    const int total = p.n_cars * RC_N_BEAMS, v = li.raycast_variant;
+    const bool tabled = v >= 1 && v <= 5;
+    if (tabled && (tables == nullptr || tables->free_blocks == nullptr)) return (int)hipErrorInvalidValue;
+    const RcLabTables lt = tabled ? *tables : RcLabTables{};
+    const size_t lds = v == 0 ? li.lds_bytes : v == 1 || v == 2 ? lt.lds_bytes_skip : v == 3 ? lt.lds_bytes_packed : 0;
+    const hipError_t e = raise_lds_limit(lds);
+    if (e != hipSuccess) return (int)e;
+    if (v == 7) {
         if (li.scan_stamps == nullptr || p.cars_per_env != 1) return (int)hipErrorInvalidValue;
         const int threads = li.car_threads, per = threads / 64;
         const long long waves = (long long)p.n_cars * li.car_split;
         launch(ev_start, ev_stop, rc_raycast_car_stamps_kernel, dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p,
                li.car_split, li.scan_stamps, li.scan_stamp_waves);
-    } else if (li.raycast_variant == 6) {
-        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 6>), dim3(li.ray_blocks), dim3(li.ray_threads), 0, s, p, total));
-    } else if (li.raycast_variant == 5) {
-        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 5>), dim3(li.ray_blocks), dim3(li.ray_threads), 0, s, p, total));
-    } else if (li.raycast_variant == 4) {
-        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 4>), dim3(li.ray_blocks), dim3(li.ray_threads), 0, s, p, total));
-    } else if (li.raycast_variant == 3) {
-        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 3>), dim3(li.ray_blocks), dim3(li.ray_threads), li.lds_bytes_packed, s, p, total));
-    } else if (li.raycast_variant == 2) {
-        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 2>), dim3(li.ray_blocks), dim3(li.ray_threads), li.lds_bytes_skip, s, p, total));
-    } else if (li.raycast_variant == 1) {
-        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 1>), dim3(li.ray_blocks), dim3(li.ray_threads), li.lds_bytes_skip, s, p, total));
-    } else if (li.raycast_variant == 0) {
-        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 0>), dim3(li.ray_blocks), dim3(li.ray_threads), li.lds_bytes, s, p, total));
+    } else if (v == 6) {
+        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 6>), dim3(li.ray_blocks), dim3(li.ray_threads), lds, s, p, lt, total));
+    } else if (v == 5) {
+        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 5>), dim3(li.ray_blocks), dim3(li.ray_threads), lds, s, p, lt, total));
+    } else if (v == 4) {
+        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 4>), dim3(li.ray_blocks), dim3(li.ray_threads), lds, s, p, lt, total));
+    } else if (v == 3) {
+        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 3>), dim3(li.ray_blocks), dim3(li.ray_threads), lds, s, p, lt, total));
+    } else if (v == 2) {
+        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 2>), dim3(li.ray_blocks), dim3(li.ray_threads), lds, s, p, lt, total));
+    } else if (v == 1) {
+        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 1>), dim3(li.ray_blocks), dim3(li.ray_threads), lds, s, p, lt, total));
+    } else if (v == 0) {
+        DISPATCH_A(p.cars_per_env, launch(ev_start, ev_stop, (rc_raycast_kernel<kA, 0>), dim3(li.ray_blocks), dim3(li.ray_threads), lds, s, p, lt, total));
     } else {
         return (int)hipErrorInvalidValue;
     }

@@ -79,19 +79,6 @@ __device__ __forceinline__ int sign_mask(float a) {            // -1 if the sign
     asm("v_ashrrev_i32 %0, 31, %1" : "=v"(r) : "v"(a));
     return r;
 }
-__device__ __forceinline__ int nonzero_mask(int a) {           // -1 if a != 0 (0 <= a < 2^31), else 0
-    int r;
-    asm("v_sub_u32 %0, 0, %1\n\tv_ashrrev_i32 %0, 31, %0" : "=v"(r) : "v"(a));
-    return r;
-}
-__device__ __forceinline__ int bfi(int mask, int a, int b) {   // (mask & a) | (~mask & b)
-    int r;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "v"(mask), "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float bfi(int mask, float a, float b) {
-    return __int_as_float(bfi(mask, __float_as_int(a), __float_as_int(b)));
-}
 // cond ? a : b through the e64 form of v_cndmask (mask in an SGPR pair, ~4.3 cycles) instead of the e32 form
 // reading VCC (~16 cycles) that hipcc picks when VCC happens to hold the condition.
 __device__ __forceinline__ float select64(bool cond, float a, float b) {

@@ -327,7 +327,7 @@ hipError_t rck_validate_tables(const RcTrackDev &t, float band, hipStream_t s, u
         p.scan_overrun = counters + 1;
         RcLaunchInfo li{};                  // rc_raycast_car_kernel<1, false, true>, one car per 64-thread workgroup
         li.raycast_variant = 7; li.car_threads = 64; li.car_split = 1; li.scan_guarded = 1;
-        e = rck_launch_raycast(p, li, s);
+        e = rck_launch_raycast(p, li, nullptr, s);
         if (e == hipSuccess) e = hipMemcpyAsync(host, counters, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }

@@ -254,7 +254,7 @@ def test_the_shipped_library_carries_no_lab_kernels(hip_lib):
     assert not build.lab_needs_build() and build.library_build_id(lab) == build.source_hash(sources=build.LAB_SOURCES)
     import ctypes
     h = ctypes.CDLL(lab)
-    for sym in ("rclab_launch_raycast", "rclab_set_lds_limits", "rclab_build_id"):
+    for sym in ("rclab_launch_raycast", "rclab_build_tables", "rclab_abi", "rclab_build_id"):
         assert hasattr(h, sym), sym
     with open(lab, "rb") as f:
         blob = f.read()

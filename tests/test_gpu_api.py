@@ -410,7 +410,7 @@ def test_the_exact_renders_estimate_never_decides_a_pixel_wrongly():
 
 
 def test_a_lab_library_built_against_other_headers_is_refused(tmp_path):
-    """RcParams and RcLaunchInfo cross the lab boundary by pointer, so a lab library built against other headers would
+    """RcParams, RcLaunchInfo and RcLabTables cross the lab boundary by pointer, so a lab library built against other headers would
     read them wrongly - wrong scans or a GPU fault, no error.  The lab says what it was built against (`rclab_abi`: struct sizes
     + the hash of the headers), the loader compares the whole string and refuses anything else, naming the build command.  Here:
     the lab's own source compiled with another headers id (a few seconds; no kernel of it ever runs)."""
@@ -442,3 +442,92 @@ print("scan", env.scan_kernel_name(), float(out["lidar"].max()))
     assert int(lines["variant"].split()[1]) != 0 and "built against other headers" in lines["variant"], lines["variant"]
     assert "some-other-tree" in lines["variant"] and "racing_dreamer_amd.build --lab" in lines["variant"]
     assert "rc_raycast_car_kernel<1" in lines["scan"] and float(lines["scan"].split()[-1]) > 1.0
+
+
+# ---- The tables of scan variants 1-5 belong to the lab: built on the first request for such a variant, owned by the track's
+# shared tables, handed to the lab's kernels at launch.  All at 8 envs on columbia, on the lab library the suite has built.
+
+def _lazy_tables_rollout(cars, variant):
+    """Two handles on one cached track, the same reset; A takes `variant` (which builds the tables), B stays on 7; five random
+    steps each.  Returns (A, B) after asserting that their scans are equal to the bit."""
+    import torch
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    a = BatchedRaceEnv("columbia", 8, cars, auto_reset=True)
+    b = BatchedRaceEnv("columbia", 8, cars, auto_reset=True)
+    a.reset(mode="random", seed=4)
+    b.reset(mode="random", seed=4)
+    a.set_raycast_variant(variant)
+    assert a.scan_kernel_name() == f"rc_raycast_kernel<{cars}, {variant}>" and "rc_raycast_car_kernel" in b.scan_kernel_name()
+    for k in range(5):
+        a.step_random(seed=6, step=k)
+        b.step_random(seed=6, step=k)
+    torch.cuda.synchronize()
+    assert torch.equal(a.views["lidar"], b.views["lidar"])
+    assert float(a.views["lidar"].max()) > 1.0
+    return a, b
+
+
+def test_lab_tables_are_built_on_request_shared_by_a_track_and_outlive_the_asking_handle():
+    import torch
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    a, b = _lazy_tables_rollout(1, 5)
+    a.close()                                              # the handle that asked for the tables goes; the track keeps them
+    b.set_raycast_variant(2)
+    c = BatchedRaceEnv("columbia", 8, 1, auto_reset=True)  # the same rollout, all of it on the default scan
+    c.reset(mode="random", seed=4)
+    for k in range(5):
+        c.step_random(seed=6, step=k)
+    for k in range(5, 10):
+        b.step_random(seed=6, step=k)
+        c.step_random(seed=6, step=k)
+    torch.cuda.synchronize()
+    assert b.scan_kernel_name() == "rc_raycast_kernel<1, 2>"
+    assert torch.equal(b.views["lidar"], c.views["lidar"])
+    b.close()
+    c.close()
+
+
+def test_lab_tables_built_on_request_serve_two_cars_per_env():
+    a, b = _lazy_tables_rollout(2, 1)                      # (the other-car intersection runs behind the lazily built table)
+    a.close()
+    b.close()
+
+
+def test_reloading_another_track_returns_a_variant_handle_to_the_default_scan():
+    import torch
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    from racing_dreamer_amd.track_assets import load_track
+    a = BatchedRaceEnv("columbia", 8, 1, auto_reset=True)
+    a.reset(mode="random", seed=4)
+    a.set_raycast_variant(3)
+    a.step_random(seed=6, step=0)
+    assert a.scan_kernel_name() == "rc_raycast_kernel<1, 3>"
+    a._load_track(load_track("treitlstrasse_v2"))
+    assert "rc_raycast_car_kernel" in a.scan_kernel_name()
+    c = BatchedRaceEnv("treitlstrasse_v2", 8, 1, auto_reset=True)
+    for env in (a, c):
+        env.reset(mode="grid")            # (a random reset draws by the env's episode count, which differs between the two handles)
+        env.step_random(seed=6, step=1)
+    torch.cuda.synchronize()
+    assert torch.equal(a.views["lidar"], c.views["lidar"]) and float(c.views["lidar"].max()) > 1.0
+    a.close()
+    c.close()
+
+
+def test_variant_6_runs_on_a_track_nobody_built_lab_tables_for():
+    """No handle is alive on columbia when this one loads it, so the track's tables are new and carry no lab block; variant 6
+    reads the quadrant planes of the shipped tables and must not need one (rc_set_raycast_variant says so where it builds)."""
+    import torch
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    a = BatchedRaceEnv("columbia", 8, 1, auto_reset=True)
+    b = BatchedRaceEnv("columbia", 8, 1, auto_reset=True)
+    a.set_raycast_variant(6)
+    for env in (a, b):
+        env.reset(mode="random", seed=4)
+        for k in range(5):
+            env.step_random(seed=6, step=k)
+    torch.cuda.synchronize()
+    assert a.scan_kernel_name() == "rc_raycast_kernel<1, 6>"
+    assert torch.equal(a.views["lidar"], b.views["lidar"]) and float(b.views["lidar"].max()) > 1.0
+    a.close()
+    b.close()
