@@ -1433,9 +1433,7 @@ int rc_scan_kernel_name(rc_env *env, char *out, size_t bytes) {
         snprintf(out, bytes, "rc_raycast_ts_kernel<%d, %s, %s>", a, li.car_split > 1 ? "true" : "false", env->params.noise_on ? "true" : "false");
     else if (li.raycast_variant != 7) snprintf(out, bytes, "rc_raycast_kernel<%d, %d>", a, li.raycast_variant);
     else if (li.scan_stamps != nullptr && a == 1) snprintf(out, bytes, "rc_raycast_car_stamps_kernel");
-    else if (li.scan_guarded) snprintf(out, bytes, "rc_raycast_car_kernel<%d, false, true>", a);
-    else if (env->params.noise_on) snprintf(out, bytes, "rc_raycast_car_noise_kernel<%d, %s>", a, li.car_split > 1 ? "true" : "false");
-    else snprintf(out, bytes, "rc_raycast_car_kernel<%d, %s, false>", a, li.car_split > 1 ? "true" : "false");
+    else rck_scan_kernel_name(env->params, li, out, bytes);          // the production scan: named where it is chosen (scan_kernel)
     return RC_OK;
 }
 

@@ -248,6 +248,7 @@ hipError_t rck_launch_dynamics(const RcParams &p, float *actions, int repeat, co
 hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s);
 hipError_t rck_launch_set_pose(const RcParams &p, const float *xyyaw_dev, hipStream_t s);
 hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, const RcLabTables *lab, hipStream_t s);   // lab: the track's block for variants 1-5, else unused
+void rck_scan_kernel_name(const RcParams &p, const RcLaunchInfo &li, char *out, size_t bytes);   // the kernel rck_launch_raycast launches for variant 7 without stamps
 hipError_t rck_launch_patch(const RcParams &p, const RcLaunchInfo &li, hipStream_t s);
 // track set (rc_set_track_set): the track-major car list, the scan and the render (the dynamics and the reset above go by RcParams::ts_n)
 hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s);

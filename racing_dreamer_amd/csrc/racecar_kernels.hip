@@ -17,6 +17,7 @@
 // Numerics: fp32, one IEEE operation per written operator (-ffp-contract=off), same order as
 // oracle/racecar_oracle.py, so results are bit-identical to the CPU oracle.
 #include <dlfcn.h>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 
@@ -447,31 +448,34 @@ __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restric
     store_state_and_obs<A>(p, t, e, car, steps, agent_steps);
 }
 
+// The env of this lane (one lane per env); false: the lane is beyond the handle's envs and leaves.
+__device__ __forceinline__ bool lane_env(const RcParams &p, int &e) {
+    e = blockIdx.x * blockDim.x + threadIdx.x;
+    return e < p.num_envs;
+}
+
 template <int A>
 __global__ __launch_bounds__(256) void rc_dynamics_kernel(RcParams p, float *__restrict__ actions, int repeat,
                                                           int rand_on, uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.num_envs) return;
-    dynamics_env<A>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+    int e;
+    if (lane_env(p, e)) dynamics_env<A>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
 }
 
 // The same with the vehicle parameters per car (rc_set_vehicle_randomization / rc_set_vehicle_params): launched only while a
-// handle's vp_mode is not off, so the kernel above stays what it was.
+// handle's vp_mode is not off.
 template <int A>
 __global__ __launch_bounds__(256) void rc_dynamics_dr_kernel(RcParams p, float *__restrict__ actions, int repeat,
                                                              int rand_on, uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.num_envs) return;
-    dynamics_env<A, true>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+    int e;
+    if (lane_env(p, e)) dynamics_env<A, true>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
 }
 
 // The same with a track per env (rc_set_track_set): launched only while the handle's track set is on.
 template <int A, bool DR>
 __global__ __launch_bounds__(256) void rc_dynamics_ts_kernel(RcParams p, float *__restrict__ actions, int repeat,
                                                              int rand_on, uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.num_envs) return;
-    dynamics_env<A, DR, true>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+    int e;
+    if (lane_env(p, e)) dynamics_env<A, DR, true>(p, actions, repeat, rand_on, rand_lo, rand_hi, rand_step, e);
 }
 
 // Where the car of rank r (position along the track) stands in RcStateDev::order - see rc_order_place_kernel.
@@ -493,9 +497,9 @@ __device__ __forceinline__ int group_block(const RcGroup &g, const int wave) {
     return b;
 }
 
-template <int A>
-__global__ __launch_bounds__(256) void rc_dynamics_group_kernel(const RcParams *__restrict__ params, RcGroup g, int repeat, int rand_on,
-                                                                uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
+template <int A, bool DR>
+__device__ __forceinline__ void dynamics_group_wave(const RcParams *__restrict__ params, const RcGroup &g, const int repeat, const int rand_on,
+                                                    const uint32_t rand_lo, const uint32_t rand_hi, const uint32_t rand_step) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
     if (wave >= g.wave_start[g.n]) return;
     const int b = group_block(g, wave);
@@ -503,20 +507,20 @@ __global__ __launch_bounds__(256) void rc_dynamics_group_kernel(const RcParams *
                                             // re-read after every store, the table not being known to stay as it is)
     const int e = (wave - g.wave_start[b]) * 64 + (int)(threadIdx.x & 63u);
     if (e >= p.num_envs) return;
-    dynamics_env<A>(p, g.actions[b], repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+    dynamics_env<A, DR>(p, g.actions[b], repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+}
+
+template <int A>
+__global__ __launch_bounds__(256) void rc_dynamics_group_kernel(const RcParams *__restrict__ params, RcGroup g, int repeat, int rand_on,
+                                                                uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
+    dynamics_group_wave<A, false>(params, g, repeat, rand_on, rand_lo, rand_hi, rand_step);
 }
 
 // (a group in which some handle's vehicle parameters are per car; a block whose handle has them off reads its nominal values)
 template <int A>
 __global__ __launch_bounds__(256) void rc_dynamics_dr_group_kernel(const RcParams *__restrict__ params, RcGroup g, int repeat, int rand_on,
                                                                    uint32_t rand_lo, uint32_t rand_hi, uint32_t rand_step) {
-    const int wave = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
-    if (wave >= g.wave_start[g.n]) return;
-    const int b = group_block(g, wave);
-    const RcParams p = params[b];
-    const int e = (wave - g.wave_start[b]) * 64 + (int)(threadIdx.x & 63u);
-    if (e >= p.num_envs) return;
-    dynamics_env<A, true>(p, g.actions[b], repeat, rand_on, rand_lo, rand_hi, rand_step, e);
+    dynamics_group_wave<A, true>(params, g, repeat, rand_on, rand_lo, rand_hi, rand_step);
 }
 
 template <int A>
@@ -538,14 +542,13 @@ __device__ __forceinline__ void reset_env(const RcParams &p, const RcTrackDev &t
     store_state_and_obs<A>(p, t, e, car, steps, agent_steps);
 }
 
+// rc_reset's mask: an env that keeps running is left as it is
+__device__ __forceinline__ bool masked_out(const uint8_t *__restrict__ mask, int e) { return mask != nullptr && mask[e] == 0; }
+
 template <int A>
 __global__ __launch_bounds__(256) void rc_reset_kernel(RcParams p, const uint8_t *__restrict__ mask) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.num_envs) return;
-    if (mask != nullptr && mask[e] == 0) {
-        // an env that keeps running: its next observation is no longer the first of an episode
-        return;
-    }
+    int e;
+    if (!lane_env(p, e) || masked_out(mask, e)) return;
     const uint32_t episode = p.st.episode[e];
     reset_env<A>(p, p.trk, e, episode);
 }
@@ -554,9 +557,8 @@ __global__ __launch_bounds__(256) void rc_reset_kernel(RcParams p, const uint8_t
 // reset above on that track
 template <int A>
 __global__ __launch_bounds__(256) void rc_reset_ts_kernel(RcParams p, const uint8_t *__restrict__ mask) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.num_envs) return;
-    if (mask != nullptr && mask[e] == 0) return;
+    int e;
+    if (!lane_env(p, e) || masked_out(mask, e)) return;
     const uint32_t episode = p.st.episode[e];
     const int tr = ts_track_of(p, e);
     const int tr_next = p.ts_started[e] ? ts_next_track(p, e, episode, tr) : tr;
@@ -570,9 +572,8 @@ __global__ __launch_bounds__(256) void rc_reset_ts_kernel(RcParams p, const uint
 // rc_reset with vehicle randomization in random mode: the reset above, then the new episode's vehicle parameters
 template <int A>
 __global__ __launch_bounds__(256) void rc_reset_dr_kernel(RcParams p, const uint8_t *__restrict__ mask) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= p.num_envs) return;
-    if (mask != nullptr && mask[e] == 0) return;
+    int e;
+    if (!lane_env(p, e) || masked_out(mask, e)) return;
     const uint32_t episode = p.st.episode[e];
     float vp[A][RC_VP_COUNT];
     draw_vehicle<A>(p, e, episode, vp);
@@ -608,10 +609,7 @@ __global__ __launch_bounds__(256) void rc_raycast_car_kernel(RcParams p, int spl
     // One car (or 1 / split of one) per wave and nothing more: several cars in sequence per wave were measured slower
     // (2 per wave + 6 %, 8 per wave + 20 %) - the hardware dispatcher balances 65 536 short waves better than any
     // static share, and a finished wave's flush is not waited for by anybody.
-    extern __shared__ uint32_t lds_words[];                              // 17 x 64 floats per wave of the workgroup
-    // LDS address of this wave's row
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
-    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const uint32_t lds_row = wave_lds_row();                             // 17 x 64 floats per wave of the workgroup
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const unsigned lane = threadIdx.x & 63u;
     const unsigned slot = wave / (unsigned)split, part = wave - slot * (unsigned)split;
@@ -623,9 +621,7 @@ __global__ __launch_bounds__(256) void rc_raycast_car_kernel(RcParams p, int spl
 
 template <int A, bool OVERLAP>
 __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *__restrict__ params, RcGroup g, int split) {
-    extern __shared__ uint32_t lds_words[];
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
-    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const uint32_t lds_row = wave_lds_row();
     // Workgroups go to the 8 XCDs in turn, each with an L2 of its own: workgroup i takes wave (i mod 8) x ceil(W / 8) + i / 8, so
     // that an XCD works through ONE stretch of the car order - one track's tables in its L2, two at a block boundary - instead
     // of every eighth car of all tracks.
@@ -634,7 +630,7 @@ __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *_
     const int wave = (launched & 7) * per_xcd + (launched >> 3);
     if ((launched >> 3) >= per_xcd || wave >= g.wave_start[g.n]) return;
     const int b = group_block(g, wave);
-    const RcParams p = params[b];           // (a copy: see rc_dynamics_group_kernel)
+    const RcParams p = params[b];           // (a copy: see dynamics_group_wave)
     const unsigned local = (unsigned)(wave - g.wave_start[b]);
     const unsigned slot = local / (unsigned)split, part = local - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
@@ -647,9 +643,7 @@ __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *_
 // instantiations, launched only while a handle's noise is on, so the production kernels above stay what they were.
 template <int A, bool OVERLAP>
 __global__ __launch_bounds__(256) void rc_raycast_car_noise_kernel(RcParams p, int split) {
-    extern __shared__ uint32_t lds_words[];
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
-    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const uint32_t lds_row = wave_lds_row();
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const unsigned lane = threadIdx.x & 63u;
     const unsigned slot = wave / (unsigned)split, part = wave - slot * (unsigned)split;
@@ -660,9 +654,7 @@ __global__ __launch_bounds__(256) void rc_raycast_car_noise_kernel(RcParams p, i
 
 template <int A, bool OVERLAP>
 __global__ __launch_bounds__(256) void rc_raycast_group_noise_kernel(const RcParams *__restrict__ params, RcGroup g, int split) {
-    extern __shared__ uint32_t lds_words[];
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
-    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const uint32_t lds_row = wave_lds_row();
     const int launched = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
     const int per_xcd = (g.wave_start[g.n] + 7) >> 3;
     const int wave = (launched & 7) * per_xcd + (launched >> 3);
@@ -738,9 +730,7 @@ __global__ __launch_bounds__(256) void rc_ts_place_kernel(RcParams p) {
 // the table by its env's track with scalar loads.  NOISE: scan_car's LiDAR noise.
 template <int A, bool OVERLAP, bool NOISE>
 __global__ __launch_bounds__(256) void rc_raycast_ts_kernel(RcParams p0, int split) {
-    extern __shared__ uint32_t lds_words[];
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
-    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const uint32_t lds_row = wave_lds_row();
     const int launched = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
     const int total = p0.n_cars * split;
     const int per_xcd = (total + 7) >> 3;
@@ -749,7 +739,7 @@ __global__ __launch_bounds__(256) void rc_raycast_ts_kernel(RcParams p0, int spl
     const unsigned slot = (unsigned)wave / (unsigned)split, part = (unsigned)wave - slot * (unsigned)split;
     const unsigned car = (unsigned)__builtin_amdgcn_readfirstlane(p0.ts_list[slot]);
     const int k = __builtin_amdgcn_readfirstlane(ts_track_of(p0, (int)(car / (unsigned)A)));
-    const RcParams p = p0.ts_table[k];      // (a copy: see rc_dynamics_group_kernel)
+    const RcParams p = p0.ts_table[k];      // (a copy: see dynamics_group_wave)
     scan_car<A, false, OVERLAP, false, NOISE>(p, car, part, split, threadIdx.x & 63u, lds_row);
 }
 
@@ -1342,36 +1332,50 @@ inline void with_flag(bool on, F &&f) {
     else f(std::false_type{});
 }
 
-// The single-handle scan's instantiations, named in ONE place: what rck_launch_raycast launches and rck_set_lds_limits checks.
-// LiDAR noise has instantiations of its own (the ABI refuses it with the bounded build); the bounded build (a validation band
-// is in force: its trip loop counts its trips) never overlaps; else a small batch (several waves per car, few per SIMD)
-// prepares the next round under the first request.
+// The single-handle scan's instantiations, named in ONE place: what rck_launch_raycast launches, rck_scan_kernel_name spells and
+// rck_set_lds_limits checks.  The bounded build (a validation band is in force: its trip loop counts its trips) never overlaps
+// and has no noise (the ABI refuses the two together); LiDAR noise has instantiations of its own; else a small batch (several
+// waves per car, few per SIMD) prepares the next round under the first request.
 using ScanKernel = void (*)(RcParams, int);
 struct ScanChoice { bool noise, guard, overlap; };
 constexpr ScanChoice kScanChoices[] = {{false, false, false}, {false, false, true}, {false, true, false}, {true, false, false}, {true, false, true}};
+static ScanChoice scan_choice(const RcParams &p, const RcLaunchInfo &li) { return {p.noise_on != 0, li.scan_guarded != 0, li.car_split > 1}; }
 template <int A>
 ScanKernel scan_kernel(const ScanChoice &c) {
-    if (c.noise) return c.overlap ? rc_raycast_car_noise_kernel<A, true> : rc_raycast_car_noise_kernel<A, false>;
     if (c.guard) return rc_raycast_car_kernel<A, false, true>;
+    if (c.noise) return c.overlap ? rc_raycast_car_noise_kernel<A, true> : rc_raycast_car_noise_kernel<A, false>;
     return c.overlap ? rc_raycast_car_kernel<A, true, false> : rc_raycast_car_kernel<A, false, false>;
+}
+void rck_scan_kernel_name(const RcParams &p, const RcLaunchInfo &li, char *out, size_t bytes) {
+    const ScanChoice c = scan_choice(p, li);
+    const char *overlap = c.overlap ? "true" : "false";
+    if (c.guard) snprintf(out, bytes, "rc_raycast_car_kernel<%d, false, true>", p.cars_per_env);
+    else if (c.noise) snprintf(out, bytes, "rc_raycast_car_noise_kernel<%d, %s>", p.cars_per_env, overlap);
+    else snprintf(out, bytes, "rc_raycast_car_kernel<%d, %s, false>", p.cars_per_env, overlap);
+}
+
+// The render and the scan address their dynamic LDS from LDS address 0: true only while they have no static LDS
+static hipError_t no_static_lds(const void *k) {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, k);
+    return e == hipSuccess && fa.sharedSizeBytes != 0 ? hipErrorInvalidValue : e;
+}
+// ... and the render's bitmap needs more of it than a kernel gets unasked
+static hipError_t raise_lds_ceiling(std::initializer_list<const void *> kernels, size_t lds_bytes) {
+    for (const void *k : kernels) {
+        hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e == hipSuccess) e = no_static_lds(k);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t rck_set_lds_limits(size_t lds_bytes) {
-    hipError_t e = hipSuccess;
-    // rc_patch_car_kernel and rc_raycast_car_kernel address their dynamic LDS from LDS address 0: true only while they have
-    // no static LDS
-    auto no_static_lds = [&](const void *k) {
-        hipFuncAttributes fa;
-        if (e == hipSuccess) e = hipFuncGetAttributes(&fa, k);
-        if (e == hipSuccess && fa.sharedSizeBytes != 0) e = hipErrorInvalidValue;
-    };
-    for (const void *k : {reinterpret_cast<const void *>(rc_patch_car_kernel<true>), reinterpret_cast<const void *>(rc_patch_car_kernel<false>)}) {
-        if (e == hipSuccess) e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        no_static_lds(k);
-    }
+    hipError_t e = raise_lds_ceiling({reinterpret_cast<const void *>(rc_patch_car_kernel<true>), reinterpret_cast<const void *>(rc_patch_car_kernel<false>)}, lds_bytes);
     for (int cars = 1; cars <= 4; ++cars)
         with_cars(cars, [&](auto a) {
-            for (const ScanChoice &c : kScanChoices) no_static_lds(reinterpret_cast<const void *>(scan_kernel<decltype(a)::value>(c)));
+            for (const ScanChoice &c : kScanChoices)
+                if (e == hipSuccess) e = no_static_lds(reinterpret_cast<const void *>(scan_kernel<decltype(a)::value>(c)));
         });
     return e;
 }
@@ -1437,20 +1441,23 @@ hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, const R
     }
     const int threads = li.car_threads, per = threads / 64;                     // waves per workgroup
     const long long waves = (long long)p.n_cars * li.car_split;
-    const ScanChoice choice = {p.noise_on != 0, li.scan_guarded != 0, li.car_split > 1};
     with_cars(p.cars_per_env, [&](auto a) {
-        launch(scan_kernel<decltype(a)::value>(choice), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split);
+        launch(scan_kernel<decltype(a)::value>(scan_choice(p, li)), dim3((unsigned)((waves + per - 1) / per)), dim3(threads), (size_t)per * kCarLdsBytes, s, p, li.car_split);
     });
     return hipGetLastError();
 }
 
+// The render's workgroups: persistent, 16 waves each, the bitmap (lds_bytes) staged once per workgroup; as many as stay resident
+static long long patch_blocks(const RcParams &p, const RcLaunchInfo &li, size_t lds_bytes) {
+    const int per_cu = lds_bytes <= 80 * 1024 ? 2 : 1;
+    const long long need = ((long long)p.n_cars + 15) / 16, resident = (long long)li.n_cu * per_cu;
+    return need < resident ? need : resident;
+}
+
 hipError_t rck_launch_patch(const RcParams &p, const RcLaunchInfo &li, hipStream_t s) {
-    // persistent 16-wave workgroups, the bitmap staged once per workgroup; as many as stay resident
     const int padded = (li.patch_variant & 4) ? 0 : (int)rc_patch_padded_bytes(p.trk.h, p.trk.w);      // (4: experiment, the unpadded bitmap)
     const size_t lds = padded ? (size_t)padded : li.lds_bytes;
-    const int per_cu = lds <= 80 * 1024 ? 2 : 1;
-    const long long need = ((long long)p.n_cars + 15) / 16, resident = (long long)li.n_cu * per_cu;
-    const int blocks = (int)(need < resident ? need : resident);
+    const int blocks = (int)patch_blocks(p, li, lds);
     if (li.patch_variant & 2) launch(rc_patch_car_kernel<false>, dim3(blocks), dim3(1024), lds, s, p, padded);     // experiment: plain stores
     else launch(rc_patch_car_kernel<true>, dim3(blocks), dim3(1024), lds, s, p, padded);
     return hipGetLastError();
@@ -1480,24 +1487,12 @@ hipError_t rck_launch_ts_raycast(const RcParams &p, const RcLaunchInfo &li, hipS
 }
 
 hipError_t rck_set_ts_lds_limit(size_t lds_bytes) {
-    hipError_t e;
-    for (const void *k : {reinterpret_cast<const void *>(rc_patch_ts_kernel<true>), reinterpret_cast<const void *>(rc_patch_ts_kernel<false>)}) {
-        e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        hipFuncAttributes fa;                   // (the bitmap is addressed from LDS address 0: no static LDS)
-        e = hipFuncGetAttributes(&fa, k);
-        if (e != hipSuccess) return e;
-        if (fa.sharedSizeBytes != 0) return hipErrorInvalidValue;
-    }
-    return hipSuccess;
+    return raise_lds_ceiling({reinterpret_cast<const void *>(rc_patch_ts_kernel<true>), reinterpret_cast<const void *>(rc_patch_ts_kernel<false>)}, lds_bytes);
 }
 
-// lds_bytes: the largest bitmap image of the set's tracks (padded or not, per track)
+// lds_bytes: the largest bitmap image of the set's tracks (padded or not, per track); a workgroup at least for every track
 hipError_t rck_launch_ts_patch(const RcParams &p, const RcLaunchInfo &li, size_t lds_bytes, hipStream_t s) {
-    const int per_cu = lds_bytes <= 80 * 1024 ? 2 : 1;
-    const long long need = ((long long)p.n_cars + 15) / 16, resident = (long long)li.n_cu * per_cu;
-    long long blocks = need < resident ? need : resident;
-    if (blocks < p.ts_n) blocks = p.ts_n;
+    const long long resident = patch_blocks(p, li, lds_bytes), blocks = resident < p.ts_n ? p.ts_n : resident;
     if (li.patch_variant & 2) launch(rc_patch_ts_kernel<false>, dim3((unsigned)blocks), dim3(1024), lds_bytes, s, p);
     else launch(rc_patch_ts_kernel<true>, dim3((unsigned)blocks), dim3(1024), lds_bytes, s, p);
     return hipGetLastError();

@@ -411,9 +411,7 @@ __global__ __launch_bounds__(1024) void rc_raycast_kernel(RcParams p, RcLabTable
 
 // The instrumented build of the same kernel (rc_debug_scan_stamps; one car per env, analysis only).
 __global__ __launch_bounds__(256) void rc_raycast_car_stamps_kernel(RcParams p, int split, unsigned long long *stamps, int n_waves) {
-    extern __shared__ uint32_t lds_words[];
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
-    const uint32_t lds_row = __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+    const uint32_t lds_row = wave_lds_row();
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
     const unsigned lane = threadIdx.x & 63u;
     const unsigned car = wave / (unsigned)split, part = wave - car * (unsigned)split;

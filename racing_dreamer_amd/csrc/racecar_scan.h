@@ -459,6 +459,12 @@ constexpr unsigned kCarFrameBytes = 4 * 32;                            // ... th
 constexpr unsigned kCarLdsBytes = kCarRowBytes + 2 * RC_FIRST_PLANES + kCarFrameBytes;  // ... and the start cell's line of the first-trip table
 // (8 waves per SIMD = 32 per CU x 4 992 bytes = 156 KB of the CU's 160 KB: the LDS still lets the scan's occupancy stand)
 static_assert(32u * kCarLdsBytes <= 160u * 1024u, "the scan's LDS must leave room for 8 waves per SIMD");
+// LDS address of this wave's kCarLdsBytes of the workgroup's dynamic LDS (scan_car's lds_row)
+__device__ __forceinline__ uint32_t wave_lds_row() {
+    extern __shared__ uint32_t lds_words[];
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)lds_words;
+    return __builtin_amdgcn_readfirstlane(lds_base + (threadIdx.x >> 6) * kCarLdsBytes);
+}
 
 // STAMPS: the instrumented build (rc_debug_scan_stamps): RC_STAMP_SLOTS uint64 per wave.  Shader-clock values (s_memtime: a
 // per-CU counter, comparable within a wave only) at fixed points of the wave's life - slot 0 entry, 1 car state arrived,
