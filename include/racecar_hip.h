@@ -328,8 +328,8 @@ int rc_follow_the_gap_reference(rc_env *env, float dt, float *detail_dev);
  * models.py:61-87 RSSM.obs_step / img_step, :339-364 ActionDecoder 'tanh_normal' and actor_version "normalized") - the posterior
  * MEAN instead of a sample and tanh(mean) instead of the best of 100 draws, in the binary32 arithmetic of DESIGN.md §2 item 12
  * (tests/policy_spec.c is its CPU restatement; the device equals it bit for bit).  rc_policy_set_sampling switches to the
- * reference's own sampled modes; rc_policy_imagine (below) runs the prior and the reward head.  The observation decoder is not
- * part of it.
+ * reference's own sampled modes; rc_policy_imagine (below) runs the prior and the reward head, rc_policy_decode
+ * (below it) the observation decoder.
  *
  * rc_policy_weights: host pointers and shapes of the checkpoint's arrays in `tf.Module.variables` order (rssm.pkl: 13 arrays,
  * actor.pkl: 10, or 14 with the batch normalisation's four).  One-dimensional arrays have rows = 1. */
@@ -438,6 +438,46 @@ typedef struct rc_policy_imagine_args {
  * horizon outside [1, 64], unknown mode, empty mask or bits beyond cars_per_env, no output asked for, reward or reward_start
  * asked for without a loaded head.  Kernels: rc_policy_imagine_kernel, rc_policy_imagine_sampled_kernel, timed under RC_K_POLICY. */
 int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *args);
+
+/* The observation decoder: what the world model believes the car sees (tests/policy_decode_spec.c is the CPU
+ * restatement, the device equals it bit for bit).  The reference's LidarOccupancyDecoder (dreamer/models.py:444-465) on a feature
+ * [stoch 30 | deter 200]: dense 230 -> 64, then Conv2DTranspose(32, 5), (16, 5), (8, 6), (1, 6), all stride 2, 'valid', ReLU -
+ * 1 x 1 -> 5 -> 13 -> 30 -> 64 pixels.  logits = the Bernoulli logits (>= 0: the last layer has a ReLU too), image = the
+ * distribution's mode, logit > 0, in the encoding of RC_F_OCCUPANCY (1 = drivable).  It is what dreamer/models.py:243-277
+ * `_image_summaries` and dreamer/evaluations/produce_reconstruction.py:36-57 draw: on the live latent the reconstruction, on the
+ * features of rc_policy_imagine the open-loop prediction.
+ *
+ * rc_policy_decoder: the decoder's ten arrays, host pointers as in rc_policy_weights; a kernel [kh, kw, out, in] is passed
+ * C-contiguous with rows = kh kw out, cols = in.  rc_policy_load_decoder checks the shapes first (RC_ERR_INVALID names the first
+ * that is wrong), needs a loaded policy and copies the arrays; d = NULL drops the decoder, and so do rc_policy_load and
+ * rc_policy_unload. */
+typedef struct rc_policy_decoder {
+    uint32_t struct_size;          /* = sizeof(rc_policy_decoder) */
+    rc_policy_array dec_h1_w, dec_h1_b;                        /* [230, 64], [64]     input [stoch, deter]                     */
+    rc_policy_array dec_h2_k, dec_h2_b;                        /* [5 5 32, 64] = [800, 64], [32]                               */
+    rc_policy_array dec_h3_k, dec_h3_b;                        /* [5 5 16, 32] = [400, 32], [16]                               */
+    rc_policy_array dec_h4_k, dec_h4_b;                        /* [6 6 8, 16] = [288, 16], [8]                                 */
+    rc_policy_array dec_h5_k, dec_h5_b;                        /* [6 6 1, 8] = [36, 8], [1]                                    */
+} rc_policy_decoder;
+int rc_policy_load_decoder(rc_env *env, const rc_policy_decoder *d);
+#define RC_POLICY_DECODE_IMAGE 64  /* the decoded image is 64 x 64, as RC_F_OCCUPANCY */
+typedef struct rc_policy_decode_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_decode_args) */
+    const float *features;         /* device float32 [rows, 230], or NULL: the live latents of rc_policy_state, one row per car */
+    int64_t rows;                  /* with features: >= 1; ignored without */
+    uint32_t slot_mask;            /* live latents only: bit a = slot a, as rc_policy_act's; with features it must be 0 */
+    float *logits;                 /* device float32 [rows, 64, 64], or NULL */
+    uint8_t *image;                /* device uint8 [rows, 64, 64], or NULL */
+    int32_t *mismatch;             /* device int32 [n_cars], or NULL; live latents only: the number of pixels in which the image
+                                      differs from the car's RC_F_OCCUPANCY in the current arena (obs_type RC_OBS_LIDAR_OCCUPANCY or
+                                      RC_OBS_LIDAR_OCCUPANCY_REFERENCE); computed whether or not `image` is asked for */
+} rc_policy_decode_args;
+/* rc_policy_decode: one launch on the handle's stream.  A pure function of its input: the agent's state, RC_F_ACTION_IN, the arena
+ * and every counter stay as they are.  Live latents: rows are indexed by car, rows of cars outside the mask are not touched.
+ * RC_ERR_INVALID: wrong struct_size, no policy loaded, no decoder loaded, no output asked for, rows < 1 or a slot mask with
+ * features, an empty mask or bits beyond cars_per_env without, mismatch with features or under obs_type RC_OBS_LIDAR.
+ * Kernel: rc_policy_decode_kernel, timed under RC_K_POLICY. */
+int rc_policy_decode(rc_env *env, const rc_policy_decode_args *args);
 
 /* ---- Episode log: return, length, progress and time of every episode, kept on the device (opt-in; off = the launches of a step
  * are what they are without it) ---------------------------------------------------------------------------------------------------

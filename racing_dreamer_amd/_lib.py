@@ -105,6 +105,21 @@ class RcPolicyImagineArgs(C.Structure):
                 ("actions_in", C.c_void_p), ("reward", C.c_void_p), ("actions", C.c_void_p), ("features", C.c_void_p), ("reward_start", C.c_void_p)]
 
 
+DECODER_KEYS = ("dec_h1_w", "dec_h1_b", "dec_h2_k", "dec_h2_b", "dec_h3_k", "dec_h3_b", "dec_h4_k", "dec_h4_b", "dec_h5_k", "dec_h5_b")
+DECODE_IMAGE = 64           # the decoded lidar_occupancy image is 64 x 64
+
+
+class RcPolicyDecoder(C.Structure):
+    """rc_policy_decoder (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, RcPolicyArray) for k in DECODER_KEYS]
+
+
+class RcPolicyDecodeArgs(C.Structure):
+    """rc_policy_decode_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("features", C.c_void_p), ("rows", C.c_int64), ("slot_mask", C.c_uint32),
+                ("logits", C.c_void_p), ("image", C.c_void_p), ("mismatch", C.c_void_p)]
+
+
 def _fill_arrays(struct, weights, names, optional=()):
     import numpy as np
     keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
@@ -115,6 +130,8 @@ def _fill_arrays(struct, weights, names, optional=()):
                 continue
             raise KeyError(f"policy weights lack {k!r}")
         a = np.ascontiguousarray(weights[k], np.float32)
+        if a.ndim == 4:                                     # a transposed convolution's [kh, kw, out, in] as [kh kw out, in]
+            a = a.reshape(-1, a.shape[3])
         if a.ndim not in (1, 2):
             raise ValueError(f"policy weights: {k} has {a.ndim} dimensions")
         keep.append(a)
@@ -135,6 +152,20 @@ def policy_heads(weights):
     h = RcPolicyHeads()
     h.struct_size = C.sizeof(RcPolicyHeads)
     return h, _fill_arrays(h, weights, HEAD_KEYS)
+
+
+def policy_decoder(weights):
+    """rc_policy_decoder over a mapping that holds the dec_* arrays of a LidarOccupancyDecoder (or an .npz path), as policy_heads;
+    None if it holds none."""
+    import numpy as np
+    if isinstance(weights, (str, os.PathLike)):
+        weights = np.load(weights)
+    keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
+    if not any(k.startswith("dec_") for k in keys):
+        return None
+    d = RcPolicyDecoder()
+    d.struct_size = C.sizeof(RcPolicyDecoder)
+    return d, _fill_arrays(d, weights, DECODER_KEYS)
 
 
 def policy_weights(weights):
@@ -180,6 +211,8 @@ SYMBOLS = {
     "rc_policy_get_sampling": (C.c_int, [C.c_void_p, _P(RcPolicySampling)]),
     "rc_policy_load_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
     "rc_policy_imagine": (C.c_int, [C.c_void_p, _P(RcPolicyImagineArgs)]),
+    "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
+    "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),
     "rc_episode_log_enable": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "rc_episode_log_disable": (C.c_int, [C.c_void_p]),
     "rc_episode_log": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p), _P(C.c_size_t)]),

@@ -142,6 +142,39 @@ def _imagine_setup(env, horizon, mode, seed, actions, slots, features, start_rew
     return args, tensors, result
 
 
+def _decode_setup(env, features, slots, logits, image, mismatch, out):
+    """policy_decode's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (features as [rows, 230] or None, the
+    slot mask, the tensors by rc_policy_decode_args field with their leading dimensions flattened, the dict to return).  What
+    the call refuses (no policy, no decoder, no output, slots or mismatch with features) is left to the library, which names it."""
+    mask = (1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
+    if features is not None:
+        if features.shape[-1] != L.POLICY_FEATURE:
+            raise ValueError(f"features must be [..., {L.POLICY_FEATURE}], got {tuple(features.shape)}")
+        lead = tuple(features.shape[:-1])
+        features = features.to(env.device, torch.float32).reshape(-1, L.POLICY_FEATURE).contiguous()
+        mask = 0 if slots is None else mask                  # (slots with features: the library refuses and says why)
+    else:
+        lead = (env.n_cars,)
+    side = L.DECODE_IMAGE
+    shapes = {}
+    if logits:
+        shapes["logits"] = (lead + (side, side), torch.float32)
+    if image:
+        shapes["image"] = (lead + (side, side), torch.uint8)
+    if mismatch:
+        shapes["mismatch"] = ((env.n_cars,), torch.int32)
+    result = {}
+    for name, (shape, dtype) in shapes.items():
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = (torch.empty if slots is None else torch.zeros)(shape, dtype=dtype, device=env.device)
+        elif t.shape != shape or t.dtype != dtype or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {env.device}")
+        result[name] = t
+    flat = {k: (v if k == "mismatch" else v.view(-1, side, side)) for k, v in result.items()}
+    return features, mask, dict(logits=flat.get("logits"), image=flat.get("image"), mismatch=flat.get("mismatch")), result
+
+
 class BatchedRaceEnv:
     def __init__(self, track: Union[str, Track], num_envs: int, cars_per_env: int = 1, obs_type: str = "lidar",
                  action_repeat: int = 1, seed: int = 0, device: int = 0, first_env: int = 0,
@@ -631,6 +664,45 @@ class BatchedRaceEnv:
         if heads is not None:
             L.check(self._lib.rc_policy_load_heads(self._h, C.byref(heads[0])))
             self._policy_has_head = True
+        self._policy_has_decoder = False                    # (and a decoder)
+        decoder = L.policy_decoder(weights)
+        if decoder is not None:
+            L.check(self._lib.rc_policy_load_decoder(self._h, C.byref(decoder[0])))
+            self._policy_has_decoder = True
+
+    @property
+    def policy_has_decoder(self) -> bool:
+        """Whether the loaded checkpoint brought a LidarOccupancyDecoder (`dec_*` arrays): `policy_decode` needs one."""
+        return bool(getattr(self, "_policy_has_decoder", False))
+
+    def _decode(self, features, mask: int, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_decode on this handle: of `features` [rows, 230] into the whole tensors, or (features None) of this handle's live
+        latents into rows [lo, hi) of the tensors (one row per car)."""
+        a = L.RcPolicyDecodeArgs(C.sizeof(L.RcPolicyDecodeArgs))
+        if features is not None:
+            a.features, a.rows, lo, hi = features.data_ptr(), features.shape[0], 0, features.shape[0]
+        a.slot_mask = mask
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else t[lo:hi].data_ptr())
+        return self._lib.rc_policy_decode(self._h, C.byref(a))
+
+    def policy_decode(self, features: Optional[torch.Tensor] = None, slots=None, logits: bool = False, image: bool = True,
+                      mismatch: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """What the world model believes the car sees (`rc_policy_decode`, one launch): the reference's LidarOccupancyDecoder on
+        every car's latent as `policy_act` last left it - the reconstruction - or on `features`, a device float32 [..., 230] =
+        stoch | deter such as `policy_imagine(features=True)["feature"]` - the open-loop prediction; the leading dimensions
+        are kept.  Returns device tensors: `logits` float32 [..., 64, 64] (the Bernoulli logits, >= 0), `image` uint8
+        [..., 64, 64] = logits > 0 in the encoding of `lidar_occupancy` (1 = drivable), `mismatch` int32 [n_cars] = the number
+        of pixels in which the image differs from the car's current `lidar_occupancy` (live latents, obs_type lidar_occupancy*).
+        Nothing else changes.  With `slots` (live latents), rows of the other cars are zero - or what `out` (tensors to write
+        into, by the same names) held."""
+        feats, mask, tensors, result = _decode_setup(self, features, slots, logits, image, mismatch, out)
+        self._enter()
+        try:
+            L.check(self._decode(feats, mask, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
 
     @property
     def policy_has_reward_head(self) -> bool:
@@ -704,6 +776,7 @@ class BatchedRaceEnv:
     def unload_policy(self) -> None:
         self._policy_state = None
         self._policy_has_head = False
+        self._policy_has_decoder = False
         L.check(self._lib.rc_policy_unload(self._h))
 
     # ------------------------------------------------------------------ episode log (include/racecar_hip.h, rc_episode_log_*)
@@ -1109,6 +1182,22 @@ class MixedTrackEnv:
         args, tensors, result = _imagine_setup(self, horizon, mode, seed, actions, slots, features, start_reward, out)
         k = self.cars_per_env
         self._fork_join(lambda p, blk: p._imagine(args, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    @property
+    def policy_has_decoder(self) -> bool:
+        return self.parts[0].policy_has_decoder
+
+    def policy_decode(self, features: Optional[torch.Tensor] = None, slots=None, logits: bool = False, image: bool = True,
+                      mismatch: bool = False, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_decode over all blocks: each block decodes its cars' latents into its rows of one tensor per
+        output; given `features` (every block holds the same decoder) go through the first block."""
+        feats, mask, tensors, result = _decode_setup(self, features, slots, logits, image, mismatch, out)
+        k = self.cars_per_env
+        if feats is not None:
+            self._ordered(lambda: self.parts[0]._decode(feats, mask, tensors, 0, 0))
+        else:
+            self._fork_join(lambda p, blk: p._decode(None, mask, tensors, blk[0] * k, blk[1] * k))
         return result
 
     def set_policy_sampling(self, mode: str = "mean", seed: int = 0, expl_amount: Optional[float] = None) -> None:

@@ -81,7 +81,34 @@ struct RcImagineCall {
     float *reward, *actions, *features, *reward_start;      // [n_cars][H], [n_cars][H][2], [n_cars][H][230], [n_cars]; any may be null
 };
 
+// The observation decoder (racecar_decode.hip): the LidarOccupancyDecoder's arrays, each repacked for the
+// order in which its kernel reads it (u, v kernel row and column, c input channel, o output channel; a 6 x 6 kernel's tap is
+// (ty, tx) with u = py + 2 ty, v = px + 2 tx for the output's parity class (py, px))
+#define RC_DEC_H1 64
+#define RC_DEC_H2 800                                             // 5 x 5 x 32
+struct RcDecodeDev {
+    const float *h1_w, *h1_b;                // [230][64], [64]
+    const float *h2_k, *h2_b;                // [c 64][(u 5 + v) 32 + o], [32]
+    const float *h3_k, *h3_b;                // [o / 4][u][v][c 32][o % 4], [16]
+    const float *h4_k, *h4_b;                // [ty][tx][c 16][py][px][o 8], [8]
+    const float *h5_k, *h5_b;                // [ty][tx][c 8][py][px], [1]
+};
+
+struct RcDecodeCall {
+    RcDecodeDev w;
+    const float *features;                   // [n_rows][230], or null: the rows of `rows` from state
+    const float *state;                      // [n_cars][RC_POLICY_STATE], read only
+    RcPolicyRows rows;                       // (live latents: row -> car; outputs are indexed by car)
+    int64_t n_rows;
+    float *logits;                           // [..][64][64] or null
+    uint8_t *image;                          // [..][64][64] or null
+    int32_t *mismatch;                       // [n_cars] or null
+    const uint8_t *occupancy;                // RC_F_OCCUPANCY [n_cars][64][64] (mismatch only)
+};
+
 hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS limit (once per process and device is enough)
 hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);      // c.mode: which kernel
 hipError_t rck_imagine_prepare();
 hipError_t rck_launch_imagine(const RcImagineCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
+hipError_t rck_decode_prepare();
+hipError_t rck_launch_decode(const RcDecodeCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);

@@ -418,6 +418,56 @@ int pol_drop_heads(rc_env *env) {
     return RC_OK;
 }
 
+// the decoder's memory and pointers go (rc_policy_load_decoder(NULL), a new rc_policy_load)
+int pol_drop_decoder(rc_env *env) {
+    if (env->pol_dec_mem) {
+        HIP_TRY(hipSetDevice(env->cfg.device));
+        HIP_TRY(hipStreamSynchronize(env->stream));
+        (void)hipFree(env->pol_dec_mem);
+        env->pol_dec_mem = nullptr;
+    }
+    env->pol_d = RcDecodeDev{};
+    return RC_OK;
+}
+
+// rc_policy_decoder's arrays in order: the shape each must have (a kernel as [kh kw out, in])
+struct DecArray { const char *name; const rc_policy_array rc_policy_decoder::*arr; int rows, cols; };
+using PDec = rc_policy_decoder;
+const DecArray kDecArrays[] = {
+    {"dec_h1_w", &PDec::dec_h1_w, 230, 64}, {"dec_h1_b", &PDec::dec_h1_b, 1, 64}, {"dec_h2_k", &PDec::dec_h2_k, 800, 64}, {"dec_h2_b", &PDec::dec_h2_b, 1, 32},
+    {"dec_h3_k", &PDec::dec_h3_k, 400, 32}, {"dec_h3_b", &PDec::dec_h3_b, 1, 16}, {"dec_h4_k", &PDec::dec_h4_k, 288, 16}, {"dec_h4_b", &PDec::dec_h4_b, 1, 8},
+    {"dec_h5_k", &PDec::dec_h5_k, 36, 8}, {"dec_h5_b", &PDec::dec_h5_b, 1, 1},
+};
+
+// The decoder's device image (RcDecodeDev says which order each array takes), every array on a 64-float boundary; at[i] = array
+// i's offset in floats.  A 6 x 6 kernel's element (u, v) = (py + 2 ty, px + 2 tx) goes to tap (ty, tx) of class (py, px).
+void pol_pack_decoder(const rc_policy_decoder &d, std::vector<float> &img, size_t (&at)[10]) {
+    for (size_t i = 0; i < 10; ++i) {
+        at[i] = img.size();
+        img.resize(img.size() + ((size_t)kDecArrays[i].rows * kDecArrays[i].cols + 63) / 64 * 64, 0.0f);
+        const float *src = (d.*(kDecArrays[i].arr)).data;
+        float *dst = img.data() + at[i];
+        const int rows = kDecArrays[i].rows, cols = kDecArrays[i].cols;
+        if (i == 2) {                            // h2 [(u 5 + v) 32 + o][c] -> [c][(u 5 + v) 32 + o]
+            for (int j = 0; j < rows; ++j)
+                for (int c = 0; c < cols; ++c) dst[(size_t)c * rows + j] = src[(size_t)j * cols + c];
+        } else if (i == 4) {                     // h3 [u][v][o 16][c 32] -> [o / 4][u][v][c][o % 4]
+            for (int uv = 0; uv < 25; ++uv)
+                for (int o = 0; o < 16; ++o)
+                    for (int c = 0; c < 32; ++c) dst[((size_t)((o >> 2) * 25 + uv) * 32 + c) * 4 + (o & 3)] = src[((size_t)uv * 16 + o) * 32 + c];
+        } else if (i == 6 || i == 8) {           // h4 [u][v][o 8][c 16] -> [ty][tx][c][py][px][o]; h5 the same with 1 output, 8 inputs
+            const int no = i == 6 ? 8 : 1, nc = cols;
+            for (int u = 0; u < 6; ++u)
+                for (int v = 0; v < 6; ++v)
+                    for (int o = 0; o < no; ++o)
+                        for (int c = 0; c < nc; ++c)
+                            dst[((size_t)(((u >> 1) * 3 + (v >> 1)) * nc + c) * 4 + (u & 1) * 2 + (v & 1)) * no + o] = src[((size_t)(u * 6 + v) * no + o) * nc + c];
+        } else {
+            std::memcpy(dst, src, (size_t)rows * cols * sizeof(float));
+        }
+    }
+}
+
 // the rows of a call over the cars in `slot_mask`, and the key of their draws under `seed`
 int pol_rows(rc_env *env, uint32_t slot_mask, uint64_t seed, const char *fn, RcPolicyRows *r) {
     if (slot_mask == 0) return fail(RC_ERR_INVALID, "%s: the slot mask is empty", fn);
@@ -452,6 +502,7 @@ int pol_launch(rc_env *env, hipError_t (*launch)(const Call &, hipEvent_t, hipEv
 // rc_policy_unload and rc_destroy; the caller has synchronised the stream
 void policy_release(rc_env *env) {
     (void)pol_drop_heads(env);
+    (void)pol_drop_decoder(env);
     if (env->pol_mem) (void)hipFree(env->pol_mem);
     if (env->pol_state) (void)hipFree(env->pol_state);
     env->pol_mem = env->pol_state = nullptr;
@@ -489,7 +540,10 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(rck_policy_prepare());
     HIP_TRY(rck_imagine_prepare());
+    HIP_TRY(rck_decode_prepare());
     rc = pol_drop_heads(env);
+    if (rc) return rc;
+    rc = pol_drop_decoder(env);
     if (rc) return rc;
     if (!env->pol_mem) HIP_TRY(hipMalloc((void **)&env->pol_mem, img.size() * sizeof(float)));
     const size_t state_bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
@@ -615,6 +669,64 @@ int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *a) {
     c.actions_in = a->actions_in;
     c.reward = a->reward; c.actions = a->actions; c.features = a->features; c.reward_start = a->reward_start;
     return pol_launch(env, rck_launch_imagine, c);
+}
+
+int rc_policy_load_decoder(rc_env *env, const rc_policy_decoder *d) {
+    if (!d) {
+        if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+        return pol_drop_decoder(env);
+    }
+    if (d->struct_size != sizeof(rc_policy_decoder))
+        return fail(RC_ERR_INVALID, "rc_policy_decoder.struct_size %u != %zu", d->struct_size, sizeof(rc_policy_decoder));
+    for (const DecArray &a : kDecArrays) {
+        const rc_policy_array &g = d->*(a.arr);
+        if (!g.data) return fail(RC_ERR_INVALID, "rc_policy_load_decoder: %s is missing", a.name);
+        if (g.rows != a.rows || g.cols != a.cols)
+            return fail(RC_ERR_INVALID, "rc_policy_load_decoder: %s has shape [%d, %d], the decoder's is [%d, %d]", a.name, g.rows, g.cols, a.rows, a.cols);
+    }
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_load_decoder: no policy loaded (rc_policy_load)");
+    std::vector<float> img;
+    size_t at[10];
+    pol_pack_decoder(*d, img, at);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    if (!env->pol_dec_mem) HIP_TRY(hipMalloc((void **)&env->pol_dec_mem, img.size() * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(env->pol_dec_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
+    const float *m = env->pol_dec_mem;
+    env->pol_d = RcDecodeDev{m + at[0], m + at[1], m + at[2], m + at[3], m + at[4], m + at[5], m + at[6], m + at[7], m + at[8], m + at[9]};
+    return RC_OK;
+}
+
+int rc_policy_decode(rc_env *env, const rc_policy_decode_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_decode_args))
+        return fail(RC_ERR_INVALID, "rc_policy_decode_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_decode_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_decode: no policy loaded (rc_policy_load)");
+    if (!env->pol_d.h1_w) return fail(RC_ERR_INVALID, "rc_policy_decode: no decoder loaded (rc_policy_load_decoder)");
+    if (!a->logits && !a->image && !a->mismatch) return fail(RC_ERR_INVALID, "rc_policy_decode: no output asked for");
+    RcDecodeCall c{};
+    if (a->features) {
+        if (a->rows < 1 || a->rows > (int64_t)INT32_MAX) return fail(RC_ERR_INVALID, "rc_policy_decode: rows %lld is outside [1, 2^31)", (long long)a->rows);
+        if (a->slot_mask) return fail(RC_ERR_INVALID, "rc_policy_decode: a slot mask (0x%x) goes with the live latents, not with given features", a->slot_mask);
+        if (a->mismatch) return fail(RC_ERR_INVALID, "rc_policy_decode: mismatch compares with the cars' own RC_F_OCCUPANCY: live latents only, not given features");
+        c.n_rows = a->rows;
+    } else {
+        const int rc = pol_rows(env, a->slot_mask, 0, "rc_policy_decode", &c.rows);
+        if (rc) return rc;
+        if (a->mismatch && env->cfg.obs_type == RC_OBS_LIDAR)
+            return fail(RC_ERR_INVALID, "rc_policy_decode: mismatch needs the rendered RC_F_OCCUPANCY (obs_type lidar_occupancy or lidar_occupancy_reference)");
+        c.n_rows = c.rows.n_active;
+    }
+    if (((uintptr_t)a->logits & 7u) || ((uintptr_t)a->image & 1u))
+        return fail(RC_ERR_INVALID, "rc_policy_decode: logits must lie on an 8-byte boundary, image on a 2-byte boundary");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    c.w = env->pol_d;
+    c.features = a->features;
+    c.state = env->pol_state;
+    c.logits = a->logits; c.image = a->image; c.mismatch = a->mismatch;
+    c.occupancy = env->params.out.patch;
+    return pol_launch(env, rck_launch_decode, c);
 }
 
 }  // extern "C"

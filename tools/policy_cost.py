@@ -14,6 +14,13 @@ loops at repeat 4, all in this one process, with the target deploy <= 1.15 x mea
 beside `policy_act` (`mean`) of the same run, with the target: time per imagined step <= (padded MACs of an imagined step / padded
 MACs of an agent step) x the agent's call + 5 %, reported as met or missed.
 
+    python tools/policy_cost.py --decode [--out profiles/policy_decode_cost.json]
+
+`--decode`: the observation decoder (rc_policy_decode) on the live latents of 65 536 cars on treitlstrasse_v2 under obs_type
+lidar_occupancy - `image` only, `logits` only, `image` + `mismatch` - beside torch.nn.functional.conv_transpose2d in fp32 on the same
+four layers plus the dense layer at the same row count, with the condition `logits` time <= torch's reported as met or missed, and
+the fp32 issue floor of the decoder's 1 423 872 fma per image.
+
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
 windows; the torch baseline is timed with stream events around a window of calls (its dozen launches per call included - that is
 what it costs).  The baseline is a RATE baseline: torch.addmm sums in another order than the spec."""
@@ -302,6 +309,88 @@ def measure_imagine(n, args):
     return res
 
 
+FMA_PER_IMAGE = 230 * 64 + 64 * 800 + 320000 + 778752 + 259200          # h1 .. h5 (issue #16's table): 1 423 872
+FMA_PER_S_PEAK = 256 * 4 * 32 * 2.4e9      # 256 CUs x 4 SIMDs x 32 fp32 fma per clock (v_pk_fma_f32: 64 FLOP / clk / SIMD) x 2.4 GHz
+
+
+def torch_decode(w, feat):
+    """The decoder's layers in plain fp32 torch: addmm, then four conv_transpose2d (stride 2) + relu; logits [n, 64, 64]."""
+    import torch
+    import torch.nn.functional as F
+    x = torch.addmm(w["dec_h1_b"], feat, w["dec_h1_w"]).view(-1, 64, 1, 1)
+    for name in ("dec_h2", "dec_h3", "dec_h4", "dec_h5"):
+        x = F.relu(F.conv_transpose2d(x, w[name + "_k"], w[name + "_b"], stride=2))
+    return x[:, 0]
+
+
+def measure_decode(n, args):
+    """Per-call device time (RC_K_POLICY) of rc_policy_decode on the live latents in three output sets, and the torch baseline."""
+    import torch
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    env = BatchedRaceEnv(args.track, n, 1, obs_type="lidar_occupancy", auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    res = {"cars": n}
+
+    def timed(call):
+        for k in range(3):
+            call()
+        windows = []
+        for r in range(args.rounds):
+            env.reset_kernel_times()
+            env.set_profiling(True, kernels=[L.K_POLICY])
+            for k in range(args.calls):
+                call()
+            env.sync()
+            env.set_profiling(False)
+            windows.append(env.kernel_times()["rc_policy_kernel"]["avg_ms"])
+        return statistics.median(windows), [round(v, 4) for v in windows]
+
+    with torch.cuda.stream(env.stream):
+        env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            env.step(None, repeat=4)
+        env.sync()
+        bufs = dict(logits=torch.empty((n, 64, 64), device=env.device), image=torch.empty((n, 64, 64), dtype=torch.uint8, device=env.device),
+                    mismatch=torch.empty(n, dtype=torch.int32, device=env.device))
+        for variant, names in (("image", ("image",)), ("logits", ("logits",)), ("image_mismatch", ("image", "mismatch"))):
+            tensors = {k: (bufs[k] if k in names else None) for k in bufs}
+            ms, windows = timed(lambda: L.check(env._decode(None, 1, tensors, 0, n)))
+            res[variant] = {"ms_per_call": round(ms, 4), "windows_ms": windows, "us_per_image": round(ms * 1e3 / n, 4),
+                            "fp32_issue_floor_ms": round(FMA_PER_IMAGE * n / FMA_PER_S_PEAK * 1e3, 4),
+                            "fraction_of_issue_floor": round(FMA_PER_IMAGE * n / FMA_PER_S_PEAK * 1e3 / ms, 3)}
+        env.sync()
+        res["mean_mismatch_pixels"] = round(float(bufs["mismatch"].float().mean()), 1)
+        # ---- the torch baseline of the same layers on the same features (its own layouts: NCHW, kernels [in, out, kh, kw])
+        w = {k: torch.from_numpy(np.ascontiguousarray(weights[k], np.float32)).to(env.device) for k in weights.files if k.startswith("dec_")}
+        for k in ("dec_h2_k", "dec_h3_k", "dec_h4_k", "dec_h5_k"):
+            w[k] = w[k].permute(3, 2, 0, 1).contiguous()
+        feat = env.policy_state[:, :230].contiguous()
+        for k in range(3):
+            ref = torch_decode(w, feat)
+        L.check(env._decode(None, 1, dict(logits=bufs["logits"], image=None, mismatch=None), 0, n))
+        env.sync()
+        res["max_abs_difference_from_torch"] = float((ref - bufs["logits"]).abs().max())
+        del ref
+        windows = []
+        for r in range(args.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k in range(max(1, args.calls // 4)):
+                torch_decode(w, feat)
+            e1.record()
+            e1.synchronize()
+            windows.append(e0.elapsed_time(e1) / max(1, args.calls // 4))
+        res["torch_fp32_ms_per_call"] = round(statistics.median(windows), 4)
+        res["torch_fp32_windows_ms"] = [round(v, 4) for v in windows]
+        res["hip_over_torch"] = round(res["logits"]["ms_per_call"] / res["torch_fp32_ms_per_call"], 3)
+        res["met"] = bool(res["logits"]["ms_per_call"] <= res["torch_fp32_ms_per_call"])
+    env.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
@@ -314,9 +403,24 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--modes", action="store_true", help="measure the sampled modes (profiles/policy_sample_cost.json)")
     ap.add_argument("--imagine", action="store_true", help="measure imagination (profiles/policy_imagine_cost.json)")
+    ap.add_argument("--decode", action="store_true", help="measure the observation decoder (profiles/policy_decode_cost.json)")
     ap.add_argument("--horizon", type=int, default=15)
     args = ap.parse_args()
     import torch
+    if args.decode:
+        if args.checkpoint == "austria":                       # (the default checkpoint has no decoder)
+            args.checkpoint, args.track = "treitlstrasse_occupancy", "treitlstrasse_v2"
+        sizes = args.envs if args.envs != [4096, 65536] else [65536]
+        out = {"tool": "tools/policy_cost.py --decode", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
+               "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle, "fma_per_image": FMA_PER_IMAGE,
+               "fp32_peak_fma_per_s": FMA_PER_S_PEAK, "condition": "logits ms_per_call <= torch_fp32_ms_per_call at the largest size",
+               "sizes": [measure_decode(n, args) for n in sizes]}
+        out["met"] = out["sizes"][-1]["met"]
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.imagine:
         out = {"tool": "tools/policy_cost.py --imagine", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
                "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle,
