@@ -44,10 +44,15 @@ __device__ __forceinline__ int4 patch_pose_of(const RcTrackDev &t, float x, floa
 }
 
 // Reset of one env in two halves.  `prepare_reset` is everything that does not depend on how the current step ends -
-// the Philox draw keyed by (global env id, episode counter) and the gather of the spawn poses - so the dynamics kernel
-// issues it next to the state loads, ahead of the integrator, instead of behind the step (that kernel runs one wave
-// per SIMD: its duration is the length of its dependent chain, and a reset used to add three round trips to it in
-// nearly every wave of a random-action rollout).  `apply_reset` installs the prepared poses when the env did finish.
+// the Philox draw keyed by (global env id, episode counter), the gather of the spawn poses and, in the random modes, the
+// progress value at the jittered pose - so the dynamics kernel calls it ahead of the integrator, behind the state loads,
+// instead of behind the step.  What the compiled kernel does with that: only the episode counter travels with the state; the
+// chain episode -> Philox -> spawn gather -> jitter -> progress_at is then waited out IN FRONT of the integration, three
+// dependent round trips in series ahead of the step's own footprint and progress loads (the kernel runs one wave per SIMD:
+// its duration is the length of that chain).  The listing is in profiles/step_entry_isa.txt; a reordering that covers the
+// gather and the progress load with the first sub-step's loads was built and measured and gained nothing that the headline
+// shows (EXPERIMENTS.md 0000.3, tools/experiments/step_entry_dynamics.patch).  `apply_reset` installs the prepared poses
+// when the env did finish.
 struct Spawn { float x, y, th, ct, st, pr; int cp; };
 
 __device__ __forceinline__ float unit_pm1(uint32_t w) { return ((float)(w >> 8) * 5.9604644775390625e-8f) * 2.0f - 1.0f; }   // [-1, 1), exact
@@ -609,10 +614,12 @@ __global__ __launch_bounds__(256) void rc_raycast_car_kernel(RcParams p, int spl
     // One car (or 1 / split of one) per wave and nothing more: several cars in sequence per wave were measured slower
     // (2 per wave + 6 %, 8 per wave + 20 %) - the hardware dispatcher balances 65 536 short waves better than any
     // static share, and a finished wave's flush is not waited for by anybody.
+    const unsigned zero = scan_args_at_entry(p, split);
     const uint32_t lds_row = wave_lds_row();                             // 17 x 64 floats per wave of the workgroup
-    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) + zero;
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned slot = wave / (unsigned)split, part = wave - slot * (unsigned)split;
+    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, GUARD>();
+    const unsigned slot = kOne ? wave : wave / (unsigned)split, part = kOne ? 0u : wave - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     // (the waves take the cars in track order - see RcStateDev::order -: 5 % of the scan at 65 536 cars, EXPERIMENTS I.11)
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[slot] : slot;
@@ -631,8 +638,9 @@ __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *_
     if ((launched >> 3) >= per_xcd || wave >= g.wave_start[g.n]) return;
     const int b = group_block(g, wave);
     const RcParams p = params[b];           // (a copy: see dynamics_group_wave)
-    const unsigned local = (unsigned)(wave - g.wave_start[b]);
-    const unsigned slot = local / (unsigned)split, part = local - slot * (unsigned)split;
+    const unsigned local = (unsigned)(wave - g.wave_start[b]) + scan_args_at_entry(p, split);      // (here: one batch of loads from the table)
+    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
+    const unsigned slot = kOne ? local : local / (unsigned)split, part = kOne ? 0u : local - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     // (this launch hands every XCD a STRETCH of the slots, not every eighth: it takes the cars by rank)
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[order_slot_of_rank(slot, (uint32_t)p.n_cars)] : slot;
@@ -643,10 +651,12 @@ __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *_
 // instantiations, launched only while a handle's noise is on, so the production kernels above stay what they were.
 template <int A, bool OVERLAP>
 __global__ __launch_bounds__(256) void rc_raycast_car_noise_kernel(RcParams p, int split) {
+    const unsigned zero = scan_args_at_entry(p, split);
     const uint32_t lds_row = wave_lds_row();
-    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) + zero;
     const unsigned lane = threadIdx.x & 63u;
-    const unsigned slot = wave / (unsigned)split, part = wave - slot * (unsigned)split;
+    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
+    const unsigned slot = kOne ? wave : wave / (unsigned)split, part = kOne ? 0u : wave - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[slot] : slot;
     scan_car<A, false, OVERLAP, false, true>(p, car, part, split, lane, lds_row);
@@ -661,8 +671,9 @@ __global__ __launch_bounds__(256) void rc_raycast_group_noise_kernel(const RcPar
     if ((launched >> 3) >= per_xcd || wave >= g.wave_start[g.n]) return;
     const int b = group_block(g, wave);
     const RcParams p = params[b];
-    const unsigned local = (unsigned)(wave - g.wave_start[b]);
-    const unsigned slot = local / (unsigned)split, part = local - slot * (unsigned)split;
+    const unsigned local = (unsigned)(wave - g.wave_start[b]) + scan_args_at_entry(p, split);      // (here: one batch of loads from the table)
+    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
+    const unsigned slot = kOne ? local : local / (unsigned)split, part = kOne ? 0u : local - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[order_slot_of_rank(slot, (uint32_t)p.n_cars)] : slot;
     scan_car<A, false, OVERLAP, false, true>(p, car, part, split, threadIdx.x & 63u, lds_row);
@@ -736,11 +747,13 @@ __global__ __launch_bounds__(256) void rc_raycast_ts_kernel(RcParams p0, int spl
     const int per_xcd = (total + 7) >> 3;
     const int wave = (launched & 7) * per_xcd + (launched >> 3);
     if ((launched >> 3) >= per_xcd || wave >= total) return;
-    const unsigned slot = (unsigned)wave / (unsigned)split, part = (unsigned)wave - slot * (unsigned)split;
+    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
+    const unsigned slot = kOne ? (unsigned)wave : (unsigned)wave / (unsigned)split, part = kOne ? 0u : (unsigned)wave - slot * (unsigned)split;
     const unsigned car = (unsigned)__builtin_amdgcn_readfirstlane(p0.ts_list[slot]);
     const int k = __builtin_amdgcn_readfirstlane(ts_track_of(p0, (int)(car / (unsigned)A)));
     const RcParams p = p0.ts_table[k];      // (a copy: see dynamics_group_wave)
-    scan_car<A, false, OVERLAP, false, NOISE>(p, car, part, split, threadIdx.x & 63u, lds_row);
+    const unsigned zero = scan_args_at_entry(p, split);      // (here: one batch of loads from the table)
+    scan_car<A, false, OVERLAP, false, NOISE>(p, car + zero, part, split, threadIdx.x & 63u, lds_row);
 }
 
 // lidar_occupancy (H11, dreamer/wrappers.py:390-408): ego-aligned 64x64 patch of the drivable area,
@@ -1340,6 +1353,10 @@ using ScanKernel = void (*)(RcParams, int);
 struct ScanChoice { bool noise, guard, overlap; };
 constexpr ScanChoice kScanChoices[] = {{false, false, false}, {false, false, true}, {false, true, false}, {true, false, false}, {true, false, true}};
 static ScanChoice scan_choice(const RcParams &p, const RcLaunchInfo &li) { return {p.noise_on != 0, li.scan_guarded != 0, li.car_split > 1}; }
+// The builds without overlap and without the bound have `split` = 1 and `part` = 0 compiled in (scan_one_wave_per_car,
+// racecar_scan.h): a launch that hands such a build another split would scan 1 / split of the cars 'split' times over, silently.
+// Every scan launcher asks this first.
+static bool scan_split_fits(bool overlap, bool guard, int split) { return split >= 1 && (overlap || guard || split == 1); }
 template <int A>
 ScanKernel scan_kernel(const ScanChoice &c) {
     if (c.guard) return rc_raycast_car_kernel<A, false, true>;
@@ -1406,6 +1423,7 @@ hipError_t rck_launch_dynamics_group(const RcGroup &g, int cars_per_env, int rep
 
 hipError_t rck_launch_raycast_group(const RcGroup &g, int cars_per_env, int split, hipStream_t s, bool noise) {
     const int waves = ((g.wave_start[g.n] + 7) / 8) * 8;     // one wave per workgroup, as the single-handle scan; whole turns of the 8 XCDs
+    if (!scan_split_fits(split > 1, false, split)) return hipErrorInvalidValue;
     with_cars(cars_per_env, [&](auto a) {
         with_flag(split > 1, [&](auto o) {
             constexpr int A = decltype(a)::value;
@@ -1439,6 +1457,8 @@ hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, const R
         rck_take_launch_events(&a, &b);
         return (hipError_t)l.launch_raycast(&p, &li, lab_tables, s, a, b);
     }
+    const ScanChoice choice = scan_choice(p, li);
+    if (!scan_split_fits(choice.overlap, choice.guard, li.car_split)) return hipErrorInvalidValue;
     const int threads = li.car_threads, per = threads / 64;                     // waves per workgroup
     const long long waves = (long long)p.n_cars * li.car_split;
     with_cars(p.cars_per_env, [&](auto a) {
@@ -1475,6 +1495,7 @@ hipError_t rck_launch_ts_list(const RcParams &p, hipStream_t s) {
 hipError_t rck_launch_ts_raycast(const RcParams &p, const RcLaunchInfo &li, hipStream_t s) {
     const int split = li.car_split;
     const long long waves = (((long long)p.n_cars * split + 7) / 8) * 8;      // one wave per workgroup; whole turns of the 8 XCDs
+    if (!scan_split_fits(split > 1, false, split)) return hipErrorInvalidValue;
     with_cars(p.cars_per_env, [&](auto a) {
         with_flag(split > 1, [&](auto o) {
             constexpr int A = decltype(a)::value;

@@ -504,9 +504,38 @@ __device__ __forceinline__ float lidar_noise(const RcParams &p, uint32_t key, ui
 
 // NOISE: range noise and dropout (lidar_noise) after the inter-car minimum - rc_raycast_*_noise_kernel; a block of a group
 // launch whose handle has the noise off (noise_on = 0) skips it.
+// The instantiations that run with ONE wave per car only: the launchers pick the plain build (no overlap, no bound) exactly when
+// car_split == 1 (scan_choice, with_flag(split > 1, ...)), so there `split` and `part` are the constants 1 and 0 - no division
+// in the kernel's prologue, literal round steps.  The bounded and the instrumented build run with any split.
+template <bool STAMPS, bool OVERLAP, bool GUARD>
+constexpr bool scan_one_wave_per_car() { return !STAMPS && !OVERLAP && !GUARD; }
+
+// What a scan wave reads of its arguments up to its round loop, asked for at the kernel's entry: an operand of an assembly
+// statement has to be in its register there, so the scalar loads go out in ONE batch in front of it and are waited for once.
+// Left to itself the compiler sinks each field's load to the block that first uses it: three batches in front of the first-trip
+// line and more behind it, each a round trip that nothing hides (a wave's start-up is serial latency).  What is left of the
+// chain: arguments, order[slot], scan_pose[car], line.
+// The operand list is what scan_car and the kernels read in front of the round loop: a field added there and not here comes back
+// as a late scalar load with a wait of its own.  After a change to that prologue, list the kernel's loads and waits again
+// (tools/step_entry_isa.py; profiles/step_entry_isa.txt is the record).
+// (Not a volatile statement: behind one the compiler takes memory for written and turns the scalar loads of order[] and
+// scan_pose[] into vector loads.  So it has a result instead, the constant 0 in a scalar register, which the caller adds to its
+// wave index: that keeps the statement alive and in front of the first use of the index.)
+__device__ __forceinline__ unsigned scan_args_at_entry(const RcParams &p, int split) {
+    const RcTrackDev &t = p.trk;
+    unsigned zero;
+    asm("s_mov_b32 %0, 0" : "=s"(zero) : "s"(split), "s"(p.n_cars), "s"(blockDim.x), "s"(p.st.order), "s"(p.st.scan_pose), "s"(t.beams), "s"(t.first_rect),
+        "s"(t.quad_rect), "s"(t.cell_pitch), "s"(t.quad_plane_bytes), "s"(t.w), "s"(t.h), "s"(t.org_x), "s"(t.org_y), "s"(t.inv_res), "s"(t.res), "s"(t.band_mh),
+        "s"(t.band2), "s"(t.tmax), "s"(p.out.lidar), "s"(p.out.lidar_u16), "s"(p.lidar_transform));
+    return zero;
+}
+
 template <int A, bool STAMPS = false, bool OVERLAP = false, bool GUARD = true, bool NOISE = false>
-__device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, const unsigned part, const int split,
+__device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, const unsigned part_arg, const int split_arg,
                                          const unsigned lane, const uint32_t lds_row, unsigned long long *stamps = nullptr) {
+    constexpr bool kOne = scan_one_wave_per_car<STAMPS, OVERLAP, GUARD>();
+    const unsigned part = kOne ? 0u : part_arg;
+    const int split = kOne ? 1 : split_arg;
     const RcTrackDev &t = p.trk;
     uint32_t noise_key = 0u;
     if (NOISE && p.noise_on) {       // the counters as they stand when the scan runs (after the step, after an auto-reset)
@@ -602,7 +631,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
     const uint32_t frame_base = pin_vgpr(lds_frame);
     constexpr int kRounds = (RC_N_BEAMS + 63) / 64;
     // (per-round steps live in vector registers: a full-rate add that reads a scalar register issues at half rate)
-    const unsigned bstep = pin_vgpr(512u * (unsigned)split), ostep = pin_vgpr(256u * (unsigned)split);
+    const unsigned bstep = kOne ? 512u : pin_vgpr(512u * (unsigned)split), ostep = kOne ? 256u : pin_vgpr(256u * (unsigned)split);
     // LDS address of this lane's slot in the wave's staged output row (lds_row = LDS address of the row: the kernel's
     // dynamic LDS is its only LDS object and starts at 0, checked by rck_set_lds_limits) and the row's end
     typedef __attribute__((address_space(3))) float *lds_f32_ptr;
