@@ -439,6 +439,52 @@ typedef struct rc_policy_imagine_args {
  * asked for without a loaded head.  Kernels: rc_policy_imagine_kernel, rc_policy_imagine_sampled_kernel, timed under RC_K_POLICY. */
 int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *args);
 
+/* Recorded sequences: the posterior chain over N recorded windows of T scans and actions (DESIGN.md §2 item 17;
+ * tests/policy_observe_spec.c is the CPU restatement, the device equals it bit for bit) - dreamer/models.py:325-336 RSSM.observe,
+ * the operation the reference runs on every replay batch: `post, prior = observe(embed, action)`, kl_divergence(post, prior) and the
+ * reward likelihood of dreamer/models.py:84-110 `_train`, and the "observe 5, imagine the rest" of models.py:243-277
+ * `_image_summaries` and dreamer/evaluations/produce_reconstruction.py:36-57.  A row is one window, not a car of the env.
+ * For t = 0 .. length - 1 from the start state: the prior step img_step under a_t = clamp(actions[row, t], -1, 1) - the action
+ * recorded WITH scan t, the one that led to it, as the reference's episodes store it (a window's first row after a reset carries
+ * action 0) -; for t < context the posterior step obs_step on scan[row, t] (metres; clip to [0, 15] / 15 - 0.5 as rc_policy_act).
+ * stoch' comes from the posterior for t < context and from the prior after it: context = length is RSSM.observe, context = K <
+ * length is observe(..[:K]) followed by RSSM.imagine(action[K:], last post) in one call.
+ *   RC_POLICY_OBSERVE_MEAN     stoch' = the mean: deterministic, what rc_policy_act's default mode computes step by step.
+ *   RC_POLICY_OBSERVE_SAMPLE   stoch' ~ Normal(mean, std), Philox4x32-10 keyed by `seed` and counted by (row_offset + row, t, index):
+ *                              not by N, the workgroup or the call history - two shards with their row_offset give the whole batch.
+ * Outputs at [row, t], each optional: features = [stoch', deter'], prior_mean / prior_std, reward = the reward head on the feature;
+ * for t < context also post_mean / post_std and kl = KL(post || prior) summed over the 30 dimensions (entries at t >= context are
+ * not written).  std = softplus(raw) + 0.1.  state_in: [rows, 232] = stoch | deter | (2 columns that are not read), NULL =
+ * RSSM.initial's zeros; state_out: the last stoch' | deter' | a_{T-1}, in rc_policy_state's layout.  A pure function of its inputs:
+ * the agent's state, RC_F_ACTION_IN, the arena and every counter stay as they are (unless the caller passes rc_policy_state's
+ * memory as state_out, after which rc_policy_act / rc_policy_imagine go on from there). */
+#define RC_POLICY_OBSERVE_MEAN 0
+#define RC_POLICY_OBSERVE_SAMPLE 1
+#define RC_POLICY_OBSERVE_MAX_LENGTH 64
+typedef struct rc_policy_observe_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_observe_args) */
+    int32_t length;                /* T in [1, RC_POLICY_OBSERVE_MAX_LENGTH]; the reference's batch_length is 50 */
+    int32_t context;               /* in [1, length]: the steps that see their scan */
+    int32_t mode;                  /* RC_POLICY_OBSERVE_* */
+    int64_t rows;                  /* N >= 1 */
+    uint64_t seed;
+    uint64_t row_offset;           /* row id of row 0 (mode SAMPLE) */
+    const float *scan;             /* device float32 [rows, T, 1080], metres */
+    const float *actions;          /* device float32 [rows, T, 2], raw in [-1, 1] (clamped) */
+    const float *state_in;         /* device float32 [rows, 232], or NULL */
+    float *features;               /* device float32 [rows, T, 230], or NULL */
+    float *post_mean, *post_std;   /* device float32 [rows, T, 30], or NULL; written for t < context */
+    float *prior_mean, *prior_std; /* device float32 [rows, T, 30], or NULL */
+    float *kl;                     /* device float32 [rows, T], or NULL; written for t < context */
+    float *reward;                 /* device float32 [rows, T], or NULL */
+    float *state_out;              /* device float32 [rows, 232], or NULL */
+} rc_policy_observe_args;
+/* rc_policy_observe: one launch for all rows and steps, on the handle's stream.  RC_ERR_INVALID: wrong struct_size, no policy
+ * loaded, the policy loaded without img2 / img3, rows outside [1, 2^31), length outside [1, 64], context outside [1, length],
+ * unknown mode, scan or actions NULL, no output asked for, reward asked for without a loaded head.  Kernels:
+ * rc_policy_observe_kernel, rc_policy_observe_sampled_kernel, timed under RC_K_POLICY. */
+int rc_policy_observe(rc_env *env, const rc_policy_observe_args *args);
+
 /* The observation decoder: what the world model believes the car sees (tests/policy_decode_spec.c is the CPU
  * restatement, the device equals it bit for bit).  The reference's LidarOccupancyDecoder (dreamer/models.py:444-465) on a feature
  * [stoch 30 | deter 200]: dense 230 -> 64, then Conv2DTranspose(32, 5), (16, 5), (8, 6), (1, 6), all stride 2, 'valid', ReLU -

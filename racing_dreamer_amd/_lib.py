@@ -105,6 +105,22 @@ class RcPolicyImagineArgs(C.Structure):
                 ("actions_in", C.c_void_p), ("reward", C.c_void_p), ("actions", C.c_void_p), ("features", C.c_void_p), ("reward_start", C.c_void_p)]
 
 
+OBSERVE_MODES = {"mean": 0, "sample": 1}                       # RC_POLICY_OBSERVE_*
+OBSERVE_MAX_LENGTH = 64
+# policy_observe's output names -> (rc_policy_observe_args field, trailing shape after [rows, T]; None: [rows, 232])
+OBSERVE_OUTPUTS = {"feature": ("features", (POLICY_FEATURE,)), "post_mean": ("post_mean", (30,)), "post_std": ("post_std", (30,)),
+                   "prior_mean": ("prior_mean", (30,)), "prior_std": ("prior_std", (30,)), "kl": ("kl", ()), "reward": ("reward", ()),
+                   "state": ("state_out", None)}
+
+
+class RcPolicyObserveArgs(C.Structure):
+    """rc_policy_observe_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("length", C.c_int32), ("context", C.c_int32), ("mode", C.c_int32), ("rows", C.c_int64),
+                ("seed", C.c_uint64), ("row_offset", C.c_uint64), ("scan", C.c_void_p), ("actions", C.c_void_p), ("state_in", C.c_void_p),
+                ("features", C.c_void_p), ("post_mean", C.c_void_p), ("post_std", C.c_void_p), ("prior_mean", C.c_void_p),
+                ("prior_std", C.c_void_p), ("kl", C.c_void_p), ("reward", C.c_void_p), ("state_out", C.c_void_p)]
+
+
 DECODER_KEYS = ("dec_h1_w", "dec_h1_b", "dec_h2_k", "dec_h2_b", "dec_h3_k", "dec_h3_b", "dec_h4_k", "dec_h4_b", "dec_h5_k", "dec_h5_b")
 DECODE_IMAGE = 64           # the decoded lidar_occupancy image is 64 x 64
 
@@ -211,6 +227,7 @@ SYMBOLS = {
     "rc_policy_get_sampling": (C.c_int, [C.c_void_p, _P(RcPolicySampling)]),
     "rc_policy_load_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
     "rc_policy_imagine": (C.c_int, [C.c_void_p, _P(RcPolicyImagineArgs)]),
+    "rc_policy_observe": (C.c_int, [C.c_void_p, _P(RcPolicyObserveArgs)]),
     "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
     "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),
     "rc_episode_log_enable": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),

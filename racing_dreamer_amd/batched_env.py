@@ -142,6 +142,49 @@ def _imagine_setup(env, horizon, mode, seed, actions, slots, features, start_rew
     return args, tensors, result
 
 
+def _observe_setup(env, lidar, action, context, mode, seed, state, row_offset, outputs, out):
+    """policy_observe's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (the filled rc_policy_observe_args, the
+    tensors it points into - keep them until the call has been made -, the dict to return)."""
+    if mode not in L.OBSERVE_MODES:
+        raise ValueError(f"observe mode must be one of {sorted(L.OBSERVE_MODES)}, got {mode!r}")
+    if lidar.dim() < 2 or lidar.shape[-1] != 1080 or action.shape[-1] != 2 or tuple(action.shape[:-1]) != tuple(lidar.shape[:-1]):
+        raise ValueError(f"lidar must be [..., T, 1080] and action [..., T, 2], got {tuple(lidar.shape)} and {tuple(action.shape)}")
+    lead, t_len = tuple(lidar.shape[:-2]), int(lidar.shape[-2])
+    rows = 1
+    for d in lead:
+        rows *= int(d)
+    if not 1 <= t_len <= L.OBSERVE_MAX_LENGTH:
+        raise ValueError(f"the sequence length must be in [1, {L.OBSERVE_MAX_LENGTH}], got {t_len}")
+    context = t_len if context is None else int(context)
+    if not 1 <= context <= t_len:
+        raise ValueError(f"context must be in [1, {t_len}], got {context}")
+    outputs = tuple(outputs)
+    unknown = [k for k in outputs if k not in L.OBSERVE_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}: choose from {sorted(L.OBSERVE_OUTPUTS)}")
+    keep = [lidar.to(env.device, torch.float32).reshape(rows, t_len, 1080).contiguous(),
+            action.to(env.device, torch.float32).reshape(rows, t_len, 2).contiguous()]
+    a = L.RcPolicyObserveArgs(C.sizeof(L.RcPolicyObserveArgs), t_len, context, L.OBSERVE_MODES[mode], rows, int(seed) & (2 ** 64 - 1),
+                              int(row_offset) & (2 ** 64 - 1), keep[0].data_ptr(), keep[1].data_ptr())
+    if state is not None:
+        if tuple(state.shape) != lead + (L.POLICY_FEATURE + 2,):
+            raise ValueError(f"state must be {lead + (L.POLICY_FEATURE + 2,)} = stoch | deter | (2 unused), got {tuple(state.shape)}")
+        keep.append(state.to(env.device, torch.float32).reshape(rows, L.POLICY_FEATURE + 2).contiguous())
+        a.state_in = keep[-1].data_ptr()
+    result = {}
+    for name in outputs:
+        field, tail = L.OBSERVE_OUTPUTS[name]
+        shape = lead + ((L.POLICY_FEATURE + 2,) if tail is None else (t_len,) + tail)
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=torch.float32, device=env.device)
+        elif t.shape != shape or t.dtype != torch.float32 or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of shape {shape} on {env.device}")
+        result[name] = t
+        setattr(a, field, t.data_ptr())
+    return a, keep, result
+
+
 def _decode_setup(env, features, slots, logits, image, mismatch, out):
     """policy_decode's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (features as [rows, 230] or None, the
     slot mask, the tensors by rc_policy_decode_args field with their leading dimensions flattened, the dict to return).  What
@@ -709,6 +752,34 @@ class BatchedRaceEnv:
         """Whether the loaded checkpoint brought a reward head (`reward_*` arrays): `policy_imagine` then returns rewards."""
         return bool(getattr(self, "_policy_has_head", False))
 
+    def policy_observe(self, lidar: torch.Tensor, action: torch.Tensor, context: Optional[int] = None, mode: str = "mean", seed: int = 0,
+                       state: Optional[torch.Tensor] = None, row_offset: int = 0, outputs=("feature",),
+                       out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """The world model over RECORDED sequences (`rc_policy_observe`, one launch): the reference's `RSSM.observe` on `lidar`
+        float32 [..., T, 1080] in metres and `action` float32 [..., T, 2], as `TrajectoryRing.sample(...)["lidar"]` / `["action"]`
+        give them; T <= 64, the leading dimensions are kept in the results.  `action[..., t, :]` is the action that led to scan t
+        (a window's first row after a reset carries action 0) and must be RAW, in [-1, 1] (values outside are clamped): that is
+        what a ring records when the env was built with `remap_actions=True`.  An env built with it off records the remapped
+        commands - convert them back before calling; nothing here converts silently.  Steps t < `context` (default: all) see
+        their scan - the posterior -, the steps after it run the prior under the recorded actions: `context=5` is the
+        reference's "observe 5, imagine the rest" summary.  mode "mean": stoch' = the mean, what `policy_act` computes step by
+        step; "sample": stoch' ~ Normal(mean, std), a function of (seed, row_offset + row, t) only, so two shards of a batch
+        called with their `row_offset` reproduce the whole.  `state` [..., 232] = stoch | deter | (2 unused) is the start
+        state; None is `RSSM.initial`'s zeros.  `outputs` names what to compute, each a device float32 tensor: `feature`
+        [..., T, 230] = stoch | deter, `post_mean`, `post_std`, `prior_mean`, `prior_std` [..., T, 30], `kl` [..., T] =
+        KL(post || prior), `reward` [..., T] (the reward head on `feature`; needs a checkpoint with one), `state` [..., 232] =
+        the last stoch | deter | action, in `policy_state`'s layout.  `post_*` and `kl` are written for t < context only: the
+        entries after it are uninitialised - or what `out` (tensors to write into, by the same names) held.  Nothing else
+        changes: not the agent's state, not `action_in`."""
+        a, keep, result = _observe_setup(self, lidar, action, context, mode, seed, state, row_offset, outputs, out)
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_observe(self._h, C.byref(a)))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        del keep
+        return result
+
     def _imagine(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
         """rc_policy_imagine on this handle, reading and writing rows [lo, hi) of the tensors (one row per car)."""
         a = L.RcPolicyImagineArgs(C.sizeof(L.RcPolicyImagineArgs), args["horizon"], args["mode"], args["mask"], args["seed"])
@@ -1182,6 +1253,16 @@ class MixedTrackEnv:
         args, tensors, result = _imagine_setup(self, horizon, mode, seed, actions, slots, features, start_reward, out)
         k = self.cars_per_env
         self._fork_join(lambda p, blk: p._imagine(args, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def policy_observe(self, lidar: torch.Tensor, action: torch.Tensor, context: Optional[int] = None, mode: str = "mean", seed: int = 0,
+                       state: Optional[torch.Tensor] = None, row_offset: int = 0, outputs=("feature",),
+                       out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_observe: recorded rows are not cars of a block (every block holds the same weights), so the
+        call goes through the first block."""
+        a, keep, result = _observe_setup(self, lidar, action, context, mode, seed, state, row_offset, outputs, out)
+        self._ordered(lambda: self.parts[0]._lib.rc_policy_observe(self.parts[0]._h, C.byref(a)))
+        del keep
         return result
 
     @property

@@ -81,6 +81,23 @@ struct RcImagineCall {
     float *reward, *actions, *features, *reward_start;      // [n_cars][H], [n_cars][H][2], [n_cars][H][230], [n_cars]; any may be null
 };
 
+// Recorded sequences (racecar_observe.hip): rows are windows [T] of scans and actions, not cars of the env
+struct RcObserveCall {
+    RcPolicyDev w;
+    RcPolicySampleDev ws;                    // (obs2's pair image: both modes)
+    RcImagineDev wi;
+    int64_t rows;
+    uint64_t row_offset;                     // row id of row 0: the draws are keyed by (row id, t)
+    int32_t length, context, sample;
+    uint32_t seed_lo, seed_hi;
+    const float *scan;                       // [rows][T][1080] metres
+    const float *actions;                    // [rows][T][2] raw
+    const float *state_in;                   // [rows][RC_POLICY_STATE] or null: zeros
+    float *features, *post_mean, *post_std, *prior_mean, *prior_std;      // [rows][T][230] / [rows][T][30]; any may be null
+    float *kl, *reward;                      // [rows][T]
+    float *state_out;                        // [rows][RC_POLICY_STATE]
+};
+
 // The observation decoder (racecar_decode.hip): the LidarOccupancyDecoder's arrays, each repacked for the
 // order in which its kernel reads it (u, v kernel row and column, c input channel, o output channel; a 6 x 6 kernel's tap is
 // (ty, tx) with u = py + 2 ty, v = px + 2 tx for the output's parity class (py, px))
@@ -110,5 +127,7 @@ hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS 
 hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);      // c.mode: which kernel
 hipError_t rck_imagine_prepare();
 hipError_t rck_launch_imagine(const RcImagineCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
+hipError_t rck_observe_prepare();
+hipError_t rck_launch_observe(const RcObserveCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
 hipError_t rck_decode_prepare();
 hipError_t rck_launch_decode(const RcDecodeCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);

@@ -540,6 +540,7 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(rck_policy_prepare());
     HIP_TRY(rck_imagine_prepare());
+    HIP_TRY(rck_observe_prepare());
     HIP_TRY(rck_decode_prepare());
     rc = pol_drop_heads(env);
     if (rc) return rc;
@@ -669,6 +670,39 @@ int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *a) {
     c.actions_in = a->actions_in;
     c.reward = a->reward; c.actions = a->actions; c.features = a->features; c.reward_start = a->reward_start;
     return pol_launch(env, rck_launch_imagine, c);
+}
+
+int rc_policy_observe(rc_env *env, const rc_policy_observe_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_observe_args))
+        return fail(RC_ERR_INVALID, "rc_policy_observe_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_observe_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_observe: no policy loaded (rc_policy_load)");
+    if (!env->pol_i.img3_w) return fail(RC_ERR_INVALID, "rc_policy_observe: the policy was loaded without the prior's layers img2 / img3");
+    if (a->rows < 1 || a->rows > (int64_t)INT32_MAX) return fail(RC_ERR_INVALID, "rc_policy_observe: rows %lld is outside [1, 2^31)", (long long)a->rows);
+    if (a->length < 1 || a->length > RC_POLICY_OBSERVE_MAX_LENGTH)
+        return fail(RC_ERR_INVALID, "rc_policy_observe: length %d is outside [1, %d]", a->length, RC_POLICY_OBSERVE_MAX_LENGTH);
+    if (a->context < 1 || a->context > a->length)
+        return fail(RC_ERR_INVALID, "rc_policy_observe: context %d is outside [1, length = %d]", a->context, a->length);
+    if (a->mode != RC_POLICY_OBSERVE_MEAN && a->mode != RC_POLICY_OBSERVE_SAMPLE) return fail(RC_ERR_INVALID, "rc_policy_observe: unknown mode %d", a->mode);
+    if (!a->scan || !a->actions) return fail(RC_ERR_INVALID, "rc_policy_observe: %s is NULL", !a->scan ? "scan" : "actions");
+    if (!a->features && !a->post_mean && !a->post_std && !a->prior_mean && !a->prior_std && !a->kl && !a->reward && !a->state_out)
+        return fail(RC_ERR_INVALID, "rc_policy_observe: no output asked for");
+    if (a->reward && !env->pol_i.rout_w)
+        return fail(RC_ERR_INVALID, "rc_policy_observe: a reward is asked for and no reward head is loaded (rc_policy_load_heads)");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    RcObserveCall c{};
+    c.w = env->pol;
+    c.ws = env->pol_s;
+    c.wi = env->pol_i;
+    c.rows = a->rows;
+    c.row_offset = a->row_offset;
+    c.length = a->length; c.context = a->context;
+    c.sample = a->mode == RC_POLICY_OBSERVE_SAMPLE;
+    c.seed_lo = seed_lo(a->seed); c.seed_hi = seed_hi(a->seed);
+    c.scan = a->scan; c.actions = a->actions; c.state_in = a->state_in;
+    c.features = a->features; c.post_mean = a->post_mean; c.post_std = a->post_std; c.prior_mean = a->prior_mean; c.prior_std = a->prior_std;
+    c.kl = a->kl; c.reward = a->reward; c.state_out = a->state_out;
+    return pol_launch(env, rck_launch_observe, c);
 }
 
 int rc_policy_load_decoder(rc_env *env, const rc_policy_decoder *d) {

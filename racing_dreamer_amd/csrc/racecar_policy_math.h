@@ -212,3 +212,21 @@ __device__ __forceinline__ void pm_imagine_normal_block(uint32_t env, uint32_t e
                                                         uint32_t block, uint32_t seed_lo, uint32_t seed_hi, float (&n)[4]) {
     pm_normal_word(env, episode, agent_step, block | (slot << 8) | (t << 12) | (PM_IMAGINE_TAG << 24), seed_lo, seed_hi, n);
 }
+
+// ---- recorded sequences: tests/policy_observe_spec.c restates what follows
+#define PM_OBSERVE_TAG 6u                  // Philox counter word 3, bits 24-31
+
+// the four normals of block `block` (0-7: the 30 normals of stoch', 2 unused) of step t of the row with the 64-bit id (row_lo, row_hi)
+__device__ __forceinline__ void pm_observe_normal_block(uint32_t row_lo, uint32_t row_hi, uint32_t t, uint32_t block, uint32_t seed_lo,
+                                                        uint32_t seed_hi, float (&n)[4]) {
+    pm_normal_word(row_lo, row_hi, t, block | (PM_OBSERVE_TAG << 24), seed_lo, seed_hi, n);
+}
+
+// one dimension of KL(post || prior) of two diagonal normals (dreamer/models.py:84-110 `_train`, tfd.kl_divergence):
+// log sq - log sp + (sp^2 + (mp - mq)^2) / (2 sq^2) - 1/2, p = post, q = prior
+__device__ __forceinline__ float pm_kl_term(float mp, float sp, float mq, float sq) {
+    const float d = mp - mq;
+    const float num = fmaf(d, d, sp * sp);
+    const float den = 2.0f * (sq * sq);
+    return ((pm_log(sq) - pm_log(sp)) + num / den) - 0.5f;
+}

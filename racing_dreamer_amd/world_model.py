@@ -1,0 +1,36 @@
+"""What the reference does with a replay batch before the gradient, on device-resident batches (`BatchedRaceEnv.policy_observe`,
+DESIGN.md §2 item 17): the open-loop summary of dreamer/models.py:243-277 `_image_summaries` (and
+dreamer/evaluations/produce_reconstruction.py:36-57) and the two scalars dreamer/models.py:84-110 `_train` logs from the world
+model.  A batch is a dict of device tensors as `TrajectoryRing.sample` returns it: `lidar` [B, T, 1080] in metres, `action`
+[B, T, 2] RAW in [-1, 1] (what a ring records when the env was built with `remap_actions=True`), and where needed
+`lidar_occupancy` [B, T, 64, 64(, 1)] and `reward` [B, T]."""
+from __future__ import annotations
+
+import math
+from typing import Dict
+
+import torch
+
+
+def open_loop_summary(env, batch: Dict[str, torch.Tensor], context: int = 5) -> Dict[str, torch.Tensor]:
+    """The reference's "observe `context` steps, imagine the rest" for a `lidar_occupancy` checkpoint: `policy_observe` with
+    `context`, then `policy_decode` on the features [B, T, 230].  Returns float32 [B, T, 64, 64] tensors `truth` (the recorded
+    occupancy), `model` (the decoder's image: the reconstruction for t < context, the open-loop prediction after it) and
+    `error` = (model - truth + 1) / 2 in {0, 1/2, 1}, and `mismatch` int64 [B, T]: the pixels in which the two differ."""
+    feat = env.policy_observe(batch["lidar"], batch["action"], context=context)["feature"]
+    model = env.policy_decode(features=feat)["image"].to(torch.float32)
+    truth = batch["lidar_occupancy"].to(model.device).reshape(model.shape).to(torch.float32)
+    return dict(truth=truth, model=model, error=(model - truth + 1) / 2, mismatch=(model != truth).flatten(-2).sum(-1))
+
+
+def model_terms(env, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """`div` = mean over the batch of KL(post || prior) and, when the checkpoint has a reward head, `reward_loglik` = the mean of
+    Normal(predicted reward, 1).log_prob(batch["reward"]): the two world-model scalars of `_train`, computed in torch from
+    `policy_observe`'s outputs (context = T: `RSSM.observe`)."""
+    head = env.policy_has_reward_head
+    out = env.policy_observe(batch["lidar"], batch["action"], outputs=("kl", "reward") if head else ("kl",))
+    terms = {"div": out["kl"].mean()}
+    if head:
+        r = batch["reward"].to(out["reward"].device, torch.float32).reshape(out["reward"].shape)
+        terms["reward_loglik"] = (-0.5 * (r - out["reward"]) ** 2 - 0.5 * math.log(2.0 * math.pi)).mean()
+    return terms

@@ -21,6 +21,13 @@ lidar_occupancy - `image` only, `logits` only, `image` + `mismatch` - beside tor
 four layers plus the dense layer at the same row count, with the condition `logits` time <= torch's reported as met or missed, and
 the fp32 issue floor of the decoder's 1 423 872 fma per image.
 
+    python tools/policy_cost.py --observe [--out profiles/policy_observe_cost.json]
+
+`--observe`: recorded sequences (rc_policy_observe) at 65 536 rows x T = 15, context = T - `mean` with the features only, with the
+reward head on top, `sample`, and `mean` with every output - beside `policy_act` (`mean`) of the same run on the same number of cars,
+with the condition: time per observed step <= 1.0 x that call (an observed step performs 0.52 of its multiply-adds), and beside the
+same 15 steps (posterior, prior and KL) in plain fp32 torch, each reported as met or missed.
+
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
 windows; the torch baseline is timed with stream events around a window of calls (its dozen launches per call included - that is
 what it costs).  The baseline is a RATE baseline: torch.addmm sums in another order than the spec."""
@@ -391,6 +398,105 @@ def measure_decode(n, args):
     return res
 
 
+MACS_OBSERVED_STEP = 32 * 200 + 2 * 200 * 600 + 200 * 200 + 200 * 60 + 1280 * 200 + 200 * 60       # 566 400: prior and posterior, both halves
+
+
+class TorchObserve(TorchAgent):
+    """T observed steps (mode mean: posterior and prior statistics, the KL, the features) in plain fp32 torch."""
+
+    def observe(self, scan, action):
+        import torch
+        import torch.nn.functional as F
+        w = self.w
+        n, T = scan.shape[:2]
+        stoch, deter = scan.new_zeros((n, 30)), scan.new_zeros((n, 200))
+        feats, kls = [], []
+        for t in range(T):
+            embed = torch.clamp(scan[:, t], 0.0, 15.0) / 15.0 - 0.5
+            x = F.elu(torch.addmm(w["img1_b"], torch.cat([stoch, torch.clamp(action[:, t], -1.0, 1.0)], 1), w["img1_w"]))
+            mx, mh = torch.addmm(w["gru_bias"][0], x, w["gru_kernel"]), torch.addmm(w["gru_bias"][1], deter, w["gru_recurrent"])
+            z, r = torch.sigmoid(mx[:, :200] + mh[:, :200]), torch.sigmoid(mx[:, 200:400] + mh[:, 200:400])
+            deter = z * deter + (1.0 - z) * torch.tanh(mx[:, 400:] + r * mh[:, 400:])
+            x = torch.addmm(w["img3_b"], F.elu(torch.addmm(w["img2_b"], deter, w["img2_w"])), w["img3_w"])
+            qm, qs = x[:, :30], F.softplus(x[:, 30:]) + 0.1
+            x = torch.addmm(w["obs2_b"], F.elu(torch.addmm(w["obs1_b"], torch.cat([deter, embed], 1), w["obs1_w"])), w["obs2_w"])
+            stoch, sp = x[:, :30], F.softplus(x[:, 30:]) + 0.1
+            kls.append((torch.log(qs) - torch.log(sp) + (sp ** 2 + (stoch - qm) ** 2) / (2.0 * qs ** 2) - 0.5).sum(1))
+            feats.append(torch.cat([stoch, deter], 1))
+        return torch.stack(feats, 1), torch.stack(kls, 1)
+
+
+def measure_observe(n, args):
+    """Per-call device time (RC_K_POLICY) of policy_act (`mean`) on n cars and of rc_policy_observe on n rows x T = args.horizon."""
+    import torch
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    env = BatchedRaceEnv(args.track, n, 1, auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    T = args.horizon
+    res = {"rows": n, "length": T, "context": T}
+
+    def timed(call):
+        for k in range(3):
+            call()
+        windows = []
+        for r in range(args.rounds):
+            env.reset_kernel_times()
+            env.set_profiling(True, kernels=[L.K_POLICY])
+            for k in range(args.calls):
+                call()
+            env.sync()
+            env.set_profiling(False)
+            windows.append(env.kernel_times()["rc_policy_kernel"]["avg_ms"])
+        return statistics.median(windows), [round(v, 4) for v in windows]
+
+    with torch.cuda.stream(env.stream):
+        out = env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            out = env.step(None, repeat=4)
+        scans, acts = [], []
+        for k in range(T):                                  # the recording: T agent steps of the same run
+            fresh = out["fresh"].view(n, 1) != 0
+            scans.append(out["lidar"].view(n, 1080).clone())
+            acts.append(torch.where(fresh, torch.zeros_like(env.policy_state[:, 230:]), env.policy_state[:, 230:]))
+            env.policy_act()
+            out = env.step(None, repeat=4)
+        scan, action = torch.stack(scans, 1).contiguous(), torch.stack(acts, 1).contiguous()
+        del scans, acts
+        env.sync()
+        act_ms, act_windows = timed(env.policy_act)
+        res["policy_act_mean_ms"], res["policy_act_mean_windows_ms"] = round(act_ms, 4), act_windows
+        every = ("feature", "post_mean", "post_std", "prior_mean", "prior_std", "kl", "state")
+        bufs = {k: torch.empty((n, 232) if k == "state" else (n, T) + L.OBSERVE_OUTPUTS[k][1], device=env.device) for k in every + ("reward",)}
+        for variant, mode, names in (("mean_features", "mean", ("feature",)), ("mean_features_reward", "mean", ("feature", "reward")),
+                                     ("sample_features", "sample", ("feature",)), ("mean_all", "mean", every)):
+            ms, windows = timed(lambda: env.policy_observe(scan, action, mode=mode, seed=1, outputs=names, out=bufs))
+            res[variant] = {"ms_per_call": round(ms, 4), "windows_ms": windows, "ms_per_observed_step": round(ms / T, 4),
+                            "step_over_policy_act": round(ms / T / act_ms, 4)}
+        res["condition_met"] = bool(res["mean_features"]["ms_per_observed_step"] <= act_ms)
+        # ---- the torch baseline of the same layers (mode mean: features, prior and posterior statistics, KL)
+        agent = TorchObserve(weights, env.device)
+        for k in range(2):
+            agent.observe(scan, action)
+        windows = []
+        for r in range(args.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k in range(max(1, args.calls // 4)):
+                agent.observe(scan, action)
+            e1.record()
+            e1.synchronize()
+            windows.append(e0.elapsed_time(e1) / max(1, args.calls // 4))
+        res["torch_fp32_ms_per_call"] = round(statistics.median(windows), 4)
+        res["torch_fp32_windows_ms"] = [round(v, 4) for v in windows]
+        res["hip_over_torch"] = round(res["mean_all"]["ms_per_call"] / res["torch_fp32_ms_per_call"], 3)
+        res["no_slower_than_torch"] = bool(res["mean_all"]["ms_per_call"] <= res["torch_fp32_ms_per_call"])
+    env.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--envs", type=int, nargs="+", default=[4096, 65536])
@@ -404,9 +510,25 @@ def main():
     ap.add_argument("--modes", action="store_true", help="measure the sampled modes (profiles/policy_sample_cost.json)")
     ap.add_argument("--imagine", action="store_true", help="measure imagination (profiles/policy_imagine_cost.json)")
     ap.add_argument("--decode", action="store_true", help="measure the observation decoder (profiles/policy_decode_cost.json)")
+    ap.add_argument("--observe", action="store_true", help="measure recorded sequences (profiles/policy_observe_cost.json)")
     ap.add_argument("--horizon", type=int, default=15)
     args = ap.parse_args()
     import torch
+    if args.observe:
+        sizes = args.envs if args.envs != [4096, 65536] else [65536]
+        out = {"tool": "tools/policy_cost.py --observe", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
+               "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle,
+               "macs_per_observed_step": MACS_OBSERVED_STEP, "macs_per_agent_step": MACS_PER_CAR, "macs_ratio": round(MACS_OBSERVED_STEP / MACS_PER_CAR, 3),
+               "condition": "mean_features ms_per_observed_step <= 1.0 x policy_act_mean_ms of the same run on as many cars, at the largest size",
+               "second_line": "mean_all ms_per_call beside the same steps in plain fp32 torch (torch_fp32_ms_per_call)",
+               "sizes": [measure_observe(n, args) for n in sizes]}
+        out["condition_met"] = out["sizes"][-1]["condition_met"]
+        out["no_slower_than_torch"] = out["sizes"][-1]["no_slower_than_torch"]
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.decode:
         if args.checkpoint == "austria":                       # (the default checkpoint has no decoder)
             args.checkpoint, args.track = "treitlstrasse_occupancy", "treitlstrasse_v2"
