@@ -590,6 +590,46 @@ int rc_episode_log(rc_env *env, void **rows_dev, size_t *capacity_rows, void **c
 int rc_episode_log_clear(rc_env *env);
 int rc_episode_log_time(rc_env *env, double *total_ms, uint64_t *launches);
 
+/* ---- Look ahead in the simulator: what would really happen from here under these actions?
+ * rc_look_ahead carries, for every env e, `candidates` action sequences of `horizon` agent steps through the env's true
+ * dynamics, each from the env's live state as the last rc_step* / rc_reset / rc_set_pose left it (the cars, steps and
+ * agent_steps, the n_step_progress windows, the cars' vehicle parameters while randomization is on, the env's current track
+ * of a track set).  Every step applies exactly what rc_step(actions, repeat) applies on a handle with auto_reset = 0 - the
+ * action convention, `repeat` sub-steps, wall and car-car collision, progress / lap / checkpoint, the slot's reward, done, the
+ * break on the finishing sub-step, time_limit_steps - with the operations of the step's own kernel, bit for bit.  A finished
+ * env is frozen, whether it finished before the call or inside the horizon: every later step has reward +0.0f and unchanged
+ * flags; the look-ahead never resets, whatever the handle's auto_reset.  No random draw is involved.
+ *   The call is pure: it reads the simulator's state and writes nothing but the arrays given here - no state array, no arena
+ * section (RC_F_ACTION_IN included), not the live n_step_progress windows (each rollout carries a private copy), not the
+ * episode log, its counters or the agent's latent.
+ *   actions: float [E, K, H, A, 2] in device memory, C-contiguous (E = num_envs, K = candidates, H = horizon, A = cars_per_env),
+ * in rc_step's convention.  Outputs, device memory, each optional (NULL), at least one required:
+ *   reward       float   [E, K, H, A]     the step's reward
+ *   flags        uint8   [E, K, H, A]     RC_LA_DONE | RC_LA_TRUNCATED | RC_LA_WALL | RC_LA_OPPONENT | RC_LA_WRONG_WAY after step t
+ *   ret          float   [E, K, A]        binary32 sum of the H rewards in step order from +0.0f
+ *   length       int32   [E, K]           steps taken until the env finished, the finishing step counted; H if it did not; 0 if it was
+ *   final_state  float   [E, K, A, 8]     x, y, theta, v, delta, omega, (lap - 1) + progress, time
+ *   pose         float   [E, K, H, A, 3]  x, y, theta after step t
+ * One launch on the handle's stream (rc_look_ahead_kernel, one lane per (env, candidate)).  RC_ERR_NEEDS_RESET before the first
+ * reset.  RC_ERR_INVALID: wrong struct_size, candidates < 1, horizon outside [1, RC_LOOK_AHEAD_MAX_HORIZON], repeat < 1,
+ * E K beyond int32, actions NULL, no output asked for.  It has no RC_K_* timer: while rc_set_profiling is on,
+ * rc_look_ahead_time reports the summed time of its launches (and their number); rc_reset_kernel_times zeroes it. */
+#define RC_LOOK_AHEAD_MAX_HORIZON 64
+enum { RC_LA_DONE = 1, RC_LA_TRUNCATED = 2, RC_LA_WALL = 4, RC_LA_OPPONENT = 8, RC_LA_WRONG_WAY = 16 };   /* flags */
+typedef struct rc_look_ahead_args {
+    uint32_t struct_size;          /* = sizeof(rc_look_ahead_args) */
+    int32_t candidates, horizon, repeat;
+    const float *actions;
+    float *reward;
+    uint8_t *flags;
+    float *ret;
+    int32_t *length;
+    float *final_state;
+    float *pose;
+} rc_look_ahead_args;
+int rc_look_ahead(rc_env *env, const rc_look_ahead_args *args);
+int rc_look_ahead_time(rc_env *env, double *total_ms, uint64_t *launches);
+
 int rc_get(rc_env *env, int32_t field, void **dev_ptr, size_t *bytes);
 int rc_copy_out(rc_env *env, int32_t field, void *host_dst, size_t bytes);
 /* The trajectory record of the last step as one contiguous device slab (fields LIDAR..TIME,

@@ -105,6 +105,24 @@ class RcPolicyImagineArgs(C.Structure):
                 ("actions_in", C.c_void_p), ("reward", C.c_void_p), ("actions", C.c_void_p), ("features", C.c_void_p), ("reward_start", C.c_void_p)]
 
 
+LOOK_AHEAD_MAX_HORIZON = 64
+LA_DONE, LA_TRUNCATED, LA_WALL, LA_OPPONENT, LA_WRONG_WAY = 1, 2, 4, 8, 16      # rc_look_ahead's flags
+# look_ahead's output names -> (rc_look_ahead_args field, torch dtype name, shape as a function of (E, K, H, A))
+LOOK_AHEAD_OUTPUTS = {"reward": ("reward", "float32", lambda E, K, H, A: (E, K, H, A)),
+                      "flags": ("flags", "uint8", lambda E, K, H, A: (E, K, H, A)),
+                      "return": ("ret", "float32", lambda E, K, H, A: (E, K, A)),
+                      "length": ("length", "int32", lambda E, K, H, A: (E, K)),
+                      "final_state": ("final_state", "float32", lambda E, K, H, A: (E, K, A, 8)),
+                      "pose": ("pose", "float32", lambda E, K, H, A: (E, K, H, A, 3))}
+
+
+class RcLookAheadArgs(C.Structure):
+    """rc_look_ahead_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("candidates", C.c_int32), ("horizon", C.c_int32), ("repeat", C.c_int32),
+                ("actions", C.c_void_p), ("reward", C.c_void_p), ("flags", C.c_void_p), ("ret", C.c_void_p), ("length", C.c_void_p),
+                ("final_state", C.c_void_p), ("pose", C.c_void_p)]
+
+
 OBSERVE_MODES = {"mean": 0, "sample": 1}                       # RC_POLICY_OBSERVE_*
 OBSERVE_MAX_LENGTH = 64
 # policy_observe's output names -> (rc_policy_observe_args field, trailing shape after [rows, T]; None: [rows, 232])
@@ -235,6 +253,8 @@ SYMBOLS = {
     "rc_episode_log": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p), _P(C.c_size_t)]),
     "rc_episode_log_clear": (C.c_int, [C.c_void_p]),
     "rc_episode_log_time": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint64)]),
+    "rc_look_ahead": (C.c_int, [C.c_void_p, _P(RcLookAheadArgs)]),
+    "rc_look_ahead_time": (C.c_int, [C.c_void_p, _P(C.c_double), _P(C.c_uint64)]),
     "rc_fill_random_actions": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32]),
     "rc_step_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]),
     "rc_step_group": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]),

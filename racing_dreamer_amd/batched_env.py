@@ -142,6 +142,37 @@ def _imagine_setup(env, horizon, mode, seed, actions, slots, features, start_rew
     return args, tensors, result
 
 
+def _look_ahead_setup(env, actions, repeat, outputs, out):
+    """look_ahead's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
+    rc_look_ahead_args field - env-major, one row per env -, the dict to return)."""
+    E, A = env.num_envs, env.cars_per_env
+    a = actions.to(env.device, torch.float32)
+    if a.dim() == 4 and A == 1:
+        a = a.unsqueeze(3)
+    if a.dim() != 5 or a.shape[0] != E or a.shape[3] != A or a.shape[4] != 2:
+        raise ValueError(f"actions must be [num_envs={E}, candidates, horizon, cars_per_env={A}, 2]"
+                         f"{' or [num_envs, candidates, horizon, 2]' if A == 1 else ''}, got shape {tuple(actions.shape)}")
+    a = a.contiguous()
+    K, H = int(a.shape[1]), int(a.shape[2])
+    if K < 1:
+        raise ValueError("look_ahead needs at least one candidate")
+    names = tuple(outputs)
+    unknown = [n for n in names if n not in L.LOOK_AHEAD_OUTPUTS]
+    if unknown:
+        raise ValueError(f"look_ahead outputs must be among {sorted(L.LOOK_AHEAD_OUTPUTS)}, got {unknown}")
+    tensors, result = {"actions": a}, {}
+    for name in names:
+        field, dtype, shape_of = L.LOOK_AHEAD_OUTPUTS[name]
+        shape, dtype = shape_of(E, K, H, A), getattr(torch, dtype)
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=env.device)
+        elif t.shape != shape or t.dtype != dtype or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {env.device}")
+        tensors[field] = result[name] = t
+    return dict(candidates=K, horizon=H, repeat=int(repeat)), tensors, result
+
+
 def _observe_setup(env, lidar, action, context, mode, seed, state, row_offset, outputs, out):
     """policy_observe's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (the filled rc_policy_observe_args, the
     tensors it points into - keep them until the call has been made -, the dict to return)."""
@@ -806,6 +837,39 @@ class BatchedRaceEnv:
             self._exit()                 # a refused call still orders torch's stream after the env's
         return result
 
+    def _look_ahead(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
+        """rc_look_ahead on this handle, reading and writing rows [lo, hi) of the tensors (one row per env)."""
+        a = L.RcLookAheadArgs(C.sizeof(L.RcLookAheadArgs), args["candidates"], args["horizon"], args["repeat"])
+        for field, t in tensors.items():
+            setattr(a, field, t[lo:hi].data_ptr())
+        return self._lib.rc_look_ahead(self._h, C.byref(a))
+
+    def look_ahead(self, actions: torch.Tensor, repeat: Optional[int] = None, outputs=("reward", "flags", "return", "length"),
+                   out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """What would really happen from here under these actions (`rc_look_ahead`, one launch): `actions` float32
+        [num_envs, K, H, cars_per_env, 2] (or [num_envs, K, H, 2] with one car per env) holds K candidate sequences of H agent
+        steps per env in `step`'s convention; every one is carried through the true dynamics from the env's live state, exactly
+        as `step(actions, repeat)` on an env without auto-reset would - a finished env is frozen: reward +0.0, flags kept, no
+        reset.  The env is not touched: no state, no view, not `action_in`, not the episode log, not the agent's latent.
+        `repeat=None`: the env's default, as `step`.  Returns device tensors by name, those of `outputs`: `reward` float32
+        [E, K, H, A], `flags` uint8 [E, K, H, A] (bit 0 done, 1 truncated, 2 wall, 3 opponent, 4 wrong_way, after step t), `return`
+        float32 [E, K, A], `length` int32 [E, K] (steps until the env finished, that step counted; H if it did not; 0 if it
+        was), `final_state` float32 [E, K, A, 8] (x, y, theta, v, delta, omega, lap - 1 + progress, time), `pose` float32
+        [E, K, H, A, 3].  `out`: tensors to write into, by the same names."""
+        args, tensors, result = _look_ahead_setup(self, actions, self.action_repeat if repeat is None else repeat, outputs, out)
+        self._enter()
+        try:
+            L.check(self._look_ahead(args, tensors, 0, self.num_envs))
+        finally:
+            self._exit()
+        return result
+
+    def look_ahead_time(self):
+        """(total ms, launches) of `look_ahead`'s kernel while profiling is on (behind `kernel_times()`, whose keys stay as they are)."""
+        ms, n = C.c_double(), C.c_uint64()
+        L.check(self._lib.rc_look_ahead_time(self._h, C.byref(ms), C.byref(n)))
+        return ms.value, int(n.value)
+
     def policy_act(self, slots=None) -> torch.Tensor:
         """One step of the loaded agent, in the mode of `set_policy_sampling` (deterministic by default), for every car (or the cars in the listed slots = car indices within
         an env, e.g. `slots=(1, 2, 3)`: trained opponents B-D next to a learner in slot A): reads `lidar` and `fresh` in place,
@@ -1253,6 +1317,13 @@ class MixedTrackEnv:
         args, tensors, result = _imagine_setup(self, horizon, mode, seed, actions, slots, features, start_reward, out)
         k = self.cars_per_env
         self._fork_join(lambda p, blk: p._imagine(args, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def look_ahead(self, actions: torch.Tensor, repeat: Optional[int] = None, outputs=("reward", "flags", "return", "length"),
+                   out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.look_ahead over all blocks: each block writes its envs' rows of one tensor per output."""
+        args, tensors, result = _look_ahead_setup(self, actions, self.parts[0].action_repeat if repeat is None else repeat, outputs, out)
+        self._fork_join(lambda p, blk: p._look_ahead(args, tensors, blk[0], blk[1]))
         return result
 
     def policy_observe(self, lidar: torch.Tensor, action: torch.Tensor, context: Optional[int] = None, mode: str = "mean", seed: int = 0,

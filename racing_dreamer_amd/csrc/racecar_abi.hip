@@ -959,6 +959,44 @@ int rc_step(rc_env *env, const float *actions_dev, int32_t repeat) {
     return single_step(env, const_cast<float *>(actions_dev), repeat, RcRandomActions{0, 0u, 0u, 0u}, "rc_step");
 }
 
+// K candidate action sequences per env through the true dynamics from the live state, which it does not touch (racecar_lookahead.hip)
+int rc_look_ahead(rc_env *env, const rc_look_ahead_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "rc_look_ahead: env or args is NULL");
+    if (a->struct_size != sizeof(rc_look_ahead_args))
+        return fail(RC_ERR_INVALID, "rc_look_ahead_args.struct_size %u != %zu", a->struct_size, sizeof(rc_look_ahead_args));
+    if (!env->has_track) return fail(RC_ERR_NO_TRACK, "rc_load_track must be called before rc_look_ahead");
+    if (!env->was_reset) return fail(RC_ERR_NEEDS_RESET, "Must reset environment.");
+    if (a->candidates < 1) return fail(RC_ERR_INVALID, "rc_look_ahead: candidates must be >= 1 (got %d)", a->candidates);
+    if (a->horizon < 1 || a->horizon > RC_LOOK_AHEAD_MAX_HORIZON)
+        return fail(RC_ERR_INVALID, "rc_look_ahead: horizon %d is outside [1, %d]", a->horizon, RC_LOOK_AHEAD_MAX_HORIZON);
+    if (a->repeat < 1) return fail(RC_ERR_INVALID, "rc_look_ahead: repeat must be >= 1 (got %d)", a->repeat);
+    const long long lanes = (long long)env->cfg.num_envs * a->candidates;
+    if (lanes > 0x7fffffffLL)
+        return fail(RC_ERR_INVALID, "rc_look_ahead: %d envs x %d candidates = %lld rollouts do not fit int32", env->cfg.num_envs, a->candidates, lanes);
+    if (!a->actions) return fail(RC_ERR_INVALID, "rc_look_ahead: actions is NULL");
+    if (!a->reward && !a->flags && !a->ret && !a->length && !a->final_state && !a->pose)
+        return fail(RC_ERR_INVALID, "rc_look_ahead: no output asked for");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    int rc = env->params.ts_n > 0 ? ts_sync_table(env) : RC_OK;
+    if (rc) return rc;
+    RcLookAhead c{};
+    c.actions = a->actions;
+    c.reward = a->reward; c.flags = a->flags; c.ret = a->ret; c.length = a->length; c.final_state = a->final_state; c.pose = a->pose;
+    c.candidates = a->candidates; c.horizon = a->horizon; c.repeat = a->repeat;
+    c.lanes = (int32_t)lanes;
+    TIMED(env, kTimeLookAhead, rck_launch_look_ahead(env->params, c, env->stream));
+    return RC_OK;
+}
+
+int rc_look_ahead_time(rc_env *env, double *total_ms, uint64_t *launches) {
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    int rc = drain_events(env);
+    if (rc) return rc;
+    if (total_ms) *total_ms = env->k_ms[kTimeLookAhead];
+    if (launches) *launches = env->k_n[kTimeLookAhead];
+    return RC_OK;
+}
+
 int rc_step_random(rc_env *env, uint64_t seed, uint32_t step, int32_t repeat) {
     return single_step(env, nullptr, repeat, RcRandomActions{1, seed_lo(seed), seed_hi(seed), step}, "rc_step_random");
 }
@@ -1317,7 +1355,7 @@ int rc_reset_kernel_times(rc_env *env) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
     int rc = drain_events(env);
     if (rc) return rc;
-    for (int k = 0; k <= RC_K_COUNT; ++k) { env->k_ms[k] = 0; env->k_n[k] = 0; }      // (the episode log's accumulator with them)
+    for (int k = 0; k < kTimeCount; ++k) { env->k_ms[k] = 0; env->k_n[k] = 0; }      // (the episode log's and the look-ahead's accumulators with them)
     return RC_OK;
 }
 

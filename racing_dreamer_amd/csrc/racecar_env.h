@@ -108,6 +108,9 @@ struct EventPair {
 // The episode log's launches of a step are timed like a kernel, under an accumulator of their own behind the public ones
 // (rc_kernel_time does not know it: rc_episode_log_time reads it).
 constexpr int kTimeEpisodeLog = RC_K_COUNT;
+// ... and so is rc_look_ahead's launch (rc_look_ahead_time reads it)
+constexpr int kTimeLookAhead = RC_K_COUNT + 1;
+constexpr int kTimeCount = RC_K_COUNT + 2;
 
 // A table of up to 8 RcParams on the device that follows its host-side contents in stream order (rc_step_group: one entry per
 // handle; a track set: one per track).  A copy is queued only when an entry or the count changed since the last upload, from one
@@ -172,8 +175,8 @@ struct rc_env {
     uint32_t profiling = 0;        // bit k set: time kernel k with HIP events (the episode log's launches: any bit)
     std::vector<EventPair> pending;
     std::vector<EventPair> free_events;
-    double k_ms[RC_K_COUNT + 1] = {0};     // (the last entry: kTimeEpisodeLog)
-    uint64_t k_n[RC_K_COUNT + 1] = {0};
+    double k_ms[kTimeCount] = {0};         // (behind the public ones: kTimeEpisodeLog, kTimeLookAhead)
+    uint64_t k_n[kTimeCount] = {0};
     int32_t dbg[RC_DBG_COUNT] = {0};   // rc_debug_set: experiment / validation knobs, all 0 = production behaviour
     // half-size record + multi-GPU gather
     CompactLayout compact{};
@@ -233,7 +236,7 @@ struct KernelTimer {
     int begin(rc_env *e, int kernel, bool bracket_mode = false) {
         env = e;
         bracket = bracket_mode;
-        if (kernel == kTimeEpisodeLog ? e->profiling == 0 : !((e->profiling >> kernel) & 1u)) return RC_OK;
+        if (kernel >= RC_K_COUNT ? e->profiling == 0 : !((e->profiling >> kernel) & 1u)) return RC_OK;
         if (e->pending.size() >= 4096) {
             int rc = drain_events(e);
             if (rc) return rc;

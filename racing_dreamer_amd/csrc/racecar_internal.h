@@ -246,6 +246,19 @@ hipError_t rck_build_spawn_table(const RcTrackDev &t, float4 *spawn_dev, hipStre
 struct RcRandomActions { int32_t on; uint32_t seed_lo, seed_hi, step; };   // on != 0: draw the actions in the dynamics kernel
 hipError_t rck_launch_dynamics(const RcParams &p, float *actions, int repeat, const RcRandomActions &ra, hipStream_t s);
 hipError_t rck_launch_reset(const RcParams &p, const uint8_t *mask_dev, hipStream_t s);
+// rc_look_ahead (racecar_lookahead.hip): one lane per (env, candidate); the arrays are the caller's (null = not asked for)
+struct RcLookAhead {
+    const float *actions;        // [E, K, H, A, 2]
+    float *reward;               // [E, K, H, A]
+    uint8_t *flags;              // [E, K, H, A]
+    float *ret;                  // [E, K, A]
+    int32_t *length;             // [E, K]
+    float *final_state;          // [E, K, A, 8]
+    float *pose;                 // [E, K, H, A, 3]
+    int32_t candidates, horizon, repeat;
+    int32_t lanes;               // E K
+};
+hipError_t rck_launch_look_ahead(const RcParams &p, const RcLookAhead &c, hipStream_t s);
 hipError_t rck_launch_set_pose(const RcParams &p, const float *xyyaw_dev, hipStream_t s);
 hipError_t rck_launch_raycast(const RcParams &p, const RcLaunchInfo &li, const RcLabTables *lab, hipStream_t s);   // lab: the track's block for variants 1-5, else unused
 void rck_scan_kernel_name(const RcParams &p, const RcLaunchInfo &li, char *out, size_t bytes);   // the kernel rck_launch_raycast launches for variant 7 without stamps

@@ -23,6 +23,7 @@
 
 #include "racecar_scan.h"      // the traversal and scan_car (shared with the lab library, racecar_lab.hip)
 #include "racecar_car.h"          // Car, wall_hit, obb_overlap (shared with the spawn-table builder, racecar_tracks.hip)
+#include "racecar_step.h"         // load_cars, the env's track in a track set, controls_of, the sub-step's body (shared with the look-ahead, racecar_lookahead.hip)
 #include "racecar_patch_exact.h"   // obs_type lidar_occupancy_reference
 
 #define RC_PATCH 64
@@ -179,21 +180,6 @@ __device__ __forceinline__ void store_vehicle(const RcParams &p, int e, const fl
 }
 
 template <int A>
-__device__ __forceinline__ void load_cars(const RcParams &p, int e, Car (&car)[A]) {
-#pragma unroll
-    for (int a = 0; a < A; ++a) {
-        const int i = e * A + a;
-        Car &c = car[a];
-        c.x = p.st.x[i]; c.y = p.st.y[i]; c.th = p.st.theta[i]; c.ct = p.st.ct[i]; c.st = p.st.st[i];
-        c.v = p.st.v[i]; c.dl = p.st.delta[i]; c.om = p.st.omega[i]; c.ac = p.st.accel[i];
-        c.pr = p.st.progress[i]; c.lap = p.st.lap[i]; c.cp = p.st.cp[i];
-        c.wall = p.st.wall[i]; c.opp = p.st.opp[i]; c.wrong = p.st.wrong[i];
-        c.done = p.st.done[i]; c.trunc = p.st.trunc[i]; c.fresh = 0;
-        c.rew = 0.0f;
-    }
-}
-
-template <int A>
 __device__ __forceinline__ void store_state_and_obs(const RcParams &p, const RcTrackDev &t, int e, const Car (&car)[A], int steps,
                                                     int agent_steps) {
 #pragma unroll
@@ -243,20 +229,7 @@ __device__ __forceinline__ void store_step_results(const RcParams &p, int e, con
     }
 }
 
-// ---- track set (rc_set_track_set): the env's track k is a lane value; the dynamics reads the few fields of track k's RcTrackDev
-// that it uses (walls, progress grid, spawn table, geometry) with per-lane loads from the owner's table, the rest stays zero.
-__device__ __forceinline__ int ts_track_of(const RcParams &p, int e) {
-    const int k = p.ts_track[e];
-    return (unsigned)k < (unsigned)p.ts_n ? k : 0;          // (a value written from outside [0, T) reads as track 0)
-}
-
-__device__ __forceinline__ void lane_track(const RcParams &p, int k, RcTrackDev &t) {
-    const RcTrackDev &s = p.ts_table[k].trk;
-    t.ray_words = s.ray_words; t.progress = s.progress; t.spawn = s.spawn;
-    t.w = s.w; t.h = s.h; t.pitch = s.pitch; t.n_centerline = s.n_centerline;
-    t.org_x = s.org_x; t.org_y = s.org_y; t.inv_res = s.inv_res;
-}
-
+// ---- track set (rc_set_track_set): ts_track_of and lane_track are in racecar_step.h
 // The track of the episode that a reset with episode value ep starts (include/racecar_hip.h, rc_set_track_set): sequential
 // k + 1 mod T; random word 0 of Philox(global env id, ep, 0, RC_TS_TAG) r, (r T) >> 32 or #{c_i <= r} with weights; manual
 // next[e] (a value outside [0, T) keeps the current track).
@@ -327,103 +300,15 @@ __device__ __forceinline__ void dynamics_env(const RcParams &p, float *__restric
         }
         p.out.action[2 * i] = a0;
         p.out.action[2 * i + 1] = a1;
-        float m = a0, s = a1;
-        if (p.remap_actions) {   // ReduceActionSpace, dreamer/wrappers.py:128-130
-            m = ((a0 + 1.0f) * 0.5f) * (p.act_hi0 - p.act_lo0) + p.act_lo0;
-            s = ((a1 + 1.0f) * 0.5f) * (p.act_hi1 - p.act_lo1) + p.act_lo1;
-        }
-        motor[a] = clampf(m, -1.0f, 1.0f);
-        steer[a] = clampf(s, -1.0f, 1.0f);
+        controls_of(p, a0, a1, motor[a], steer[a]);
         any_done |= car[a].done != 0;
     }
 
     if (!any_done) {
         for (int sub = 0; sub < repeat; ++sub) {   // ActionRepeat, dreamer/wrappers.py:107-116
-            // --- kinematic bicycle, explicit Euler (H2)
-#pragma unroll
-            for (int a = 0; a < A; ++a) {
-                Car &c = car[a];
-                const float m = motor[a];
-                const float accel_max = DR ? vp[a][RC_VP_ACCEL_MAX] : RCS_ACCEL_MAX, drag = DR ? vp[a][RC_VP_DRAG] : RCS_DRAG;
-                const float max_vel = DR ? vp[a][RC_VP_MAX_VEL] : RCS_MAX_VEL, steer_step = DR ? vp[a][RC_VP_STEER_STEP] : RCS_STEER_STEP;
-                const float steer_gain = DR ? -vp[a][RC_VP_WHEEL_MAX] : RCS_STEER_GAIN;
-                const float force = fabsf(m) * accel_max;
-                const float acc = (m >= 0.0f ? force : -force) - drag * c.v;
-                c.v = clampf(c.v + acc * RCS_DT, 0.0f, max_vel);
-                const float dd = clampf(steer[a] * steer_gain - c.dl, -steer_step, steer_step);
-                c.dl = c.dl + dd;
-                float sd, cd;
-                sincos32(c.dl, sd, cd);
-                c.om = (c.v / RCS_WHEELBASE) * (sd / cd);
-                c.x = c.x + (c.v * c.ct) * RCS_DT;
-                c.y = c.y + (c.v * c.st) * RCS_DT;
-                float th = c.th + c.om * RCS_DT;
-                th = th > RCS_PI ? th - RCS_TWO_PI : th;
-                th = th < -RCS_PI ? th + RCS_TWO_PI : th;
-                c.th = th;
-                sincos32(th, c.st, c.ct);
-                c.ac = acc;
-            }
-            steps += 1;
-            // --- collisions (H5)
-#pragma unroll
-            for (int a = 0; a < A; ++a) {
-                car[a].wall = wall_hit(t, car[a]);
-                car[a].opp = 0;
-            }
-#pragma unroll
-            for (int a = 0; a < A; ++a)
-#pragma unroll
-                for (int b = a + 1; b < A; ++b) {
-                    const int o = obb_overlap(car[a], car[b]);
-                    car[a].opp |= o;
-                    car[b].opp |= o;
-                }
-            // --- progress, lap, reward, done (H4, H15)
-            const float time = (float)steps * RCS_DT;
-            bool stop = false;
-#pragma unroll
-            for (int a = 0; a < A; ++a) {
-                Car &c = car[a];
-                float p_new = progress_at(t, c.x, c.y);
-                const float p_old = c.pr;
-                const int lap_old = c.lap, cp_old = c.cp;
-                p_new = p_new >= 0.0f ? p_new : p_old;
-                int cp_new = (int)(p_new * (float)RCS_N_CHECKPOINTS);
-                cp_new = cp_new < RCS_N_CHECKPOINTS - 1 ? cp_new : RCS_N_CHECKPOINTS - 1;
-                int d = cp_new - cp_old;
-                d = d < 0 ? d + RCS_N_CHECKPOINTS : d;
-                const bool fwd = d > 0 && d <= RCS_N_CHECKPOINTS / 2;
-                const bool bwd = d > RCS_N_CHECKPOINTS / 2;
-                const int lap = lap_old + ((fwd && cp_new < cp_old) ? 1 : 0) - ((bwd && cp_new > cp_old) ? 1 : 0);
-                c.wrong = fwd ? 0 : (bwd ? 1 : c.wrong);
-                c.cp = (fwd || bwd) ? cp_new : cp_old;
-                c.lap = lap;
-                c.pr = p_new;
-                const bool collided = (c.wall | c.opp) != 0;
-                float r;
-                bool done;
-                const int task = p.car_task[a];
-                if (task == 2) {
-                    // n_step_progress, the secondary agents' task of baselines/scenarios/max_progress/columbia.yml:17-18:
-                    // total progress gained over the last n_steps sub-steps, no collision term, never done
-                    float *h = p.st.nstep_hist + (size_t)(e * A + a) * RC_NSTEP_MAX + (steps % p.n_steps);
-                    const float total = (float)(lap - 1) + p_new;
-                    r = (total - *h) * RCS_PROGRESS_REWARD;
-                    *h = total;
-                    done = false;
-                } else if (task == 0) {
-                    const float delta = (float)(lap - lap_old) + (p_new - p_old);
-                    r = delta * RCS_PROGRESS_REWARD + (collided ? p.collision_reward : 0.0f);
-                    done = (collided && p.terminate_on_collision) || lap > p.laps || time > p.time_limit;
-                } else {   // baselines/racing/environment/tasks.py:6-18
-                    r = c.wall ? -1.0f : -rcd::exp32(fabsf(steer[a]) - c.v);
-                    done = false;
-                }
-                c.rew = c.rew + r;
-                c.done = done ? 1 : 0;
-                stop |= done;
-            }
+#define RC_NSTEP_SLOT(a, k) (p.st.nstep_hist + (size_t)(e * A + a) * RC_NSTEP_MAX + (k))
+#include "racecar_substep.inc"      // one sub-step: the text the look-ahead's dynamics_substep is made of (racecar_step.h)
+#undef RC_NSTEP_SLOT
             if (stop) break;
         }
         agent_steps += 1;

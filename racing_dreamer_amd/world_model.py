@@ -34,3 +34,23 @@ def model_terms(env, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
         r = batch["reward"].to(out["reward"].device, torch.float32).reshape(out["reward"].shape)
         terms["reward_loglik"] = (-0.5 * (r - out["reward"]) ** 2 - 0.5 * math.log(2.0 * math.pi)).mean()
     return terms
+
+
+def imagined_vs_simulated(env, horizon: int = 15, mode: str = "mean", seed: int = 0, repeat=None) -> Dict[str, torch.Tensor]:
+    """The world model's dream beside what the simulator would really do, without spending the run:
+    `policy_imagine` from every car's latent under the actor's own actions, then `look_ahead` with one candidate per env - those
+    actions - from the env's live state.  Returns `predicted` and `simulated` float32 [n_cars, horizon] (the reward head's
+    reward and the true one of each step), `alive` bool [n_cars, horizon] (the steps after which the car's env was not yet
+    finished: later pairs compare a dream with a frozen env) and `action` [n_cars, horizon, 2].  Both calls are pure - no state,
+    no `action_in`, no latent changes - so this can run at every step of a live run.  `repeat`: the action repeat of the simulated
+    steps (None: the env's default, as `step`).  Needs a checkpoint with a reward head."""
+    if not env.policy_has_reward_head:
+        raise RuntimeError("imagined_vs_simulated needs a checkpoint with a reward head (reward_* arrays)")
+    E, A, h = env.num_envs, env.cars_per_env, int(horizon)
+    dream = env.policy_imagine(h, mode, seed)
+    actions = dream["action"].reshape(E, A, h, 2).permute(0, 2, 1, 3).reshape(E, 1, h, A, 2)
+    real = env.look_ahead(actions, repeat=repeat, outputs=("reward", "flags"))
+    simulated = real["reward"].reshape(E, h, A).permute(0, 2, 1).reshape(E * A, h)
+    finished = ((real["flags"].reshape(E, h, A) & 1) != 0).any(dim=2)                       # [E, h]: some slot's done bit after step t
+    alive = (~finished).unsqueeze(1).expand(E, A, h).reshape(E * A, h)
+    return dict(predicted=dream["reward"], simulated=simulated, alive=alive, action=dream["action"])

@@ -2,7 +2,10 @@
 own actor (`env.policy_imagine`), then the real env is driven with exactly those actions from the same states, and the head's
 predicted reward is set beside the simulated reward of each step.
 
-    python tools/imagine_open_loop.py [--tracks austria columbia] [--envs 1024] [--out profiles/imagine_open_loop.json]
+    python tools/imagine_open_loop.py [--tracks austria columbia] [--envs 1024] [--out profiles/imagine_open_loop.json] [--pure]
+
+`--pure` takes the pairs from `world_model.imagined_vs_simulated` instead - the same dream, the simulated side from
+`env.look_ahead`, which leaves the env where it stands (the finishing step of an env is not counted there either).
 
 A record for users, with no pass or fail threshold: the reward scale of the simulator the checkpoints were trained on against this
 one's is not pinned."""
@@ -28,15 +31,21 @@ def measure(track, args):
         env.step(None, repeat=4)
     env.policy_act()                                        # the latent takes in the last scan: the dream starts where the env stands
     n, h = env.n_cars, args.horizon
-    dream = env.policy_imagine(h, "mean")
-    real, alive = [], torch.ones(n, dtype=torch.bool, device=env.device)
-    ok = []
-    for t in range(h):
-        out = env.step(dream["action"][:, t].reshape(env.num_envs, env.cars_per_env, 2), repeat=4)
-        real.append(out["reward"].reshape(n).clone())
-        alive &= out["fresh"].reshape(n) == 0               # (an env that was reset on the way has left the imagined episode)
-        ok.append(alive.clone())
-    real, ok, pred = torch.stack(real, 1).cpu().numpy().astype(np.float64), torch.stack(ok, 1).cpu().numpy(), dream["reward"].cpu().numpy().astype(np.float64)
+    if args.pure:
+        from racing_dreamer_amd.world_model import imagined_vs_simulated
+        pairs = imagined_vs_simulated(env, h, "mean", repeat=4)
+        real, ok, pred = (pairs[k].cpu().numpy() for k in ("simulated", "alive", "predicted"))
+        real, pred = real.astype(np.float64), pred.astype(np.float64)
+    else:
+        dream = env.policy_imagine(h, "mean")
+        real, alive = [], torch.ones(n, dtype=torch.bool, device=env.device)
+        ok = []
+        for t in range(h):
+            out = env.step(dream["action"][:, t].reshape(env.num_envs, env.cars_per_env, 2), repeat=4)
+            real.append(out["reward"].reshape(n).clone())
+            alive &= out["fresh"].reshape(n) == 0               # (an env that was reset on the way has left the imagined episode)
+            ok.append(alive.clone())
+        real, ok, pred = torch.stack(real, 1).cpu().numpy().astype(np.float64), torch.stack(ok, 1).cpu().numpy(), dream["reward"].cpu().numpy().astype(np.float64)
     env.close()
     rows = []
     for slot in range(args.cars):
@@ -62,9 +71,10 @@ def main():
     ap.add_argument("--settle", type=int, default=60)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pure", action="store_true", help="simulated rewards from env.look_ahead (world_model.imagined_vs_simulated): the env is not driven")
     args = ap.parse_args()
     out = {"tool": "tools/imagine_open_loop.py", "checkpoint": args.checkpoint, "envs": args.envs, "cars_per_env": args.cars, "horizon": args.horizon,
-           "settle_agent_steps": args.settle, "repeat": 4, "mode": "mean", "threshold": None, "rows": [r for tr in args.tracks for r in measure(tr, args)]}
+           "settle_agent_steps": args.settle, "repeat": 4, "mode": "mean", **({"pure": True} if args.pure else {}), "threshold": None, "rows": [r for tr in args.tracks for r in measure(tr, args)]}
     print(json.dumps(out))
     if args.out:
         with open(args.out, "w") as f:
