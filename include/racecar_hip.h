@@ -439,6 +439,49 @@ typedef struct rc_policy_imagine_args {
  * asked for without a loaded head.  Kernels: rc_policy_imagine_kernel, rc_policy_imagine_sampled_kernel, timed under RC_K_POLICY. */
 int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *args);
 
+/* Planning in the latent: K candidate action sequences per start latent, carried through the world model and scored by its reward
+ * head (tests/policy_dream_spec.c is the CPU restatement, the device equals it bit for bit) - the dream's
+ * counterpart of rc_look_ahead, what PlaNet-style random shooting or the cross-entropy method ask of a world model.  Rows are pairs
+ * (start s, candidate k), k in [0, candidates); all K rows of a start begin from the same latent:
+ *   state_in = NULL   the live latents of rc_policy_state: one start per car whose slot is in slot_mask, as rc_policy_imagine; the
+ *                     arrays are indexed by car ([n_cars, K, ...]), rows of cars outside the mask are not touched; RC_F_FRESH is
+ *                     not looked at.  The start id is the global car id (first_env + env) * cars_per_env + slot.
+ *   state_in given    device float32 [starts, 232] in rc_policy_state's layout (the last two columns are not read; rc_policy_observe's
+ *                     state_out fits as it is: observe a replay window, then plan from its end).  Nothing to do with the env's cars:
+ *                     slot_mask must be 0.  The start id is row_offset + s (64 bits).
+ * For t = 0 .. horizon - 1 a row does what open-loop rc_policy_imagine does: a = clamp(actions_in[s, k, t], -1, 1); the prior step
+ * img_step (ros_agent/models/dreamer/models.py:44-52 RSSM.imagine: img1, GRU, img2, img3); the reward head on the new feature
+ * (dreamer/models.py:301-318 DenseDecoder).  The actor is never run.  Modes are rc_policy_imagine's: RC_POLICY_IMAGINE_MEAN, and
+ * RC_POLICY_IMAGINE_SAMPLE: stoch' ~ Normal(mean, softplus(raw) + 0.1), Philox4x32-10 keyed by `seed` and counted by (start id,
+ * candidate, t, index) under tag 7 (counter word 3, bits 24-31) - not by K, the workgroup, the mask, the shard or the call history;
+ * a caller who wants fresh draws at every step changes `seed`.
+ * Outputs, each optional, at least one: ret [starts, K] = sum_t discount^t r_t, accumulated in binary32 in step order (acc = 0, w = 1;
+ * acc = fmaf(w, r_t, acc); w = w * discount); reward [starts, K, H]; final_feature [starts, K, 230] = the feature after step H - 1
+ * (for a caller's own value head: a bootstrap value).  A pure function of its inputs: the agent's state, RC_F_ACTION_IN, the arena,
+ * the episode log and every counter stay as they are. */
+typedef struct rc_policy_dream_ahead_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_dream_ahead_args) */
+    int32_t horizon;               /* H in [1, RC_POLICY_IMAGINE_MAX_HORIZON] */
+    int32_t mode;                  /* RC_POLICY_IMAGINE_* */
+    int32_t candidates;            /* K >= 1; starts x K < 2^31 */
+    uint32_t slot_mask;            /* live latents: bit a = slot a, as rc_policy_act's; with state_in: 0 */
+    float discount;                /* in [0, 1]; 1: the plain sum */
+    uint64_t seed;
+    int64_t starts;                /* with state_in: its rows, >= 1 (live latents: not read) */
+    uint64_t row_offset;           /* with state_in: the start id of start 0 (mode SAMPLE) */
+    const float *state_in;         /* device float32 [starts, 232], or NULL: the live latents */
+    const float *actions_in;       /* device float32 [starts, K, H, 2], raw in [-1, 1] (clamped) */
+    float *ret;                    /* device float32 [starts, K], or NULL */
+    float *reward;                 /* device float32 [starts, K, H], or NULL */
+    float *final_feature;          /* device float32 [starts, K, 230], or NULL */
+} rc_policy_dream_ahead_args;
+/* rc_policy_dream_ahead: one launch on the handle's stream.  RC_ERR_INVALID: wrong struct_size, no policy loaded, the policy loaded
+ * without img2 / img3, ret or reward asked for without a loaded head, horizon outside [1, 64], candidates < 1 or starts x candidates
+ * not below 2^31, unknown mode, discount not finite or outside [0, 1], actions_in NULL, no output asked for, state_in together with
+ * a non-zero mask or starts < 1, live latents with an empty mask or bits beyond cars_per_env.  Kernels: rc_policy_dream_kernel,
+ * rc_policy_dream_sampled_kernel, timed under RC_K_POLICY. */
+int rc_policy_dream_ahead(rc_env *env, const rc_policy_dream_ahead_args *args);
+
 /* Recorded sequences: the posterior chain over N recorded windows of T scans and actions (DESIGN.md §2 item 17;
  * tests/policy_observe_spec.c is the CPU restatement, the device equals it bit for bit) - dreamer/models.py:325-336 RSSM.observe,
  * the operation the reference runs on every replay batch: `post, prior = observe(embed, action)`, kl_divergence(post, prior) and the

@@ -105,6 +105,18 @@ class RcPolicyImagineArgs(C.Structure):
                 ("actions_in", C.c_void_p), ("reward", C.c_void_p), ("actions", C.c_void_p), ("features", C.c_void_p), ("reward_start", C.c_void_p)]
 
 
+# dream_ahead's output names -> (rc_policy_dream_ahead_args field, trailing shape after [starts, K] as a function of H)
+DREAM_AHEAD_OUTPUTS = {"return": ("ret", lambda H: ()), "reward": ("reward", lambda H: (H,)),
+                       "final_feature": ("final_feature", lambda H: (POLICY_FEATURE,))}
+
+
+class RcPolicyDreamAheadArgs(C.Structure):
+    """rc_policy_dream_ahead_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("horizon", C.c_int32), ("mode", C.c_int32), ("candidates", C.c_int32), ("slot_mask", C.c_uint32),
+                ("discount", C.c_float), ("seed", C.c_uint64), ("starts", C.c_int64), ("row_offset", C.c_uint64), ("state_in", C.c_void_p),
+                ("actions_in", C.c_void_p), ("ret", C.c_void_p), ("reward", C.c_void_p), ("final_feature", C.c_void_p)]
+
+
 LOOK_AHEAD_MAX_HORIZON = 64
 LA_DONE, LA_TRUNCATED, LA_WALL, LA_OPPONENT, LA_WRONG_WAY = 1, 2, 4, 8, 16      # rc_look_ahead's flags
 # look_ahead's output names -> (rc_look_ahead_args field, torch dtype name, shape as a function of (E, K, H, A))
@@ -245,6 +257,7 @@ SYMBOLS = {
     "rc_policy_get_sampling": (C.c_int, [C.c_void_p, _P(RcPolicySampling)]),
     "rc_policy_load_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
     "rc_policy_imagine": (C.c_int, [C.c_void_p, _P(RcPolicyImagineArgs)]),
+    "rc_policy_dream_ahead": (C.c_int, [C.c_void_p, _P(RcPolicyDreamAheadArgs)]),
     "rc_policy_observe": (C.c_int, [C.c_void_p, _P(RcPolicyObserveArgs)]),
     "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
     "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),

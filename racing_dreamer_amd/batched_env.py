@@ -142,6 +142,53 @@ def _imagine_setup(env, horizon, mode, seed, actions, slots, features, start_rew
     return args, tensors, result
 
 
+def _dream_setup(env, actions, mode, seed, state, row_offset, slots, discount, outputs, out):
+    """dream_ahead's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
+    rc_policy_dream_ahead_args field - one row per start -, the dict to return).  What only the library can tell (no policy, no
+    head, slots with a state, the size of starts x K) is left to it, which names it."""
+    if mode not in L.IMAGINE_MODES:
+        raise ValueError(f"dream_ahead mode must be one of {sorted(L.IMAGINE_MODES)}, got {mode!r}")
+    S = env.n_cars
+    if state is not None:
+        if state.dim() < 1 or state.shape[-1] != L.POLICY_FEATURE + 2 or state.numel() == 0:
+            raise ValueError(f"state must be [starts >= 1, {L.POLICY_FEATURE + 2}] = stoch | deter | (2 unused), got {tuple(state.shape)}")
+        S = state.numel() // (L.POLICY_FEATURE + 2)
+    a = actions.to(env.device, torch.float32)
+    if a.dim() != 4 or a.shape[0] != S or a.shape[3] != 2:
+        raise ValueError(f"actions must be [starts={S}, candidates, horizon, 2], got shape {tuple(actions.shape)}")
+    a = a.contiguous()
+    K, H = int(a.shape[1]), int(a.shape[2])
+    if K < 1:
+        raise ValueError("dream_ahead needs at least one candidate")
+    if not 1 <= H <= L.IMAGINE_MAX_HORIZON:
+        raise ValueError(f"horizon must be in [1, {L.IMAGINE_MAX_HORIZON}], got {H}")
+    discount = float(discount)
+    if not 0.0 <= discount <= 1.0:
+        raise ValueError(f"discount must be in [0, 1], got {discount}")
+    names = tuple(outputs)
+    unknown = [n for n in names if n not in L.DREAM_AHEAD_OUTPUTS]
+    if unknown:
+        raise ValueError(f"dream_ahead outputs must be among {sorted(L.DREAM_AHEAD_OUTPUTS)}, got {unknown}")
+    tensors, result = {"actions_in": a, "ret": None, "reward": None, "final_feature": None}, {}
+    if state is not None:
+        tensors["state_in"] = state.to(env.device, torch.float32).reshape(S, L.POLICY_FEATURE + 2).contiguous()
+        mask = 0 if slots is None else sum({1 << int(b) for b in slots})        # (slots with a state: the library refuses and says why)
+    else:
+        mask = (1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(b) for b in slots})
+    for name in names:
+        field, tail = L.DREAM_AHEAD_OUTPUTS[name]
+        shape = (S, K) + tail(H)
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = (torch.empty if slots is None else torch.zeros)(shape, dtype=torch.float32, device=env.device)
+        elif t.shape != shape or t.dtype != torch.float32 or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of shape {shape} on {env.device}")
+        tensors[field] = result[name] = t
+    args = dict(horizon=H, mode=L.IMAGINE_MODES[mode], candidates=K, mask=mask, discount=discount, seed=int(seed) & (2 ** 64 - 1),
+                starts=S, row_offset=int(row_offset) & (2 ** 64 - 1), live=state is None)
+    return args, tensors, result
+
+
 def _look_ahead_setup(env, actions, repeat, outputs, out):
     """look_ahead's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
     rc_look_ahead_args field - env-major, one row per env -, the dict to return)."""
@@ -837,6 +884,36 @@ class BatchedRaceEnv:
             self._exit()                 # a refused call still orders torch's stream after the env's
         return result
 
+    def _dream_ahead(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_dream_ahead on this handle: from its live latents, reading and writing rows [lo, hi) of the tensors (one row per
+        car), or from a given state, the whole tensors."""
+        a = L.RcPolicyDreamAheadArgs(C.sizeof(L.RcPolicyDreamAheadArgs), args["horizon"], args["mode"], args["candidates"], args["mask"],
+                                     args["discount"], args["seed"], args["starts"], args["row_offset"])
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else (t[lo:hi] if args["live"] else t).data_ptr())
+        return self._lib.rc_policy_dream_ahead(self._h, C.byref(a))
+
+    def dream_ahead(self, actions: torch.Tensor, mode: str = "mean", seed: int = 0, state: Optional[torch.Tensor] = None, row_offset: int = 0,
+                    slots=None, discount: float = 1.0, outputs=("return",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """Plan in the dream (`rc_policy_dream_ahead`, one launch): `actions` float32 [S, K, H, 2] raw in [-1, 1] (clamped) holds K
+        candidate sequences of H steps per start latent; every one is carried through the world model open loop, exactly as
+        `policy_imagine(actions=...)` would carry it, and scored by the reward head - `look_ahead`'s counterpart in the latent.
+        The starts are every car's latent as `policy_act` last left it (S = n_cars; with `slots`, rows of the other cars are
+        zero - or what `out` held), or `state` float32 [S, 232] = stoch | deter | (2 unused) in `policy_state`'s layout, e.g.
+        `policy_observe(..., outputs=("state",))["state"]`: observe a replay window, then plan from its end.  mode "mean": the
+        prior's mean; "sample": stoch' ~ Normal(mean, std), a function of (seed, start id, candidate, t) only - the start id is
+        the global car id, or `row_offset` + the row of `state`, so shards of a batch reproduce the whole.  `outputs` names
+        what to compute, each a device float32 tensor: `return` [S, K] = sum_t discount^t reward_t, `reward` [S, K, H],
+        `final_feature` [S, K, 230] = stoch | deter after the last step (for a value head of the caller's).  `return` and
+        `reward` need a checkpoint with a reward head.  Nothing else changes: not the agent's state, not `action_in`."""
+        args, tensors, result = _dream_setup(self, actions, mode, seed, state, row_offset, slots, discount, outputs, out)
+        self._enter()
+        try:
+            L.check(self._dream_ahead(args, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
+
     def _look_ahead(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
         """rc_look_ahead on this handle, reading and writing rows [lo, hi) of the tensors (one row per env)."""
         a = L.RcLookAheadArgs(C.sizeof(L.RcLookAheadArgs), args["candidates"], args["horizon"], args["repeat"])
@@ -1317,6 +1394,18 @@ class MixedTrackEnv:
         args, tensors, result = _imagine_setup(self, horizon, mode, seed, actions, slots, features, start_reward, out)
         k = self.cars_per_env
         self._fork_join(lambda p, blk: p._imagine(args, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def dream_ahead(self, actions: torch.Tensor, mode: str = "mean", seed: int = 0, state: Optional[torch.Tensor] = None, row_offset: int = 0,
+                    slots=None, discount: float = 1.0, outputs=("return",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.dream_ahead over all blocks: each block plans from its cars' latents into its rows of one tensor per
+        output; a given `state` (every block holds the same weights) goes through the first block."""
+        args, tensors, result = _dream_setup(self, actions, mode, seed, state, row_offset, slots, discount, outputs, out)
+        k = self.cars_per_env
+        if state is not None:
+            self._ordered(lambda: self.parts[0]._dream_ahead(args, tensors, 0, 0))
+        else:
+            self._fork_join(lambda p, blk: p._dream_ahead(args, tensors, blk[0] * k, blk[1] * k))
         return result
 
     def look_ahead(self, actions: torch.Tensor, repeat: Optional[int] = None, outputs=("reward", "flags", "return", "length"),

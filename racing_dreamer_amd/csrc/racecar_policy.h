@@ -81,6 +81,23 @@ struct RcImagineCall {
     float *reward, *actions, *features, *reward_start;      // [n_cars][H], [n_cars][H][2], [n_cars][H][230], [n_cars]; any may be null
 };
 
+// Planning in the latent (racecar_dream.hip): rows are pairs (start, candidate), row = start x K + candidate
+struct RcDreamCall {
+    RcPolicyDev w;
+    RcImagineDev wi;
+    const float *state;                      // live: [n_cars][RC_POLICY_STATE] of the handle; else the caller's [starts][RC_POLICY_STATE]; read only
+    RcPolicyRows rows;                       // live: start -> car (the caller's arrays are indexed by car)
+    int32_t live;
+    int32_t candidates;                      // K
+    int64_t n_rows;                          // starts x K < 2^31 (live: the mask's cars x K)
+    uint64_t row_offset;                     // not live: the start id of start 0; the draws are keyed by (start id, candidate, t)
+    int32_t horizon, sample;
+    uint32_t seed_lo, seed_hi;
+    float discount;
+    const float *actions_in;                 // [starts][K][H][2] raw
+    float *ret, *reward, *final_feature;     // [starts][K], [starts][K][H], [starts][K][230]; any may be null
+};
+
 // Recorded sequences (racecar_observe.hip): rows are windows [T] of scans and actions, not cars of the env
 struct RcObserveCall {
     RcPolicyDev w;
@@ -127,6 +144,8 @@ hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS 
 hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);      // c.mode: which kernel
 hipError_t rck_imagine_prepare();
 hipError_t rck_launch_imagine(const RcImagineCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
+hipError_t rck_dream_prepare();
+hipError_t rck_launch_dream(const RcDreamCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                    // c.sample: which kernel
 hipError_t rck_observe_prepare();
 hipError_t rck_launch_observe(const RcObserveCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
 hipError_t rck_decode_prepare();

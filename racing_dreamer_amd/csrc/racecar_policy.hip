@@ -540,6 +540,7 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(rck_policy_prepare());
     HIP_TRY(rck_imagine_prepare());
+    HIP_TRY(rck_dream_prepare());
     HIP_TRY(rck_observe_prepare());
     HIP_TRY(rck_decode_prepare());
     rc = pol_drop_heads(env);
@@ -670,6 +671,53 @@ int rc_policy_imagine(rc_env *env, const rc_policy_imagine_args *a) {
     c.actions_in = a->actions_in;
     c.reward = a->reward; c.actions = a->actions; c.features = a->features; c.reward_start = a->reward_start;
     return pol_launch(env, rck_launch_imagine, c);
+}
+
+int rc_policy_dream_ahead(rc_env *env, const rc_policy_dream_ahead_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_dream_ahead_args))
+        return fail(RC_ERR_INVALID, "rc_policy_dream_ahead_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_dream_ahead_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: no policy loaded (rc_policy_load)");
+    if (!env->pol_i.img3_w) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: the policy was loaded without the prior's layers img2 / img3");
+    if (a->horizon < 1 || a->horizon > RC_POLICY_IMAGINE_MAX_HORIZON)
+        return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: horizon %d is outside [1, %d]", a->horizon, RC_POLICY_IMAGINE_MAX_HORIZON);
+    if (a->candidates < 1) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: candidates %d is below 1", a->candidates);
+    if (a->mode != RC_POLICY_IMAGINE_MEAN && a->mode != RC_POLICY_IMAGINE_SAMPLE) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: unknown mode %d", a->mode);
+    if (!(a->discount >= 0.0f && a->discount <= 1.0f))
+        return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: discount %g is not a number in [0, 1]", (double)a->discount);
+    if (!a->actions_in) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: actions_in is NULL");
+    if (!a->ret && !a->reward && !a->final_feature) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: no output asked for");
+    if ((a->ret || a->reward) && !env->pol_i.rout_w)
+        return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: a reward is asked for and no reward head is loaded (rc_policy_load_heads)");
+    RcDreamCall c{};
+    int64_t starts;
+    if (a->state_in) {
+        if (a->slot_mask) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: a slot mask (0x%x) goes with the live latents, not with a given state_in", a->slot_mask);
+        if (a->starts < 1) return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: starts %lld is below 1", (long long)a->starts);
+        starts = a->starts;
+        c.state = a->state_in;
+        c.row_offset = a->row_offset;
+    } else {
+        const int rc = pol_rows(env, a->slot_mask, a->seed, "rc_policy_dream_ahead", &c.rows);
+        if (rc) return rc;
+        starts = c.rows.n_active;
+        c.state = env->pol_state;
+        c.live = 1;
+    }
+    if (starts > (int64_t)INT32_MAX / a->candidates)
+        return fail(RC_ERR_INVALID, "rc_policy_dream_ahead: %lld starts x %d candidates is not below 2^31", (long long)starts, a->candidates);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    c.w = env->pol;
+    c.wi = env->pol_i;
+    c.candidates = a->candidates;
+    c.n_rows = starts * a->candidates;
+    c.horizon = a->horizon;
+    c.sample = a->mode == RC_POLICY_IMAGINE_SAMPLE;
+    c.seed_lo = seed_lo(a->seed); c.seed_hi = seed_hi(a->seed);
+    c.discount = a->discount;
+    c.actions_in = a->actions_in;
+    c.ret = a->ret; c.reward = a->reward; c.final_feature = a->final_feature;
+    return pol_launch(env, rck_launch_dream, c);
 }
 
 int rc_policy_observe(rc_env *env, const rc_policy_observe_args *a) {

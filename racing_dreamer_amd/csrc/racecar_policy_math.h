@@ -213,6 +213,16 @@ __device__ __forceinline__ void pm_imagine_normal_block(uint32_t env, uint32_t e
     pm_normal_word(env, episode, agent_step, block | (slot << 8) | (t << 12) | (PM_IMAGINE_TAG << 24), seed_lo, seed_hi, n);
 }
 
+// ---- planning in the latent: tests/policy_dream_spec.c restates what follows
+#define PM_DREAM_TAG 7u                    // Philox counter word 3, bits 24-31
+
+// the four normals of block `block` (0-7: the 30 normals of stoch', 2 unused) of step t of candidate `cand` of the start with the
+// 64-bit id (id_lo, id_hi): t < 64 sits in bits 8-13 of word 3
+__device__ __forceinline__ void pm_dream_normal_block(uint32_t id_lo, uint32_t id_hi, uint32_t cand, uint32_t t, uint32_t block,
+                                                      uint32_t seed_lo, uint32_t seed_hi, float (&n)[4]) {
+    pm_normal_word(id_lo, id_hi, cand, block | (t << 8) | (PM_DREAM_TAG << 24), seed_lo, seed_hi, n);
+}
+
 // ---- recorded sequences: tests/policy_observe_spec.c restates what follows
 #define PM_OBSERVE_TAG 6u                  // Philox counter word 3, bits 24-31
 

@@ -1,10 +1,16 @@
 """Planning against the simulator's true dynamics (`BatchedRaceEnv.look_ahead`): a random-shooting
-baseline beside the learned agents, and an expert that sees further than follow-the-gap.
+baseline beside the learned agents, and an expert that sees further than follow-the-gap - and the same planners against the
+world model's dream (`BatchedRaceEnv.dream_ahead`, item 19: PlaNet-style random shooting and the cross-entropy method on the
+imagined return of a checkpoint with a reward head).
 
     env.reset(mode="random", seed=0)
     for _ in range(steps):
         shooting_act(env, candidates=64, horizon=15)       # writes action_in
         env.step(None)
+
+`dream_shooting_act` and `dream_cem_act` take `shooting_act`'s place in that loop after `policy_act` has carried the latents to
+the current observation (on an env built with `remap_actions=True`: the dream's actions are raw, in [-1, 1], and what is written
+into `action_in` is raw too).
 
 The candidates are generated in torch on the env's device; the look-ahead is one launch; the choice is a few torch operations
 on [num_envs, candidates] - nothing here is a hot path of its own."""
@@ -59,4 +65,64 @@ def shooting_act(env, candidates: Union[int, torch.Tensor] = 64, horizon: int = 
     ret = env.look_ahead(seq, repeat=repeat, outputs=("return",))["return"]
     best = first_best(ret[:, :, 0])
     action_in.copy_(seq[torch.arange(E, device=seq.device), best, 0].reshape(action_in.shape))
+    return action_in
+
+
+def to_dream_actions(seq: torch.Tensor) -> torch.Tensor:
+    """`look_ahead`'s candidates [E, K, H, A, 2] as `dream_ahead`'s [E * A, K, H, 2]: one start per car, car = env * A + slot."""
+    E, K, H, A, _ = seq.shape
+    return seq.permute(0, 3, 1, 2, 4).reshape(E * A, K, H, 2).contiguous()
+
+
+def _needs_head(env, who: str) -> None:
+    if not env.policy_has_reward_head:
+        raise RuntimeError(f"{who} needs a checkpoint with a reward head (reward_* arrays)")
+
+
+def dream_shooting_act(env, candidates: Union[int, torch.Tensor] = 64, horizon: int = 15, hold: int = 5, seed: int = 0, slots=None) -> torch.Tensor:
+    """Random shooting in the dream: the candidates of `shooting_candidates` (or a tensor of explicit sequences
+    [num_envs, K, H, cars_per_env, 2]), each car's own sequences scored by the imagined return from its live latent
+    (`dream_ahead`, mode "mean"), the highest taken - the lowest index among equals.  Writes that candidate's first action into
+    `action_in` for the cars in `slots` (None: every car; the others keep theirs) and returns `action_in`."""
+    _needs_head(env, "dream_shooting_act")
+    E, A = env.num_envs, env.cars_per_env
+    action_in = env.views["action_in"]
+    seq = candidates if torch.is_tensor(candidates) else shooting_candidates(env, candidates, horizon, hold, seed)
+    seq = seq.to(action_in.device, torch.float32).reshape(E, -1, seq.shape[2], A, 2)
+    acts = to_dream_actions(seq)                                                           # [E A, K, H, 2]
+    ret = env.dream_ahead(acts, slots=slots, outputs=("return",))["return"]                # [E A, K]
+    best = first_best(ret)
+    first = acts[torch.arange(E * A, device=acts.device), best, 0].reshape(E, A, 2)
+    flat = action_in.reshape(E, A, 2)
+    for a in (range(A) if slots is None else sorted({int(b) for b in slots})):
+        flat[:, a] = first[:, a]
+    return action_in
+
+
+def dream_cem_act(env, candidates: int = 64, horizon: int = 15, iterations: int = 3, elites: int = 8, seed: int = 0) -> torch.Tensor:
+    """The cross-entropy method in the dream (PlaNet's planner): per car a Gaussian over the sequence [H, 2], mean 0 and
+    standard deviation 1 at first; `iterations` times, `candidates` sequences are drawn from it (clipped to [-1, 1]), scored by
+    the imagined return from the car's live latent, and the Gaussian is refit to the `elites` best (mean, and the biased
+    standard deviation).  All draws come from one torch generator seeded with `seed`.  Writes the first action of the final
+    mean into `action_in` and returns `action_in`."""
+    _needs_head(env, "dream_cem_act")
+    K, H, n_it, top = int(candidates), int(horizon), int(iterations), int(elites)
+    if K < 1 or H < 1 or n_it < 1 or not 1 <= top <= K:
+        raise ValueError(f"candidates, horizon and iterations must be >= 1 and elites in [1, candidates] (got {candidates}, {horizon}, {iterations}, {elites})")
+    n = env.num_envs * env.cars_per_env
+    action_in = env.views["action_in"]
+    device = action_in.device
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    mean = torch.zeros((n, 1, H, 2), dtype=torch.float32, device=device)
+    std = torch.ones((n, 1, H, 2), dtype=torch.float32, device=device)
+    rows = torch.arange(n, device=device).unsqueeze(1)
+    for _ in range(n_it):
+        noise = torch.randn((n, K, H, 2), generator=gen, dtype=torch.float32, device=device)
+        acts = (mean + std * noise).clamp_(-1.0, 1.0)
+        ret = torch.nan_to_num(env.dream_ahead(acts, outputs=("return",))["return"], nan=float("-inf"))
+        elite = acts[rows, ret.topk(top, dim=1).indices]                                   # [n, top, H, 2]
+        mean = elite.mean(dim=1, keepdim=True)
+        std = elite.std(dim=1, unbiased=False, keepdim=True)
+    action_in.copy_(mean[:, 0, 0].reshape(action_in.shape))
     return action_in

@@ -54,3 +54,40 @@ def imagined_vs_simulated(env, horizon: int = 15, mode: str = "mean", seed: int 
     finished = ((real["flags"].reshape(E, h, A) & 1) != 0).any(dim=2)                       # [E, h]: some slot's done bit after step t
     alive = (~finished).unsqueeze(1).expand(E, A, h).reshape(E * A, h)
     return dict(predicted=dream["reward"], simulated=simulated, alive=alive, action=dream["action"])
+
+
+def rank_correlation(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Spearman's rank correlation of the rows of a and b [E, K], float64 [E]: Pearson's correlation of the ranks, equal values
+    sharing the mean of their ranks; NaN for a row that is constant in a or in b."""
+    def ranks(x):
+        x = x.to(torch.float64)
+        less = (x.unsqueeze(2) > x.unsqueeze(1)).sum(dim=2)                  # entries below x[e, i]
+        equal = (x.unsqueeze(2) == x.unsqueeze(1)).sum(dim=2)                # entries equal to it, itself counted
+        return less.to(torch.float64) + (equal.to(torch.float64) - 1.0) / 2.0
+    ra, rb = ranks(a), ranks(b)
+    da, db = ra - ra.mean(dim=1, keepdim=True), rb - rb.mean(dim=1, keepdim=True)
+    return (da * db).sum(dim=1) / torch.sqrt((da * da).sum(dim=1) * (db * db).sum(dim=1))
+
+
+def dream_vs_truth(env, candidates: torch.Tensor, repeat=None) -> Dict[str, torch.Tensor]:
+    """The same K candidate sequences scored in the dream and in the simulator, for an env with one car
+    per env: `candidates` float32 [num_envs, K, H, 1, 2] (or [num_envs, K, H, 2]), raw in [-1, 1] - the env must have been
+    built with `remap_actions=True`, so that `look_ahead` reads them as the dream does.  Returns per env `imagined` and `true`
+    float32 [E, K] (`dream_ahead`'s return from the live latent, `look_ahead`'s from the live state), `rank_correlation`
+    float64 [E] (Spearman), `argmax_agree` bool [E] (the first best of both is the same candidate), `regret` float32 [E] = the
+    best true return minus the true return of the dream's choice (>= 0).  Both calls are pure, so this can run at any step of a
+    live run.  `repeat`: as `look_ahead`.  Needs a checkpoint with a reward head."""
+    from .planning import first_best, to_dream_actions
+    if not env.policy_has_reward_head:
+        raise RuntimeError("dream_vs_truth needs a checkpoint with a reward head (reward_* arrays)")
+    if env.cars_per_env != 1:
+        raise ValueError(f"dream_vs_truth compares per env: it needs one car per env, got {env.cars_per_env}")
+    E = env.num_envs
+    seq = candidates.to(env.device, torch.float32)
+    seq = seq.reshape(E, seq.shape[1], seq.shape[2], 1, 2)
+    imagined = env.dream_ahead(to_dream_actions(seq), outputs=("return",))["return"]
+    true = env.look_ahead(seq, repeat=repeat, outputs=("return",))["return"][:, :, 0]
+    pick, best = first_best(imagined), first_best(true)
+    rows = torch.arange(E, device=true.device)
+    return dict(imagined=imagined, true=true, rank_correlation=rank_correlation(imagined, true), argmax_agree=pick == best,
+                regret=true[rows, best] - true[rows, pick])
