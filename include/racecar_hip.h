@@ -482,6 +482,66 @@ typedef struct rc_policy_dream_ahead_args {
  * rc_policy_dream_sampled_kernel, timed under RC_K_POLICY. */
 int rc_policy_dream_ahead(rc_env *env, const rc_policy_dream_ahead_args *args);
 
+/* The critic and the lambda-return: the forward half of the reference's behaviour learning (dreamer/models.py:113-133 in
+ * `Dreamer.train`; tests/policy_returns_spec.c is the CPU restatement, the device equals it bit for bit).
+ * The rollout is rc_policy_imagine's - closed loop under the actor or open loop under actions_in, in its two modes - and on every
+ * imagined feature run the reward head, the value head (value(feat).mode()) and the pcont head (pcont(feat).mean() = sigmoid of
+ * the logit), each DenseDecoder (models.py:301-318) and each only when an output needs it.  Then, with r, v, p [H] of a row and
+ * p_t = discount where no pcont head is loaded (dreamer/tools.py:396-418 `lambda_return` through `static_scan(reverse=True)`, and
+ * models.py:121-125's cumprod), in binary32:
+ *   R_{H-1} = v_{H-1};  for t = H - 2 .. 0:  in_t = fmaf(p_t * v_{t+1}, 1 - lambda_, r_t),  R_t = fmaf(p_t * lambda_, R_{t+1}, in_t)
+ *   returns[t] = R_t;  weight[0] = 1,  weight[t] = weight[t-1] * p_{t-1}                                          (t < H - 1)
+ * Starts:
+ *   state_in = NULL   the live latents of rc_policy_state, one per car whose slot is in slot_mask; arrays are indexed by car, rows
+ *                     of cars outside the mask are not touched; the draws of RC_POLICY_IMAGINE_SAMPLE are rc_policy_imagine's
+ *                     own, so the same seed gives the same dream.
+ *   state_in given    device float32 [starts, 232] in rc_policy_state's layout (the last two columns are not read); slot_mask
+ *                     must be 0.  The draws are keyed by `seed` and counted by (row_offset + row, t, index) under tag 8 (counter
+ *                     word 3, bits 24-31): not by the workgroup, the shard or the call history.
+ * horizon = 0 runs the heads on the starting features alone (the *_start outputs): the same entry scores arbitrary features.
+ *
+ * rc_policy_critic: the two heads' arrays, host pointers as in rc_policy_heads; the pcont head is optional as a whole (all its
+ * data pointers NULL).  rc_policy_load_critic checks the shapes first (RC_ERR_INVALID names the first that is wrong), needs a
+ * loaded policy and copies the arrays; h = NULL drops both heads, and so do rc_policy_load and rc_policy_unload. */
+typedef struct rc_policy_critic {
+    uint32_t struct_size;          /* = sizeof(rc_policy_critic) */
+    rc_policy_array value_h0_w, value_h0_b;                    /* [230, 400], [400]   input [stoch, deter]                     */
+    rc_policy_array value_h1_w, value_h1_b;                    /* [400, 400], [400]                                            */
+    rc_policy_array value_h2_w, value_h2_b;                    /* [400, 400], [400]                                            */
+    rc_policy_array value_hout_w, value_hout_b;                /* [400, 1], [1]                                                */
+    rc_policy_array pcont_h0_w, pcont_h0_b;                    /* the same shapes, or all eight data = NULL: no pcont head     */
+    rc_policy_array pcont_h1_w, pcont_h1_b;
+    rc_policy_array pcont_h2_w, pcont_h2_b;
+    rc_policy_array pcont_hout_w, pcont_hout_b;
+} rc_policy_critic;
+int rc_policy_load_critic(rc_env *env, const rc_policy_critic *h);
+typedef struct rc_policy_returns_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_returns_args) */
+    int32_t horizon;               /* H in [0, RC_POLICY_IMAGINE_MAX_HORIZON]; 0: *_start outputs only; returns, weight: H >= 2 */
+    int32_t mode;                  /* RC_POLICY_IMAGINE_* */
+    uint32_t slot_mask;            /* live latents: bit a = slot a, as rc_policy_act's; with state_in: 0 */
+    float lambda_;                 /* in [0, 1]; the reference's disclam is 0.95 */
+    float discount;                /* in [0, 1]: the constant pcont when no pcont head is loaded; the reference's is 0.99 */
+    uint64_t seed;
+    int64_t starts;                /* with state_in: its rows, in [1, 2^31) (live latents: not read) */
+    uint64_t row_offset;           /* with state_in: the id of row 0 (mode SAMPLE) */
+    const float *state_in;         /* device float32 [starts, 232], or NULL: the live latents */
+    const float *actions_in;       /* device float32 [rows, H, 2] raw (clamped), or NULL: the actor's own actions */
+    float *reward, *value, *pcont; /* device float32 [rows, H], or NULL */
+    float *returns, *weight;       /* device float32 [rows, H - 1], or NULL */
+    float *actions;                /* device float32 [rows, H, 2], or NULL */
+    float *features;               /* device float32 [rows, H, 230], or NULL */
+    float *reward_start, *value_start, *pcont_start;      /* device float32 [rows], or NULL: the heads on the starting feature */
+} rc_policy_returns_args;
+/* rc_policy_returns: one launch on the handle's stream; rows = n_cars (live) or starts.  A pure function of its inputs: the agent's
+ * state, RC_F_ACTION_IN, the arena, the episode log and every counter stay as they are.  RC_ERR_INVALID: wrong struct_size, no
+ * policy loaded, the policy loaded without img2 / img3, no output asked for, value, returns or value_start without a value head,
+ * reward, returns or reward_start without a reward head, pcont_start without a pcont head, horizon outside [0, 64] or too short
+ * for the outputs asked for, unknown mode, lambda_ or discount not finite or outside [0, 1], state_in together with a non-zero mask
+ * or starts outside [1, 2^31), live latents with an empty mask or bits beyond cars_per_env.  Kernels: rc_policy_returns_kernel,
+ * rc_policy_returns_sampled_kernel, timed under RC_K_POLICY. */
+int rc_policy_returns(rc_env *env, const rc_policy_returns_args *args);
+
 /* Recorded sequences: the posterior chain over N recorded windows of T scans and actions (DESIGN.md §2 item 17;
  * tests/policy_observe_spec.c is the CPU restatement, the device equals it bit for bit) - dreamer/models.py:325-336 RSSM.observe,
  * the operation the reference runs on every replay batch: `post, prior = observe(embed, action)`, kl_divergence(post, prior) and the

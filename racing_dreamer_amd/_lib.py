@@ -117,6 +117,34 @@ class RcPolicyDreamAheadArgs(C.Structure):
                 ("actions_in", C.c_void_p), ("ret", C.c_void_p), ("reward", C.c_void_p), ("final_feature", C.c_void_p)]
 
 
+_CRITIC_LAYERS = ("h0_w", "h0_b", "h1_w", "h1_b", "h2_w", "h2_b", "hout_w", "hout_b")
+VALUE_KEYS = tuple("value_" + k for k in _CRITIC_LAYERS)
+PCONT_KEYS = tuple("pcont_" + k for k in _CRITIC_LAYERS)
+CRITIC_KEYS = VALUE_KEYS + PCONT_KEYS
+
+
+class RcPolicyCritic(C.Structure):
+    """rc_policy_critic (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, RcPolicyArray) for k in CRITIC_KEYS]
+
+
+# policy_returns' output names -> (rc_policy_returns_args field, trailing shape after [rows] as a function of H)
+RETURNS_OUTPUTS = {"reward": ("reward", lambda H: (H,)), "value": ("value", lambda H: (H,)), "pcont": ("pcont", lambda H: (H,)),
+                   "returns": ("returns", lambda H: (H - 1,)), "weight": ("weight", lambda H: (H - 1,)),
+                   "actions": ("actions", lambda H: (H, 2)), "features": ("features", lambda H: (H, POLICY_FEATURE)),
+                   "reward_start": ("reward_start", lambda H: ()), "value_start": ("value_start", lambda H: ()),
+                   "pcont_start": ("pcont_start", lambda H: ())}
+
+
+class RcPolicyReturnsArgs(C.Structure):
+    """rc_policy_returns_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("horizon", C.c_int32), ("mode", C.c_int32), ("slot_mask", C.c_uint32), ("lambda_", C.c_float),
+                ("discount", C.c_float), ("seed", C.c_uint64), ("starts", C.c_int64), ("row_offset", C.c_uint64), ("state_in", C.c_void_p),
+                ("actions_in", C.c_void_p), ("reward", C.c_void_p), ("value", C.c_void_p), ("pcont", C.c_void_p), ("returns", C.c_void_p),
+                ("weight", C.c_void_p), ("actions", C.c_void_p), ("features", C.c_void_p), ("reward_start", C.c_void_p),
+                ("value_start", C.c_void_p), ("pcont_start", C.c_void_p)]
+
+
 LOOK_AHEAD_MAX_HORIZON = 64
 LA_DONE, LA_TRUNCATED, LA_WALL, LA_OPPONENT, LA_WRONG_WAY = 1, 2, 4, 8, 16      # rc_look_ahead's flags
 # look_ahead's output names -> (rc_look_ahead_args field, torch dtype name, shape as a function of (E, K, H, A))
@@ -200,6 +228,21 @@ def policy_heads(weights):
     return h, _fill_arrays(h, weights, HEAD_KEYS)
 
 
+def policy_critic(weights):
+    """rc_policy_critic over a mapping that holds the value_* arrays and, optionally, the pcont_* arrays (or an .npz path), as
+    policy_heads; None if it holds no value_* array."""
+    import numpy as np
+    if isinstance(weights, (str, os.PathLike)):
+        weights = np.load(weights)
+    keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
+    if not any(k.startswith("value_") for k in keys):
+        return None
+    h = RcPolicyCritic()
+    h.struct_size = C.sizeof(RcPolicyCritic)
+    pcont = PCONT_KEYS if any(k.startswith("pcont_") for k in keys) else ()
+    return h, _fill_arrays(h, weights, VALUE_KEYS + pcont)
+
+
 def policy_decoder(weights):
     """rc_policy_decoder over a mapping that holds the dec_* arrays of a LidarOccupancyDecoder (or an .npz path), as policy_heads;
     None if it holds none."""
@@ -258,6 +301,8 @@ SYMBOLS = {
     "rc_policy_load_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
     "rc_policy_imagine": (C.c_int, [C.c_void_p, _P(RcPolicyImagineArgs)]),
     "rc_policy_dream_ahead": (C.c_int, [C.c_void_p, _P(RcPolicyDreamAheadArgs)]),
+    "rc_policy_load_critic": (C.c_int, [C.c_void_p, _P(RcPolicyCritic)]),
+    "rc_policy_returns": (C.c_int, [C.c_void_p, _P(RcPolicyReturnsArgs)]),
     "rc_policy_observe": (C.c_int, [C.c_void_p, _P(RcPolicyObserveArgs)]),
     "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
     "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),

@@ -189,6 +189,64 @@ def _dream_setup(env, actions, mode, seed, state, row_offset, slots, discount, o
     return args, tensors, result
 
 
+def _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, row_offset, slots, outputs, out):
+    """policy_returns' arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
+    rc_policy_returns_args field - one row per start -, the dict to return).  What only the library can tell (no policy, a missing
+    head, slots with a state, a horizon too short for the outputs) is left to it, which names it."""
+    if mode not in L.IMAGINE_MODES:
+        raise ValueError(f"policy_returns mode must be one of {sorted(L.IMAGINE_MODES)}, got {mode!r}")
+    H, S = int(horizon), env.n_cars
+    if not 0 <= H <= L.IMAGINE_MAX_HORIZON:
+        raise ValueError(f"horizon must be in [0, {L.IMAGINE_MAX_HORIZON}], got {horizon}")
+    if state is not None:
+        if state.dim() < 1 or state.shape[-1] != L.POLICY_FEATURE + 2 or state.numel() == 0:
+            raise ValueError(f"state must be [starts >= 1, {L.POLICY_FEATURE + 2}] = stoch | deter | (2 unused), got {tuple(state.shape)}")
+        S = state.numel() // (L.POLICY_FEATURE + 2)
+    lambda_, discount = float(lambda_), float(discount)
+    if not 0.0 <= lambda_ <= 1.0 or not 0.0 <= discount <= 1.0:
+        raise ValueError(f"lambda_ and discount must be in [0, 1], got {lambda_} and {discount}")
+    names = tuple(outputs)
+    unknown = [n for n in names if n not in L.RETURNS_OUTPUTS]
+    if unknown:
+        raise ValueError(f"policy_returns outputs must be among {sorted(L.RETURNS_OUTPUTS)}, got {unknown}")
+    tensors, result = {"state_in": None, "actions_in": None}, {}
+    tensors.update({field: None for field, _ in L.RETURNS_OUTPUTS.values()})
+    if actions is not None and H > 0:
+        tensors["actions_in"] = actions.to(env.device, torch.float32).reshape(S, H, 2).contiguous()
+    if state is not None:
+        tensors["state_in"] = state.to(env.device, torch.float32).reshape(S, L.POLICY_FEATURE + 2).contiguous()
+        mask = 0 if slots is None else sum({1 << int(b) for b in slots})        # (slots with a state: the library refuses and says why)
+    else:
+        mask = (1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(b) for b in slots})
+    for name in names:
+        field, tail = L.RETURNS_OUTPUTS[name]
+        shape = (S,) + tuple(max(d, 0) for d in tail(H))
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = (torch.empty if slots is None else torch.zeros)(shape, dtype=torch.float32, device=env.device)
+        elif t.shape != shape or t.dtype != torch.float32 or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of shape {shape} on {env.device}")
+        tensors[field] = result[name] = t
+    args = dict(horizon=H, mode=L.IMAGINE_MODES[mode], mask=mask, lambda_=lambda_, discount=discount, seed=int(seed) & (2 ** 64 - 1),
+                starts=S, row_offset=int(row_offset) & (2 ** 64 - 1), live=state is None)
+    return args, tensors, result
+
+
+def _value_setup(env, features, slots, outputs):
+    """policy_value as an H = 0 policy_returns: (the state [rows, 232] or None, the leading shape, the *_start output names)."""
+    names = tuple(outputs)
+    unknown = [n for n in names if n not in ("reward", "value", "pcont")]
+    if unknown:
+        raise ValueError(f"policy_value outputs must be among ['pcont', 'reward', 'value'], got {unknown}")
+    if features is None:
+        return None, (env.n_cars,), tuple(n + "_start" for n in names)
+    if features.shape[-1] != L.POLICY_FEATURE or features.numel() == 0:
+        raise ValueError(f"features must be [..., {L.POLICY_FEATURE}] with at least one row, got {tuple(features.shape)}")
+    lead = tuple(features.shape[:-1])
+    flat = features.to(env.device, torch.float32).reshape(-1, L.POLICY_FEATURE)
+    return torch.nn.functional.pad(flat, (0, 2)), lead, tuple(n + "_start" for n in names)
+
+
 def _look_ahead_setup(env, actions, repeat, outputs, out):
     """look_ahead's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
     rc_look_ahead_args field - env-major, one row per env -, the dict to return)."""
@@ -790,6 +848,74 @@ class BatchedRaceEnv:
         if decoder is not None:
             L.check(self._lib.rc_policy_load_decoder(self._h, C.byref(decoder[0])))
             self._policy_has_decoder = True
+        self._policy_has_value = self._policy_has_pcont = False      # (and a critic)
+        if L.policy_critic(weights) is not None:
+            self.load_critic(weights)
+
+    def load_critic(self, weights) -> None:
+        """Load the critic of a Dreamer agent beside the loaded policy (`rc_policy_load_critic`): a mapping (or an .npz path) with
+        the value head's `value_h0_w` .. `value_hout_b` (DenseDecoder((), 3, 400): [230, 400], [400], 2 x ([400, 400], [400]),
+        [400, 1], [1]) and, optionally, the pcont head's `pcont_*` of the same shapes - `critic.init_critic` makes a synthetic
+        pair, `critic.critic_from_variables` picks a trained one out of the reference's `variables.pkl`.  None drops both heads;
+        so do `load_policy` and `unload_policy`.  Shapes are checked by the library."""
+        if weights is None:
+            L.check(self._lib.rc_policy_load_critic(self._h, None))
+            self._policy_has_value = self._policy_has_pcont = False
+            return
+        critic = L.policy_critic(weights)
+        if critic is None:
+            raise KeyError("critic weights lack the value_* arrays")
+        L.check(self._lib.rc_policy_load_critic(self._h, C.byref(critic[0])))
+        self._policy_has_value = True
+        self._policy_has_pcont = bool(critic[0].pcont_hout_w.data)
+
+    @property
+    def policy_has_value_head(self) -> bool:
+        """Whether a value head is loaded (`value_*` arrays: `load_critic`, or a checkpoint that holds them)."""
+        return bool(getattr(self, "_policy_has_value", False))
+
+    @property
+    def policy_has_pcont_head(self) -> bool:
+        """Whether a pcont head is loaded (`pcont_*` arrays); without one `policy_returns` uses the constant `discount`."""
+        return bool(getattr(self, "_policy_has_pcont", False))
+
+    def _returns(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_returns on this handle: from its live latents, reading and writing rows [lo, hi) of the tensors (one row per
+        car), or from a given state, the whole tensors."""
+        a = L.RcPolicyReturnsArgs(C.sizeof(L.RcPolicyReturnsArgs), args["horizon"], args["mode"], args["mask"], args["lambda_"], args["discount"],
+                                  args["seed"], args["starts"], args["row_offset"])
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else (t[lo:hi] if args["live"] else t).data_ptr())
+        return self._lib.rc_policy_returns(self._h, C.byref(a))
+
+    def policy_returns(self, horizon: int = 15, mode: str = "mean", seed: int = 0, lambda_: float = 0.95, discount: float = 0.99,
+                       actions: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None, row_offset: int = 0, slots=None,
+                       outputs=("returns", "weight"), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """The forward half of the reference's behaviour learning (`rc_policy_returns`, one launch; dreamer/models.py:113-133):
+        `policy_imagine`'s rollout - closed loop, or open loop under `actions` [S, horizon, 2] - with the reward, value and pcont
+        heads on every imagined feature, then the lambda-return and the discount weights, all on the device.  The starts are
+        every car's latent as `policy_act` last left it (S = n_cars, `policy_imagine`'s draws for the same seed; with `slots`,
+        rows of the other cars are zero - or what `out` held), or `state` float32 [S, 232] = stoch | deter | (2 unused), whose
+        draws in mode "sample" depend on (seed, `row_offset` + row, t) only, so shards of a batch reproduce the whole.  Without
+        a pcont head pcont is the constant `discount`.  `outputs` names what to compute, each a device float32 tensor:
+        `returns`, `weight` [S, H - 1] (H >= 2; returns[t] = R_t, weight = cumprod([1, pcont[:-2]])), `reward`, `value`, `pcont`
+        [S, H], `actions` [S, H, 2], `features` [S, H, 230], `reward_start`, `value_start`, `pcont_start` [S] (the heads on the
+        starting feature; horizon 0 asks for them alone).  Nothing else changes: not the agent's state, not `action_in`."""
+        args, tensors, result = _returns_setup(self, horizon, mode, seed, lambda_, discount, actions, state, row_offset, slots, outputs, out)
+        self._enter()
+        try:
+            L.check(self._returns(args, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
+
+    def policy_value(self, features: Optional[torch.Tensor] = None, slots=None, outputs=("value",)) -> Dict[str, torch.Tensor]:
+        """The heads on given features (a horizon-0 `policy_returns`): `features` float32 [..., 230] = stoch | deter, e.g.
+        `dream_ahead(...)["final_feature"]`, or None for every car's live latent (with `slots`: the other cars' rows are zero).
+        `outputs` among "value", "reward", "pcont"; each comes back as a device float32 tensor of the leading shape."""
+        state, lead, names = _value_setup(self, features, slots, outputs)
+        got = self.policy_returns(horizon=0, state=state, slots=slots, outputs=names)
+        return {n[:-6]: got[n].reshape(lead) for n in names}
 
     @property
     def policy_has_decoder(self) -> bool:
@@ -989,6 +1115,7 @@ class BatchedRaceEnv:
         self._policy_state = None
         self._policy_has_head = False
         self._policy_has_decoder = False
+        self._policy_has_value = self._policy_has_pcont = False
         L.check(self._lib.rc_policy_unload(self._h))
 
     # ------------------------------------------------------------------ episode log (include/racecar_hip.h, rc_episode_log_*)
@@ -1407,6 +1534,40 @@ class MixedTrackEnv:
         else:
             self._fork_join(lambda p, blk: p._dream_ahead(args, tensors, blk[0] * k, blk[1] * k))
         return result
+
+    def load_critic(self, weights) -> None:
+        """The critic on every block (BatchedRaceEnv.load_critic)."""
+        if isinstance(weights, (str, os.PathLike)):
+            weights = dict(np.load(weights))
+        for p in self.parts:
+            p.load_critic(weights)
+
+    @property
+    def policy_has_value_head(self) -> bool:
+        return self.parts[0].policy_has_value_head
+
+    @property
+    def policy_has_pcont_head(self) -> bool:
+        return self.parts[0].policy_has_pcont_head
+
+    def policy_returns(self, horizon: int = 15, mode: str = "mean", seed: int = 0, lambda_: float = 0.95, discount: float = 0.99,
+                       actions: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None, row_offset: int = 0, slots=None,
+                       outputs=("returns", "weight"), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_returns over all blocks: each block starts from its cars' latents and writes its rows of one tensor
+        per output; a given `state` (every block holds the same weights) goes through the first block."""
+        args, tensors, result = _returns_setup(self, horizon, mode, seed, lambda_, discount, actions, state, row_offset, slots, outputs, out)
+        k = self.cars_per_env
+        if state is not None:
+            self._ordered(lambda: self.parts[0]._returns(args, tensors, 0, 0))
+        else:
+            self._fork_join(lambda p, blk: p._returns(args, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def policy_value(self, features: Optional[torch.Tensor] = None, slots=None, outputs=("value",)) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_value: given features go through the first block, live latents through every block."""
+        state, lead, names = _value_setup(self, features, slots, outputs)
+        got = self.policy_returns(horizon=0, state=state, slots=slots, outputs=names)
+        return {n[:-6]: got[n].reshape(lead) for n in names}
 
     def look_ahead(self, actions: torch.Tensor, repeat: Optional[int] = None, outputs=("reward", "flags", "return", "length"),
                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:

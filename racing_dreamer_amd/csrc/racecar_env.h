@@ -202,6 +202,8 @@ struct rc_env {
     float *pol_heads_mem = nullptr;    // rc_policy_load_heads
     RcDecodeDev pol_d{};               // rc_policy_decode: the decoder's repacked arrays (null = none loaded)
     float *pol_dec_mem = nullptr;      // rc_policy_load_decoder
+    RcCriticDev pol_c{};               // rc_policy_returns: the value head and the pcont head (null = none loaded)
+    float *pol_critic_mem = nullptr;   // rc_policy_load_critic
     rc_policy_sampling pol_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};      // rc_policy_set_sampling
     float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
     float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)

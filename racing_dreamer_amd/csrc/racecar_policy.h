@@ -98,6 +98,36 @@ struct RcDreamCall {
     float *ret, *reward, *final_feature;     // [starts][K], [starts][K][H], [starts][K][230]; any may be null
 };
 
+// The critic (racecar_returns.hip): the value head and the optional pcont head, DenseDecoder((), 3, 400)
+// each, packed like the reward head
+struct RcCriticDev {
+    const float *vh_w[3], *vh_b[3];          // value head [230][416], 2 x [400][416]; [416]; null = no critic loaded
+    const float *vout_w, *vout_b;            // [400][32], [32]         its one output column
+    const float *ph_w[3], *ph_b[3];          // pcont head, the same shapes; null = none (a constant pcont)
+    const float *pout_w, *pout_b;
+};
+
+// Rows are starts: the cars of the mask (live: arrays indexed by car) or the rows of a given state
+struct RcReturnsCall {
+    RcPolicyDev w;
+    RcPolicySampleDev ws;
+    RcImagineDev wi;
+    RcCriticDev wc;
+    const float *state;                      // live: [n_cars][RC_POLICY_STATE] of the handle; else the caller's [starts][RC_POLICY_STATE]; read only
+    RcPolicyRows rows;                       // live: row -> car, and the key of its draws (rc_policy_imagine's)
+    int32_t live;
+    int64_t n_rows;                          // < 2^31
+    uint64_t row_offset;                     // not live: the id of row 0; the draws are keyed by (row id, t)
+    int32_t horizon, sample;
+    uint32_t seed_lo, seed_hi;               // (not live)
+    float lambda, discount;
+    const float *actions_in;                 // [rows][H][2] raw, or null: the actor's own
+    float *reward, *value, *pcont;           // [rows][H]; any output may be null
+    float *returns, *weight;                 // [rows][H - 1]
+    float *actions, *features;               // [rows][H][2], [rows][H][230]
+    float *reward_start, *value_start, *pcont_start;      // [rows]
+};
+
 // Recorded sequences (racecar_observe.hip): rows are windows [T] of scans and actions, not cars of the env
 struct RcObserveCall {
     RcPolicyDev w;
@@ -148,5 +178,7 @@ hipError_t rck_dream_prepare();
 hipError_t rck_launch_dream(const RcDreamCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                    // c.sample: which kernel
 hipError_t rck_observe_prepare();
 hipError_t rck_launch_observe(const RcObserveCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
+hipError_t rck_returns_prepare();
+hipError_t rck_launch_returns(const RcReturnsCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
 hipError_t rck_decode_prepare();
 hipError_t rck_launch_decode(const RcDecodeCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);

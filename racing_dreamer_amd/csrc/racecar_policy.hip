@@ -364,6 +364,26 @@ const PolImage<PH> kHeadImages[] = {
     {"reward_hout_w", &PH::reward_hout_w, 400, 1, false, 1, 1, 1, LDSM, POL_DST(pol_i.rout_w)},
     {"reward_hout_b", &PH::reward_hout_b, 1, 1, false, 1, 1, 1, LDSM, POL_DST(pol_i.rout_b)},
 };
+// the critic's two heads (rc_policy_load_critic): the pcont head is optional as a whole
+using PC = rc_policy_critic;
+const PolImage<PC> kCriticImages[] = {
+    {"value_h0_w", &PC::value_h0_w, 230, 400, false, 1, 400, 400, LD4, POL_DST(pol_c.vh_w[0])},
+    {"value_h0_b", &PC::value_h0_b, 1, 400, false, 1, 400, 400, LD4, POL_DST(pol_c.vh_b[0])},
+    {"value_h1_w", &PC::value_h1_w, 400, 400, false, 1, 400, 400, LD4, POL_DST(pol_c.vh_w[1])},
+    {"value_h1_b", &PC::value_h1_b, 1, 400, false, 1, 400, 400, LD4, POL_DST(pol_c.vh_b[1])},
+    {"value_h2_w", &PC::value_h2_w, 400, 400, false, 1, 400, 400, LD4, POL_DST(pol_c.vh_w[2])},
+    {"value_h2_b", &PC::value_h2_b, 1, 400, false, 1, 400, 400, LD4, POL_DST(pol_c.vh_b[2])},
+    {"value_hout_w", &PC::value_hout_w, 400, 1, false, 1, 1, 1, LDSM, POL_DST(pol_c.vout_w)},
+    {"value_hout_b", &PC::value_hout_b, 1, 1, false, 1, 1, 1, LDSM, POL_DST(pol_c.vout_b)},
+    {"pcont_h0_w", &PC::pcont_h0_w, 230, 400, true, 1, 400, 400, LD4, POL_DST(pol_c.ph_w[0])},
+    {"pcont_h0_b", &PC::pcont_h0_b, 1, 400, true, 1, 400, 400, LD4, POL_DST(pol_c.ph_b[0])},
+    {"pcont_h1_w", &PC::pcont_h1_w, 400, 400, true, 1, 400, 400, LD4, POL_DST(pol_c.ph_w[1])},
+    {"pcont_h1_b", &PC::pcont_h1_b, 1, 400, true, 1, 400, 400, LD4, POL_DST(pol_c.ph_b[1])},
+    {"pcont_h2_w", &PC::pcont_h2_w, 400, 400, true, 1, 400, 400, LD4, POL_DST(pol_c.ph_w[2])},
+    {"pcont_h2_b", &PC::pcont_h2_b, 1, 400, true, 1, 400, 400, LD4, POL_DST(pol_c.ph_b[2])},
+    {"pcont_hout_w", &PC::pcont_hout_w, 400, 1, true, 1, 1, 1, LDSM, POL_DST(pol_c.pout_w)},
+    {"pcont_hout_b", &PC::pcont_hout_b, 1, 1, true, 1, 1, 1, LDSM, POL_DST(pol_c.pout_b)},
+};
 #undef POL_DST
 const rc_policy_sampling kPolSamplingDefault = {(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};
 
@@ -427,6 +447,18 @@ int pol_drop_decoder(rc_env *env) {
         env->pol_dec_mem = nullptr;
     }
     env->pol_d = RcDecodeDev{};
+    return RC_OK;
+}
+
+// the critic's memory and pointers go (rc_policy_load_critic(NULL), a new rc_policy_load)
+int pol_drop_critic(rc_env *env) {
+    if (env->pol_critic_mem) {
+        HIP_TRY(hipSetDevice(env->cfg.device));
+        HIP_TRY(hipStreamSynchronize(env->stream));
+        (void)hipFree(env->pol_critic_mem);
+        env->pol_critic_mem = nullptr;
+    }
+    env->pol_c = RcCriticDev{};
     return RC_OK;
 }
 
@@ -503,6 +535,7 @@ int pol_launch(rc_env *env, hipError_t (*launch)(const Call &, hipEvent_t, hipEv
 void policy_release(rc_env *env) {
     (void)pol_drop_heads(env);
     (void)pol_drop_decoder(env);
+    (void)pol_drop_critic(env);
     if (env->pol_mem) (void)hipFree(env->pol_mem);
     if (env->pol_state) (void)hipFree(env->pol_state);
     env->pol_mem = env->pol_state = nullptr;
@@ -543,9 +576,12 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(rck_dream_prepare());
     HIP_TRY(rck_observe_prepare());
     HIP_TRY(rck_decode_prepare());
+    HIP_TRY(rck_returns_prepare());
     rc = pol_drop_heads(env);
     if (rc) return rc;
     rc = pol_drop_decoder(env);
+    if (rc) return rc;
+    rc = pol_drop_critic(env);
     if (rc) return rc;
     if (!env->pol_mem) HIP_TRY(hipMalloc((void **)&env->pol_mem, img.size() * sizeof(float)));
     const size_t state_bytes = (size_t)env->n_cars * RC_POLICY_STATE * sizeof(float);
@@ -718,6 +754,85 @@ int rc_policy_dream_ahead(rc_env *env, const rc_policy_dream_ahead_args *a) {
     c.actions_in = a->actions_in;
     c.ret = a->ret; c.reward = a->reward; c.final_feature = a->final_feature;
     return pol_launch(env, rck_launch_dream, c);
+}
+
+int rc_policy_load_critic(rc_env *env, const rc_policy_critic *h) {
+    if (!h) {
+        if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+        return pol_drop_critic(env);
+    }
+    if (h->struct_size != sizeof(rc_policy_critic))
+        return fail(RC_ERR_INVALID, "rc_policy_critic.struct_size %u != %zu", h->struct_size, sizeof(rc_policy_critic));
+    const int rc = pol_check(kCriticImages, *h, "rc_policy_load_critic", "the head's");
+    if (rc) return rc;
+    int n_pcont = 0;
+    for (const PolImage<PC> &im : kCriticImages) n_pcont += im.optional && (h->*(im.arr)).data;
+    if (n_pcont != 0 && n_pcont != 8) return fail(RC_ERR_INVALID, "rc_policy_load_critic: %d of the eight pcont_* arrays given (all or none)", n_pcont);
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_load_critic: no policy loaded (rc_policy_load)");
+    std::vector<float> img;
+    size_t at[sizeof(kCriticImages) / sizeof(kCriticImages[0])];
+    pol_pack(kCriticImages, *h, img, at);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    if (!env->pol_critic_mem) HIP_TRY(hipMalloc((void **)&env->pol_critic_mem, img.size() * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(env->pol_critic_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
+    pol_point(kCriticImages, *h, env, env->pol_critic_mem, at);
+    return RC_OK;
+}
+
+int rc_policy_returns(rc_env *env, const rc_policy_returns_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_returns_args))
+        return fail(RC_ERR_INVALID, "rc_policy_returns_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_returns_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_returns: no policy loaded (rc_policy_load)");
+    if (!env->pol_i.img3_w) return fail(RC_ERR_INVALID, "rc_policy_returns: the policy was loaded without the prior's layers img2 / img3");
+    const bool steps = a->reward || a->value || a->pcont || a->returns || a->weight || a->actions || a->features;
+    if (!steps && !a->reward_start && !a->value_start && !a->pcont_start) return fail(RC_ERR_INVALID, "rc_policy_returns: no output asked for");
+    if ((a->value || a->returns || a->value_start) && !env->pol_c.vout_w)
+        return fail(RC_ERR_INVALID, "rc_policy_returns: a value is asked for and no value head is loaded (rc_policy_load_critic)");
+    if ((a->reward || a->returns || a->reward_start) && !env->pol_i.rout_w)
+        return fail(RC_ERR_INVALID, "rc_policy_returns: a reward is asked for and no reward head is loaded (rc_policy_load_heads)");
+    if (a->pcont_start && !env->pol_c.pout_w)
+        return fail(RC_ERR_INVALID, "rc_policy_returns: pcont_start is asked for and no pcont head is loaded (rc_policy_load_critic)");
+    const int h_min = (a->returns || a->weight) ? 2 : (steps ? 1 : 0);
+    if (a->horizon < h_min || a->horizon > RC_POLICY_IMAGINE_MAX_HORIZON)
+        return fail(RC_ERR_INVALID, "rc_policy_returns: horizon %d is outside [%d, %d] (0: the *_start outputs alone; returns and weight: 2 and more)",
+                    a->horizon, h_min, RC_POLICY_IMAGINE_MAX_HORIZON);
+    if (a->mode != RC_POLICY_IMAGINE_MEAN && a->mode != RC_POLICY_IMAGINE_SAMPLE) return fail(RC_ERR_INVALID, "rc_policy_returns: unknown mode %d", a->mode);
+    if (!(a->lambda_ >= 0.0f && a->lambda_ <= 1.0f))
+        return fail(RC_ERR_INVALID, "rc_policy_returns: lambda_ %g is not a number in [0, 1]", (double)a->lambda_);
+    if (!(a->discount >= 0.0f && a->discount <= 1.0f))
+        return fail(RC_ERR_INVALID, "rc_policy_returns: discount %g is not a number in [0, 1]", (double)a->discount);
+    RcReturnsCall c{};
+    if (a->state_in) {
+        if (a->slot_mask) return fail(RC_ERR_INVALID, "rc_policy_returns: a slot mask (0x%x) goes with the live latents, not with a given state_in", a->slot_mask);
+        if (a->starts < 1 || a->starts > (int64_t)INT32_MAX)
+            return fail(RC_ERR_INVALID, "rc_policy_returns: starts %lld is outside [1, 2^31)", (long long)a->starts);
+        c.n_rows = a->starts;
+        c.state = a->state_in;
+        c.row_offset = a->row_offset;
+    } else {
+        const int rc = pol_rows(env, a->slot_mask, a->seed, "rc_policy_returns", &c.rows);
+        if (rc) return rc;
+        c.n_rows = c.rows.n_active;
+        c.state = env->pol_state;
+        c.live = 1;
+    }
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    c.w = env->pol;
+    c.ws = env->pol_s;
+    c.wi = env->pol_i;
+    c.wc = env->pol_c;
+    c.horizon = a->horizon;
+    c.sample = a->mode == RC_POLICY_IMAGINE_SAMPLE;
+    c.seed_lo = seed_lo(a->seed); c.seed_hi = seed_hi(a->seed);
+    c.lambda = a->lambda_; c.discount = a->discount;
+    c.actions_in = a->horizon > 0 ? a->actions_in : nullptr;
+    c.reward = a->reward; c.value = a->value; c.pcont = a->pcont; c.returns = a->returns; c.weight = a->weight;
+    c.actions = a->actions; c.features = a->features;
+    c.reward_start = a->reward_start; c.value_start = a->value_start; c.pcont_start = a->pcont_start;
+    return pol_launch(env, rck_launch_returns, c);
 }
 
 int rc_policy_observe(rc_env *env, const rc_policy_observe_args *a) {

@@ -223,6 +223,16 @@ __device__ __forceinline__ void pm_dream_normal_block(uint32_t id_lo, uint32_t i
     pm_normal_word(id_lo, id_hi, cand, block | (t << 8) | (PM_DREAM_TAG << 24), seed_lo, seed_hi, n);
 }
 
+// ---- lambda-returns from given states: tests/policy_returns_spec.c restates what follows
+#define PM_RETURNS_TAG 8u                  // Philox counter word 3, bits 24-31
+
+// the four normals of block `block` (0-7: the 30 normals of stoch', 2 unused; PM_BLOCK_ACTION: words 0-1 the action draw) of
+// imagined step t of the start with the 64-bit id (id_lo, id_hi)
+__device__ __forceinline__ void pm_returns_normal_block(uint32_t id_lo, uint32_t id_hi, uint32_t t, uint32_t block, uint32_t seed_lo,
+                                                        uint32_t seed_hi, float (&n)[4]) {
+    pm_normal_word(id_lo, id_hi, t, block | (PM_RETURNS_TAG << 24), seed_lo, seed_hi, n);
+}
+
 // ---- recorded sequences: tests/policy_observe_spec.c restates what follows
 #define PM_OBSERVE_TAG 6u                  // Philox counter word 3, bits 24-31
 

@@ -79,18 +79,34 @@ def _needs_head(env, who: str) -> None:
         raise RuntimeError(f"{who} needs a checkpoint with a reward head (reward_* arrays)")
 
 
-def dream_shooting_act(env, candidates: Union[int, torch.Tensor] = 64, horizon: int = 15, hold: int = 5, seed: int = 0, slots=None) -> torch.Tensor:
+def _dream_score(env, acts: torch.Tensor, bootstrap: bool, discount: float, **where) -> torch.Tensor:
+    """[starts, K]: the imagined return of every candidate - `dream_ahead`'s call of the planners as it always was - or, with
+    `bootstrap`, the discounted return plus discount^H times the value head on the feature the candidate ends in
+    (`policy_value`): a plan that sees beyond its horizon.  `where`: the caller's `slots`, passed on as it always passed them."""
+    if not bootstrap:
+        return env.dream_ahead(acts, **where, outputs=("return",))["return"]
+    if not env.policy_has_value_head:
+        raise RuntimeError("bootstrap=True needs a value head (load_critic, or a checkpoint with value_* arrays)")
+    got = env.dream_ahead(acts, **where, discount=discount, outputs=("return", "final_feature"))
+    value = env.policy_value(got["final_feature"])["value"]
+    return got["return"] + float(discount) ** int(acts.shape[2]) * value
+
+
+def dream_shooting_act(env, candidates: Union[int, torch.Tensor] = 64, horizon: int = 15, hold: int = 5, seed: int = 0, slots=None,
+                       bootstrap: bool = False, discount: float = 0.99) -> torch.Tensor:
     """Random shooting in the dream: the candidates of `shooting_candidates` (or a tensor of explicit sequences
     [num_envs, K, H, cars_per_env, 2]), each car's own sequences scored by the imagined return from its live latent
     (`dream_ahead`, mode "mean"), the highest taken - the lowest index among equals.  Writes that candidate's first action into
-    `action_in` for the cars in `slots` (None: every car; the others keep theirs) and returns `action_in`."""
+    `action_in` for the cars in `slots` (None: every car; the others keep theirs) and returns `action_in`.  `bootstrap=True`
+    (needs a value head): the score is the return discounted by `discount` plus discount^H times the value of the final
+    feature; `discount` is not read otherwise."""
     _needs_head(env, "dream_shooting_act")
     E, A = env.num_envs, env.cars_per_env
     action_in = env.views["action_in"]
     seq = candidates if torch.is_tensor(candidates) else shooting_candidates(env, candidates, horizon, hold, seed)
     seq = seq.to(action_in.device, torch.float32).reshape(E, -1, seq.shape[2], A, 2)
     acts = to_dream_actions(seq)                                                           # [E A, K, H, 2]
-    ret = env.dream_ahead(acts, slots=slots, outputs=("return",))["return"]                # [E A, K]
+    ret = _dream_score(env, acts, bootstrap, discount, slots=slots)                            # [E A, K]
     best = first_best(ret)
     first = acts[torch.arange(E * A, device=acts.device), best, 0].reshape(E, A, 2)
     flat = action_in.reshape(E, A, 2)
@@ -99,12 +115,13 @@ def dream_shooting_act(env, candidates: Union[int, torch.Tensor] = 64, horizon: 
     return action_in
 
 
-def dream_cem_act(env, candidates: int = 64, horizon: int = 15, iterations: int = 3, elites: int = 8, seed: int = 0) -> torch.Tensor:
+def dream_cem_act(env, candidates: int = 64, horizon: int = 15, iterations: int = 3, elites: int = 8, seed: int = 0,
+                  bootstrap: bool = False, discount: float = 0.99) -> torch.Tensor:
     """The cross-entropy method in the dream (PlaNet's planner): per car a Gaussian over the sequence [H, 2], mean 0 and
     standard deviation 1 at first; `iterations` times, `candidates` sequences are drawn from it (clipped to [-1, 1]), scored by
     the imagined return from the car's live latent, and the Gaussian is refit to the `elites` best (mean, and the biased
     standard deviation).  All draws come from one torch generator seeded with `seed`.  Writes the first action of the final
-    mean into `action_in` and returns `action_in`."""
+    mean into `action_in` and returns `action_in`.  `bootstrap`, `discount`: as `dream_shooting_act`."""
     _needs_head(env, "dream_cem_act")
     K, H, n_it, top = int(candidates), int(horizon), int(iterations), int(elites)
     if K < 1 or H < 1 or n_it < 1 or not 1 <= top <= K:
@@ -120,7 +137,7 @@ def dream_cem_act(env, candidates: int = 64, horizon: int = 15, iterations: int 
     for _ in range(n_it):
         noise = torch.randn((n, K, H, 2), generator=gen, dtype=torch.float32, device=device)
         acts = (mean + std * noise).clamp_(-1.0, 1.0)
-        ret = torch.nan_to_num(env.dream_ahead(acts, outputs=("return",))["return"], nan=float("-inf"))
+        ret = torch.nan_to_num(_dream_score(env, acts, bootstrap, discount), nan=float("-inf"))
         elite = acts[rows, ret.topk(top, dim=1).indices]                                   # [n, top, H, 2]
         mean = elite.mean(dim=1, keepdim=True)
         std = elite.std(dim=1, unbiased=False, keepdim=True)

@@ -36,6 +36,25 @@ def model_terms(env, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return terms
 
 
+def behaviour_terms(env, batch: Dict[str, torch.Tensor], horizon: int = 15, lambda_: float = 0.95, seed: int = 0,
+                    discount: float = 0.99) -> Dict[str, torch.Tensor]:
+    """The forward half of the reference's behaviour learning on a replay batch (dreamer/models.py:113-133),
+    two launches: `policy_observe(mode="sample")` gives the posterior features [B, T, 230]; when a pcont head is loaded each
+    window's last step is dropped (`_imagine_ahead`, models.py:214-215); every remaining feature is a start of one
+    `policy_returns(mode="sample")` under the actor.  Returns `returns`, `weight` [S, H - 1] and `value` [S, H] (S = B x T or
+    B x (T - 1), window-major) and the two scalars of the reference, summed in float64: `actor_loss` = -mean(weight * returns),
+    `value_loss` = -mean(weight * Normal(value[:, :-1], 1).log_prob(returns)).  Forward only: no gradient flows anywhere."""
+    feat = env.policy_observe(batch["lidar"], batch["action"], mode="sample", seed=seed, outputs=("feature",))["feature"]
+    if env.policy_has_pcont_head:
+        feat = feat[..., :-1, :]
+    state = torch.nn.functional.pad(feat.reshape(-1, feat.shape[-1]), (0, 2))
+    out = env.policy_returns(horizon, "sample", seed=seed, lambda_=lambda_, discount=discount, state=state, outputs=("returns", "weight", "value"))
+    w, ret, val = out["weight"].double(), out["returns"].double(), out["value"][:, :-1].double()
+    out["actor_loss"] = -(w * ret).mean()
+    out["value_loss"] = -(w * (-0.5 * (val - ret) ** 2 - 0.5 * math.log(2.0 * math.pi))).mean()
+    return out
+
+
 def imagined_vs_simulated(env, horizon: int = 15, mode: str = "mean", seed: int = 0, repeat=None) -> Dict[str, torch.Tensor]:
     """The world model's dream beside what the simulator would really do, without spending the run:
     `policy_imagine` from every car's latent under the actor's own actions, then `look_ahead` with one candidate per env - those

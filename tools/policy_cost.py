@@ -28,6 +28,14 @@ reward head on top, `sample`, and `mean` with every output - beside `policy_act`
 with the condition: time per observed step <= 1.0 x that call (an observed step performs 0.52 of its multiply-adds), and beside the
 same 15 steps (posterior, prior and KL) in plain fp32 torch, each reported as met or missed.
 
+    python tools/policy_cost.py --returns [--out profiles/policy_returns_cost.json]
+
+`--returns`: the critic and the lambda-return (rc_policy_returns) at 65 536 starts x H = 15, `mean`, outputs returns + weight, both
+heads of a synthetic critic - beside rc_policy_imagine with the reward output on the same cars in the same run, with the condition:
+time per step <= 1.734 x that call's (the ratio of the nominal multiply-adds) x 1.05, reported as met or missed; also the value head
+alone (1.367), `sample`, policy_value on 65 536 x 230 features, and - a record, not a condition - the three heads and a Python
+lambda-return in plain fp32 torch on features already in memory.
+
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
 windows; the torch baseline is timed with stream events around a window of calls (its dozen launches per call included - that is
 what it costs).  The baseline is a RATE baseline: torch.addmm sums in another order than the spec."""
@@ -316,6 +324,123 @@ def measure_imagine(n, args):
     return res
 
 
+# ---- the critic and the lambda-return: nominal multiply-adds per imagined step
+MACS_RETURNS_BASE = MACS_IMAGINED_STEP + 200 * 30                  # actor + prior (img3's 60 columns) + reward head: 1 123 600
+MACS_CRITIC_HEAD = 230 * 400 + 2 * 400 * 400 + 400                 # DenseDecoder((), 3, 400): 412 400
+
+
+class TorchReturns(TorchImagine):
+    """The three heads on given features [n, H, 230] in plain fp32 torch, and the lambda-return as a Python loop over the horizon."""
+
+    def __init__(self, weights, critic, device):
+        import torch
+        super().__init__(weights, device)
+        self.c = {k: torch.from_numpy(v).to(device) for k, v in critic.items()}
+
+    def head(self, w, prefix, layers, h):
+        import torch
+        import torch.nn.functional as F
+        for i in range(layers):
+            h = F.elu(torch.addmm(w[f"{prefix}_h{i}_b"], h, w[f"{prefix}_h{i}_w"]))
+        return torch.addmm(w[f"{prefix}_hout_b"], h, w[f"{prefix}_hout_w"])
+
+    def returns(self, features, lambda_):
+        import torch
+        n, h, _ = features.shape
+        flat = features.reshape(n * h, 230)
+        r = self.head(self.w, "reward", 2, flat).reshape(n, h)
+        v = self.head(self.c, "value", 3, flat).reshape(n, h)
+        p = torch.sigmoid(self.head(self.c, "pcont", 3, flat)).reshape(n, h)
+        agg, out = v[:, -1], []
+        for t in range(h - 2, -1, -1):
+            agg = r[:, t] + p[:, t] * v[:, t + 1] * (1.0 - lambda_) + p[:, t] * lambda_ * agg
+            out.append(agg)
+        weight = torch.cumprod(torch.cat([torch.ones_like(p[:, :1]), p[:, :-2]], 1), 1)
+        return torch.stack(out[::-1], 1), weight
+
+
+def measure_returns(n, args):
+    """Per-call device time (RC_K_POLICY) of rc_policy_returns at H = args.horizon beside rc_policy_imagine with the reward output on
+    the same cars in the same run; the value head alone, mode sample, policy_value on n x 230 features; the torch restatement."""
+    import torch
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    from racing_dreamer_amd.critic import init_critic
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    env = BatchedRaceEnv(args.track, n, 1, auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    critic = init_critic(0)
+    env.load_critic(critic)
+    h = args.horizon
+    res = {"cars": n, "horizon": h}
+
+    def timed(call):
+        for k in range(3):
+            call()
+        windows = []
+        for r in range(args.rounds):
+            env.reset_kernel_times()
+            env.set_profiling(True, kernels=[L.K_POLICY])
+            for k in range(args.calls):
+                call()
+            env.sync()
+            env.set_profiling(False)
+            windows.append(env.kernel_times()["rc_policy_kernel"]["avg_ms"])
+        return statistics.median(windows), [round(v, 4) for v in windows]
+
+    def entry(ms, windows, macs, steps):
+        return {"ms_per_call": round(ms, 4), "windows_ms": windows, "ms_per_step": round(ms / steps, 4),
+                "tflops": round(2 * macs * n * steps / (ms * 1e-3) / 1e12, 2)}
+
+    with torch.cuda.stream(env.stream):
+        env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            env.step(None, repeat=4)
+        env.sync()
+        reward = torch.empty((n, h), device=env.device)
+        a = dict(horizon=h, mode=L.IMAGINE_MODES["mean"], seed=1, mask=1)
+        tensors = dict(actions_in=None, reward=reward, actions=None, features=None, reward_start=None)
+        ms, windows = timed(lambda: L.check(env._imagine(a, tensors, 0, n)))
+        res["imagine_mean_reward"] = entry(ms, windows, MACS_RETURNS_BASE, h)
+        base = ms / h
+        out = {k: torch.empty((n, h - 1), device=env.device) for k in ("returns", "weight")}
+        out["value"] = torch.empty((n, h), device=env.device)
+        for name, mode, pcont, names, macs in (("mean_returns_weight", "mean", True, ("returns", "weight"), MACS_RETURNS_BASE + 2 * MACS_CRITIC_HEAD),
+                                               ("sample_returns_weight", "sample", True, ("returns", "weight"), MACS_RETURNS_BASE + 2 * MACS_CRITIC_HEAD),
+                                               ("mean_returns_value_head_alone", "mean", False, ("returns",), MACS_RETURNS_BASE + MACS_CRITIC_HEAD)):
+            env.load_critic(critic if pcont else {k: v for k, v in critic.items() if k.startswith("value_")})
+            ms, windows = timed(lambda: env.policy_returns(h, mode, seed=1, outputs=names, out=out))
+            res[name] = entry(ms, windows, macs, h)
+            res[name]["step_over_imagine_step"] = round(ms / h / base, 4)
+        env.load_critic(critic)
+        for name, ratio in (("mean_returns_weight", (MACS_RETURNS_BASE + 2 * MACS_CRITIC_HEAD) / MACS_RETURNS_BASE),
+                            ("mean_returns_value_head_alone", (MACS_RETURNS_BASE + MACS_CRITIC_HEAD) / MACS_RETURNS_BASE)):
+            limit = ratio * base * 1.05
+            res[name].update(macs_ratio=round(ratio, 3), target_ms_per_step=round(limit, 4), met=bool(res[name]["ms_per_step"] <= limit),
+                             step_over_target=round(res[name]["ms_per_step"] / limit, 4))
+        feats = env.policy_imagine(1, features=True)["feature"].reshape(n, 230).contiguous()
+        ms, windows = timed(lambda: env.policy_value(feats))
+        res["policy_value_features"] = entry(ms, windows, MACS_CRITIC_HEAD, 1)
+        # ---- a record, not a condition: the three heads and the recursion in plain fp32 torch on features already in memory
+        features = env.policy_imagine(h, features=True)["feature"]
+        agent = TorchReturns(weights, critic, env.device)
+        for k in range(2):
+            agent.returns(features, 0.95)
+        windows = []
+        for r in range(args.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k in range(max(1, args.calls // 4)):
+                agent.returns(features, 0.95)
+            e1.record()
+            e1.synchronize()
+            windows.append(e0.elapsed_time(e1) / max(1, args.calls // 4))
+        res["torch_fp32_heads_and_recursion_ms_per_call"] = round(statistics.median(windows), 4)
+    env.close()
+    return res
+
+
 FMA_PER_IMAGE = 230 * 64 + 64 * 800 + 320000 + 778752 + 259200          # h1 .. h5 (issue #16's table): 1 423 872
 FMA_PER_S_PEAK = 256 * 4 * 32 * 2.4e9      # 256 CUs x 4 SIMDs x 32 fp32 fma per clock (v_pk_fma_f32: 64 FLOP / clk / SIMD) x 2.4 GHz
 
@@ -511,9 +636,24 @@ def main():
     ap.add_argument("--imagine", action="store_true", help="measure imagination (profiles/policy_imagine_cost.json)")
     ap.add_argument("--decode", action="store_true", help="measure the observation decoder (profiles/policy_decode_cost.json)")
     ap.add_argument("--observe", action="store_true", help="measure recorded sequences (profiles/policy_observe_cost.json)")
+    ap.add_argument("--returns", action="store_true", help="measure the critic and the lambda-return (profiles/policy_returns_cost.json)")
     ap.add_argument("--horizon", type=int, default=15)
     args = ap.parse_args()
     import torch
+    if args.returns:
+        sizes = args.envs if args.envs != [4096, 65536] else [65536]
+        out = {"tool": "tools/policy_cost.py --returns", "track": args.track, "checkpoint": args.checkpoint, "critic": "critic.init_critic(0)",
+               "device": torch.cuda.get_device_name(0), "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle,
+               "macs_per_step_actor_prior_reward": MACS_RETURNS_BASE, "macs_per_critic_head": MACS_CRITIC_HEAD,
+               "macs_per_step_with_both_heads": MACS_RETURNS_BASE + 2 * MACS_CRITIC_HEAD, "spread_allowance": 1.05,
+               "condition": "mean_returns_weight ms_per_step <= macs_ratio x imagine_mean_reward ms_per_step of the same run x 1.05, at the largest size",
+               "sizes": [measure_returns(n, args) for n in sizes]}
+        out["condition_met"] = out["sizes"][-1]["mean_returns_weight"]["met"]
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.observe:
         sizes = args.envs if args.envs != [4096, 65536] else [65536]
         out = {"tool": "tools/policy_cost.py --observe", "track": args.track, "checkpoint": args.checkpoint, "device": torch.cuda.get_device_name(0),
