@@ -153,6 +153,11 @@ __device__ __forceinline__ uint32_t select_mask_u(unsigned long long m, uint32_t
     asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
     return r;
 }
+__device__ __forceinline__ uint32_t mask_as_flag(unsigned long long m) {                // m ? 1 : 0, no register for either constant
+    uint32_t r;
+    asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(m));
+    return r;
+}
 __device__ __forceinline__ unsigned long long cmp_nlt_f32_s(float a, float b) {        // the same with a wave-uniform b
     unsigned long long m;
     asm("v_cmp_nlt_f32_e64 %0, %1, %2" : "=s"(m) : "v"(a), "s"(b));
@@ -235,8 +240,11 @@ __device__ __forceinline__ unsigned first_trip_entry(uint32_t lds_line, float dy
 }
 // The same, and the LDS address of the ray's quadrant record in the wave's frame table (scan_car: 32 bytes per quadrant
 // q = 2 (dy < 0) + (dx < 0) behind the first-trip line): q32 = 32 q is what both addresses are made of, the line's
-// quadrant offset being 2 RC_FIRST_BINS q = 4 q32 bytes.
-__device__ __forceinline__ unsigned first_trip_entry_frame(uint32_t lds_line, uint32_t frame_base, float dy, float idx, int nx, int ny, uint32_t &frame_addr) {
+// quadrant offset being 2 RC_FIRST_BINS q = 4 q32 bytes.  Both are formed from ONE register, lds_line: the frame table stands
+// kFrameFromLine bytes behind it, a constant that the reads of the record carry as their immediate offset (frame_addr is
+// returned WITHOUT it), so the wave pins one LDS address per car and no round rematerialises the other from a scalar.
+constexpr uint32_t kFrameFromLine = 2u * RC_FIRST_BIAS + 2u * RC_FIRST_PLANES;
+__device__ __forceinline__ unsigned first_trip_entry_frame(uint32_t lds_line, float dy, float idx, int nx, int ny, uint32_t &frame_addr) {
     static_assert(2u * RC_FIRST_BINS == 4u * 32u, "a quadrant of the first-trip line is four frame records long");
     float slope;
     asm("v_mul_f32_e64 %0, |%1|, |%2|" : "=v"(slope) : "v"(dy), "v"(idx));
@@ -245,7 +253,7 @@ __device__ __forceinline__ unsigned first_trip_entry_frame(uint32_t lds_line, ui
     asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(q32) : "v"(ny), "v"(64u), "v"((unsigned)nx & 32u));
     asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(w) : "v"(q32), "v"(bin));          // bin + 2 q32: twice that = 2 bin + 128 q
     asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(addr) : "v"(w), "v"(lds_line));
-    frame_addr = q32 + frame_base;
+    frame_addr = q32 + lds_line;
     typedef const __attribute__((address_space(3))) uint16_t *lds_u16_ptr;
     return *(lds_u16_ptr)(uintptr_t)addr;
 }
@@ -314,13 +322,15 @@ template <bool FROM_PLANE, class Between = NothingBetween, bool GUARD = true, bo
 __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackDev &t, const TravConst &k, float gx, float gy,
                                               float dx, float dy, float idx, float idy, int nx, int ny, int ix, int iy,
                                               unsigned v, bool in_grid, int *wave_trips = nullptr, int *wave_exact = nullptr,
-                                              Between between = Between(), int *overrun = nullptr, uint32_t frame_addr = 0) {
+                                              Between between = Between(), int *overrun = nullptr, uint32_t frame_addr = 0,
+                                              bool zero_time = true) {
     const int pitch2 = t.cell_pitch * 2;
     const char *qb = reinterpret_cast<const char *>(qr);
     // mirrored origin, the origin of the position estimate, the start cell (i~ = ~i on a mirrored axis) and the part of
     // the table address that depends on the quadrant only
     float gmx, gmy, hx, hy;
     uint32_t Tx, Ty, qoff;
+    float tt = 0.0f;
     if (FRAME_LDS) {
         // all seven depend on the car and the ray's QUADRANT only: the wave computed the four records once (scan_car) and
         // every ray reads its own - two 16-byte LDS reads instead of nine vector instructions per ray
@@ -328,6 +338,7 @@ __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackD
         const v4u a = *(lds_v4u_cptr)(uintptr_t)frame_addr, b = *(lds_v4u_cptr)(uintptr_t)(frame_addr + 16u);
         gmx = __uint_as_float(a.x); gmy = __uint_as_float(a.y); hx = __uint_as_float(a.z); hy = __uint_as_float(a.w);
         Tx = b.x; Ty = b.y; qoff = b.z;
+        tt = __uint_as_float(b.w);                                        // the record's last word is +0.0f: the time starts in the register the read fills
     } else {
         gmx = __uint_as_float(__float_as_uint(gx) ^ ((uint32_t)nx & 0x80000000u));
         gmy = __uint_as_float(__float_as_uint(gy) ^ ((uint32_t)ny & 0x80000000u));
@@ -341,13 +352,17 @@ __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackD
         if (in_grid) v = *reinterpret_cast<const uint16_t *>(qb + mad_u24(Ty, pitch2, (Tx << 1) + qoff));
     }
     const float band2 = t.band2;
-    float tt = 0.0f;
     // A trip in two halves: `trip_head` ends with the REQUEST for the new cell's entry, `trip_tail` has the band test, the
     // exact path and the wait.  The entry is requested from the estimate as soon as the cell is known - the band test and
     // its branch are then off the chain entry -> trip -> request that a wave's time consists of (a lane in the band asks
     // again in the tail) - and as inline assembly with its own wait: the compiler sinks a C++ load below the branch.
-    uint32_t xe = 0, ye = 0, xflag = 0;                                   // xflag: 1 = left through the x side (per lane: a lane
-    float zo = 0.0f;                                                      // mask in a scalar pair cannot live across `between`)
+    // Which side the lane left through.  Read by the exact path only, which few trips take: with nothing between the two halves
+    // of a trip the compare's lane mask stays in its scalar pair (xside) and the trip holds no instruction for it; across a
+    // `between` - the caller's code, whose scalar registers are its own - it lives per lane (xflag: 1 = the x side).
+    constexpr bool kSideInMask = std::is_same<Between, NothingBetween>::value;
+    uint32_t xe = 0, ye = 0, xflag = 0;
+    unsigned long long xside = 0;
+    float zo = 0.0f;
     unsigned vnew = 0;
     auto trip_head = [&]() {
         if (wave_trips) *wave_trips += 1;                                 // (instrumented build only: this LANE's trips)
@@ -365,15 +380,15 @@ __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackD
         float zxo = zx, zyo = zy;
         asm volatile("" : "+v"(zxo), "+v"(zyo));                          // (keeps the band test's arithmetic behind the request)
         zo = select_mask(xm, zyo, zxo);                                   // the other axis
-        xflag = select_mask_u(xm, 1u, 0u);
+        if (kSideInMask) xside = xm; else xflag = mask_as_flag(xm);
     };
     auto trip_tail = [&]() {
         if (cmp_lt_f32_s(__builtin_amdgcn_fractf(zo + 0.5f), band2)) {    // within `band` of a boundary: exact count
             // (first let the request land: its register must not be handed to anything else while it is under way)
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(vnew));
             if (wave_exact) *wave_exact += 1;
-            const unsigned long long xm = cmp_ne_u32(xflag, 0u);
-            const uint32_t tie = xflag;
+            const unsigned long long xm = kSideInMask ? xside : cmp_ne_u32(xflag, 0u);
+            const uint32_t tie = kSideInMask ? mask_as_flag(xm) : xflag;
             // the current cell on that axis = boundary - extent (the old Tx, Ty are not kept: no register copies per trip)
             // (the entry through an opaque copy: shared with the loop condition, `v & 255` would stay a separate
             // instruction in every trip instead of folding into the compare's byte select)
@@ -400,7 +415,7 @@ __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackD
         if (!started) return 0.0f;
         trip_tail();
     } else if ((v & 255u) == 0) {
-        return 0.0f;                                                      // the sensor sits in a stop cell
+        return tt;                                                        // the sensor sits in a stop cell: 0.0f
     }
     if (GUARD) {
         // THE BOUNDED FORM of the loop: a wave-level trip budget of w + h + 2, counted on the scalar unit behind the trip's
@@ -434,9 +449,16 @@ __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackD
     // its product with 1/d < 0 is -0.0, which the range then carries; here it is +0.  A ray that stops at time 0 never
     // left its origin; it crossed x at all only if it started on the far face of its column, and when it crossed both
     // axes (a corner) the spec stepped y first - so its last crossing was the x one iff it left the start column.
-    // (a wave-uniform branch that is almost never taken: one compare per round; the start cell is recomputed inside it
-    // rather than kept in a register across the loop)
-    if (__builtin_amdgcn_ballot_w64(tt == 0.0f) != 0) {
+    // (a wave-uniform branch that is almost never taken; the start cell is recomputed inside it rather than kept in a
+    // register across the loop)
+    // zero_time: the CALLER's promise that a boundary time of this ray can be zero at all; false skips the compare.  A boundary
+    // time is fl(fl(b~ - g~) * |1/d|) with b~ an integer.  The difference of two floats is 0 only if they are equal, so the first
+    // factor vanishes only if g is an integer; a non-zero one underflows in the product only if |b~ - g~| |1/d| < 2^-126
+    // (whatever the denormal mode), which with |1/d| >= 1/4 (|d| <= |ct| + |st| <= 4, scan_car) takes |b~ - g~| < 2^-124 - and a
+    // float that is no integer lies at least 2^-24 from every integer but 0.  So a zero time needs, on one axis, g integral or
+    // |g| < 2^-124: a property of the sensor's position, the same for all rays of a car (scan_car tests it once per car, with
+    // the wider |g| < 2^-100).
+    if (zero_time && __builtin_amdgcn_ballot_w64(tt == 0.0f) != 0) {
         int mx = nx;
         asm volatile("" : "+v"(mx));
         const uint32_t sgn = (uint32_t)(Tx != (uint32_t)(ix ^ mx) + kCellMagicBits ? mx : ny) & 0x80000000u;
@@ -570,8 +592,20 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
     // the wave's first beam pair does not depend on the car: requested before the car's state, so the two round trips
     // overlap (a wave's start-up - state, start cell, first-trip line - is serial latency that nothing else hides)
     const char *beams = reinterpret_cast<const char *>(t.beams);        // padded to 17 * 64 entries (rc_load_track)
-    unsigned boff = lane * 8u + 512u * part;                             // byte offset of this lane's beam pair
-    float2 bm = *reinterpret_cast<const float2 *>(beams + boff);
+    // A round's 512 bytes of the beam table start at a wave-uniform address, formed on the scalar side; the lane's offset into
+    // them never changes.  (The base through an opaque scalar copy: otherwise the compiler adds the lane's offset to the table's
+    // address once, in a register pair, and the round's offset to that pair in every round.  The lane's offset likewise - in
+    // place, so it stays in its one register -: its widening to 64 bits is otherwise hoisted out of the rounds and the load no
+    // longer sees "scalar base + 32-bit lane offset".  Behind the statement the pointer has to be told to be a global one again.)
+    unsigned lane8 = lane * 8u;
+    auto beam_pair = [&](unsigned round) -> float2 {
+        const char *base = beams + 512u * round;
+        asm("" : "+s"(base), "+v"(lane8));
+        typedef const __attribute__((address_space(1))) v2f *global_v2f_ptr;
+        const v2f b = *(global_v2f_ptr)((uintptr_t)base + lane8);
+        return make_float2(b.x, b.y);
+    };
+    float2 bm = beam_pair(part);
     // all four state words in one scalar 16-byte load
     const float4 sp = p.st.scan_pose[car];
     float ct = sp.z, st = sp.w;
@@ -605,7 +639,11 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         typedef __attribute__((address_space(3))) v2u_t *lds_v2u_ptr;
         *(lds_v2u_ptr)(uintptr_t)(lds_first + 8u * lane) = w;
     }
-    const uint32_t first_line = lds_first - 2u * RC_FIRST_BIAS;          // (the slope bins are biased: first_trip_entry)
+    // (the slope bins are biased: first_trip_entry.  Pinned: the one LDS address the rounds' prepare is made of)
+    const uint32_t first_line = pin_vgpr(lds_first - 2u * RC_FIRST_BIAS);
+    // Can a ray of this car have a boundary time of zero (ray_traverse, zero_time)?  Only with the sensor on a cell boundary.
+    const bool zero_time = __builtin_amdgcn_readfirstlane((int)(gx == floorf(gx)) | (int)(gy == floorf(gy)) | (int)(fabsf(gx) < 0x1p-100f) |
+                                                          (int)(fabsf(gy) < 0x1p-100f)) != 0;
     // wave-uniform operands of the trip, in vector registers
     const TravConst kc = trav_const(t);
     const TravConst k = {pin_vgpr(kc.band_mh), pin_vgpr(kc.res), pin_vgpr(kc.kx), pin_vgpr(kc.ky), pin_vgpr(kc.c00)};
@@ -615,6 +653,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
     // q's record (the very expressions ray_traverse evaluates per ray otherwise: the bits are the same) and every ray reads its
     // own with two 16-byte LDS reads: 7 vector instructions per round and 4 registers less.
     const uint32_t lds_frame = lds_first + 2u * RC_FIRST_PLANES;
+    static_assert(kFrameFromLine + 32u < 65536u, "the frame record is read at an immediate offset from the first-trip line's address");
     if (lane < 4u) {
         const int qnx = (lane & 1u) ? -1 : 0, qny = (lane & 2u) ? -1 : 0;
         const float qgmx = __uint_as_float(__float_as_uint(gx) ^ ((uint32_t)qnx & 0x80000000u));
@@ -624,20 +663,23 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         const uint32_t qq = (((uint32_t)qnx & kc.kx) + ((uint32_t)qny & kc.ky)) + kc.c00;
         typedef __attribute__((address_space(3))) v4u *lds_v4u_wptr;
         const v4u fa = {__float_as_uint(qgmx), __float_as_uint(qgmy), __float_as_uint(qhx), __float_as_uint(qhy)};
-        const v4u fb = {qTx, qTy, qq, 0u};
+        const v4u fb = {qTx, qTy, qq, 0u};                                    // (the last word: the ray's time at its start, +0.0f)
         *(lds_v4u_wptr)(uintptr_t)(lds_frame + 32u * lane) = fa;
         *(lds_v4u_wptr)(uintptr_t)(lds_frame + 32u * lane + 16u) = fb;
     }
-    const uint32_t frame_base = pin_vgpr(lds_frame);
     constexpr int kRounds = (RC_N_BEAMS + 63) / 64;
-    // (per-round steps live in vector registers: a full-rate add that reads a scalar register issues at half rate)
-    const unsigned bstep = kOne ? 512u : pin_vgpr(512u * (unsigned)split), ostep = kOne ? 256u : pin_vgpr(256u * (unsigned)split);
+    // (the output slot's step lives in a vector register: a full-rate add that reads a scalar register issues at half rate; the
+    // beam table's offset is the round's, formed on the scalar side)
+    const unsigned ostep = kOne ? 256u : pin_vgpr(256u * (unsigned)split);
     // LDS address of this lane's slot in the wave's staged output row (lds_row = LDS address of the row: the kernel's
     // dynamic LDS is its only LDS object and starts at 0, checked by rck_set_lds_limits) and the row's end
     typedef __attribute__((address_space(3))) float *lds_f32_ptr;
     typedef const __attribute__((address_space(3))) v4u *lds_v4u_ptr;
     uint32_t oslot = lds_row + lane * 4u + 256u * part;
-    const uint32_t oend = lds_row + 4u * RC_N_BEAMS;
+    // Which lanes have a beam in a round is wave-uniform but for the last one (56 of 64): a constant lane mask chosen by the
+    // scalar round counter, set as the exec mask without a vector compare
+    constexpr unsigned long long kLastRoundLanes = (1ull << (RC_N_BEAMS - 64 * (kRounds - 1))) - 1ull;
+    static_assert(RC_N_BEAMS - 64 * (kRounds - 1) > 0 && RC_N_BEAMS - 64 * (kRounds - 1) < 64, "the last round is a partial one");
     // Software pipeline over the rounds: while round r is traversed, round r + 1's direction, reciprocals, sign masks
     // and first-trip entry are already computed / in flight (and round r + 2's beam pair is being fetched), so no
     // round starts by waiting for its start entry.  Two register sets take turns (the loop body holds two rounds), so
@@ -650,11 +692,11 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         r.dy = ct * b.y + st * b.x;
         ray_reciprocals(r.dx, r.dy, r.idx, r.idy);
         r.nx = sign_mask(r.dx); r.ny = sign_mask(r.dy);
-        r.v = first_trip_entry_frame(first_line, frame_base, r.dy, r.idx, r.nx, r.ny, r.fa);
+        r.v = first_trip_entry_frame(first_line, r.dy, r.idx, r.nx, r.ny, r.fa);
     };
-    // one round: prepare `nxt` for round + split, traverse `cur`, store.  false: this lane has no beam in the round
-    auto stage = [&](int round, const Ray &cur, Ray &nxt) -> bool {
-        if (oslot >= oend) return false;                                  // last round: 56 of 64 lanes
+    // one round: prepare `nxt` for round + split, traverse `cur`, store
+    auto stage = [&](int round, const Ray &cur, Ray &nxt) {
+        if (!__builtin_amdgcn_inverse_ballot_w64(round == kRounds - 1 ? kLastRoundLanes : ~0ull)) return;   // this lane has no beam in the round
         phase(t_rest);
         // `cur` was requested a whole round ago and has arrived: say so BEFORE the next round's loads go out, or the
         // compiler, unable to count the conditional loads in flight, waits for all of them at the first use of cur.v
@@ -662,23 +704,33 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         __builtin_amdgcn_s_waitcnt(0x0F70);
         phase(t_wait);
         // the next round is prepared while the first request of this one is under way (ray_traverse calls it there)
+        // (the round counter through an opaque scalar copy: shared with the loop's own tests, the compiler keeps the outcome of
+        // `round + split < kRounds` per lane across the blocks in between - a select, a compare and a readfirstlane per round)
+        int rnd = round;
+        asm("" : "+s"(rnd));
         auto prepare_next = [&]() {
-            if (round + split < kRounds) {
+            if (rnd + split < kRounds) {
                 prepare(bm, nxt);                                         // (the padded beams of the last round included)
-                boff += bstep;
-                if (round + 2 * split < kRounds) bm = *reinterpret_cast<const float2 *>(beams + boff);
+                if (rnd + 2 * split < kRounds) bm = beam_pair((unsigned)(rnd + 2 * split));
+            } else {
+                // No round will read `nxt`: say so.  Its entry is otherwise live across this round's traversal - the trip loop then
+                // starts with a copy of cur.v - and, every assignment to it being the widening of a 16-bit load, kept as 16 bits
+                // between the blocks and widened again (an AND) in every round.  (No instruction: an undefined register.)
+                unsigned nothing;
+                asm("" : "=v"(nothing));
+                nxt.v = nothing;
             }
         };
         float rng;
         if (OVERLAP) {
             rng = ray_traverse<false, decltype(prepare_next), GUARD, true>(t.quad_rect, t, k, gx, gy, cur.dx, cur.dy, cur.idx, cur.idy, cur.nx, cur.ny, ixv, iyv, cur.v, true,
-                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, prepare_next, GUARD ? &overrun : nullptr, cur.fa);
+                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, prepare_next, GUARD ? &overrun : nullptr, cur.fa + kFrameFromLine, zero_time);
         } else {
             prepare_next();
             if (STAMPS) asm volatile("" :: "v"(nxt.idx), "v"(nxt.idy));
             phase(t_prep);
             rng = ray_traverse<false, NothingBetween, GUARD, true>(t.quad_rect, t, k, gx, gy, cur.dx, cur.dy, cur.idx, cur.idy, cur.nx, cur.ny, ixv, iyv, cur.v, true,
-                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, NothingBetween(), GUARD ? &overrun : nullptr, cur.fa);
+                                      STAMPS ? &wave_trips : nullptr, STAMPS ? &wave_exact : nullptr, NothingBetween(), GUARD ? &overrun : nullptr, cur.fa + kFrameFromLine, zero_time);
         }
         if (STAMPS) asm volatile("" :: "v"(rng));
         phase(t_trav);
@@ -694,8 +746,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
             }
         }
         if (NOISE && p.noise_on) rng = lidar_noise(p, noise_key, (unsigned)round * 64u + lane, rng);
-        if (p.lidar_transform == 1) rng = rng / RCS_MAX_RANGE - 0.5f;                 // dreamer/tools.py:274
-        else if (p.lidar_transform == 2) rng = rng * (1.0f / RCS_MAX_RANGE);          // single_agent.py:92-99
+        // (the row is staged in METRES: lidar_transform is applied once per car, in the flush below)
         if (STAMPS) asm volatile("" :: "v"(rng));
         phase(t_post);
         *(lds_f32_ptr)(uintptr_t)oslot = rng;                             // staged: see the flush below
@@ -714,17 +765,16 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
             // (read the clock AFTER the counting: the builtin alone may be scheduled ahead of it)
             asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_mark) : "s"(most), "s"(nib_lo), "s"(nib_hi));
         }
-        return true;
     };
     Ray ra, rb;
     prepare(bm, ra);
     if (STAMPS) { asm volatile("" :: "v"(ra.v)); stamp(2); t_mark = __builtin_amdgcn_s_memtime(); }
-    boff += bstep;
-    if ((int)part + split < kRounds) bm = *reinterpret_cast<const float2 *>(beams + boff);
+    if ((int)part + split < kRounds) bm = beam_pair(part + (unsigned)split);
+    // (a scalar loop: no lane leaves it early - the lanes without a beam in the last round sit that round out)
     for (int round = (int)part; round < kRounds; round += 2 * split) {
-        if (!stage(round, ra, rb)) break;
+        stage(round, ra, rb);
         if (round + split >= kRounds) break;
-        if (!stage(round + split, rb, ra)) break;
+        stage(round + split, rb, ra);
     }
     if (GUARD && overrun != 0 && p.scan_overrun != nullptr && lane == 0) atomicAdd(p.scan_overrun, 1u);
     // Flush the wave's ranges from LDS to the output row.  A store per round costs more than its 256 bytes: loads and
@@ -739,6 +789,14 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
     // costs the scan 2 160 more bytes of stores per car and ~30 instructions.
     char *out16 = reinterpret_cast<char *>(p.out.lidar_u16);            // wave-uniform, null when not asked for
     if (out16 != nullptr) out16 += (size_t)car * (2 * RC_N_BEAMS);
+    // lidar_transform, decided once per car: the staged row is in metres, and the common case - no transform - has neither the
+    // ladder nor a copy in its rounds.  One IEEE operation per written operator on the same operands as ever: the same bits.
+    const int transform = p.lidar_transform;
+    auto transformed = [&](float r) -> float {
+        if (transform == 1) return r / RCS_MAX_RANGE - 0.5f;              // dreamer/tools.py:274
+        if (transform == 2) return r * (1.0f / RCS_MAX_RANGE);            // single_agent.py:92-99
+        return r;
+    };
     const float q_off = p.lidar_transform == 1 ? 0.5f : 0.0f;
     const float q_scale = p.lidar_transform == 0 ? 65535.0f / RCS_MAX_RANGE : 65535.0f;
     if (split == 1) {                   // the whole row is this wave's: 270 16-byte vectors, 5 stores of 1 KB
@@ -746,7 +804,11 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         for (int k = 0; k < (RC_N_BEAMS / 4 + 63) / 64; ++k) {
             const unsigned o = (lane + 64u * (unsigned)k) * 16u;
             if (o < 4u * RC_N_BEAMS) {
-                const v4u val = *(lds_v4u_ptr)(uintptr_t)(lds_row + o);
+                v4u val = *(lds_v4u_ptr)(uintptr_t)(lds_row + o);
+                if (transform != 0) {                                     // (wave-uniform)
+                    val.x = __float_as_uint(transformed(__uint_as_float(val.x))); val.y = __float_as_uint(transformed(__uint_as_float(val.y)));
+                    val.z = __float_as_uint(transformed(__uint_as_float(val.z))); val.w = __float_as_uint(transformed(__uint_as_float(val.w)));
+                }
                 __builtin_nontemporal_store(val, reinterpret_cast<v4u *>(out_bytes + o));    // streamed: leaves the tables in L2 (1 % faster)
                 if (out16 != nullptr) {
                     typedef unsigned v2u __attribute__((ext_vector_type(2)));
@@ -758,7 +820,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         }
     } else {
         for (unsigned o = lane * 4u + 256u * part; o < 4u * RC_N_BEAMS; o += 256u * (unsigned)split) {
-            const float v = *(lds_f32_ptr)(uintptr_t)(lds_row + o);
+            const float v = transformed(*(lds_f32_ptr)(uintptr_t)(lds_row + o));
             *reinterpret_cast<float *>(out_bytes + o) = v;
             if (out16 != nullptr) *reinterpret_cast<uint16_t *>(out16 + (o >> 1)) = (uint16_t)quantise_pair(v, v, q_off, q_scale);
         }
