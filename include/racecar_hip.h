@@ -542,6 +542,58 @@ typedef struct rc_policy_returns_args {
  * rc_policy_returns_sampled_kernel, timed under RC_K_POLICY. */
 int rc_policy_returns(rc_env *env, const rc_policy_returns_args *args);
 
+/* Fitting the critic on the device: the reference's value update (dreamer/models.py:129-137: value_loss = -mean(weight *
+ * value(feat).log_prob(stop_gradient(returns))) under value_opt, which owns the value head's eight arrays alone; dreamer/tools.py:421-455
+ * `Optimizer`: clip_by_global_norm, then Adam) - one MLP's forward pass, backward pass, global-norm clip and Adam on tensors that
+ * rc_policy_returns leaves on the device (tests/policy_fit_spec.c is the CPU restatement, the device equals it
+ * bit for bit).  The pcont head is the same network under a Bernoulli likelihood with soft targets (models.py:101-105).  With o the
+ * head's output on features[i], t = target[i], w = weight[i] (1 where weight is NULL), N = rows:
+ *   value   loss = -(1/N) sum w (-(o - t)^2 / 2 - log(2 pi) / 2)                       delta_o = w (o - t) / N
+ *   pcont   loss = -(1/N) sum w (t log sigmoid(o) + (1 - t) log(1 - sigmoid(o)))       delta_o = w (sigmoid(o) - t) / N
+ * The gradient's sum over the rows has a fixed order that depends on N alone (no atomics: two steps on the same inputs give the same
+ * bits on any grid).  norm = sqrt(sum g^2) over the eight arrays; g <- g clip / max(norm, clip) (clip 0: no clipping); a step whose
+ * norm is not finite changes nothing and does not count (the reference's LossScaleOptimizer skips it; the loss scale itself is the
+ * identity under precision 32 and is not modelled).  Adam as TF's ResourceApplyAdam, t = the steps taken including this one:
+ *   m <- beta1 m + (1 - beta1) g;  v <- beta2 v + (1 - beta2) g^2;  w <- w - lr sqrt(1 - beta2^t) / (1 - beta1^t) m / (sqrt(v) + epsilon)
+ * (beta^t is a running product in binary64 kept with the moments on the device: a power from the host would have to know whether
+ * the last step was skipped).  No weight decay (the reference's config has 0).  The new weights are written where rc_policy_returns
+ * and every other reader of the critic find them; the other head, the policy, the latents, the arena and every counter stay as they are.
+ *   rc_policy_fit_begin  opens the optimizer of one head (it must be loaded: rc_policy_load_critic): moments zero, step 0.  One per
+ *                        head, both may be open; a second begin starts over.  rc_policy_load_critic, rc_policy_load and
+ *                        rc_policy_unload close them.
+ *   rc_policy_fit_step   one update, stream-ordered on the handle's stream, no synchronisation.  status, when given, receives
+ *                        loss, grad_norm (before the clip), skipped (0 / 1) and the step count after this step.
+ *   rc_policy_fit_end    frees the optimizer's state; the fitted weights stay loaded.
+ *   rc_policy_read_critic copies the loaded heads back into the caller's host arrays (data pointers to [rows, cols] float32 of the
+ *                        checkpoint's shapes, written despite the const; the pcont_* pointers may be NULL): the inverse of
+ *                        rc_policy_load_critic's packing.  Synchronises the stream.
+ * RC_ERR_INVALID: wrong struct_size, unknown head, the head not loaded (begin), no optimizer open for the head (step), features or
+ * target NULL, rows outside [1, 2^31), a hyper-parameter negative or not finite, a beta outside [0, 1); read_critic: no critic
+ * loaded, a wrong shape, pcont_* asked for without a pcont head.  Kernels: rc_policy_fit_rows_kernel, rc_policy_fit_wgrad_kernel,
+ * rc_policy_fit_sums_kernel, rc_policy_fit_scale_kernel, rc_policy_fit_apply_kernel (and rc_policy_fit_transpose_kernel in begin),
+ * timed together under RC_K_POLICY. */
+#define RC_POLICY_FIT_VALUE 0
+#define RC_POLICY_FIT_PCONT 1
+typedef struct rc_policy_fit_config {
+    uint32_t struct_size;          /* = sizeof(rc_policy_fit_config) */
+    int32_t head;                  /* RC_POLICY_FIT_* */
+} rc_policy_fit_config;
+typedef struct rc_policy_fit_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_fit_args) */
+    int32_t head;                  /* RC_POLICY_FIT_* */
+    int64_t rows;                  /* N in [1, 2^31) */
+    const float *features;         /* device float32 [rows, 230] = stoch | deter */
+    const float *target;           /* device float32 [rows] */
+    const float *weight;           /* device float32 [rows], or NULL: all 1 */
+    float lr, clip;                /* the reference's value_lr 8e-5 and grad_clip 1.0 (dream.py:88); clip 0: none */
+    float beta1, beta2, epsilon;   /* TF's 0.9, 0.999, 1e-7 */
+    float *status;                 /* device float32 [4] = loss, grad_norm, skipped, step; or NULL */
+} rc_policy_fit_args;
+int rc_policy_fit_begin(rc_env *env, const rc_policy_fit_config *cfg);
+int rc_policy_fit_step(rc_env *env, const rc_policy_fit_args *args);
+int rc_policy_fit_end(rc_env *env, int32_t head);
+int rc_policy_read_critic(rc_env *env, rc_policy_critic *out);
+
 /* Recorded sequences: the posterior chain over N recorded windows of T scans and actions (DESIGN.md §2 item 17;
  * tests/policy_observe_spec.c is the CPU restatement, the device equals it bit for bit) - dreamer/models.py:325-336 RSSM.observe,
  * the operation the reference runs on every replay batch: `post, prior = observe(embed, action)`, kl_divergence(post, prior) and the

@@ -145,6 +145,22 @@ class RcPolicyReturnsArgs(C.Structure):
                 ("value_start", C.c_void_p), ("pcont_start", C.c_void_p)]
 
 
+FIT_HEADS = {"value": 0, "pcont": 1}                            # RC_POLICY_FIT_*
+CRITIC_SHAPES = ((230, 400), (400,), (400, 400), (400,), (400, 400), (400,), (400, 1), (1,))      # of VALUE_KEYS / PCONT_KEYS
+
+
+class RcPolicyFitConfig(C.Structure):
+    """rc_policy_fit_config (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("head", C.c_int32)]
+
+
+class RcPolicyFitArgs(C.Structure):
+    """rc_policy_fit_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("head", C.c_int32), ("rows", C.c_int64), ("features", C.c_void_p), ("target", C.c_void_p),
+                ("weight", C.c_void_p), ("lr", C.c_float), ("clip", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float),
+                ("epsilon", C.c_float), ("status", C.c_void_p)]
+
+
 LOOK_AHEAD_MAX_HORIZON = 64
 LA_DONE, LA_TRUNCATED, LA_WALL, LA_OPPONENT, LA_WRONG_WAY = 1, 2, 4, 8, 16      # rc_look_ahead's flags
 # look_ahead's output names -> (rc_look_ahead_args field, torch dtype name, shape as a function of (E, K, H, A))
@@ -303,6 +319,10 @@ SYMBOLS = {
     "rc_policy_dream_ahead": (C.c_int, [C.c_void_p, _P(RcPolicyDreamAheadArgs)]),
     "rc_policy_load_critic": (C.c_int, [C.c_void_p, _P(RcPolicyCritic)]),
     "rc_policy_returns": (C.c_int, [C.c_void_p, _P(RcPolicyReturnsArgs)]),
+    "rc_policy_fit_begin": (C.c_int, [C.c_void_p, _P(RcPolicyFitConfig)]),
+    "rc_policy_fit_step": (C.c_int, [C.c_void_p, _P(RcPolicyFitArgs)]),
+    "rc_policy_fit_end": (C.c_int, [C.c_void_p, C.c_int32]),
+    "rc_policy_read_critic": (C.c_int, [C.c_void_p, _P(RcPolicyCritic)]),
     "rc_policy_observe": (C.c_int, [C.c_void_p, _P(RcPolicyObserveArgs)]),
     "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
     "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),

@@ -247,6 +247,26 @@ def _value_setup(env, features, slots, outputs):
     return torch.nn.functional.pad(flat, (0, 2)), lead, tuple(n + "_start" for n in names)
 
 
+def _fit_setup(env, features, target, weight, head):
+    """critic_fit's tensors (shared by BatchedRaceEnv and MixedTrackEnv): contiguous float32 [N, 230], [N], [N] or None on the
+    env's device, and the status block."""
+    if head not in L.FIT_HEADS:
+        raise ValueError(f"head must be one of {sorted(L.FIT_HEADS)}, got {head!r}")
+    if features.shape[-1] != L.POLICY_FEATURE or features.numel() == 0:
+        raise ValueError(f"features must be [..., {L.POLICY_FEATURE}] with at least one row, got {tuple(features.shape)}")
+    feat = features.to(env.device, torch.float32).reshape(-1, L.POLICY_FEATURE).contiguous()
+    n = feat.shape[0]
+    tgt = target.to(env.device, torch.float32).reshape(-1).contiguous()
+    wgt = None if weight is None else weight.to(env.device, torch.float32).reshape(-1).contiguous()
+    if tgt.numel() != n or (wgt is not None and wgt.numel() != n):
+        raise ValueError(f"features have {n} rows, target {tgt.numel()}" + ("" if wgt is None else f", weight {wgt.numel()}"))
+    return feat, tgt, wgt, torch.empty(4, dtype=torch.float32, device=env.device)
+
+
+def _fit_status(status):
+    return {"loss": status[0], "grad_norm": status[1], "skipped": status[2], "step": status[3]}
+
+
 def _look_ahead_setup(env, actions, repeat, outputs, out):
     """look_ahead's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
     rc_look_ahead_args field - env-major, one row per env -, the dict to return)."""
@@ -917,6 +937,67 @@ class BatchedRaceEnv:
         got = self.policy_returns(horizon=0, state=state, slots=slots, outputs=names)
         return {n[:-6]: got[n].reshape(lead) for n in names}
 
+    def _fit(self, head, feat, tgt, wgt, status, hyper) -> int:
+        a = L.RcPolicyFitArgs(C.sizeof(L.RcPolicyFitArgs), L.FIT_HEADS[head], feat.shape[0], feat.data_ptr(), tgt.data_ptr(),
+                              None if wgt is None else wgt.data_ptr(), hyper["lr"], hyper["clip"], hyper["beta1"], hyper["beta2"],
+                              hyper["epsilon"], None if status is None else status.data_ptr())
+        return self._lib.rc_policy_fit_step(self._h, C.byref(a))
+
+    def critic_fit_begin(self, head: str = "value") -> None:
+        """Open the optimizer of a loaded head, "value" or "pcont" (`rc_policy_fit_begin`): Adam moments zero, step 0.  One per
+        head; `load_critic`, `load_policy` and `unload_policy` close them."""
+        if head not in L.FIT_HEADS:
+            raise ValueError(f"head must be one of {sorted(L.FIT_HEADS)}, got {head!r}")
+        cfg = L.RcPolicyFitConfig(C.sizeof(L.RcPolicyFitConfig), L.FIT_HEADS[head])
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_fit_begin(self._h, C.byref(cfg)))
+        finally:
+            self._exit()
+
+    def critic_fit(self, features: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, head: str = "value",
+                   lr: float = 8e-5, clip: float = 1.0, beta1: float = 0.9, beta2: float = 0.999,
+                   epsilon: float = 1e-7) -> Dict[str, torch.Tensor]:
+        """One step of the reference's value update on the device (`rc_policy_fit_step`; dreamer/models.py:129-137,
+        dreamer/tools.py:421-455): the head's forward and backward pass on `features` [..., 230] = stoch | deter against `target`
+        [...] (for the value head `policy_returns`' returns on `features[:, :-1]`) under `weight` [...] or None, the global-norm
+        clip (`clip` 0: none) and Adam, all on the device and in the env's stream: no synchronisation, no host copy.  Inputs
+        that are not contiguous float32 are made so.  The defaults are the reference's value_lr and grad_clip and TF's Adam.
+        Returns device scalars: `loss`, `grad_norm` (before the clip), `skipped` (1: the norm was not finite, nothing changed),
+        `step` (the steps taken).  The fitted weights are what `policy_returns`, `policy_value` and the planners read next."""
+        feat, tgt, wgt, status = _fit_setup(self, features, target, weight, head)
+        hyper = dict(lr=lr, clip=clip, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        self._enter()
+        try:
+            L.check(self._fit(head, feat, tgt, wgt, status, hyper))
+        finally:
+            self._exit()
+        return _fit_status(status)
+
+    def critic_fit_end(self, head: str = "value") -> None:
+        """Free the optimizer's state (`rc_policy_fit_end`); the fitted weights stay loaded."""
+        if head not in L.FIT_HEADS:
+            raise ValueError(f"head must be one of {sorted(L.FIT_HEADS)}, got {head!r}")
+        L.check(self._lib.rc_policy_fit_end(self._h, L.FIT_HEADS[head]))
+
+    def critic_weights(self) -> Dict[str, np.ndarray]:
+        """The loaded critic as NumPy arrays under `VALUE_KEYS` (and `PCONT_KEYS` with a pcont head), as `load_critic` takes
+        them (`rc_policy_read_critic`; waits for the env's stream)."""
+        keys = L.VALUE_KEYS + (L.PCONT_KEYS if self.policy_has_pcont_head else ())
+        out = {k: np.empty(shape, np.float32) for k, shape in zip(keys, L.CRITIC_SHAPES * 2)}
+        c = L.RcPolicyCritic()
+        c.struct_size = C.sizeof(L.RcPolicyCritic)
+        for k, a in out.items():
+            arr = getattr(c, k)
+            arr.data = a.ctypes.data
+            arr.rows, arr.cols = (1, a.shape[0]) if a.ndim == 1 else a.shape
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_read_critic(self._h, C.byref(c)))
+        finally:
+            self._exit()
+        return out
+
     @property
     def policy_has_decoder(self) -> bool:
         """Whether the loaded checkpoint brought a LidarOccupancyDecoder (`dec_*` arrays): `policy_decode` needs one."""
@@ -1568,6 +1649,29 @@ class MixedTrackEnv:
         state, lead, names = _value_setup(self, features, slots, outputs)
         got = self.policy_returns(horizon=0, state=state, slots=slots, outputs=names)
         return {n[:-6]: got[n].reshape(lead) for n in names}
+
+    def critic_fit_begin(self, head: str = "value") -> None:
+        """BatchedRaceEnv.critic_fit_begin on every block."""
+        for p in self.parts:
+            p.critic_fit_begin(head)
+
+    def critic_fit(self, features: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, head: str = "value",
+                   lr: float = 8e-5, clip: float = 1.0, beta1: float = 0.9, beta2: float = 0.999,
+                   epsilon: float = 1e-7) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.critic_fit on every block with the same inputs: the step is deterministic, so the blocks' critics stay
+        byte-identical.  The status is the first block's."""
+        feat, tgt, wgt, status = _fit_setup(self, features, target, weight, head)
+        hyper = dict(lr=lr, clip=clip, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        self._fork_join(lambda p, blk: p._fit(head, feat, tgt, wgt, status if p is self.parts[0] else None, hyper))
+        return _fit_status(status)
+
+    def critic_fit_end(self, head: str = "value") -> None:
+        for p in self.parts:
+            p.critic_fit_end(head)
+
+    def critic_weights(self) -> Dict[str, np.ndarray]:
+        """The first block's critic (every block holds the same)."""
+        return self.parts[0].critic_weights()
 
     def look_ahead(self, actions: torch.Tensor, repeat: Optional[int] = None, outputs=("reward", "flags", "return", "length"),
                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:

@@ -29,6 +29,17 @@ def init_critic(seed: int, pcont: bool = True, pcont_bias: float = 3.0) -> dict:
     return out
 
 
+def save_critic(path, env) -> None:
+    """The env's loaded critic - as `critic_fit` last left it - into an .npz of `env.critic_weights()`."""
+    np.savez(path, **env.critic_weights())
+
+
+def load_critic_file(path) -> dict:
+    """What `save_critic` wrote, as the mapping `BatchedRaceEnv.load_critic` takes."""
+    with np.load(path) as f:
+        return {k: np.ascontiguousarray(f[k], np.float32) for k in f.files if k in VALUE_KEYS + PCONT_KEYS}
+
+
 def critic_from_variables(arrays) -> dict:
     """The critic out of a `variables.pkl`-ordered list of arrays (dreamer/models.py:30-50: ..., reward, [pcont,] value, actor):
     the reward head is found by its six shapes in a row ([230, 400], [400], [400, 400], [400], [400, 1], [1]); a pcont head

@@ -151,6 +151,7 @@ struct StagedTable {
 };
 
 struct P2p;                        // the peer-copy all-gather's state (racecar_gather.hip)
+struct RcFit;                      // the critic's optimizers (racecar_fit.hip)
 
 struct rc_env {
     rc_config cfg{};
@@ -204,6 +205,7 @@ struct rc_env {
     float *pol_dec_mem = nullptr;      // rc_policy_load_decoder
     RcCriticDev pol_c{};               // rc_policy_returns: the value head and the pcont head (null = none loaded)
     float *pol_critic_mem = nullptr;   // rc_policy_load_critic
+    RcFit *fit = nullptr;              // rc_policy_fit_begin: the critic's optimizers and their scratch (racecar_fit.hip)
     rc_policy_sampling pol_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};      // rc_policy_set_sampling
     float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
     float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)
@@ -227,6 +229,7 @@ struct rc_env {
 };
 
 int drain_events(rc_env *env);      // folds the finished event pairs into the accumulators (racecar_abi.hip)
+int fit_release(rc_env *env);       // closes the critic's optimizers: whoever replaces or drops the critic (racecar_fit.hip)
 
 // Times what lies between begin() and end() under accumulator `kernel`.  One launch: the launch itself carries the two timestamps
 // (rck_set_launch_events).  `bracket`: the pair is recorded on the stream around whatever is queued in between (the episode log's

@@ -452,6 +452,8 @@ int pol_drop_decoder(rc_env *env) {
 
 // the critic's memory and pointers go (rc_policy_load_critic(NULL), a new rc_policy_load)
 int pol_drop_critic(rc_env *env) {
+    const int rc = fit_release(env);     // (an optimizer holds pointers into the critic's memory)
+    if (rc) return rc;
     if (env->pol_critic_mem) {
         HIP_TRY(hipSetDevice(env->cfg.device));
         HIP_TRY(hipStreamSynchronize(env->stream));
@@ -774,10 +776,43 @@ int rc_policy_load_critic(rc_env *env, const rc_policy_critic *h) {
     size_t at[sizeof(kCriticImages) / sizeof(kCriticImages[0])];
     pol_pack(kCriticImages, *h, img, at);
     HIP_TRY(hipSetDevice(env->cfg.device));
+    const int rc_fit = fit_release(env);                    // new weights: the moments and the transposed images are another critic's
+    if (rc_fit) return rc_fit;
     if (!env->pol_critic_mem) HIP_TRY(hipMalloc((void **)&env->pol_critic_mem, img.size() * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(env->pol_critic_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
     HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
     pol_point(kCriticImages, *h, env, env->pol_critic_mem, at);
+    return RC_OK;
+}
+
+// The inverse of rc_policy_load_critic's packing: the images as rc_policy_fit_step last left them, the padding dropped
+int rc_policy_read_critic(rc_env *env, rc_policy_critic *out) {
+    if (!env || !out) return fail(RC_ERR_INVALID, "NULL argument");
+    if (out->struct_size != sizeof(rc_policy_critic))
+        return fail(RC_ERR_INVALID, "rc_policy_critic.struct_size %u != %zu", out->struct_size, sizeof(rc_policy_critic));
+    if (!env->pol_critic_mem || !env->pol_c.vout_w) return fail(RC_ERR_INVALID, "rc_policy_read_critic: no critic loaded (rc_policy_load_critic)");
+    const int rc = pol_check(kCriticImages, *out, "rc_policy_read_critic", "the head's");
+    if (rc) return rc;
+    for (const PolImage<PC> &im : kCriticImages)
+        if (im.optional && (out->*(im.arr)).data && !env->pol_c.pout_w)
+            return fail(RC_ERR_INVALID, "rc_policy_read_critic: %s is asked for and no pcont head is loaded", im.name);
+    constexpr size_t n_img = sizeof(kCriticImages) / sizeof(kCriticImages[0]);
+    size_t at[n_img], total = 0;
+    for (size_t i = 0; i < n_img; ++i) {                    // pol_pack's offsets: every image on a 64-float boundary
+        at[i] = total;
+        total += (kCriticImages[i].floats() + 63) / 64 * 64;
+    }
+    std::vector<float> img(total);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(hipMemcpyAsync(img.data(), env->pol_critic_mem, total * sizeof(float), hipMemcpyDeviceToHost, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));
+    for (size_t i = 0; i < n_img; ++i) {
+        const PolImage<PC> &im = kCriticImages[i];
+        float *dst = const_cast<float *>((out->*(im.arr)).data);
+        if (!dst) continue;
+        for (int k = 0; k < im.rows; ++k)
+            for (int j = 0; j < im.cols; ++j) dst[(size_t)k * im.cols + j] = img[at[i] + (size_t)k * im.ld + j];
+    }
     return RC_OK;
 }
 

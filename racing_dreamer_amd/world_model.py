@@ -55,6 +55,40 @@ def behaviour_terms(env, batch: Dict[str, torch.Tensor], horizon: int = 15, lamb
     return out
 
 
+def value_learning_step(env, batch: Dict[str, torch.Tensor], horizon: int = 15, lambda_: float = 0.95, discount: float = 0.99,
+                        seed: int = 0, **fit) -> Dict[str, torch.Tensor]:
+    """The reference's value update on a replay batch (dreamer/models.py:113-137), three launches and no host
+    copy: `behaviour_terms`' two - `policy_observe(mode="sample")`, each window's last step dropped when a pcont head is loaded,
+    `policy_returns(mode="sample", outputs=("features", "returns", "weight"))` - then `critic_fit(features[:, :-1], returns,
+    weight)` on the value head, whose optimizer must be open (`critic_fit_begin`).  `fit` goes to `critic_fit` (lr, clip, ...).
+    Returns the fit's status (`loss`, `grad_norm`, `skipped`, `step`) and `value_loss` = `loss`: what `behaviour_terms` calls
+    value_loss, on the weights before the update."""
+    feat = env.policy_observe(batch["lidar"], batch["action"], mode="sample", seed=seed, outputs=("feature",))["feature"]
+    if env.policy_has_pcont_head:
+        feat = feat[..., :-1, :]
+    state = torch.nn.functional.pad(feat.reshape(-1, feat.shape[-1]), (0, 2))
+    out = env.policy_returns(horizon, "sample", seed=seed, lambda_=lambda_, discount=discount, state=state,
+                             outputs=("features", "returns", "weight"))
+    status = env.critic_fit(out["features"][:, :-1], out["returns"], out["weight"], head="value", **fit)
+    status["value_loss"] = status["loss"]
+    return status
+
+
+def pcont_learning_step(env, batch: Dict[str, torch.Tensor], discount: float = 0.99, seed: int = 0, **fit) -> Dict[str, torch.Tensor]:
+    """One step of the pcont head ALONE on a replay batch, the world model frozen: the head on the posterior features
+    (`policy_observe(mode="sample")`) against the soft targets `discount * batch["discount"]` [B, T] (dreamer/models.py:101-105),
+    through `critic_fit(head="pcont")`, whose optimizer must be open.  This is NOT the reference's rule: there the pcont likelihood
+    is a term of the model loss and its gradient also reaches the RSSM and the encoder; here nothing but the head's eight arrays
+    moves.  The reference multiplies the term by `pcont_scale` = 10 inside the loss: a caller who wants that passes `weight=10`
+    (a tensor of the targets' shape, or a number).  Returns the fit's status."""
+    weight = fit.pop("weight", None)
+    feat = env.policy_observe(batch["lidar"], batch["action"], mode="sample", seed=seed, outputs=("feature",))["feature"]
+    target = discount * batch["discount"].to(feat.device, torch.float32).reshape(feat.shape[:-1])
+    if weight is not None and not torch.is_tensor(weight):
+        weight = torch.full_like(target, float(weight))
+    return env.critic_fit(feat, target, weight, head="pcont", **fit)
+
+
 def imagined_vs_simulated(env, horizon: int = 15, mode: str = "mean", seed: int = 0, repeat=None) -> Dict[str, torch.Tensor]:
     """The world model's dream beside what the simulator would really do, without spending the run:
     `policy_imagine` from every car's latent under the actor's own actions, then `look_ahead` with one candidate per env - those

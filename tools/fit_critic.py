@@ -3,12 +3,16 @@
 with its bootstrap agrees better with the simulator.  (Needs a GPU.)
 
     python tools/fit_critic.py [--checkpoint austria] [--envs 1024] [--iterations 400] [--out profiles/fit_critic_austria.json]
+    python tools/fit_critic.py --fit device --out profiles/fit_critic_device_austria.json
 
-No shipped checkpoint holds a value head; the reference trains one beside the actor (dreamer/models.py:113-133, value_lr 8e-5 and
-grad_clip 100 of dream.py:86-88).  Each iteration here: one agent step of a running env under `policy_act`; one
+No shipped checkpoint holds a value head; the reference trains one beside the actor (dreamer/models.py:113-137, value_lr 8e-5 of
+dream.py:86 and grad_clip 1.0 of dream.py:88).  Each iteration here: one agent step of a running env under `policy_act`; one
 `policy_returns(mode="sample", outputs=("features", "returns", "weight"))` from the live latents with the critic as it stands - the
-targets; one torch Adam step on value_loss = -mean(weight * Normal(value(features[:, :-1]), 1).log_prob(returns)) for a
-230-400-400-400-1 ELU MLP; `load_critic` with the new weights.  No pcont head is fitted: pcont is the constant discount 0.99.
+targets; one Adam step on value_loss = -mean(weight * Normal(value(features[:, :-1]), 1).log_prob(returns)) for a
+230-400-400-400-1 ELU MLP.  `--fit torch` (the default, what produced profiles/fit_critic_austria.json): torch autograd and
+torch.optim.Adam, then `load_critic` with the new weights - a copy to the host and back in every iteration; its `--clip` defaults
+to the 100 that profile was recorded with.  `--fit device`: `critic_fit` (rc_policy_fit_step: the reference's clip 1.0 and TF's
+Adam), nothing leaves the GPU inside the loop.  No pcont head is fitted: pcont is the constant discount 0.99.
 
 The record: the loss curve, the sha256 of the final weights (which are not kept: they are not reference data), and - next to
 profiles/dream_ahead_agreement.json's numbers - how well 64 candidates' scores in the dream at H = 15 agree with the simulator's true
@@ -48,8 +52,13 @@ def main():
     ap.add_argument("--lambda", dest="lambda_", type=float, default=0.95)
     ap.add_argument("--settle", type=int, default=60)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fit", choices=("torch", "device"), default="torch", help="torch: autograd, torch.optim.Adam and load_critic "
+                    "(what profiles/fit_critic_austria.json was recorded with); device: critic_fit, no host copy inside the loop")
+    ap.add_argument("--clip", type=float, default=None, help="global-norm clip; default 100 with --fit torch, so that "
+                    "profiles/fit_critic_austria.json stays what produced it, and the reference's 1.0 (dream.py:88) with --fit device")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    clip = args.clip if args.clip is not None else (100.0 if args.fit == "torch" else 1.0)
     import torch
     from racing_dreamer_amd import _lib as L
     from racing_dreamer_amd.batched_env import BatchedRaceEnv
@@ -78,6 +87,8 @@ def main():
         env.load_critic({k: v.detach().cpu().numpy() for k, v in params.items()})
 
     upload()
+    if args.fit == "device":
+        env.critic_fit_begin("value")
     curve = []
     with torch.cuda.stream(env.stream):
         env.reset(mode="random", seed=1)
@@ -91,15 +102,23 @@ def main():
                                      outputs=("features", "returns", "weight"))
             feat = got["features"][:, :-1].reshape(-1, L.POLICY_FEATURE)
             target, weight = got["returns"].reshape(-1), got["weight"].reshape(-1)
-            loss = -(weight * (-0.5 * (value_of(feat) - target) ** 2 - 0.5 * math.log(2.0 * math.pi))).mean()
-            opt.zero_grad()
-            loss.backward()
-            torch.nn.utils.clip_grad_norm_(list(params.values()), 100.0)
-            opt.step()
-            upload()
-            if it % 10 == 0 or it == args.iterations - 1:
+            if args.fit == "device":
+                loss = env.critic_fit(feat, target, weight, head="value", lr=8e-5, clip=clip)["loss"]
+            else:
+                loss = -(weight * (-0.5 * (value_of(feat) - target) ** 2 - 0.5 * math.log(2.0 * math.pi))).mean()
+                opt.zero_grad()
+                loss.backward()
+                torch.nn.utils.clip_grad_norm_(list(params.values()), clip)
+                opt.step()
+                upload()
+            if it % 10 == 0 or it == args.iterations - 1:        # (the record reads two scalars back: outside the fit itself)
                 curve.append({"iteration": it, "value_loss": round(float(loss.detach()), 6), "mean_return": round(float(target.mean()), 5)})
-        digest = hashlib.sha256(b"".join(params[k].detach().cpu().numpy().tobytes() for k in L.VALUE_KEYS)).hexdigest()
+        if args.fit == "device":
+            fitted = env.critic_weights()
+            env.critic_fit_end("value")
+        else:
+            fitted = {k: params[k].detach().cpu().numpy() for k in L.VALUE_KEYS}
+        digest = hashlib.sha256(b"".join(fitted[k].tobytes() for k in L.VALUE_KEYS)).hexdigest()
 
         # ---- the agreement of the dream's scores with the simulator, without and with the bootstrap
         long_h = 2 * h
@@ -118,7 +137,8 @@ def main():
                                                     "regret": stats(tr[rows, best] - tr[rows, pick])}
         env.sync()
     out = {"tool": "tools/fit_critic.py", "device": torch.cuda.get_device_name(0), "checkpoint": args.checkpoint, "track": args.track, "envs": n,
-           "iterations": args.iterations, "horizon": h, "lambda": args.lambda_, "discount": args.discount, "optimizer": "Adam lr 8e-5, grad clip 100",
+           "iterations": args.iterations, "horizon": h, "lambda": args.lambda_, "discount": args.discount, "fit": args.fit,
+           "optimizer": f"{'torch.optim.Adam' if args.fit == 'torch' else 'critic_fit (TF Adam)'} lr 8e-5, grad clip {clip:g}",
            "initial_critic": f"critic.init_critic({args.seed}, pcont=False)", "pcont": "constant discount (no pcont head fitted)",
            "loss_curve": curve, "final_value_weights_sha256": digest, "candidates": args.candidates, "long_horizon": long_h, "repeat": REPEAT,
            "chance_argmax_agreement": round(1.0 / args.candidates, 5), "threshold": None, "agreement": agreement}

@@ -36,6 +36,14 @@ time per step <= 1.734 x that call's (the ratio of the nominal multiply-adds) x 
 alone (1.367), `sample`, policy_value on 65 536 x 230 features, and - a record, not a condition - the three heads and a Python
 lambda-return in plain fp32 torch on features already in memory.
 
+    python tools/policy_cost.py --fit [--out profiles/policy_fit_cost.json]
+
+`--fit`: one step of the critic's fit (rc_policy_fit_step: forward, backward, clip, Adam on the value head) at 14 336 rows (tools/fit_critic.py's
+1 024 envs x 14) and 35 000 rows (the reference's 2 500 starts x 14), beside the same iteration done the way tools/fit_critic.py --fit
+torch does it - torch autograd, clip_grad_norm_, Adam.step and the load_critic upload with the synchronisation it forces - with the
+condition: device step <= 1.0 x that, reported as met or missed; and, a record without a threshold, the same torch step without the
+upload.  All three are wall-clock times per iteration over a window of iterations that ends with a synchronisation.
+
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
 windows; the torch baseline is timed with stream events around a window of calls (its dozen launches per call included - that is
 what it costs).  The baseline is a RATE baseline: torch.addmm sums in another order than the spec."""
@@ -441,6 +449,82 @@ def measure_returns(n, args):
     return res
 
 
+MACS_FIT_ROW = (230 * 400 + 2 * 400 * 400 + 400) * 2 + 2 * 400 * 400 + 400      # forward + weight gradients + backward data: 1 145 200
+
+
+def measure_fit(rows, args):
+    """Wall-clock time per iteration of critic_fit beside tools/fit_critic.py's torch step with and without its load_critic upload."""
+    import math
+    import torch
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    from racing_dreamer_amd.critic import init_critic
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    env = BatchedRaceEnv(args.track, 64, 1, auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    start = init_critic(0, pcont=False)
+    env.load_critic(start)
+    gen = torch.Generator(device="cpu").manual_seed(0)
+    feat = torch.randn((rows, 230), generator=gen).to(env.device)
+    target = torch.randn((rows,), generator=gen).to(env.device)
+    weight = torch.rand((rows,), generator=gen).to(env.device)
+    params = {k: torch.from_numpy(v).to(env.device).requires_grad_(True) for k, v in start.items()}
+    opt = torch.optim.Adam(list(params.values()), lr=8e-5)
+
+    def torch_step(upload):
+        x = feat
+        for i in range(3):
+            x = torch.nn.functional.elu(torch.addmm(params[f"value_h{i}_b"], x, params[f"value_h{i}_w"]))
+        value = torch.addmm(params["value_hout_b"], x, params["value_hout_w"])[:, 0]
+        loss = -(weight * (-0.5 * (value - target) ** 2 - 0.5 * math.log(2.0 * math.pi))).mean()
+        opt.zero_grad()
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(list(params.values()), 100.0)
+        opt.step()
+        if upload:
+            env.load_critic({k: v.detach().cpu().numpy() for k, v in params.items()})
+
+    def wall(call, iters):
+        for k in range(3):
+            call()
+        env.sync()
+        torch.cuda.synchronize()
+        windows = []
+        for r in range(args.rounds):
+            t0 = time.perf_counter()
+            for k in range(iters):
+                call()
+            env.sync()
+            torch.cuda.synchronize()
+            windows.append((time.perf_counter() - t0) * 1e3 / iters)
+        return statistics.median(windows), [round(v, 4) for v in windows]
+
+    res = {"rows": rows}
+    with torch.cuda.stream(env.stream):
+        ms, windows = wall(lambda: torch_step(True), args.calls)
+        res["torch_step_with_load_critic_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
+        ms, windows = wall(lambda: torch_step(False), args.calls)
+        res["torch_step_without_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
+        env.load_critic(start)
+        env.critic_fit_begin("value")
+        ms, windows = wall(lambda: env.critic_fit(feat, target, weight), args.calls)
+        res["critic_fit"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows,
+                             "tflops": round(2 * MACS_FIT_ROW * rows / (ms * 1e-3) / 1e12, 2)}
+        env.reset_kernel_times()
+        env.set_profiling(True, kernels=[L.K_POLICY])
+        for k in range(args.calls):
+            env.critic_fit(feat, target, weight)
+        env.sync()
+        env.set_profiling(False)
+        res["critic_fit"]["device_ms_five_launches"] = round(env.kernel_times()["rc_policy_kernel"]["avg_ms"], 4)
+        env.critic_fit_end("value")
+    base = res["torch_step_with_load_critic_upload"]["ms_per_iteration"]
+    res["critic_fit"].update(over_torch_with_upload=round(ms / base, 4), met=bool(ms <= base),
+                             over_torch_without_upload=round(ms / res["torch_step_without_upload"]["ms_per_iteration"], 4))
+    env.close()
+    return res
+
+
 FMA_PER_IMAGE = 230 * 64 + 64 * 800 + 320000 + 778752 + 259200          # h1 .. h5 (issue #16's table): 1 423 872
 FMA_PER_S_PEAK = 256 * 4 * 32 * 2.4e9      # 256 CUs x 4 SIMDs x 32 fp32 fma per clock (v_pk_fma_f32: 64 FLOP / clk / SIMD) x 2.4 GHz
 
@@ -637,9 +721,23 @@ def main():
     ap.add_argument("--decode", action="store_true", help="measure the observation decoder (profiles/policy_decode_cost.json)")
     ap.add_argument("--observe", action="store_true", help="measure recorded sequences (profiles/policy_observe_cost.json)")
     ap.add_argument("--returns", action="store_true", help="measure the critic and the lambda-return (profiles/policy_returns_cost.json)")
+    ap.add_argument("--fit", action="store_true", help="measure the critic's fit (profiles/policy_fit_cost.json)")
     ap.add_argument("--horizon", type=int, default=15)
     args = ap.parse_args()
     import torch
+    if args.fit:
+        sizes = args.envs if args.envs != [4096, 65536] else [14336, 35000]
+        out = {"tool": "tools/policy_cost.py --fit", "checkpoint": args.checkpoint, "critic": "critic.init_critic(0, pcont=False)",
+               "device": torch.cuda.get_device_name(0), "iterations_per_window": args.calls, "windows": args.rounds,
+               "macs_per_row_forward_backward": MACS_FIT_ROW, "clock": "wall clock per iteration over a window that ends with a synchronisation",
+               "condition": "critic_fit ms_per_iteration <= 1.0 x torch_step_with_load_critic_upload ms_per_iteration of the same run, at every size",
+               "sizes": [measure_fit(n, args) for n in sizes]}
+        out["condition_met"] = all(s["critic_fit"]["met"] for s in out["sizes"])
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     if args.returns:
         sizes = args.envs if args.envs != [4096, 65536] else [65536]
         out = {"tool": "tools/policy_cost.py --returns", "track": args.track, "checkpoint": args.checkpoint, "critic": "critic.init_critic(0)",
