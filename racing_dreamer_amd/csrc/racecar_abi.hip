@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "racecar_beam_pairs.h"
 #include "racecar_env.h"
 #include "racecar_spec.h"
 
@@ -691,7 +692,7 @@ struct TrackKey { uint64_t key = 0xcbf29ce484222325ull, sum2 = 0; };
 struct TrackHostTables {         // what the host prepares for the upload
     size_t bm_bytes = 0;
     std::vector<uint32_t> ray, drv;
-    std::vector<float> beams, foot;
+    std::vector<float> beams, beam_pairs, foot;   // beam_pairs: the same words, two rounds side by side (racecar_beam_pairs.h)
 };
 
 int check_track_source(const rc_env *env, const TrackSource &src) {
@@ -760,6 +761,9 @@ int make_host_tables(const TrackSource &src, TrackHostTables &ht) {
     // the one-wave-per-car scan relies on no beam being exactly axis-parallel in the sensor frame (racecar_kernels.hip)
     for (int i = 0; i < 2 * RC_N_BEAMS; ++i)
         if (!(std::fabs(ht.beams[i]) >= 1e-4f)) return fail(RC_ERR_INVALID, "beam table holds a zero component");
+    static_assert(RC_BEAM_ROUNDS == (RC_N_BEAMS + 63) / 64, "racecar_beam_pairs.h and the scan disagree on the rounds");
+    ht.beam_pairs.assign((size_t)RC_BEAM_PAIR_RECORDS * 64 * 4, 0.0f);
+    rc_pair_beams(ht.beams.data(), ht.beam_pairs.data());
     return RC_OK;
 }
 
@@ -787,8 +791,9 @@ int upload_track(const TrackSource &src, const TrackHostTables &ht, TrackTables 
     const size_t prog_bytes = align_up((size_t)h * w * 4, 64);
     const size_t cl_bytes = align_up((size_t)n_centerline * 16, 64);
     const size_t beam_bytes = align_up(ht.beams.size() * 4, 64), foot_bytes = align_up(ht.foot.size() * 4, 64);
+    const size_t pair_bytes = align_up(ht.beam_pairs.size() * 4, 64);
     const size_t spawn_bytes = align_up((size_t)n_centerline * 32, 64);
-    const size_t total = 2 * bm_bytes + prog_bytes + cl_bytes + spawn_bytes + beam_bytes + foot_bytes + 4 * quad_plane_bytes + first_bytes;
+    const size_t total = 2 * bm_bytes + prog_bytes + cl_bytes + spawn_bytes + beam_bytes + pair_bytes + foot_bytes + 4 * quad_plane_bytes + first_bytes;
     HIP_TRY(hipMalloc(&tt->mem, total));
     char *m = (char *)tt->mem;
     RcTrackDev &t = tt->t;
@@ -798,6 +803,7 @@ int upload_track(const TrackSource &src, const TrackHostTables &ht, TrackTables 
     HIP_TRY(hipMemcpy(m, src.centerline, (size_t)n_centerline * 16, hipMemcpyHostToDevice)); t.centerline = (const float *)m; m += cl_bytes;
     t.spawn = (const float4 *)m; m += spawn_bytes;            // filled on the device (build_device_tables)
     HIP_TRY(hipMemcpy(m, ht.beams.data(), ht.beams.size() * 4, hipMemcpyHostToDevice)); t.beams = (const float *)m; m += beam_bytes;
+    HIP_TRY(hipMemcpy(m, ht.beam_pairs.data(), ht.beam_pairs.size() * 4, hipMemcpyHostToDevice)); t.beam_pairs = (const float *)m; m += pair_bytes;
     HIP_TRY(hipMemcpy(m, ht.foot.data(), ht.foot.size() * 4, hipMemcpyHostToDevice)); t.footprint = (const float *)m; m += foot_bytes;
     t.cell_pitch = cell_pitch;
     t.quad_rect = (const uint16_t *)m; m += 4 * quad_plane_bytes;      // filled on the device

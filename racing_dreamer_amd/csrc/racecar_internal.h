@@ -37,6 +37,8 @@ struct RcTrackDev {
     float org_x, org_y, res, inv_res, tmax;
     float band, band_mh, band2;  // scan variants 6/7: half-width of the zone around a cell boundary in which the other-axis cell
                                  // is counted exactly = (max(w, h) + 2) * 2^-21 cells; band - 0.5; 2 * band
+    const float *beam_pairs;     // [9 * 64][4]: the words of `beams` again, entry 64 k + lane = beams 128 k + lane and 128 k + 64 + lane
+                                 // (rounds 2 k and 2 k + 1 of the one-wave-per-car scan in one 16-byte load; racecar_beam_pairs.h)
 };
 
 // The tables of the lab library's scan variants 1-5 (racecar_lab.hip).  The shipped kernels read none of them: the lab builds

@@ -499,11 +499,11 @@ __global__ __launch_bounds__(256) void rc_raycast_car_kernel(RcParams p, int spl
     // One car (or 1 / split of one) per wave and nothing more: several cars in sequence per wave were measured slower
     // (2 per wave + 6 %, 8 per wave + 20 %) - the hardware dispatcher balances 65 536 short waves better than any
     // static share, and a finished wave's flush is not waited for by anybody.
-    const unsigned zero = scan_args_at_entry(p, split);
+    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, GUARD>();
+    const unsigned zero = scan_args_at_entry<kOne>(p, split);
     const uint32_t lds_row = wave_lds_row();                             // 17 x 64 floats per wave of the workgroup
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) + zero;
     const unsigned lane = threadIdx.x & 63u;
-    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, GUARD>();
     const unsigned slot = kOne ? wave : wave / (unsigned)split, part = kOne ? 0u : wave - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     // (the waves take the cars in track order - see RcStateDev::order -: 5 % of the scan at 65 536 cars, EXPERIMENTS I.11)
@@ -523,8 +523,8 @@ __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *_
     if ((launched >> 3) >= per_xcd || wave >= g.wave_start[g.n]) return;
     const int b = group_block(g, wave);
     const RcParams p = params[b];           // (a copy: see dynamics_group_wave)
-    const unsigned local = (unsigned)(wave - g.wave_start[b]) + scan_args_at_entry(p, split);      // (here: one batch of loads from the table)
     constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
+    const unsigned local = (unsigned)(wave - g.wave_start[b]) + scan_args_at_entry<kOne>(p, split);      // (here: one batch of loads from the table)
     const unsigned slot = kOne ? local : local / (unsigned)split, part = kOne ? 0u : local - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     // (this launch hands every XCD a STRETCH of the slots, not every eighth: it takes the cars by rank)
@@ -536,11 +536,11 @@ __global__ __launch_bounds__(256) void rc_raycast_group_kernel(const RcParams *_
 // instantiations, launched only while a handle's noise is on, so the production kernels above stay what they were.
 template <int A, bool OVERLAP>
 __global__ __launch_bounds__(256) void rc_raycast_car_noise_kernel(RcParams p, int split) {
-    const unsigned zero = scan_args_at_entry(p, split);
+    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
+    const unsigned zero = scan_args_at_entry<kOne>(p, split);
     const uint32_t lds_row = wave_lds_row();
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) + zero;
     const unsigned lane = threadIdx.x & 63u;
-    constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
     const unsigned slot = kOne ? wave : wave / (unsigned)split, part = kOne ? 0u : wave - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[slot] : slot;
@@ -556,8 +556,8 @@ __global__ __launch_bounds__(256) void rc_raycast_group_noise_kernel(const RcPar
     if ((launched >> 3) >= per_xcd || wave >= g.wave_start[g.n]) return;
     const int b = group_block(g, wave);
     const RcParams p = params[b];
-    const unsigned local = (unsigned)(wave - g.wave_start[b]) + scan_args_at_entry(p, split);      // (here: one batch of loads from the table)
     constexpr bool kOne = scan_one_wave_per_car<false, OVERLAP, false>();
+    const unsigned local = (unsigned)(wave - g.wave_start[b]) + scan_args_at_entry<kOne>(p, split);      // (here: one batch of loads from the table)
     const unsigned slot = kOne ? local : local / (unsigned)split, part = kOne ? 0u : local - slot * (unsigned)split;
     if (slot >= (unsigned)p.n_cars) return;
     const unsigned car = p.st.order != nullptr ? (unsigned)p.st.order[order_slot_of_rank(slot, (uint32_t)p.n_cars)] : slot;
@@ -637,7 +637,7 @@ __global__ __launch_bounds__(256) void rc_raycast_ts_kernel(RcParams p0, int spl
     const unsigned car = (unsigned)__builtin_amdgcn_readfirstlane(p0.ts_list[slot]);
     const int k = __builtin_amdgcn_readfirstlane(ts_track_of(p0, (int)(car / (unsigned)A)));
     const RcParams p = p0.ts_table[k];      // (a copy: see dynamics_group_wave)
-    const unsigned zero = scan_args_at_entry(p, split);      // (here: one batch of loads from the table)
+    const unsigned zero = scan_args_at_entry<kOne>(p, split);      // (here: one batch of loads from the table)
     scan_car<A, false, OVERLAP, false, NOISE>(p, car + zero, part, split, threadIdx.x & 63u, lds_row);
 }
 

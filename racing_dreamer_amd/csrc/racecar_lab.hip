@@ -411,7 +411,7 @@ __global__ __launch_bounds__(1024) void rc_raycast_kernel(RcParams p, RcLabTable
 
 // The instrumented build of the same kernel (rc_debug_scan_stamps; one car per env, analysis only).
 __global__ __launch_bounds__(256) void rc_raycast_car_stamps_kernel(RcParams p, int split, unsigned long long *stamps, int n_waves) {
-    const unsigned zero = scan_args_at_entry(p, split);
+    const unsigned zero = scan_args_at_entry<false>(p, split);
     const uint32_t lds_row = wave_lds_row();
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) + zero;
     const unsigned lane = threadIdx.x & 63u;

@@ -142,6 +142,7 @@ __device__ __forceinline__ unsigned long long cmp_nlt_f32(float a, float b) {   
 }
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
+typedef float v4f __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned long long cmp_lt_f32(float a, float b) {             // lane mask of a < b
     unsigned long long m;
@@ -386,7 +387,9 @@ __device__ __forceinline__ float ray_traverse(const uint16_t *qr, const RcTrackD
         if (cmp_lt_f32_s(__builtin_amdgcn_fractf(zo + 0.5f), band2)) {    // within `band` of a boundary: exact count
             // (first let the request land: its register must not be handed to anything else while it is under way)
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(vnew));
-            if (wave_exact) *wave_exact += 1;
+            // (instrumented build only: this LANE's exact counts - all of them in the low half, in the high half those on a trip
+            // whose number, counted over the lane's rounds, is odd: scan_car turns that into the trip's parity within its round)
+            if (wave_exact) *wave_exact += (wave_trips != nullptr && (*wave_trips & 1) != 0) ? 0x10001 : 1;
             const unsigned long long xm = kSideInMask ? xside : cmp_ne_u32(xflag, 0u);
             const uint32_t tie = kSideInMask ? mask_as_flag(xm) : xflag;
             // the current cell on that axis = boundary - extent (the old Tx, Ty are not kept: no register copies per trip)
@@ -493,7 +496,9 @@ __device__ __forceinline__ uint32_t wave_lds_row() {
 // 2 first-trip line staged and first round prepared, 20 rounds done, 21 flush issued; the chip-wide 100 MHz clock
 // (s_memrealtime) at entry / flush in 6 / 7; the phases of a round summed over the wave's rounds in 27 (wait), 28 (prepare),
 // 29 (traversal), 3 (inter-car returns, transform), 4 (store to LDS), 30 (the rest); 22 wave-level trips, 23 lanes that ever
-// took the exact path, 25 / 26 trips per round (a nibble each), 24 HW_ID, 5 XCC_ID.
+// took the exact path, 25 / 26 trips per round (a nibble each), 24 HW_ID, 5 XCC_ID; per RAY (a lane in a round), summed over the
+// wave's rounds: 8 - 12 rays that stopped after 1, 2, 3, 4 and 5 or more trips, 13 rounds in which rays stopped after an odd AND
+// after an even number of trips, 14 / 15 rays that took the exact path on an odd / on an even trip of theirs.
 // OVERLAP: the next round is prepared under the first request of the current one (ray_traverse's `between`) instead of
 // ahead of the traversal.
 // LiDAR noise (rc_set_lidar_noise; oracle side: tests/dr_oracle.py).  lowbias32 (C. Wellons' 32-bit integer hash: two
@@ -543,10 +548,12 @@ constexpr bool scan_one_wave_per_car() { return !STAMPS && !OVERLAP && !GUARD; }
 // (Not a volatile statement: behind one the compiler takes memory for written and turns the scalar loads of order[] and
 // scan_pose[] into vector loads.  So it has a result instead, the constant 0 in a scalar register, which the caller adds to its
 // wave index: that keeps the statement alive and in front of the first use of the index.)
+// ONE_WAVE: the build runs one wave per car (scan_one_wave_per_car) and reads the beam table's paired image, not the per-round one.
+template <bool ONE_WAVE>
 __device__ __forceinline__ unsigned scan_args_at_entry(const RcParams &p, int split) {
     const RcTrackDev &t = p.trk;
     unsigned zero;
-    asm("s_mov_b32 %0, 0" : "=s"(zero) : "s"(split), "s"(p.n_cars), "s"(blockDim.x), "s"(p.st.order), "s"(p.st.scan_pose), "s"(t.beams), "s"(t.first_rect),
+    asm("s_mov_b32 %0, 0" : "=s"(zero) : "s"(split), "s"(p.n_cars), "s"(blockDim.x), "s"(p.st.order), "s"(p.st.scan_pose), "s"(ONE_WAVE ? t.beam_pairs : t.beams), "s"(t.first_rect),
         "s"(t.quad_rect), "s"(t.cell_pitch), "s"(t.quad_plane_bytes), "s"(t.w), "s"(t.h), "s"(t.org_x), "s"(t.org_y), "s"(t.inv_res), "s"(t.res), "s"(t.band_mh),
         "s"(t.band2), "s"(t.tmax), "s"(p.out.lidar), "s"(p.out.lidar_u16), "s"(p.lidar_transform));
     return zero;
@@ -587,6 +594,7 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         }
     };
     unsigned long long nib_lo = 0, nib_hi = 0;
+    int exact_before = 0, rays_by_trips[5] = {0, 0, 0, 0, 0}, rounds_both_parities = 0, rays_exact_odd = 0, rays_exact_even = 0;
     stamp(0);
     if (STAMPS) stamp_value(6, __builtin_amdgcn_s_memrealtime());       // the 100 MHz reference clock, one for the whole chip (s_memtime is per CU)
     // the wave's first beam pair does not depend on the car: requested before the car's state, so the two round trips
@@ -605,7 +613,22 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         const v2f b = *(global_v2f_ptr)((uintptr_t)base + lane8);
         return make_float2(b.x, b.y);
     };
-    float2 bm = beam_pair(part);
+    // One wave per car: the wave walks all 17 rounds in order, so it reads the table's PAIRED image (RcTrackDev::beam_pairs, entry
+    // 64 k + lane = the pairs of rounds 2 k and 2 k + 1) - one 16-byte load per two rounds.  The L1 counts 16 quad requests per
+    // wave-level load whatever its width, so that is 8 vector-memory instructions per car less, and no address step in the odd
+    // rounds.  `at` = 512 x (the even round): the record's offset.  The builds that run with any split take rounds part, part +
+    // split, ...: they keep the per-round table.
+    const char *beam_pairs = reinterpret_cast<const char *>(t.beam_pairs);
+    unsigned lane16 = lane * 16u;
+    auto beam_quad = [&](unsigned at) -> v4f {
+        const char *base = beam_pairs + at;
+        asm("" : "+s"(base), "+v"(lane16));
+        typedef const __attribute__((address_space(1))) v4f *global_v4f_ptr;
+        return *(global_v4f_ptr)((uintptr_t)base + lane16);
+    };
+    float2 bm = make_float2(0.0f, 0.0f);
+    v4f bq = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (kOne) bq = beam_quad(0u); else bm = beam_pair(part);
     // all four state words in one scalar 16-byte load
     const float4 sp = p.st.scan_pose[car];
     float ct = sp.z, st = sp.w;
@@ -694,8 +717,9 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         r.nx = sign_mask(r.dx); r.ny = sign_mask(r.dy);
         r.v = first_trip_entry_frame(first_line, r.dy, r.idx, r.nx, r.ny, r.fa);
     };
-    // one round: prepare `nxt` for round + split, traverse `cur`, store
-    auto stage = [&](int round, const Ray &cur, Ray &nxt) {
+    // one round: prepare `nxt` for round + split, traverse `cur`, store.  (second: the second round of a pass of the loop below - with
+    // one wave per car an odd round, whose successor's beams are the first half of the record that the even round asked for)
+    auto stage = [&](int round, const Ray &cur, Ray &nxt, const bool second) {
         if (!__builtin_amdgcn_inverse_ballot_w64(round == kRounds - 1 ? kLastRoundLanes : ~0ull)) return;   // this lane has no beam in the round
         phase(t_rest);
         // `cur` was requested a whole round ago and has arrived: say so BEFORE the next round's loads go out, or the
@@ -709,7 +733,12 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         int rnd = round;
         asm("" : "+s"(rnd));
         auto prepare_next = [&]() {
-            if (rnd + split < kRounds) {
+            if (kOne && second) {
+                prepare(make_float2(bq.x, bq.y), nxt);                    // (an odd round is never the last; its record came in a round ago)
+            } else if (kOne && rnd + 1 < kRounds) {
+                prepare(make_float2(bq.z, bq.w), nxt);
+                if (rnd + 2 < kRounds) bq = beam_quad(512u * (unsigned)(rnd + 2));   // (rounds 16 and "17": the latter is zeros, not read)
+            } else if (!kOne && rnd + split < kRounds) {
                 prepare(bm, nxt);                                         // (the padded beams of the last round included)
                 if (rnd + 2 * split < kRounds) bm = beam_pair((unsigned)(rnd + 2 * split));
             } else {
@@ -760,6 +789,17 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
             total_trips += most;
             const unsigned long long n = (unsigned long long)most;
             if (round_index < 16) nib_lo |= n << (4 * round_index); else nib_hi |= n << (4 * (round_index - 16));
+            // this lane's ray: its trips, and on which of them (odd / even, counted within the round) it took the exact path
+            const int mine = wave_trips - trips_before, ex = wave_exact - exact_before;
+            const int ex_all = ex & 0xffff, ex_odd_total = ex >> 16;
+            const int ex_odd = (trips_before & 1) ? ex_all - ex_odd_total : ex_odd_total;
+            auto lanes = [](bool c) { return (int)__builtin_popcountll(__builtin_amdgcn_ballot_w64(c)); };
+            for (int n = 1; n <= 4; ++n) rays_by_trips[n - 1] += lanes(mine == n);
+            rays_by_trips[4] += lanes(mine >= 5);
+            rounds_both_parities += (lanes(mine > 0 && (mine & 1) != 0) != 0 && lanes(mine > 0 && (mine & 1) == 0) != 0) ? 1 : 0;
+            rays_exact_odd += lanes(ex_odd > 0);
+            rays_exact_even += lanes(ex_all - ex_odd > 0);
+            exact_before = wave_exact;
             trips_before = wave_trips;
             ++round_index;
             // (read the clock AFTER the counting: the builtin alone may be scheduled ahead of it)
@@ -767,14 +807,14 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         }
     };
     Ray ra, rb;
-    prepare(bm, ra);
+    prepare(kOne ? make_float2(bq.x, bq.y) : bm, ra);
     if (STAMPS) { asm volatile("" :: "v"(ra.v)); stamp(2); t_mark = __builtin_amdgcn_s_memtime(); }
-    if ((int)part + split < kRounds) bm = beam_pair(part + (unsigned)split);
+    if (!kOne && (int)part + split < kRounds) bm = beam_pair(part + (unsigned)split);   // (one wave per car: round 1 came with round 0)
     // (a scalar loop: no lane leaves it early - the lanes without a beam in the last round sit that round out)
     for (int round = (int)part; round < kRounds; round += 2 * split) {
-        stage(round, ra, rb);
+        stage(round, ra, rb, false);
         if (round + split >= kRounds) break;
-        stage(round + split, rb, ra);
+        stage(round + split, rb, ra, true);
     }
     if (GUARD && overrun != 0 && p.scan_overrun != nullptr && lane == 0) atomicAdd(p.scan_overrun, 1u);
     // Flush the wave's ranges from LDS to the output row.  A store per round costs more than its 256 bytes: loads and
@@ -838,6 +878,10 @@ __device__ __forceinline__ void scan_car(const RcParams &p, const unsigned car, 
         stamp_value(4, t_store);
         stamp_value(25, nib_lo);
         stamp_value(26, nib_hi);
+        for (int n = 0; n < 5; ++n) stamp_value(8 + n, (unsigned long long)rays_by_trips[n]);
+        stamp_value(13, (unsigned long long)rounds_both_parities);
+        stamp_value(14, (unsigned long long)rays_exact_odd);
+        stamp_value(15, (unsigned long long)rays_exact_even);
         stamp_value(24, (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | ((32 - 1) << 11)));   // HW_ID
         stamp_value(5, (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | ((32 - 1) << 11)));   // XCC_ID
     }

@@ -7,7 +7,10 @@ its 17 rounds, rounds done, flush issued - and counts its wave-level trips.  Pri
 in shader cycles and the cycles per wave-level trip; analysis only.  Read shares and ratios off it, not times: the instrumented
 build holds 6 waves per SIMD instead of 8 and reads the clock six times per round - its launch takes 1.9 x the production kernel's
 (316 us against 166 at 65 536 cars, tools/small_batch_stamps.py); and `s_memtime` is a per-CU counter (stamps of two CUs are not
-comparable: slots 6 / 7 hold the chip-wide 100 MHz clock for that)."""
+comparable: slots 6 / 7 hold the chip-wide 100 MHz clock for that).  Slots 8 - 15 count RAYS (a lane in a round), summed over the wave's
+rounds: 8 - 12 rays that stopped after 1, 2, 3, 4 and 5 or more trips, 13 rounds that held rays stopping after an odd and after an
+even number of trips, 14 / 15 rays that took the exact path on an odd / even trip of theirs (what tests/test_gpu_scan_pairs.py asks of
+its poses; not printed here)."""
 import argparse
 import os
 import sys
