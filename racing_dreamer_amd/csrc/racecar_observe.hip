@@ -16,74 +16,31 @@
 // obs2 and img3 read their ld-64 pair images (mean columns in tile 0, raw std in tile 1) in both modes, on one wave; their
 // softplus and the KL's logarithms are spread over the four waves, and the softplus of a std nobody asked for is not taken.  Only the requested outputs leave the CU.  DESIGN.md §4 has the LDS budget.
 #include "racecar_env.h"
-#include "racecar_policy_math.h"
-#include "racecar_policy_tiles.h"
-#include <hip/hip_ext.h>
+#include "racecar_rollout.h"
 
 namespace {
 
 constexpr int SCK = 120;                       // beams per staged piece of the scan (9 pieces), as rc_policy_kernel's
 constexpr int N_BEAMS = 1080;
-constexpr int ZS = 233;                        // row stride of Z (41 mod 64, odd: the 32 rows on 32 banks)
-constexpr int Z_STOCH = RC_POLICY_DETER, Z_ACTION = RC_POLICY_DETER + RC_POLICY_STOCH;
-constexpr int FEAT = RC_POLICY_STOCH + RC_POLICY_DETER;
 // columns of X (img3: the prior, kept until obs2's KL of the same step) and of Y (obs2: the posterior) behind the activations
 constexpr int P_MEAN = 256, P_STD = 288;       // [256, 286) the mean, [288, 318) the raw std, then the std
 constexpr int P_KL = 320;                      // Y[320, 350) the KL's terms of a row
-constexpr size_t kLdsBytes = (size_t)(2 * PM * XS + PM * ZS) * sizeof(float);
+constexpr size_t kLdsBytes = RO_LDS_XYZ;
 constexpr size_t kLdsBytesSampled = kLdsBytes + (size_t)PM * PN * sizeof(float);             // + a step's normals
 
-struct ObLayer {
-    const float *a;          // LDS input, first column; rows `as` apart
-    int k;
-    const float *a2;         // second part of the input (weight rows k ..), or k2 = 0
-    int k2, as;
-    const float *w, *b;
-    int ld, n;
-    float *d;                // LDS output [32][XS], first column; null: the head's one column -> reward[row, t]
-};
-
-// One wave's 32-column tiles col0, col0 + 128, ... of a layer: ELU into LDS, or the reward head's output column
-template <int TN>
-__device__ __forceinline__ void ob_dense(const RcObserveCall &c, const ObLayer &L, int64_t row0, int t, int col0, int lane) {
-    const int cc = lane & 31, half = lane >> 5;
-    int col[TN];
-#pragma unroll
-    for (int i = 0; i < TN; ++i) col[i] = col0 + 128 * i;
-    pm_f32x16 acc[TN];
-    pm_bias<TN>(acc, L.b, col, cc);
-    pm_gemm<TN>(acc, L.a + cc * L.as + half, L.k / 2, L.w + (size_t)half * L.ld + cc, L.ld, col);
-    if (L.k2) pm_gemm<TN>(acc, L.a2 + cc * L.as + half, L.k2 / 2, L.w + (size_t)(L.k + half) * L.ld + cc, L.ld, col);
-#pragma unroll
-    for (int i = 0; i < TN; ++i) {
-        const int j = col[i] + cc;
-        if (j >= L.n) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = pm_row(r, half);
-            if (L.d) L.d[row * XS + j] = pm_elu(acc[i][r]);
-            else if (row0 + row < c.rows) c.reward[(size_t)(row0 + row) * c.length + t] = acc[i][r];
-        }
-    }
-}
+enum { OK_REWARD = RO_OUT };
 
 // img3 (POST = false, input X) and obs2 (POST = true, input Y) on one wave: the mean columns (tile 0) and the raw std columns
 // (tile 1) of the ld-64 pair image into columns [256, 288) and [288, 320) of the buffer the layer read
 template <bool POST>
 __device__ __forceinline__ void ob_pair(const RcObserveCall &c, float *X, float *Y, int lane) {
-    const int cc = lane & 31, half = lane >> 5;
-    const int col[2] = {0, 32};
-    pm_f32x16 acc[2];
-    const float *w = POST ? c.ws.obs2_w : c.wi.img3_w;
     float *io = POST ? Y : X;
-    pm_bias<2>(acc, POST ? c.ws.obs2_b : c.wi.img3_b, col, cc);
-    pm_gemm<2>(acc, io + cc * XS + half, RC_POLICY_DETER / 2, w + (size_t)half * RC_POLICY_LDPAIR + cc, RC_POLICY_LDPAIR, col);
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int row = pm_row(r, half);
-        io[row * XS + P_MEAN + cc] = acc[0][r];
-        io[row * XS + P_STD + cc] = acc[1][r];
-    }
+    const RoLayer L = {io, RC_POLICY_DETER, nullptr, 0, XS, POST ? c.ws.obs2_w : c.wi.img3_w, POST ? c.ws.obs2_b : c.wi.img3_b,
+                       RC_POLICY_LDPAIR, 32, io, RO_OUT, nullptr};
+    ro_dense_pair(L, lane, [&](int row, int j, float mean, float raw) {
+        io[row * XS + P_MEAN + j] = mean;
+        io[row * XS + P_STD + j] = raw;
+    });
 }
 
 // What follows a pair layer, one (row, column) per thread and pass: std = softplus(raw) + 0.1 where somebody reads it, the
@@ -120,20 +77,17 @@ __device__ __forceinline__ void ob_pair_finish(const RcObserveCall &c, float *X,
 template <bool SAMPLED>
 __device__ __forceinline__ void ob_observe(const RcObserveCall &c) {
     extern __shared__ float ob_lds[];
-    float *X = ob_lds, *Y = ob_lds + PM * XS, *Z = ob_lds + 2 * PM * XS;
-    float *normals = Z + PM * ZS;                            // [32][PN]   (sampled only)
+    const RoLds lds = ro_carve(ob_lds);
+    float *X = lds.X, *Y = lds.Y, *Z = lds.Z;
+    float *normals = lds.rest;                               // [32][PN]   (sampled only)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, cc = lane & 31, half = lane >> 5;
     const int64_t row0 = (int64_t)blockIdx.x * PM;
     const int T = c.length;
 
+    // a row's window in the caller's arrays, -1 past the end
+    auto window = [&](int row) { return row0 + row < c.rows ? row0 + row : (int64_t)-1; };
     // the start state: stoch | deter of state_in (its action columns are not read), or RSSM.initial's zeros; zero rows past the end
-    for (int idx = tid; idx < PM * ZS; idx += PT) {
-        const int row = idx / ZS, j = idx - row * ZS;
-        float v = 0.0f;
-        if (c.state_in && row0 + row < c.rows && j < FEAT)
-            v = c.state_in[(size_t)(row0 + row) * RC_POLICY_STATE + (j < RC_POLICY_DETER ? RC_POLICY_STOCH + j : j - RC_POLICY_DETER)];
-        Z[idx] = v;
-    }
+    ro_load_latent_rows(c.state_in, [&](int row) { return c.state_in ? window(row) : (int64_t)-1; }, Z, tid);
     __syncthreads();
 
     const bool head = c.reward != nullptr;
@@ -142,22 +96,20 @@ __device__ __forceinline__ void ob_observe(const RcObserveCall &c) {
         const bool observed = t < c.context;
         // (an observed step's prior is computed only where something of it is asked for: nothing else reads it)
         const bool need_prior = !observed || c.prior_mean || c.prior_std || c.kl;
+        // the row's place in the caller's [rows][T] arrays at this step
+        auto at_step = [&](int row) { return row0 + row < c.rows ? (row0 + row) * T + t : (int64_t)-1; };
         if constexpr (SAMPLED) {
-            // thread (row, block) = (tid / 8, tid % 8) draws block `block` of step t of its row
-            const int row = tid >> 3, blk = tid & 7;
-            float n[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (row0 + row < c.rows) {
+            ro_stage_normals(normals, [&](int row) { return row0 + row < c.rows; }, [&](int row, uint32_t blk, float (&n)[4]) {
                 const uint64_t id = c.row_offset + (uint64_t)(row0 + row);
-                pm_observe_normal_block((uint32_t)id, (uint32_t)(id >> 32), (uint32_t)t, (uint32_t)blk, c.seed_lo, c.seed_hi, n);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) normals[row * PN + 4 * blk + i] = n[i];
+                pm_observe_normal_block((uint32_t)id, (uint32_t)(id >> 32), (uint32_t)t, blk, c.seed_lo, c.seed_hi, n);
+            }, false, tid);
         }
-        if (tid < 2 * PM) {
-            const int row = tid >> 1, j = tid & 1;
-            Z[row * ZS + Z_ACTION + j] = row0 + row < c.rows ? pm_clamp_action(c.actions[((size_t)(row0 + row) * T + t) * 2 + j]) : 0.0f;
-        }
+        ro_stage_actions(c.actions, nullptr, at_step, Z, tid);
         __syncthreads();
+        // the head's one column
+        auto out = [&](const RoLayer &L, int row, int, float v) {
+            if (row0 + row < c.rows) L.g[(size_t)(row0 + row) * T + t] = v;
+        };
 
         // ---- the prior step (img_step), then the head's three layers; the posterior sits between them (below)
         const int last = head ? 6 : 3;
@@ -222,13 +174,7 @@ __device__ __forceinline__ void ob_observe(const RcObserveCall &c) {
                     }
                 }
                 // feature[t] = [stoch', deter'] from the latent (its next writer is a barrier away); after the last step the state
-                if (c.features) {
-                    for (int idx = tid; idx < PM * FEAT; idx += PT) {
-                        const int row = idx / FEAT, j = idx - row * FEAT;
-                        if (row0 + row < c.rows)
-                            c.features[((size_t)(row0 + row) * T + t) * FEAT + j] = Z[row * ZS + (j < RC_POLICY_STOCH ? Z_STOCH + j : j - RC_POLICY_STOCH)];
-                    }
-                }
+                if (c.features) ro_store_features(c.features, at_step, Z, tid);
                 if (c.state_out && t == T - 1) {
                     for (int idx = tid; idx < PM * RC_POLICY_STATE; idx += PT) {
                         const int row = idx / RC_POLICY_STATE, j = idx - row * RC_POLICY_STATE;
@@ -239,48 +185,19 @@ __device__ __forceinline__ void ob_observe(const RcObserveCall &c) {
                 }
                 continue;
             }
-            ObLayer L;
+            RoLayer L;
             switch (layer) {
-            case 0: L = {Z + Z_STOCH, 32, nullptr, 0, ZS, c.w.img1_w, c.w.img1_b, RC_POLICY_LD200, RC_POLICY_DETER, X}; break;
-            case 1: L = {Y, RC_POLICY_DETER, nullptr, 0, XS, c.wi.img2_w, c.wi.img2_b, RC_POLICY_LD200, RC_POLICY_DETER, X}; break;
-            case 3: L = {Z + Z_STOCH, RC_POLICY_STOCH, Z, RC_POLICY_DETER, ZS, c.wi.rh_w[0], c.wi.rh_b[0], RC_POLICY_LD400, RC_POLICY_UNITS, X}; break;
-            case 4: L = {X, RC_POLICY_UNITS, nullptr, 0, XS, c.wi.rh_w[1], c.wi.rh_b[1], RC_POLICY_LD400, RC_POLICY_UNITS, Y}; break;
-            default: L = {Y, RC_POLICY_UNITS, nullptr, 0, XS, c.wi.rout_w, c.wi.rout_b, RC_POLICY_LDSMALL, 1, nullptr}; break;
+            case 0: L = ro_img1(Z, c.w, X); break;
+            case 1: L = ro_img2(Y, c.wi, X); break;
+            case 3: L = ro_first(Z, c.wi.rh_w[0], c.wi.rh_b[0], X); break;
+            case 4: L = ro_hidden(X, c.wi.rh_w[1], c.wi.rh_b[1], Y); break;
+            default: L = ro_column(Y, c.wi.rout_w, c.wi.rout_b, OK_REWARD, c.reward); break;
             }
-            if (layer == 1) {
-                // the new deter into the latent: the GRU's readers of the old one are through, nothing reads Z in this phase
-                for (int idx = tid; idx < PM * RC_POLICY_DETER; idx += PT) {
-                    const int row = idx / RC_POLICY_DETER, j = idx - row * RC_POLICY_DETER;
-                    Z[row * ZS + j] = Y[row * XS + j];
-                }
-            }
-            const int n_tiles = (L.n + 31) / 32;
-            const int mine = wave < n_tiles && (layer != 1 || need_prior) ? (n_tiles - wave + 3) / 4 : 0;      // tiles wave, wave + 4, ...
-            if (mine == 1) ob_dense<1>(c, L, row0, t, 32 * wave, lane);
-            else if (mine == 2) ob_dense<2>(c, L, row0, t, 32 * wave, lane);
-            else if (mine == 3) ob_dense<3>(c, L, row0, t, 32 * wave, lane);
-            else if (mine == 4) ob_dense<4>(c, L, row0, t, 32 * wave, lane);
+            if (layer == 1) ro_commit_deter(Y, Z, tid);
+            if (layer != 1 || need_prior) ro_layer(L, wave, lane, out);
             __syncthreads();
             if (layer != 0) continue;
-
-            // ---- GRU on x = X[0, 200) and h = Z[0, 200), as rc_policy_kernel's: the new deter goes to Y[0, 200)
-#pragma unroll 1
-            for (int jt = wave; jt < RC_POLICY_LD200 / 32; jt += 4) {
-                const int col[3] = {32 * jt, RC_POLICY_LD200 + 32 * jt, 2 * RC_POLICY_LD200 + 32 * jt};
-                pm_f32x16 mx[3], mh[3];
-                pm_bias<3>(mx, c.w.gru_b, col, cc);
-                pm_gemm<3>(mx, X + cc * XS + half, RC_POLICY_DETER / 2, c.w.gru_k + (size_t)half * RC_POLICY_LDGRU + cc, RC_POLICY_LDGRU, col);
-                pm_bias<3>(mh, c.w.gru_b + RC_POLICY_LDGRU, col, cc);
-                pm_gemm<3>(mh, Z + cc * ZS + half, RC_POLICY_DETER / 2, c.w.gru_r + (size_t)half * RC_POLICY_LDGRU + cc, RC_POLICY_LDGRU, col);
-                const int j = 32 * jt + cc;
-                if (j < RC_POLICY_DETER) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int row = pm_row(r, half);
-                        Y[row * XS + j] = pm_gru(mx[0][r], mx[1][r], mx[2][r], mh[0][r], mh[1][r], mh[2][r], Z[row * ZS + j]);
-                    }
-                }
-            }
+            ro_gru(c.w, X, Z, Y, wave, lane);
             __syncthreads();
         }
     }
@@ -291,15 +208,9 @@ __device__ __forceinline__ void ob_observe(const RcObserveCall &c) {
 __global__ __launch_bounds__(PT) void rc_policy_observe_kernel(RcObserveCall c) { ob_observe<false>(c); }
 __global__ __launch_bounds__(PT) void rc_policy_observe_sampled_kernel(RcObserveCall c) { ob_observe<true>(c); }
 
-hipError_t rck_observe_prepare() {
-    const hipError_t e = hipFuncSetAttribute((const void *)rc_policy_observe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void *)rc_policy_observe_sampled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytesSampled);
-}
+hipError_t rck_observe_prepare() { return ro_prepare(rc_policy_observe_kernel, rc_policy_observe_sampled_kernel, kLdsBytes, kLdsBytesSampled); }
 
 hipError_t rck_launch_observe(const RcObserveCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s) {
-    const unsigned blocks = (unsigned)((c.rows + PM - 1) / PM);
-    if (!c.sample) hipExtLaunchKernelGGL(rc_policy_observe_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytes, s, start, stop, 0u, c);
-    else hipExtLaunchKernelGGL(rc_policy_observe_sampled_kernel, dim3(blocks), dim3(PT), (uint32_t)kLdsBytesSampled, s, start, stop, 0u, c);
-    return hipGetLastError();
+    return ro_launch(c.sample ? rc_policy_observe_sampled_kernel : rc_policy_observe_kernel, c.rows, c.sample ? kLdsBytesSampled : kLdsBytes,
+                     c, start, stop, s);
 }

@@ -1,7 +1,8 @@
-// The MFMA machinery the Dreamer kernels share (racecar_policy.hip: the agent; racecar_imagine.hip: imagination): one workgroup of
-// four waves owns 32 cars = the rows of v_mfma_f32_32x32x2_f32 tiles; activations lie in LDS rows of an odd stride, weights are
-// read from L2 straight into the B operand.  Below the k loop (pm_gemm): the row-to-car map of a call and the packing of the
-// stored latent into LDS.  The dense wrappers, the tile ladder and the GRU loop are each kernel's own (DESIGN.md §4 says why).
+// The MFMA machinery the Dreamer kernels share (racecar_policy.hip: the agent; racecar_fit.hip and racecar_decode.hip; through
+// racecar_rollout.h the four rollout units): one workgroup of four waves owns 32 cars = the rows of v_mfma_f32_32x32x2_f32 tiles;
+// activations lie in LDS rows of an odd stride, weights are read from L2 straight into the B operand.  Below the k loop (pm_gemm):
+// the row-to-car map of a call and the packing of the stored latent into LDS.  The dense wrapper, the tile ladder and the GRU loop
+// of the rollout units are in racecar_rollout.h; the agent and the fit keep their own (DESIGN.md §4 says why).
 // Not part of the public interface.
 #pragma once
 #include "racecar_policy.h"
