@@ -680,6 +680,63 @@ typedef struct rc_policy_decode_args {
  * Kernel: rc_policy_decode_kernel, timed under RC_K_POLICY. */
 int rc_policy_decode(rc_env *env, const rc_policy_decode_args *args);
 
+/* rc_policy_decode_loglik: rc_policy_decode with the Bernoulli log-likelihood of a target image, `image_pred.log_prob(
+ * data['lidar_occupancy'])` of dreamer/models.py:99 (tests/policy_decode_loglik_spec.c fixes the order of
+ * summation, the device equals it bit for bit): loglik = sum over the 64 x 64 pixels of x logit - softplus(logit), x = 1 where the
+ * target's byte is not 0.  A second instantiation of the same kernel body; rc_policy_decode and its args are as they were. */
+typedef struct rc_policy_decode_loglik_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_decode_loglik_args) */
+    const float *features;         /* device float32 [rows, 230], or NULL: the live latents, one row per car */
+    int64_t rows;                  /* with features: >= 1; ignored without */
+    uint32_t slot_mask;            /* live latents only; with features it must be 0 */
+    const uint8_t *target;         /* with features: device uint8 [rows, 64, 64] on a 2-byte boundary, or NULL (then no loglik); live
+                                      latents: must be NULL - the target is the car's own RC_F_OCCUPANCY in the current arena */
+    float *loglik;                 /* device float32 [rows], or NULL */
+    float *logits;                 /* device float32 [rows, 64, 64], or NULL: as rc_policy_decode's */
+    uint8_t *image;                /* device uint8 [rows, 64, 64], or NULL: as rc_policy_decode's */
+} rc_policy_decode_loglik_args;
+/* One launch on the handle's stream, pure as rc_policy_decode.  RC_ERR_INVALID: wrong struct_size, no policy loaded, no decoder
+ * loaded, no output asked for, rows < 1 or a slot mask with features, loglik with features and no target, an empty mask or bits
+ * beyond cars_per_env without features, a target with live latents, loglik on live latents under obs_type RC_OBS_LIDAR.
+ * Kernel: rc_policy_decode_loglik_kernel, timed under RC_K_POLICY. */
+int rc_policy_decode_loglik(rc_env *env, const rc_policy_decode_loglik_args *args);
+
+/* The LiDAR distance decoder: what scan the world model expects (tests/policy_lidar_decode_spec.c is the CPU
+ * restatement, the device equals it bit for bit).  The reference's LidarDistanceDecoder (dreamer/models.py:424-441), the decoder of
+ * obs_type `lidar`, on a feature [stoch 30 | deter 200]: dense1 230 -> 256 (no activation), dense2 256 -> 512 (ReLU), params
+ * 512 -> 2160 (leaky ReLU, slope 0.2), then tfpl.IndependentNormal(1080): loc = the first 1080 outputs, scale = softplus of the
+ * last 1080, both in the model's units scan_m / 15 - 0.5.  loglik = sum over the beams b of
+ * -((y_b - loc_b) / scale_b)^2 / 2 - log(scale_b) - log(2 pi) / 2 with y = the target scan, clipped to [0, 15] m and brought to the
+ * model's units on the device, in the order of summation the spec fixes: `image_pred.log_prob(data['lidar'])` of
+ * dreamer/models.py:99.  No shipped checkpoint carries this decoder: the caller brings the six arrays (host pointers as in
+ * rc_policy_weights).  rc_policy_load_lidar_decoder checks the shapes first (RC_ERR_INVALID names the first that is wrong), needs a
+ * loaded policy and copies the arrays; d = NULL drops the decoder, and so do rc_policy_load and rc_policy_unload. */
+typedef struct rc_policy_lidar_decoder {
+    uint32_t struct_size;          /* = sizeof(rc_policy_lidar_decoder) */
+    rc_policy_array ldec_dense1_w, ldec_dense1_b;              /* [230, 256], [256]   input [stoch, deter]                     */
+    rc_policy_array ldec_dense2_w, ldec_dense2_b;              /* [256, 512], [512]                                            */
+    rc_policy_array ldec_params_w, ldec_params_b;              /* [512, 2160], [2160] columns: loc 1080, then raw scale 1080   */
+} rc_policy_lidar_decoder;
+int rc_policy_load_lidar_decoder(rc_env *env, const rc_policy_lidar_decoder *d);
+typedef struct rc_policy_decode_lidar_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_decode_lidar_args) */
+    const float *features;         /* device float32 [rows, 230], or NULL: the live latents of rc_policy_state, one row per car */
+    int64_t rows;                  /* with features: >= 1; ignored without */
+    uint32_t slot_mask;            /* live latents only: bit a = slot a, as rc_policy_act's; with features it must be 0 */
+    const float *target;           /* with features: device float32 [rows, 1080] in metres, or NULL (then no loglik); live latents:
+                                      must be NULL - the target is the car's own RC_F_LIDAR in the current arena */
+    float *mean;                   /* device float32 [rows, 1080], or NULL: loc, the distribution's mode */
+    float *std;                    /* device float32 [rows, 1080], or NULL: scale */
+    float *loglik;                 /* device float32 [rows], or NULL */
+} rc_policy_decode_lidar_args;
+/* rc_policy_decode_lidar: one launch on the handle's stream.  A pure function of its input: the agent's state, RC_F_ACTION_IN, the
+ * arena and every counter stay as they are.  Live latents: rows are indexed by car, rows of cars outside the mask are not touched.
+ * RC_ERR_INVALID: wrong struct_size, no policy loaded, no LiDAR decoder loaded, no output asked for, rows < 1 or a slot mask with
+ * features, loglik with features and no target, an empty mask or bits beyond cars_per_env without features, a target with live
+ * latents, loglik on live latents under a lidar_transform other than RC_LIDAR_METRES.
+ * Kernel: rc_policy_decode_lidar_kernel, timed under RC_K_POLICY. */
+int rc_policy_decode_lidar(rc_env *env, const rc_policy_decode_lidar_args *args);
+
 /* ---- Episode log: return, length, progress and time of every episode, kept on the device (opt-in; off = the launches of a step
  * are what they are without it) ---------------------------------------------------------------------------------------------------
  * What the reference computes on the host from each recorded episode (dreamer/callbacks.py:56-100, summarize_episode /

@@ -210,6 +210,29 @@ class RcPolicyDecodeArgs(C.Structure):
                 ("logits", C.c_void_p), ("image", C.c_void_p), ("mismatch", C.c_void_p)]
 
 
+class RcPolicyDecodeLoglikArgs(C.Structure):
+    """rc_policy_decode_loglik_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("features", C.c_void_p), ("rows", C.c_int64), ("slot_mask", C.c_uint32),
+                ("target", C.c_void_p), ("loglik", C.c_void_p), ("logits", C.c_void_p), ("image", C.c_void_p)]
+
+
+LIDAR_DECODER_KEYS = ("ldec_dense1_w", "ldec_dense1_b", "ldec_dense2_w", "ldec_dense2_b", "ldec_params_w", "ldec_params_b")
+LIDAR_DECODER_SHAPES = ((230, 256), (256,), (256, 512), (512,), (512, 2160), (2160,))
+# policy_decode_lidar's output names -> trailing shape after the leading dimensions
+DECODE_LIDAR_OUTPUTS = {"mean": (RC_N_BEAMS,), "std": (RC_N_BEAMS,), "loglik": ()}
+
+
+class RcPolicyLidarDecoder(C.Structure):
+    """rc_policy_lidar_decoder (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, RcPolicyArray) for k in LIDAR_DECODER_KEYS]
+
+
+class RcPolicyDecodeLidarArgs(C.Structure):
+    """rc_policy_decode_lidar_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("features", C.c_void_p), ("rows", C.c_int64), ("slot_mask", C.c_uint32),
+                ("target", C.c_void_p), ("mean", C.c_void_p), ("std", C.c_void_p), ("loglik", C.c_void_p)]
+
+
 def _fill_arrays(struct, weights, names, optional=()):
     import numpy as np
     keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
@@ -273,6 +296,20 @@ def policy_decoder(weights):
     return d, _fill_arrays(d, weights, DECODER_KEYS)
 
 
+def policy_lidar_decoder(weights):
+    """rc_policy_lidar_decoder over a mapping that holds the ldec_* arrays of a LidarDistanceDecoder (or an .npz path), as
+    policy_heads; None if it holds none."""
+    import numpy as np
+    if isinstance(weights, (str, os.PathLike)):
+        weights = np.load(weights)
+    keys = set(weights.files) if hasattr(weights, "files") else set(weights.keys())
+    if not any(k.startswith("ldec_") for k in keys):
+        return None
+    d = RcPolicyLidarDecoder()
+    d.struct_size = C.sizeof(RcPolicyLidarDecoder)
+    return d, _fill_arrays(d, weights, LIDAR_DECODER_KEYS)
+
+
 def policy_weights(weights):
     """rc_policy_weights over a mapping of float32 arrays (or an .npz path).  Returns (struct, the arrays it points into -
     keep them alive until rc_policy_load has returned)."""
@@ -326,6 +363,9 @@ SYMBOLS = {
     "rc_policy_observe": (C.c_int, [C.c_void_p, _P(RcPolicyObserveArgs)]),
     "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
     "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),
+    "rc_policy_decode_loglik": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeLoglikArgs)]),
+    "rc_policy_load_lidar_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyLidarDecoder)]),
+    "rc_policy_decode_lidar": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeLidarArgs)]),
     "rc_episode_log_enable": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32]),
     "rc_episode_log_disable": (C.c_int, [C.c_void_p]),
     "rc_episode_log": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(C.c_size_t), _P(C.c_void_p), _P(C.c_size_t)]),

@@ -374,6 +374,82 @@ def _decode_setup(env, features, slots, logits, image, mismatch, out):
     return features, mask, dict(logits=flat.get("logits"), image=flat.get("image"), mismatch=flat.get("mismatch")), result
 
 
+def _decode_loglik_setup(env, target, features, slots, outputs, out):
+    """policy_decode_loglik's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (features as [rows, 230] or None, the
+    slot mask, the target as uint8 [rows, 64, 64] or None, the output tensors by rc_policy_decode_loglik_args field with their
+    leading dimensions flattened, the dict to return).  The refusals are the library's."""
+    mask = (1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
+    side = L.DECODE_IMAGE
+    kinds = {"loglik": ((), torch.float32), "logits": ((side, side), torch.float32), "image": ((side, side), torch.uint8)}
+    outputs = tuple(outputs)
+    unknown = [k for k in outputs if k not in kinds]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}: choose from {sorted(kinds)}")
+    if features is not None:
+        if features.shape[-1] != L.POLICY_FEATURE:
+            raise ValueError(f"features must be [..., {L.POLICY_FEATURE}], got {tuple(features.shape)}")
+        lead = tuple(features.shape[:-1])
+        features = features.to(env.device, torch.float32).reshape(-1, L.POLICY_FEATURE).contiguous()
+        mask = 0 if slots is None else mask                  # (slots with features: the library refuses and says why)
+    else:
+        lead = (env.n_cars,)
+    if target is not None:
+        n = 1
+        for d in lead:
+            n *= int(d)
+        if target.numel() != n * side * side:
+            raise ValueError(f"target must be {lead + (side, side)} (or with a trailing 1), got {tuple(target.shape)}")
+        target = target.to(env.device, torch.uint8).reshape(-1, side, side).contiguous()
+    result, flat = {}, {}
+    for name in outputs:
+        tail, dtype = kinds[name]
+        shape = lead + tail
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = (torch.empty if slots is None else torch.zeros)(shape, dtype=dtype, device=env.device)
+        elif t.shape != shape or t.dtype != dtype or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {env.device}")
+        result[name] = t
+        flat[name] = t.view((-1,) + tail)
+    return features, mask, target, dict(loglik=flat.get("loglik"), logits=flat.get("logits"), image=flat.get("image")), result
+
+
+def _decode_lidar_setup(env, features, slots, target, outputs, out):
+    """policy_decode_lidar's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (features as [rows, 230] or None, the
+    slot mask, the target as [rows, 1080] or None, the output tensors by rc_policy_decode_lidar_args field with their leading
+    dimensions flattened, the dict to return).  What the call refuses (no policy, no decoder, no output, slots with features,
+    loglik without a target, a target with live latents) is left to the library, which names it."""
+    mask = (1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(a) for a in slots})
+    outputs = tuple(outputs)
+    unknown = [k for k in outputs if k not in L.DECODE_LIDAR_OUTPUTS]
+    if unknown:
+        raise ValueError(f"unknown outputs {unknown}: choose from {sorted(L.DECODE_LIDAR_OUTPUTS)}")
+    if features is not None:
+        if features.shape[-1] != L.POLICY_FEATURE:
+            raise ValueError(f"features must be [..., {L.POLICY_FEATURE}], got {tuple(features.shape)}")
+        lead = tuple(features.shape[:-1])
+        features = features.to(env.device, torch.float32).reshape(-1, L.POLICY_FEATURE).contiguous()
+        mask = 0 if slots is None else mask                  # (slots with features: the library refuses and says why)
+    else:
+        lead = (env.n_cars,)
+    if target is not None:
+        if tuple(target.shape) != lead + (L.RC_N_BEAMS,):
+            raise ValueError(f"target must be {lead + (L.RC_N_BEAMS,)} in metres, got {tuple(target.shape)}")
+        target = target.to(env.device, torch.float32).reshape(-1, L.RC_N_BEAMS).contiguous()
+    result, flat = {}, {}
+    for name in outputs:
+        tail = L.DECODE_LIDAR_OUTPUTS[name]
+        shape = lead + tail
+        t = None if out is None else out.get(name)
+        if t is None:
+            t = (torch.empty if slots is None else torch.zeros)(shape, dtype=torch.float32, device=env.device)
+        elif t.shape != shape or t.dtype != torch.float32 or t.device != torch.device(env.device) or not t.is_contiguous():
+            raise ValueError(f"out[{name!r}] must be a contiguous float32 tensor of shape {shape} on {env.device}")
+        result[name] = t
+        flat[name] = t.view((-1,) + tail)
+    return features, mask, target, dict(mean=flat.get("mean"), std=flat.get("std"), loglik=flat.get("loglik")), result
+
+
 class BatchedRaceEnv:
     def __init__(self, track: Union[str, Track], num_envs: int, cars_per_env: int = 1, obs_type: str = "lidar",
                  action_repeat: int = 1, seed: int = 0, device: int = 0, first_env: int = 0,
@@ -868,6 +944,9 @@ class BatchedRaceEnv:
         if decoder is not None:
             L.check(self._lib.rc_policy_load_decoder(self._h, C.byref(decoder[0])))
             self._policy_has_decoder = True
+        self._policy_has_lidar_decoder = False              # (and a LiDAR distance decoder)
+        if L.policy_lidar_decoder(weights) is not None:
+            self.load_lidar_decoder(weights)
         self._policy_has_value = self._policy_has_pcont = False      # (and a critic)
         if L.policy_critic(weights) is not None:
             self.load_critic(weights)
@@ -1028,6 +1107,82 @@ class BatchedRaceEnv:
         self._enter()
         try:
             L.check(self._decode(feats, mask, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
+
+    def _decode_loglik(self, features, mask: int, target, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_decode_loglik on this handle, as `_decode`."""
+        a = L.RcPolicyDecodeLoglikArgs(C.sizeof(L.RcPolicyDecodeLoglikArgs))
+        if features is not None:
+            a.features, a.rows, lo, hi = features.data_ptr(), features.shape[0], 0, features.shape[0]
+        a.slot_mask = mask
+        a.target = None if target is None else target[lo:hi].data_ptr()
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else t[lo:hi].data_ptr())
+        return self._lib.rc_policy_decode_loglik(self._h, C.byref(a))
+
+    def policy_decode_loglik(self, target: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None, slots=None,
+                             outputs=("loglik",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """The LidarOccupancyDecoder's log-probability of an occupancy image (`rc_policy_decode_loglik`, one launch): `loglik`
+        float32 [...] = the sum over the 64 x 64 pixels of x logit - softplus(logit), on `features` [..., 230] against `target`
+        uint8 [..., 64, 64] (1 = drivable), or on every car's live latent against its own current `lidar_occupancy` (`target`
+        stays None; obs_type lidar_occupancy*).  `outputs` may also name `logits` and `image`, as `policy_decode` returns them,
+        from the same launch.  Nothing else changes; `slots` and `out` as `policy_decode`'s."""
+        feats, mask, tgt, tensors, result = _decode_loglik_setup(self, target, features, slots, outputs, out)
+        self._enter()
+        try:
+            L.check(self._decode_loglik(feats, mask, tgt, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
+
+    def load_lidar_decoder(self, weights) -> None:
+        """Load a LidarDistanceDecoder beside the loaded policy (`rc_policy_load_lidar_decoder`): a mapping (or an .npz path) with
+        `ldec_dense1_w` [230, 256], `ldec_dense1_b` [256], `ldec_dense2_w` [256, 512], `ldec_dense2_b` [512], `ldec_params_w`
+        [512, 2160], `ldec_params_b` [2160] - `decoder.init_lidar_decoder` makes a synthetic one,
+        `decoder.lidar_decoder_from_variables` picks a trained one out of the reference's `variables.pkl`.  None drops it; so do
+        `load_policy` and `unload_policy`.  Shapes are checked by the library."""
+        if weights is None:
+            L.check(self._lib.rc_policy_load_lidar_decoder(self._h, None))
+            self._policy_has_lidar_decoder = False
+            return
+        dec = L.policy_lidar_decoder(weights)
+        if dec is None:
+            raise KeyError("decoder weights lack the ldec_* arrays")
+        L.check(self._lib.rc_policy_load_lidar_decoder(self._h, C.byref(dec[0])))
+        self._policy_has_lidar_decoder = True
+
+    @property
+    def policy_has_lidar_decoder(self) -> bool:
+        """Whether a LidarDistanceDecoder is loaded (`ldec_*` arrays): `policy_decode_lidar` needs one."""
+        return bool(getattr(self, "_policy_has_lidar_decoder", False))
+
+    def _decode_lidar(self, features, mask: int, target, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_decode_lidar on this handle: of `features` [rows, 230] into the whole tensors, or (features None) of this
+        handle's live latents into rows [lo, hi) of the tensors (one row per car)."""
+        a = L.RcPolicyDecodeLidarArgs(C.sizeof(L.RcPolicyDecodeLidarArgs))
+        if features is not None:
+            a.features, a.rows, lo, hi = features.data_ptr(), features.shape[0], 0, features.shape[0]
+        a.slot_mask = mask
+        a.target = None if target is None else target[lo:hi].data_ptr()
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else t[lo:hi].data_ptr())
+        return self._lib.rc_policy_decode_lidar(self._h, C.byref(a))
+
+    def policy_decode_lidar(self, features: Optional[torch.Tensor] = None, slots=None, target: Optional[torch.Tensor] = None,
+                            outputs=("mean",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """What scan the world model expects (`rc_policy_decode_lidar`, one launch): the reference's LidarDistanceDecoder on every
+        car's latent as `policy_act` last left it, or on `features`, a device float32 [..., 230] = stoch | deter such as
+        `policy_observe(...)["feature"]` or `policy_imagine(features=True)["feature"]`; the leading dimensions are kept.
+        `outputs` among `mean`, `std` float32 [..., 1080] - loc and scale of the Normal over the beams, in the model's units
+        scan_m / 15 - 0.5 - and `loglik` float32 [...], the log-probability of `target` float32 [..., 1080] in METRES (given
+        features), or of the car's own current `lidar` (live latents; `target` stays None).  Nothing else changes.  With `slots`
+        (live latents), rows of the other cars are zero - or what `out` (tensors to write into, by the same names) held."""
+        feats, mask, tgt, tensors, result = _decode_lidar_setup(self, features, slots, target, outputs, out)
+        self._enter()
+        try:
+            L.check(self._decode_lidar(feats, mask, tgt, tensors, 0, self.n_cars))
         finally:
             self._exit()                 # a refused call still orders torch's stream after the env's
         return result
@@ -1196,6 +1351,7 @@ class BatchedRaceEnv:
         self._policy_state = None
         self._policy_has_head = False
         self._policy_has_decoder = False
+        self._policy_has_lidar_decoder = False
         self._policy_has_value = self._policy_has_pcont = False
         L.check(self._lib.rc_policy_unload(self._h))
 
@@ -1704,6 +1860,40 @@ class MixedTrackEnv:
             self._ordered(lambda: self.parts[0]._decode(feats, mask, tensors, 0, 0))
         else:
             self._fork_join(lambda p, blk: p._decode(None, mask, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def policy_decode_loglik(self, target: Optional[torch.Tensor] = None, features: Optional[torch.Tensor] = None, slots=None,
+                             outputs=("loglik",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_decode_loglik over all blocks, as `policy_decode`."""
+        feats, mask, tgt, tensors, result = _decode_loglik_setup(self, target, features, slots, outputs, out)
+        k = self.cars_per_env
+        if feats is not None:
+            self._ordered(lambda: self.parts[0]._decode_loglik(feats, mask, tgt, tensors, 0, 0))
+        else:
+            self._fork_join(lambda p, blk: p._decode_loglik(None, mask, tgt, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def load_lidar_decoder(self, weights) -> None:
+        """The LiDAR distance decoder on every block (BatchedRaceEnv.load_lidar_decoder)."""
+        if isinstance(weights, (str, os.PathLike)):
+            weights = dict(np.load(weights))
+        for p in self.parts:
+            p.load_lidar_decoder(weights)
+
+    @property
+    def policy_has_lidar_decoder(self) -> bool:
+        return self.parts[0].policy_has_lidar_decoder
+
+    def policy_decode_lidar(self, features: Optional[torch.Tensor] = None, slots=None, target: Optional[torch.Tensor] = None,
+                            outputs=("mean",), out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_decode_lidar over all blocks: each block decodes its cars' latents into its rows of one tensor per
+        output; given `features` (every block holds the same decoder) go through the first block."""
+        feats, mask, tgt, tensors, result = _decode_lidar_setup(self, features, slots, target, outputs, out)
+        k = self.cars_per_env
+        if feats is not None:
+            self._ordered(lambda: self.parts[0]._decode_lidar(feats, mask, tgt, tensors, 0, 0))
+        else:
+            self._fork_join(lambda p, blk: p._decode_lidar(None, mask, tgt, tensors, blk[0] * k, blk[1] * k))
         return result
 
     def set_policy_sampling(self, mode: str = "mean", seed: int = 0, expl_amount: Optional[float] = None) -> None:

@@ -12,7 +12,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libracecar_hip.so")
 # one unit per subsystem ("where things live"); SCAN_SOURCE holds the scan kernels that verify_scan_assembly reads
 SCAN_SOURCE = "racecar_kernels.hip"
-SOURCES = [SCAN_SOURCE, "racecar_tracks.hip", "racecar_agents.hip", "racecar_gather.hip", "racecar_abi.hip", "racecar_policy.hip", "racecar_imagine.hip", "racecar_dream.hip", "racecar_returns.hip", "racecar_fit.hip", "racecar_observe.hip", "racecar_decode.hip", "racecar_episode.hip", "racecar_lookahead.hip"]
+SOURCES = [SCAN_SOURCE, "racecar_tracks.hip", "racecar_agents.hip", "racecar_gather.hip", "racecar_abi.hip", "racecar_policy.hip", "racecar_imagine.hip", "racecar_dream.hip", "racecar_returns.hip", "racecar_fit.hip", "racecar_observe.hip", "racecar_decode.hip", "racecar_decode_lidar.hip", "racecar_episode.hip", "racecar_lookahead.hip"]
 HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_env.h", "racecar_car.h", "racecar_step.h", "racecar_substep.inc", "racecar_spec.h", "racecar_scan.h", "racecar_beam_pairs.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", "racecar_policy_tiles.h", "racecar_rollout.h", "racecar_episode.h", os.path.join("..", "..", "include", "racecar_hip.h")]
 # The lab library: scan variants 0-6 and the instrumented build of the scan (racecar_lab.hip).  NOT part of the shipped
 # library; built by build_lab() - which tools/ and the variant tests call - and loaded by libracecar_hip.so on first use.
@@ -125,6 +125,8 @@ CHECKED_KERNELS = (
     ("rc_policy_observe_sampled_kernel", None, False, "shipped"),
     ("rc_look_ahead_kernel", None, False, "shipped"),           # (a look-ahead keeps an env's cars in registers through the horizon: a spill would sit in its sub-step)
     ("rc_policy_decode_kernel", 4, False, "shipped"),           # (the decoder: two workgroups of eight waves per CU; a spill would sit in its tap loops)
+    ("rc_policy_decode_loglik_kernel", 4, False, "shipped"),    # (the same body with the Bernoulli log-likelihood)
+    ("rc_policy_decode_lidar_kernel", None, False, "shipped"),  # (the LiDAR decoder: four MFMA accumulator tiles per wave and their prefetched operands)
 )
 NO_SPILL_KERNELS = tuple(k for k, _, _, _ in CHECKED_KERNELS)
 MIN_WAVES_PER_SIMD = {k: w for k, w, _, _ in CHECKED_KERNELS if w is not None}

@@ -17,6 +17,12 @@
 // `acc > 0 ? acc : 0` removes).  h4 and h5 have a 6 x 6 kernel: all four classes have the same 3 x 3 taps and the same input
 // pixels, so a lane computes all four (h4: a wave takes the two classes of one py) and an activation is loaded once for them.
 // Intermediate activations never leave the CU.  DESIGN.md §4 has the LDS budget, the wave assignment and the issue floor.
+//
+// rc_policy_decode_loglik_kernel is the same body instantiated with the Bernoulli log-likelihood (DESIGN.md §2 item 22;
+// tests/policy_decode_loglik_spec.c): per row the sum over the pixels of x logit - softplus(logit) against a target image x.
+// Its order: a thread adds the terms of its 8 pixels (item tid, then tid + 512; in an item rows py, in a row px) from +0.0f, a
+// wave adds its 64 threads in a binary tree over the lane (distance 1, 2, ..., 32), thread 0 adds the 8 waves in ascending order
+// from +0.0f.  rc_policy_decode_kernel is the instantiation without it: none of this is in its code.
 #include "racecar_env.h"
 #include "racecar_policy_tiles.h"
 #include <hip/hip_ext.h>
@@ -40,7 +46,8 @@ constexpr int N_H2PAD = 8 * S2 * S2 * 4, N_H3PAD = 4 * S3 * S3 * 4, N_H4PAD = 2 
 constexpr int O_FEAT = 0, O_H1 = O_FEAT + DG * FEAT, O_H2 = O_H1 + DG * RC_DEC_H1, O_A = O_H2 + DG * RC_DEC_H2, O_B = O_A + N_H4PAD,
               O_CNT = O_B + N_H3PAD, N_LDS = O_CNT + 4;
 constexpr size_t kLdsBytes = (size_t)N_LDS * sizeof(float);
-static_assert(2 * kLdsBytes <= 160 * 1024, "two workgroups per CU");
+constexpr size_t kLdsLoglikBytes = kLdsBytes + (DT / 64) * sizeof(float);      // the log-likelihood's eight wave sums behind the rest
+static_assert(2 * kLdsLoglikBytes <= 160 * 1024, "two workgroups per CU");
 static_assert(O_A % 4 == 0 && O_B % 4 == 0, "the maps are read 16 bytes at a time");
 
 __device__ __forceinline__ float dc_relu(float v) { return v > 0.0f ? v : 0.0f; }
@@ -137,7 +144,9 @@ __device__ __forceinline__ void dc_h5(const RcDecodeDev &w, const float *A, int 
 
 }  // namespace
 
-__global__ __launch_bounds__(DT) void rc_policy_decode_kernel(RcDecodeCall c) {
+// LL: with the log-likelihood of `target` [..][64][64] (indexed as the outputs are) into `loglik` [..]
+template <bool LL>
+__device__ __forceinline__ void dc_decode(const RcDecodeCall &c, const uint8_t *target, float *loglik) {
     extern __shared__ float dc_lds[];
     float *feat = dc_lds + O_FEAT, *h1 = dc_lds + O_H1, *h2 = dc_lds + O_H2, *A = dc_lds + O_A, *B = dc_lds + O_B;
     int *cnt = reinterpret_cast<int *>(dc_lds + O_CNT);
@@ -215,6 +224,7 @@ __global__ __launch_bounds__(DT) void rc_policy_decode_kernel(RcDecodeCall c) {
         __syncthreads();
         // h5 and the outputs: two blocks of 2 x 2 pixels per thread
         int differ = 0;
+        float ll = 0.0f;
 #pragma unroll 1
         for (int i = 0; i < 2; ++i) {
             const int item = tid + DT * i, Y = item >> 5, X = item & 31;
@@ -228,6 +238,28 @@ __global__ __launch_bounds__(DT) void rc_policy_decode_kernel(RcDecodeCall c) {
                 if (c.logits) *reinterpret_cast<dc_f2 *>(c.logits + p) = (dc_f2){v0, v1};
                 if (c.image) *reinterpret_cast<uint16_t *>(c.image + p) = (uint16_t)bits;
                 if (c.mismatch) differ += __popc(bits ^ (uint32_t)*reinterpret_cast<const uint16_t *>(c.occupancy + p));
+                if constexpr (LL) {
+                    if (loglik) {
+                        const uint32_t x = *reinterpret_cast<const uint16_t *>(target + p);
+                        ll = ll + (((x & 0xffu) ? v0 : 0.0f) - pm_softplus(v0));
+                        ll = ll + (((x >> 8) ? v1 : 0.0f) - pm_softplus(v1));
+                    }
+                }
+            }
+        }
+        if constexpr (LL) {
+            if (loglik) {                                                          // (the same for every thread)
+                float *wsum = dc_lds + N_LDS;
+#pragma unroll
+                for (int m = 1; m < 64; m <<= 1) ll = ll + __shfl_xor(ll, m, 64);
+                if (lane == 0) wsum[wave] = ll;
+                __syncthreads();
+                if (tid == 0) {
+                    float sum = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < DT / 64; ++k) sum = sum + wsum[k];
+                    loglik[at] = sum;
+                }
             }
         }
         if (c.mismatch) {
@@ -239,12 +271,24 @@ __global__ __launch_bounds__(DT) void rc_policy_decode_kernel(RcDecodeCall c) {
     }
 }
 
+__global__ __launch_bounds__(DT) void rc_policy_decode_kernel(RcDecodeCall c) { dc_decode<false>(c, nullptr, nullptr); }
+
+__global__ __launch_bounds__(DT) void rc_policy_decode_loglik_kernel(RcDecodeLoglikCall c) { dc_decode<true>(c.d, c.target, c.loglik); }
+
 hipError_t rck_decode_prepare() {
-    return hipFuncSetAttribute((const void *)rc_policy_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    const hipError_t e = hipFuncSetAttribute((const void *)rc_policy_decode_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute((const void *)rc_policy_decode_loglik_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsLoglikBytes);
 }
 
 hipError_t rck_launch_decode(const RcDecodeCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s) {
     const unsigned blocks = (unsigned)((c.n_rows + DG - 1) / DG);
     hipExtLaunchKernelGGL(rc_policy_decode_kernel, dim3(blocks), dim3(DT), (uint32_t)kLdsBytes, s, start, stop, 0u, c);
+    return hipGetLastError();
+}
+
+hipError_t rck_launch_decode_loglik(const RcDecodeLoglikCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s) {
+    const unsigned blocks = (unsigned)((c.d.n_rows + DG - 1) / DG);
+    hipExtLaunchKernelGGL(rc_policy_decode_loglik_kernel, dim3(blocks), dim3(DT), (uint32_t)kLdsLoglikBytes, s, start, stop, 0u, c);
     return hipGetLastError();
 }

@@ -203,6 +203,8 @@ struct rc_env {
     float *pol_heads_mem = nullptr;    // rc_policy_load_heads
     RcDecodeDev pol_d{};               // rc_policy_decode: the decoder's repacked arrays (null = none loaded)
     float *pol_dec_mem = nullptr;      // rc_policy_load_decoder
+    RcLidarDecodeDev pol_ld{};         // rc_policy_decode_lidar: the LiDAR distance decoder's images (null = none loaded)
+    float *pol_ldec_mem = nullptr;     // rc_policy_load_lidar_decoder
     RcCriticDev pol_c{};               // rc_policy_returns: the value head and the pcont head (null = none loaded)
     float *pol_critic_mem = nullptr;   // rc_policy_load_critic
     RcFit *fit = nullptr;              // rc_policy_fit_begin: the critic's optimizers and their scratch (racecar_fit.hip)

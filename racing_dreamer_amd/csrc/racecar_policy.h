@@ -170,6 +170,38 @@ struct RcDecodeCall {
     const uint8_t *occupancy;                // RC_F_OCCUPANCY [n_cars][64][64] (mismatch only)
 };
 
+// The LiDAR distance decoder (racecar_decode_lidar.hip): LidarDistanceDecoder's three dense layers.  The
+// last layer's image is padded so that every 32-column tile of a (loc, scale) pair lies inside it: loc columns at [0, 1080),
+// scale columns at [RC_LDEC_HALF, RC_LDEC_HALF + 1080), the rest zero (weights and bias).
+#define RC_LDEC_H1 256
+#define RC_LDEC_H2 512
+#define RC_LDEC_BEAMS 1080
+#define RC_LDEC_HALF 1088                                         // 34 tiles
+#define RC_LDEC_LD (2 * RC_LDEC_HALF)
+struct RcLidarDecodeDev {
+    const float *d1_w, *d1_b;                // [230][256], [256]
+    const float *d2_w, *d2_b;                // [256][512], [512]
+    const float *p_w, *p_b;                  // [512][2176], [2176]
+};
+
+struct RcLidarDecodeCall {
+    RcLidarDecodeDev w;
+    const float *features;                   // [n_rows][230], or null: the rows of `rows` from state
+    const float *state;                      // [n_cars][RC_POLICY_STATE], read only
+    RcPolicyRows rows;                       // (live latents: row -> car; outputs and the target are indexed by car)
+    int64_t n_rows;
+    const float *target;                     // [..][1080] metres (loglik only): the caller's, or the arena's RC_F_LIDAR
+    float *mean, *std;                       // [..][1080] or null
+    float *loglik;                           // [..] or null
+};
+
+// The same decoder with the Bernoulli log-likelihood of a target image (rc_policy_decode_loglik)
+struct RcDecodeLoglikCall {
+    RcDecodeCall d;
+    const uint8_t *target;                   // [..][64][64], indexed as the outputs are (loglik only): the caller's, or RC_F_OCCUPANCY
+    float *loglik;                           // [..] or null
+};
+
 hipError_t rck_policy_prepare();             // raises the kernel's dynamic-LDS limit (once per process and device is enough)
 hipError_t rck_launch_policy(const RcPolicyCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);      // c.mode: which kernel
 hipError_t rck_imagine_prepare();
@@ -182,3 +214,6 @@ hipError_t rck_returns_prepare();
 hipError_t rck_launch_returns(const RcReturnsCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
 hipError_t rck_decode_prepare();
 hipError_t rck_launch_decode(const RcDecodeCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);
+hipError_t rck_launch_decode_loglik(const RcDecodeLoglikCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);      // (rck_decode_prepare covers it)
+hipError_t rck_decode_lidar_prepare();
+hipError_t rck_launch_decode_lidar(const RcLidarDecodeCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);

@@ -450,6 +450,45 @@ int pol_drop_decoder(rc_env *env) {
     return RC_OK;
 }
 
+// the LiDAR distance decoder's memory and pointers go (rc_policy_load_lidar_decoder(NULL), a new rc_policy_load)
+int pol_drop_lidar_decoder(rc_env *env) {
+    if (env->pol_ldec_mem) {
+        HIP_TRY(hipSetDevice(env->cfg.device));
+        HIP_TRY(hipStreamSynchronize(env->stream));
+        (void)hipFree(env->pol_ldec_mem);
+        env->pol_ldec_mem = nullptr;
+    }
+    env->pol_ld = RcLidarDecodeDev{};
+    return RC_OK;
+}
+
+// rc_policy_lidar_decoder's arrays in order: the shape each must have, and the row stride of its device image
+struct LdecArray { const char *name; const rc_policy_array rc_policy_lidar_decoder::*arr; int rows, cols, ld; };
+using PLdec = rc_policy_lidar_decoder;
+const LdecArray kLdecArrays[] = {
+    {"ldec_dense1_w", &PLdec::ldec_dense1_w, 230, RC_LDEC_H1, RC_LDEC_H1}, {"ldec_dense1_b", &PLdec::ldec_dense1_b, 1, RC_LDEC_H1, RC_LDEC_H1},
+    {"ldec_dense2_w", &PLdec::ldec_dense2_w, RC_LDEC_H1, RC_LDEC_H2, RC_LDEC_H2}, {"ldec_dense2_b", &PLdec::ldec_dense2_b, 1, RC_LDEC_H2, RC_LDEC_H2},
+    {"ldec_params_w", &PLdec::ldec_params_w, RC_LDEC_H2, 2 * RC_LDEC_BEAMS, RC_LDEC_LD}, {"ldec_params_b", &PLdec::ldec_params_b, 1, 2 * RC_LDEC_BEAMS, RC_LDEC_LD},
+};
+
+// The decoder's device image, every array on a 64-float boundary; at[i] = array i's offset in floats.  The last layer's 2160
+// columns go to two padded halves, loc at [0, 1080) and scale at [RC_LDEC_HALF, RC_LDEC_HALF + 1080), the padding zero
+// (racecar_decode_lidar.hip, "the partial tile")
+void pol_pack_lidar_decoder(const rc_policy_lidar_decoder &d, std::vector<float> &img, size_t (&at)[6]) {
+    for (size_t i = 0; i < 6; ++i) {
+        const LdecArray &a = kLdecArrays[i];
+        at[i] = img.size();
+        img.resize(img.size() + ((size_t)a.rows * a.ld + 63) / 64 * 64, 0.0f);
+        const float *src = (d.*(a.arr)).data;
+        float *dst = img.data() + at[i];
+        for (int k = 0; k < a.rows; ++k)
+            for (int j = 0; j < a.cols; ++j) {
+                const int col = a.ld == RC_LDEC_LD && j >= RC_LDEC_BEAMS ? RC_LDEC_HALF + j - RC_LDEC_BEAMS : j;
+                dst[(size_t)k * a.ld + col] = src[(size_t)k * a.cols + j];
+            }
+    }
+}
+
 // the critic's memory and pointers go (rc_policy_load_critic(NULL), a new rc_policy_load)
 int pol_drop_critic(rc_env *env) {
     const int rc = fit_release(env);     // (an optimizer holds pointers into the critic's memory)
@@ -537,6 +576,7 @@ int pol_launch(rc_env *env, hipError_t (*launch)(const Call &, hipEvent_t, hipEv
 void policy_release(rc_env *env) {
     (void)pol_drop_heads(env);
     (void)pol_drop_decoder(env);
+    (void)pol_drop_lidar_decoder(env);
     (void)pol_drop_critic(env);
     if (env->pol_mem) (void)hipFree(env->pol_mem);
     if (env->pol_state) (void)hipFree(env->pol_state);
@@ -578,10 +618,13 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(rck_dream_prepare());
     HIP_TRY(rck_observe_prepare());
     HIP_TRY(rck_decode_prepare());
+    HIP_TRY(rck_decode_lidar_prepare());
     HIP_TRY(rck_returns_prepare());
     rc = pol_drop_heads(env);
     if (rc) return rc;
     rc = pol_drop_decoder(env);
+    if (rc) return rc;
+    rc = pol_drop_lidar_decoder(env);
     if (rc) return rc;
     rc = pol_drop_critic(env);
     if (rc) return rc;
@@ -959,6 +1002,98 @@ int rc_policy_decode(rc_env *env, const rc_policy_decode_args *a) {
     c.logits = a->logits; c.image = a->image; c.mismatch = a->mismatch;
     c.occupancy = env->params.out.patch;
     return pol_launch(env, rck_launch_decode, c);
+}
+
+int rc_policy_decode_loglik(rc_env *env, const rc_policy_decode_loglik_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_decode_loglik_args))
+        return fail(RC_ERR_INVALID, "rc_policy_decode_loglik_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_decode_loglik_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: no policy loaded (rc_policy_load)");
+    if (!env->pol_d.h1_w) return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: no decoder loaded (rc_policy_load_decoder)");
+    if (!a->loglik && !a->logits && !a->image) return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: no output asked for");
+    RcDecodeLoglikCall c{};
+    if (a->features) {
+        if (a->rows < 1 || a->rows > (int64_t)INT32_MAX) return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: rows %lld is outside [1, 2^31)", (long long)a->rows);
+        if (a->slot_mask) return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: a slot mask (0x%x) goes with the live latents, not with given features", a->slot_mask);
+        if (a->loglik && !a->target) return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: loglik of given features needs a target image");
+        c.d.n_rows = a->rows;
+        c.target = a->target;
+    } else {
+        const int rc = pol_rows(env, a->slot_mask, 0, "rc_policy_decode_loglik", &c.d.rows);
+        if (rc) return rc;
+        if (a->target) return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: the live latents are scored against the cars' own RC_F_OCCUPANCY: target must be NULL");
+        if (a->loglik && env->cfg.obs_type == RC_OBS_LIDAR)
+            return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: loglik needs the rendered RC_F_OCCUPANCY (obs_type lidar_occupancy or lidar_occupancy_reference)");
+        c.d.n_rows = c.d.rows.n_active;
+        c.target = env->params.out.patch;
+    }
+    if (((uintptr_t)a->logits & 7u) || ((uintptr_t)a->image & 1u) || ((uintptr_t)c.target & 1u))
+        return fail(RC_ERR_INVALID, "rc_policy_decode_loglik: logits must lie on an 8-byte boundary, image and target on a 2-byte boundary");
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    c.d.w = env->pol_d;
+    c.d.features = a->features;
+    c.d.state = env->pol_state;
+    c.d.logits = a->logits; c.d.image = a->image;
+    c.loglik = a->loglik;
+    return pol_launch(env, rck_launch_decode_loglik, c);
+}
+
+int rc_policy_load_lidar_decoder(rc_env *env, const rc_policy_lidar_decoder *d) {
+    if (!d) {
+        if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+        return pol_drop_lidar_decoder(env);
+    }
+    if (d->struct_size != sizeof(rc_policy_lidar_decoder))
+        return fail(RC_ERR_INVALID, "rc_policy_lidar_decoder.struct_size %u != %zu", d->struct_size, sizeof(rc_policy_lidar_decoder));
+    for (const LdecArray &a : kLdecArrays) {
+        const rc_policy_array &g = d->*(a.arr);
+        if (!g.data) return fail(RC_ERR_INVALID, "rc_policy_load_lidar_decoder: %s is missing", a.name);
+        if (g.rows != a.rows || g.cols != a.cols)
+            return fail(RC_ERR_INVALID, "rc_policy_load_lidar_decoder: %s has shape [%d, %d], the decoder's is [%d, %d]", a.name, g.rows, g.cols, a.rows, a.cols);
+    }
+    if (!env) return fail(RC_ERR_INVALID, "env is NULL");
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_load_lidar_decoder: no policy loaded (rc_policy_load)");
+    std::vector<float> img;
+    size_t at[6];
+    pol_pack_lidar_decoder(*d, img, at);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    if (!env->pol_ldec_mem) HIP_TRY(hipMalloc((void **)&env->pol_ldec_mem, img.size() * sizeof(float)));
+    HIP_TRY(hipMemcpyAsync(env->pol_ldec_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
+    const float *m = env->pol_ldec_mem;
+    env->pol_ld = RcLidarDecodeDev{m + at[0], m + at[1], m + at[2], m + at[3], m + at[4], m + at[5]};
+    return RC_OK;
+}
+
+int rc_policy_decode_lidar(rc_env *env, const rc_policy_decode_lidar_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_decode_lidar_args))
+        return fail(RC_ERR_INVALID, "rc_policy_decode_lidar_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_decode_lidar_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: no policy loaded (rc_policy_load)");
+    if (!env->pol_ld.d1_w) return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: no LiDAR decoder loaded (rc_policy_load_lidar_decoder)");
+    if (!a->mean && !a->std && !a->loglik) return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: no output asked for");
+    RcLidarDecodeCall c{};
+    if (a->features) {
+        if (a->rows < 1 || a->rows > (int64_t)INT32_MAX) return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: rows %lld is outside [1, 2^31)", (long long)a->rows);
+        if (a->slot_mask) return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: a slot mask (0x%x) goes with the live latents, not with given features", a->slot_mask);
+        if (a->loglik && !a->target) return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: loglik of given features needs a target scan");
+        c.n_rows = a->rows;
+        c.target = a->target;
+    } else {
+        const int rc = pol_rows(env, a->slot_mask, 0, "rc_policy_decode_lidar", &c.rows);
+        if (rc) return rc;
+        if (a->target) return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: the live latents are scored against the cars' own RC_F_LIDAR: target must be NULL");
+        if (a->loglik && env->cfg.lidar_transform != RC_LIDAR_METRES)
+            return fail(RC_ERR_INVALID, "rc_policy_decode_lidar: loglik reads the scan in metres (lidar_transform RC_LIDAR_METRES)");
+        c.n_rows = c.rows.n_active;
+        c.target = env->params.out.lidar;
+    }
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    c.w = env->pol_ld;
+    c.features = a->features;
+    c.state = env->pol_state;
+    c.mean = a->mean; c.std = a->std; c.loglik = a->loglik;
+    return pol_launch(env, rck_launch_decode_lidar, c);
 }
 
 }  // extern "C"

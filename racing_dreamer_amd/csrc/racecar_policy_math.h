@@ -233,6 +233,9 @@ __device__ __forceinline__ void pm_returns_normal_block(uint32_t id_lo, uint32_t
     pm_normal_word(id_lo, id_hi, t, block | (PM_RETURNS_TAG << 24), seed_lo, seed_hi, n);
 }
 
+// ---- the LiDAR distance decoder: tests/policy_lidar_decode_spec.c restates its use
+#define PM_HALF_LOG_2PI 0.9189385332f      // log(2 pi) / 2 rounded to binary32: the constant of a normal's log-density
+
 // ---- recorded sequences: tests/policy_observe_spec.c restates what follows
 #define PM_OBSERVE_TAG 6u                  // Philox counter word 3, bits 24-31
 

@@ -36,6 +36,71 @@ def model_terms(env, batch: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     return terms
 
 
+def _lidar_decoder_needed(env, what: str) -> None:
+    if not getattr(env, "policy_has_lidar_decoder", False):
+        raise RuntimeError(f"{what} needs a LidarDistanceDecoder (load_lidar_decoder, or ldec_* arrays in the checkpoint)")
+
+
+def _image_term(env, batch, feat, what: str) -> torch.Tensor:
+    """The mean over the features' leading dimensions of the loaded decoder's log-probability of the recorded observation: the
+    LidarDistanceDecoder's of `lidar` when one is loaded, else the LidarOccupancyDecoder's of `lidar_occupancy`; float64."""
+    if getattr(env, "policy_has_lidar_decoder", False):
+        scan = batch["lidar"].reshape(feat.shape[:-1] + (1080,))
+        return env.policy_decode_lidar(features=feat, target=scan, outputs=("loglik",))["loglik"].double().mean()
+    if getattr(env, "policy_has_decoder", False):
+        return env.policy_decode_loglik(target=batch["lidar_occupancy"], features=feat, outputs=("loglik",))["loglik"].double().mean()
+    raise RuntimeError(f"{what} needs an observation decoder: a LidarDistanceDecoder (load_lidar_decoder, or ldec_* arrays in the "
+                       f"checkpoint) or a LidarOccupancyDecoder (dec_* arrays)")
+
+
+def image_loglik(env, batch: Dict[str, torch.Tensor], mode: str = "sample", seed: int = 0) -> torch.Tensor:
+    """`likes.image` of dreamer/models.py:99: the mean over [B, T] of the decoder's log-probability of the recorded observation on
+    the posterior features (`policy_observe`, context = T), a float64 scalar on the device.  It uses whichever decoder is loaded:
+    `policy_decode_lidar` against `batch["lidar"]`, else `policy_decode_loglik` against `batch["lidar_occupancy"]`."""
+    feat = env.policy_observe(batch["lidar"], batch["action"], mode=mode, seed=seed, outputs=("feature",))["feature"]
+    return _image_term(env, batch, feat, "image_loglik")
+
+
+def model_loss(env, batch: Dict[str, torch.Tensor], kl_scale: float = 1.0, free_nats: float = 3.0, pcont_scale: float = 10.0,
+               discount: float = 0.99, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """The world-model loss of dreamer/models.py:99-110 on a replay batch, forward only, every term from the device: one
+    `policy_observe(mode="sample", seed)` - the posterior is sampled, as training does - gives the features, the KL and the
+    reward head's prediction; the loaded decoder the image term (as `image_loglik`); `policy_value` the pcont head's probability (when a pcont
+    head is loaded; its soft target is `discount * batch["discount"]`).  Returns float64 device scalars: `div` (the mean KL, before
+    the free nats), `image_loglik`, `reward_loglik`, `pcont_loglik` (already times `pcont_scale`, as the reference's
+    `likes.pcont`) and `model_loss = kl_scale * max(div, free_nats) - (image_loglik + reward_loglik + pcont_loglik)`.  The
+    defaults are dream.py:73-76.  Needs a reward head and a decoder."""
+    if not (getattr(env, "policy_has_lidar_decoder", False) or getattr(env, "policy_has_decoder", False)):
+        raise RuntimeError("model_loss needs an observation decoder (a LidarDistanceDecoder or a LidarOccupancyDecoder)")
+    if not env.policy_has_reward_head:
+        raise RuntimeError("model_loss needs a checkpoint with a reward head (reward_* arrays)")
+    obs = env.policy_observe(batch["lidar"], batch["action"], mode="sample", seed=seed, outputs=("feature", "kl", "reward"))
+    feat, lead = obs["feature"], obs["feature"].shape[:-1]
+    out = {"div": obs["kl"].double().mean()}
+    out["image_loglik"] = _image_term(env, batch, feat, "model_loss")
+    r = batch["reward"].to(feat.device, torch.float64).reshape(lead)
+    out["reward_loglik"] = (-0.5 * (r - obs["reward"].double()) ** 2 - 0.5 * math.log(2.0 * math.pi)).mean()
+    likes = out["image_loglik"] + out["reward_loglik"]
+    if env.policy_has_pcont_head:
+        p = env.policy_value(features=feat, outputs=("pcont",))["pcont"].double()
+        t = discount * batch["discount"].to(feat.device, torch.float64).reshape(lead)
+        out["pcont_loglik"] = pcont_scale * (t * torch.log(p) + (1.0 - t) * torch.log1p(-p)).mean()
+        likes = likes + out["pcont_loglik"]
+    out["model_loss"] = kl_scale * torch.clamp(out["div"], min=free_nats) - likes
+    return out
+
+
+def lidar_open_loop_summary(env, batch: Dict[str, torch.Tensor], context: int = 5) -> Dict[str, torch.Tensor]:
+    """The `lidar` branch of dreamer/models.py:246-258 `_image_summaries` without the rasteriser: `policy_observe` with `context`,
+    then `policy_decode_lidar` on the features.  Returns float32 [B, T, 1080] tensors in metres: `truth` (the recorded scan),
+    `model` = (mean + 0.5) * 15 (the reconstruction for t < context, the open-loop prediction after it) and `error` = model - truth."""
+    _lidar_decoder_needed(env, "lidar_open_loop_summary")
+    feat = env.policy_observe(batch["lidar"], batch["action"], context=context)["feature"]
+    model = (env.policy_decode_lidar(features=feat, outputs=("mean",))["mean"] + 0.5) * 15.0
+    truth = batch["lidar"].to(model.device, torch.float32).reshape(model.shape)
+    return dict(truth=truth, model=model, error=model - truth)
+
+
 def behaviour_terms(env, batch: Dict[str, torch.Tensor], horizon: int = 15, lambda_: float = 0.95, seed: int = 0,
                     discount: float = 0.99) -> Dict[str, torch.Tensor]:
     """The forward half of the reference's behaviour learning on a replay batch (dreamer/models.py:113-133),

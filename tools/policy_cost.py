@@ -15,6 +15,7 @@ beside `policy_act` (`mean`) of the same run, with the target: time per imagined
 MACs of an agent step) x the agent's call + 5 %, reported as met or missed.
 
     python tools/policy_cost.py --decode [--out profiles/policy_decode_cost.json]
+    python tools/policy_cost.py --decode-lidar [--out profiles/policy_decode_lidar_cost.json]
 
 `--decode`: the observation decoder (rc_policy_decode) on the live latents of 65 536 cars on treitlstrasse_v2 under obs_type
 lidar_occupancy - `image` only, `logits` only, `image` + `mismatch` - beside torch.nn.functional.conv_transpose2d in fp32 on the same
@@ -607,6 +608,120 @@ def measure_decode(n, args):
     return res
 
 
+MACS_LIDAR_DECODER = 230 * 256 + 256 * 512 + 512 * 2160           # dense1, dense2, params: 1 295 872
+
+
+def torch_lidar_loglik(w, feat, scan):
+    """LidarDistanceDecoder and Normal.log_prob in plain fp32 torch: three addmm, relu, leaky_relu, softplus; loglik [n]."""
+    import torch
+    import torch.nn.functional as F
+    x = torch.addmm(w["ldec_dense1_b"], feat, w["ldec_dense1_w"])
+    x = F.relu(torch.addmm(w["ldec_dense2_b"], x, w["ldec_dense2_w"]))
+    x = F.leaky_relu(torch.addmm(w["ldec_params_b"], x, w["ldec_params_w"]), 0.2)
+    y = torch.clamp(scan, 0.0, 15.0) / 15.0 - 0.5
+    return torch.distributions.Normal(x[:, :1080], F.softplus(x[:, 1080:])).log_prob(y).sum(1)
+
+
+def measure_decode_lidar(n, args):
+    """Per-call device time (RC_K_POLICY) of rc_policy_decode_lidar on the live latents of n cars in three output sets, beside the
+    `mean` agent call of the same run scaled by the ratio of multiply-adds and beside the same layers in plain fp32 torch; then
+    the occupancy decoder's loglik launch beside policy_decode(logits=True) plus the torch sum."""
+    import torch
+    import torch.nn.functional as F
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    from racing_dreamer_amd.decoder import init_lidar_decoder
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    ldec = init_lidar_decoder(0, -3.0)
+    res = {"cars": n}
+
+    def timed(env, call, calls):
+        for k in range(3):
+            call()
+        windows = []
+        for r in range(args.rounds):
+            env.reset_kernel_times()
+            env.set_profiling(True, kernels=[L.K_POLICY])
+            for k in range(calls):
+                call()
+            env.sync()
+            env.set_profiling(False)
+            windows.append(env.kernel_times()["rc_policy_kernel"]["avg_ms"])
+        return statistics.median(windows), [round(v, 4) for v in windows]
+
+    def torch_timed(call, calls):
+        for k in range(3):
+            call()
+        windows = []
+        for r in range(args.rounds):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for k in range(calls):
+                call()
+            e1.record()
+            e1.synchronize()
+            windows.append(e0.elapsed_time(e1) / calls)
+        return statistics.median(windows), [round(v, 4) for v in windows]
+
+    env = BatchedRaceEnv(args.track, n, 1, auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    env.load_lidar_decoder(ldec)
+    with torch.cuda.stream(env.stream):
+        env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            env.step(None, repeat=4)
+        env.sync()
+        act_ms, act_windows = timed(env, env.policy_act, args.calls)
+        res["policy_act_mean_ms"], res["policy_act_windows_ms"] = round(act_ms, 4), act_windows
+        bufs = dict(mean=torch.empty((n, 1080), device=env.device), std=torch.empty((n, 1080), device=env.device),
+                    loglik=torch.empty(n, device=env.device))
+        for variant, names in (("loglik", ("loglik",)), ("mean", ("mean",)), ("all", ("mean", "std", "loglik"))):
+            tensors = {k: (bufs[k] if k in names else None) for k in bufs}
+            ms, windows = timed(env, lambda: L.check(env._decode_lidar(None, 1, None, tensors, 0, n)), args.calls)
+            res[variant] = {"ms_per_call": round(ms, 4), "windows_ms": windows, "us_per_row": round(ms * 1e3 / n, 4),
+                            "tflops": round(2 * MACS_LIDAR_DECODER * n / (ms * 1e-3) / 1e12, 2)}
+        ratio = MACS_LIDAR_DECODER / MACS_PER_CAR
+        res["loglik"]["target_ms"] = round(act_ms * ratio * 1.05, 4)
+        res["loglik"]["over_scaled_agent_call"] = round(res["loglik"]["ms_per_call"] / (act_ms * ratio), 3)
+        res["loglik"]["met"] = bool(res["loglik"]["ms_per_call"] <= act_ms * ratio * 1.05)
+        w = {k: torch.from_numpy(v).to(env.device) for k, v in ldec.items()}
+        feat, scan = env.policy_state[:, :230].contiguous(), env.views["lidar"].view(n, 1080)
+        ref = torch_lidar_loglik(w, feat, scan)
+        env.sync()
+        res["max_relative_difference_from_torch"] = float(((ref - bufs["loglik"]).abs() / ref.abs()).max())
+        del ref
+        t_ms, t_windows = torch_timed(lambda: torch_lidar_loglik(w, feat, scan), max(1, args.calls // 4))
+        res["torch_fp32_ms_per_call"], res["torch_fp32_windows_ms"] = round(t_ms, 4), t_windows
+        res["hip_over_torch"] = round(res["loglik"]["ms_per_call"] / t_ms, 3)
+        res["no_slower_than_torch"] = bool(res["loglik"]["ms_per_call"] <= t_ms)
+    env.close()
+    del bufs
+    torch.cuda.empty_cache()
+    # ---- the occupancy decoder: loglik in the launch, beside logits out and the sum in torch
+    occ_w = np.load(os.path.join(ROOT, "tests", "golden", "dreamer_policy_treitlstrasse_occupancy.npz"))
+    env = BatchedRaceEnv("treitlstrasse_v2", n, 1, obs_type="lidar_occupancy", auto_reset=True, remap_actions=True)
+    env.load_policy(occ_w)
+    with torch.cuda.stream(env.stream):
+        env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            env.step(None, repeat=4)
+        env.sync()
+        loglik, logits = torch.empty(n, device=env.device), torch.empty((n, 64, 64), device=env.device)
+        seen = env.views["lidar_occupancy"].view(n, 64, 64)
+        ms, windows = timed(env, lambda: L.check(env._decode_loglik(None, 1, None, dict(loglik=loglik, logits=None, image=None), 0, n)), max(1, args.calls // 4))
+        occ = {"loglik_launch_ms": round(ms, 4), "loglik_launch_windows_ms": windows}
+        ms, windows = timed(env, lambda: L.check(env._decode(None, 1, dict(logits=logits, image=None, mismatch=None), 0, n)), max(1, args.calls // 4))
+        occ["decode_logits_ms"], occ["decode_logits_windows_ms"] = round(ms, 4), windows
+        t_ms, t_windows = torch_timed(lambda: (seen.float() * logits - F.softplus(logits)).flatten(1).sum(1), max(1, args.calls // 4))
+        occ["torch_sum_ms"], occ["torch_sum_windows_ms"] = round(t_ms, 4), t_windows
+        occ["loglik_launch_over_logits_plus_torch_sum"] = round(occ["loglik_launch_ms"] / (occ["decode_logits_ms"] + t_ms), 3)
+        res["occupancy"] = occ
+    env.close()
+    return res
+
+
 MACS_OBSERVED_STEP = 32 * 200 + 2 * 200 * 600 + 200 * 200 + 200 * 60 + 1280 * 200 + 200 * 60       # 566 400: prior and posterior, both halves
 
 
@@ -719,6 +834,7 @@ def main():
     ap.add_argument("--modes", action="store_true", help="measure the sampled modes (profiles/policy_sample_cost.json)")
     ap.add_argument("--imagine", action="store_true", help="measure imagination (profiles/policy_imagine_cost.json)")
     ap.add_argument("--decode", action="store_true", help="measure the observation decoder (profiles/policy_decode_cost.json)")
+    ap.add_argument("--decode-lidar", action="store_true", help="measure the LiDAR distance decoder (profiles/policy_decode_lidar_cost.json)")
     ap.add_argument("--observe", action="store_true", help="measure recorded sequences (profiles/policy_observe_cost.json)")
     ap.add_argument("--returns", action="store_true", help="measure the critic and the lambda-return (profiles/policy_returns_cost.json)")
     ap.add_argument("--fit", action="store_true", help="measure the critic's fit (profiles/policy_fit_cost.json)")
@@ -761,6 +877,22 @@ def main():
                "second_line": "mean_all ms_per_call beside the same steps in plain fp32 torch (torch_fp32_ms_per_call)",
                "sizes": [measure_observe(n, args) for n in sizes]}
         out["condition_met"] = out["sizes"][-1]["condition_met"]
+        out["no_slower_than_torch"] = out["sizes"][-1]["no_slower_than_torch"]
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
+    if args.decode_lidar:
+        sizes = args.envs if args.envs != [4096, 65536] else [65536]
+        out = {"tool": "tools/policy_cost.py --decode-lidar", "track": args.track, "checkpoint": args.checkpoint,
+               "decoder": "decoder.init_lidar_decoder(0, -3.0)", "device": torch.cuda.get_device_name(0), "calls_per_window": args.calls,
+               "windows": args.rounds, "settle_agent_steps": args.settle, "macs_per_row": MACS_LIDAR_DECODER, "macs_per_agent_step": MACS_PER_CAR,
+               "macs_ratio": round(MACS_LIDAR_DECODER / MACS_PER_CAR, 4), "spread_allowance": 1.05,
+               "condition": "loglik ms_per_call <= macs_ratio x policy_act_mean_ms of the same run x 1.05, at the largest size",
+               "second_condition": "loglik ms_per_call <= torch_fp32_ms_per_call (three addmm and Normal.log_prob) of the same run",
+               "sizes": [measure_decode_lidar(n, args) for n in sizes]}
+        out["condition_met"] = out["sizes"][-1]["loglik"]["met"]
         out["no_slower_than_torch"] = out["sizes"][-1]["no_slower_than_torch"]
         print(json.dumps(out))
         if args.out:
