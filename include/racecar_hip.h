@@ -482,6 +482,42 @@ typedef struct rc_policy_dream_ahead_args {
  * rc_policy_dream_sampled_kernel, timed under RC_K_POLICY. */
 int rc_policy_dream_ahead(rc_env *env, const rc_policy_dream_ahead_args *args);
 
+/* The dream's backward pass: the gradient of rc_policy_dream_ahead's return with respect to the raw action sequence and to the start
+ * latent (tests/policy_dream_grad_spec.c is the CPU restatement, the device equals it bit for bit) - what
+ * gradient-based planning in the latent asks of a world model.  Starts, rows, modes, the draws and their keys are
+ * rc_policy_dream_ahead's; the forward is its step, and `ret` and `reward` come out byte for byte as it gives them.  The backward
+ * differentiates, for t = horizon - 1 .. 0, the reward head (dreamer/models.py:301-318 DenseDecoder) and the prior step
+ * (models.py:369-380 RSSM.img_step: img1, the GRU, img2, img3 and, in mode SAMPLE, stoch' = mean + (softplus(raw) + 0.1) n with the
+ * step's own normal n held fixed) with respect to their inputs only: no weight gradient.  The clamp of the raw action to [-1, 1]
+ * passes the gradient where -1 <= a <= 1 (inclusive, as tf.clip_by_value) and gives exactly +0 elsewhere.
+ * Outputs, each optional, at least one: grad_actions [starts, K, H, 2] = d ret / d actions_in; grad_state [starts, K, 230] = d ret /
+ * d (stoch | deter) of the start; ret [starts, K]; reward [starts, K, H].  A reward head must be loaded.  The activations of the
+ * forward are kept in a scratch the handle owns (2 240 floats per row and step, at most 1 GiB, grown on demand, released with the
+ * policy); the rows are cut into chunks of chunk_rows (0: as many as the scratch's limit holds), one launch per chunk - the results
+ * do not depend on the chunking.  A pure function of its inputs otherwise, as rc_policy_dream_ahead. */
+typedef struct rc_policy_dream_grad_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_dream_grad_args) */
+    int32_t horizon;               /* H in [1, RC_POLICY_IMAGINE_MAX_HORIZON] */
+    int32_t mode;                  /* RC_POLICY_IMAGINE_* */
+    int32_t candidates;            /* K >= 1; starts x K < 2^31 */
+    uint32_t slot_mask;            /* live latents: bit a = slot a, as rc_policy_act's; with state_in: 0 */
+    float discount;                /* in [0, 1]; 1: the plain sum */
+    uint64_t seed;
+    int64_t starts;                /* with state_in: its rows, >= 1 (live latents: not read) */
+    uint64_t row_offset;           /* with state_in: the start id of start 0 (mode SAMPLE) */
+    int64_t chunk_rows;            /* rows per launch, rounded up to a multiple of 32; 0: derived from the scratch's limit */
+    const float *state_in;         /* device float32 [starts, 232], or NULL: the live latents */
+    const float *actions_in;       /* device float32 [starts, K, H, 2], raw */
+    float *grad_actions;           /* device float32 [starts, K, H, 2], or NULL */
+    float *grad_state;             /* device float32 [starts, K, 230], or NULL */
+    float *ret;                    /* device float32 [starts, K], or NULL */
+    float *reward;                 /* device float32 [starts, K, H], or NULL */
+} rc_policy_dream_grad_args;
+/* rc_policy_dream_grad: one launch per chunk on the handle's stream.  RC_ERR_INVALID: as rc_policy_dream_ahead, and no reward head
+ * loaded whatever is asked for, chunk_rows < 0.  Kernels: rc_policy_dream_grad_kernel, rc_policy_dream_grad_sampled_kernel (and, at
+ * the first call after the weights were loaded, rc_policy_dream_grad_transpose_kernel), timed under RC_K_POLICY. */
+int rc_policy_dream_grad(rc_env *env, const rc_policy_dream_grad_args *args);
+
 /* The critic and the lambda-return: the forward half of the reference's behaviour learning (dreamer/models.py:113-133 in
  * `Dreamer.train`; tests/policy_returns_spec.c is the CPU restatement, the device equals it bit for bit).
  * The rollout is rc_policy_imagine's - closed loop under the actor or open loop under actions_in, in its two modes - and on every

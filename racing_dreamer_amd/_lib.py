@@ -117,6 +117,19 @@ class RcPolicyDreamAheadArgs(C.Structure):
                 ("actions_in", C.c_void_p), ("ret", C.c_void_p), ("reward", C.c_void_p), ("final_feature", C.c_void_p)]
 
 
+# dream_ahead_grad's output names -> (rc_policy_dream_grad_args field, trailing shape after [starts, K] as a function of H)
+DREAM_GRAD_OUTPUTS = {"grad_actions": ("grad_actions", lambda H: (H, 2)), "grad_state": ("grad_state", lambda H: (POLICY_FEATURE,)),
+                      "return": ("ret", lambda H: ()), "reward": ("reward", lambda H: (H,))}
+
+
+class RcPolicyDreamGradArgs(C.Structure):
+    """rc_policy_dream_grad_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("horizon", C.c_int32), ("mode", C.c_int32), ("candidates", C.c_int32), ("slot_mask", C.c_uint32),
+                ("discount", C.c_float), ("seed", C.c_uint64), ("starts", C.c_int64), ("row_offset", C.c_uint64), ("chunk_rows", C.c_int64),
+                ("state_in", C.c_void_p), ("actions_in", C.c_void_p), ("grad_actions", C.c_void_p), ("grad_state", C.c_void_p),
+                ("ret", C.c_void_p), ("reward", C.c_void_p)]
+
+
 _CRITIC_LAYERS = ("h0_w", "h0_b", "h1_w", "h1_b", "h2_w", "h2_b", "hout_w", "hout_b")
 VALUE_KEYS = tuple("value_" + k for k in _CRITIC_LAYERS)
 PCONT_KEYS = tuple("pcont_" + k for k in _CRITIC_LAYERS)
@@ -354,6 +367,7 @@ SYMBOLS = {
     "rc_policy_load_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
     "rc_policy_imagine": (C.c_int, [C.c_void_p, _P(RcPolicyImagineArgs)]),
     "rc_policy_dream_ahead": (C.c_int, [C.c_void_p, _P(RcPolicyDreamAheadArgs)]),
+    "rc_policy_dream_grad": (C.c_int, [C.c_void_p, _P(RcPolicyDreamGradArgs)]),
     "rc_policy_load_critic": (C.c_int, [C.c_void_p, _P(RcPolicyCritic)]),
     "rc_policy_returns": (C.c_int, [C.c_void_p, _P(RcPolicyReturnsArgs)]),
     "rc_policy_fit_begin": (C.c_int, [C.c_void_p, _P(RcPolicyFitConfig)]),

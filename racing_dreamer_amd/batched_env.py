@@ -142,12 +142,14 @@ def _imagine_setup(env, horizon, mode, seed, actions, slots, features, start_rew
     return args, tensors, result
 
 
-def _dream_setup(env, actions, mode, seed, state, row_offset, slots, discount, outputs, out):
+def _dream_setup(env, actions, mode, seed, state, row_offset, slots, discount, outputs, out, table=None, who="dream_ahead"):
     """dream_ahead's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
     rc_policy_dream_ahead_args field - one row per start -, the dict to return).  What only the library can tell (no policy, no
-    head, slots with a state, the size of starts x K) is left to it, which names it."""
+    head, slots with a state, the size of starts x K) is left to it, which names it.  `table`, `who`: dream_ahead_grad's outputs
+    (L.DREAM_GRAD_OUTPUTS) and name - the two calls share everything else."""
+    table = L.DREAM_AHEAD_OUTPUTS if table is None else table
     if mode not in L.IMAGINE_MODES:
-        raise ValueError(f"dream_ahead mode must be one of {sorted(L.IMAGINE_MODES)}, got {mode!r}")
+        raise ValueError(f"{who} mode must be one of {sorted(L.IMAGINE_MODES)}, got {mode!r}")
     S = env.n_cars
     if state is not None:
         if state.dim() < 1 or state.shape[-1] != L.POLICY_FEATURE + 2 or state.numel() == 0:
@@ -159,24 +161,25 @@ def _dream_setup(env, actions, mode, seed, state, row_offset, slots, discount, o
     a = a.contiguous()
     K, H = int(a.shape[1]), int(a.shape[2])
     if K < 1:
-        raise ValueError("dream_ahead needs at least one candidate")
+        raise ValueError(f"{who} needs at least one candidate")
     if not 1 <= H <= L.IMAGINE_MAX_HORIZON:
         raise ValueError(f"horizon must be in [1, {L.IMAGINE_MAX_HORIZON}], got {H}")
     discount = float(discount)
     if not 0.0 <= discount <= 1.0:
         raise ValueError(f"discount must be in [0, 1], got {discount}")
     names = tuple(outputs)
-    unknown = [n for n in names if n not in L.DREAM_AHEAD_OUTPUTS]
+    unknown = [n for n in names if n not in table]
     if unknown:
-        raise ValueError(f"dream_ahead outputs must be among {sorted(L.DREAM_AHEAD_OUTPUTS)}, got {unknown}")
-    tensors, result = {"actions_in": a, "ret": None, "reward": None, "final_feature": None}, {}
+        raise ValueError(f"{who} outputs must be among {sorted(table)}, got {unknown}")
+    tensors, result = {"actions_in": a}, {}
+    tensors.update({field: None for field, _ in table.values()})
     if state is not None:
         tensors["state_in"] = state.to(env.device, torch.float32).reshape(S, L.POLICY_FEATURE + 2).contiguous()
         mask = 0 if slots is None else sum({1 << int(b) for b in slots})        # (slots with a state: the library refuses and says why)
     else:
         mask = (1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(b) for b in slots})
     for name in names:
-        field, tail = L.DREAM_AHEAD_OUTPUTS[name]
+        field, tail = table[name]
         shape = (S, K) + tail(H)
         t = None if out is None else out.get(name)
         if t is None:
@@ -187,6 +190,13 @@ def _dream_setup(env, actions, mode, seed, state, row_offset, slots, discount, o
     args = dict(horizon=H, mode=L.IMAGINE_MODES[mode], candidates=K, mask=mask, discount=discount, seed=int(seed) & (2 ** 64 - 1),
                 starts=S, row_offset=int(row_offset) & (2 ** 64 - 1), live=state is None)
     return args, tensors, result
+
+
+def _chunk_rows(chunk_rows) -> int:
+    n = int(chunk_rows)
+    if n < 0:
+        raise ValueError(f"chunk_rows must be >= 0, got {chunk_rows}")
+    return n
 
 
 def _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, row_offset, slots, outputs, out):
@@ -1276,6 +1286,34 @@ class BatchedRaceEnv:
             self._exit()                 # a refused call still orders torch's stream after the env's
         return result
 
+    def _dream_grad(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_dream_grad on this handle: rows as `_dream_ahead` takes them."""
+        a = L.RcPolicyDreamGradArgs(C.sizeof(L.RcPolicyDreamGradArgs), args["horizon"], args["mode"], args["candidates"], args["mask"],
+                                    args["discount"], args["seed"], args["starts"], args["row_offset"], args["chunk_rows"])
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else (t[lo:hi] if args["live"] else t).data_ptr())
+        return self._lib.rc_policy_dream_grad(self._h, C.byref(a))
+
+    def dream_ahead_grad(self, actions: torch.Tensor, mode: str = "mean", seed: int = 0, state: Optional[torch.Tensor] = None, row_offset: int = 0,
+                         slots=None, discount: float = 1.0, outputs=("grad_actions", "return"), out: Optional[Dict[str, torch.Tensor]] = None,
+                         chunk_rows: int = 0) -> Dict[str, torch.Tensor]:
+        """The gradient of `dream_ahead`'s return (`rc_policy_dream_grad`): `actions`, `mode`, `seed`, `state`, `row_offset`, `slots`
+        and `discount` are `dream_ahead`'s, and so are `return` [S, K] and `reward` [S, K, H], byte for byte.  `grad_actions`
+        [S, K, H, 2] is d return / d actions - exactly zero where the raw action lies outside [-1, 1], where `dream_ahead` clamps
+        it -, `grad_state` [S, K, 230] is d return / d (stoch | deter) of the start.  In mode "sample" the step's normals are
+        held fixed (the reparameterised gradient).  The forward's activations are kept in a scratch the env owns (at most
+        1 GiB, released with the policy); the rows go through it in chunks of `chunk_rows` (0: as many as fit), one launch per
+        chunk, and the results do not depend on the chunking.  Needs a checkpoint with a reward head.  Nothing else changes."""
+        args, tensors, result = _dream_setup(self, actions, mode, seed, state, row_offset, slots, discount, outputs, out, L.DREAM_GRAD_OUTPUTS,
+                                             "dream_ahead_grad")
+        args["chunk_rows"] = _chunk_rows(chunk_rows)
+        self._enter()
+        try:
+            L.check(self._dream_grad(args, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
+
     def _look_ahead(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
         """rc_look_ahead on this handle, reading and writing rows [lo, hi) of the tensors (one row per env)."""
         a = L.RcLookAheadArgs(C.sizeof(L.RcLookAheadArgs), args["candidates"], args["horizon"], args["repeat"])
@@ -1770,6 +1808,20 @@ class MixedTrackEnv:
             self._ordered(lambda: self.parts[0]._dream_ahead(args, tensors, 0, 0))
         else:
             self._fork_join(lambda p, blk: p._dream_ahead(args, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def dream_ahead_grad(self, actions: torch.Tensor, mode: str = "mean", seed: int = 0, state: Optional[torch.Tensor] = None, row_offset: int = 0,
+                         slots=None, discount: float = 1.0, outputs=("grad_actions", "return"), out: Optional[Dict[str, torch.Tensor]] = None,
+                         chunk_rows: int = 0) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.dream_ahead_grad over all blocks, forwarded the way `dream_ahead` is."""
+        args, tensors, result = _dream_setup(self, actions, mode, seed, state, row_offset, slots, discount, outputs, out, L.DREAM_GRAD_OUTPUTS,
+                                             "dream_ahead_grad")
+        args["chunk_rows"] = _chunk_rows(chunk_rows)
+        k = self.cars_per_env
+        if state is not None:
+            self._ordered(lambda: self.parts[0]._dream_grad(args, tensors, 0, 0))
+        else:
+            self._fork_join(lambda p, blk: p._dream_grad(args, tensors, blk[0] * k, blk[1] * k))
         return result
 
     def load_critic(self, weights) -> None:

@@ -98,6 +98,26 @@ struct RcDreamCall {
     float *ret, *reward, *final_feature;     // [starts][K], [starts][K][H], [starts][K][230]; any may be null
 };
 
+// The dream's backward pass (racecar_dream_grad.hip): the transposed weight images, [units above][units
+// below rounded up to whole tiles], the padding zero - pm_gemm's B operand is coalesced backward as it is forward
+#define RC_POLICY_LDT 256
+struct RcDreamGradDev {
+    const float *img1_t;                     // [200][32]
+    const float *gruk_t, *grur_t;            // [600][256]: the gate units z, r, candidate one behind the other
+    const float *img2_t;                     // [200][256]
+    const float *img3_t;                     // [60][256]: the 30 mean units, then the 30 raw std units
+    const float *rh0_t;                      // [400][256]: 230 columns, stoch | deter
+    const float *rh1_t;                      // [400][416]
+};
+
+struct RcDreamGradCall {
+    RcDreamCall d;                           // the forward's record; d.n_rows: the END of this launch's rows, d.final_feature unused
+    RcDreamGradDev wt;
+    int64_t row_begin;                       // the first row of this launch (a multiple of 32): workgroup b owns rows row_begin + 32 b ..
+    float *stash;                            // [rows of the launch rounded up to 32][H][RC_DREAM_GRAD_STASH]
+    float *grad_actions, *grad_state;        // [starts][K][H][2], [starts][K][230]; any may be null
+};
+
 // The critic (racecar_returns.hip): the value head and the optional pcont head, DenseDecoder((), 3, 400)
 // each, packed like the reward head
 struct RcCriticDev {
@@ -208,6 +228,7 @@ hipError_t rck_imagine_prepare();
 hipError_t rck_launch_imagine(const RcImagineCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
 hipError_t rck_dream_prepare();
 hipError_t rck_launch_dream(const RcDreamCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                    // c.sample: which kernel
+hipError_t rck_dream_grad_prepare();
 hipError_t rck_observe_prepare();
 hipError_t rck_launch_observe(const RcObserveCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
 hipError_t rck_returns_prepare();

@@ -428,6 +428,8 @@ void pol_point(const PolImage<W> (&table)[N], const W &w, rc_env *env, const flo
 
 // the reward head's memory and pointers go (rc_policy_load_heads(NULL), a new rc_policy_load); the prior's layers stay
 int pol_drop_heads(rc_env *env) {
+    const int rc = dream_grad_release(env);      // (its transposed images were made from these weights)
+    if (rc) return rc;
     if (env->pol_heads_mem) {
         HIP_TRY(hipSetDevice(env->cfg.device));
         HIP_TRY(hipStreamSynchronize(env->stream));
@@ -616,6 +618,7 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(rck_policy_prepare());
     HIP_TRY(rck_imagine_prepare());
     HIP_TRY(rck_dream_prepare());
+    HIP_TRY(rck_dream_grad_prepare());
     HIP_TRY(rck_observe_prepare());
     HIP_TRY(rck_decode_prepare());
     HIP_TRY(rck_decode_lidar_prepare());
@@ -720,6 +723,8 @@ int rc_policy_load_heads(rc_env *env, const rc_policy_heads *h) {
     size_t at[sizeof(kHeadImages) / sizeof(kHeadImages[0])];
     pol_pack(kHeadImages, *h, img, at);
     HIP_TRY(hipSetDevice(env->cfg.device));
+    const int rc_grad = dream_grad_release(env);            // new weights: the transposed images are another head's
+    if (rc_grad) return rc_grad;
     if (!env->pol_heads_mem) HIP_TRY(hipMalloc((void **)&env->pol_heads_mem, img.size() * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(env->pol_heads_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
     HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
@@ -799,6 +804,54 @@ int rc_policy_dream_ahead(rc_env *env, const rc_policy_dream_ahead_args *a) {
     c.actions_in = a->actions_in;
     c.ret = a->ret; c.reward = a->reward; c.final_feature = a->final_feature;
     return pol_launch(env, rck_launch_dream, c);
+}
+
+int rc_policy_dream_grad(rc_env *env, const rc_policy_dream_grad_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_dream_grad_args))
+        return fail(RC_ERR_INVALID, "rc_policy_dream_grad_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_dream_grad_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: no policy loaded (rc_policy_load)");
+    if (!env->pol_i.img3_w) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: the policy was loaded without the prior's layers img2 / img3");
+    if (!env->pol_i.rout_w) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: no reward head is loaded (rc_policy_load_heads)");
+    if (a->horizon < 1 || a->horizon > RC_POLICY_IMAGINE_MAX_HORIZON)
+        return fail(RC_ERR_INVALID, "rc_policy_dream_grad: horizon %d is outside [1, %d]", a->horizon, RC_POLICY_IMAGINE_MAX_HORIZON);
+    if (a->candidates < 1) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: candidates %d is below 1", a->candidates);
+    if (a->mode != RC_POLICY_IMAGINE_MEAN && a->mode != RC_POLICY_IMAGINE_SAMPLE) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: unknown mode %d", a->mode);
+    if (!(a->discount >= 0.0f && a->discount <= 1.0f))
+        return fail(RC_ERR_INVALID, "rc_policy_dream_grad: discount %g is not a number in [0, 1]", (double)a->discount);
+    if (a->chunk_rows < 0) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: chunk_rows %lld is below 0", (long long)a->chunk_rows);
+    if (!a->actions_in) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: actions_in is NULL");
+    if (!a->grad_actions && !a->grad_state && !a->ret && !a->reward) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: no output asked for");
+    RcDreamGradCall c{};
+    int64_t starts;
+    if (a->state_in) {
+        if (a->slot_mask) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: a slot mask (0x%x) goes with the live latents, not with a given state_in", a->slot_mask);
+        if (a->starts < 1) return fail(RC_ERR_INVALID, "rc_policy_dream_grad: starts %lld is below 1", (long long)a->starts);
+        starts = a->starts;
+        c.d.state = a->state_in;
+        c.d.row_offset = a->row_offset;
+    } else {
+        const int rc = pol_rows(env, a->slot_mask, a->seed, "rc_policy_dream_grad", &c.d.rows);
+        if (rc) return rc;
+        starts = c.d.rows.n_active;
+        c.d.state = env->pol_state;
+        c.d.live = 1;
+    }
+    if (starts > (int64_t)INT32_MAX / a->candidates)
+        return fail(RC_ERR_INVALID, "rc_policy_dream_grad: %lld starts x %d candidates is not below 2^31", (long long)starts, a->candidates);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    c.d.w = env->pol;
+    c.d.wi = env->pol_i;
+    c.d.candidates = a->candidates;
+    c.d.n_rows = starts * a->candidates;
+    c.d.horizon = a->horizon;
+    c.d.sample = a->mode == RC_POLICY_IMAGINE_SAMPLE;
+    c.d.seed_lo = seed_lo(a->seed); c.d.seed_hi = seed_hi(a->seed);
+    c.d.discount = a->discount;
+    c.d.actions_in = a->actions_in;
+    c.d.ret = a->ret; c.d.reward = a->reward;
+    c.grad_actions = a->grad_actions; c.grad_state = a->grad_state;
+    return dream_grad_run(env, c, a->chunk_rows);
 }
 
 int rc_policy_load_critic(rc_env *env, const rc_policy_critic *h) {

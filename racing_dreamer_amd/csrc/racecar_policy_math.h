@@ -68,6 +68,7 @@ __device__ __forceinline__ float pm_preprocess(float scan_m) {
 }
 
 // tf.keras GRUCell, reset_after = True (models.py:61-87 through the cell): gates from the two matmuls' z, r and candidate columns
+// (racecar_dream_grad.hip's dg_gru restates these four lines with the gates named, to keep them for the backward: change both)
 __device__ __forceinline__ float pm_gru(float xz, float xr, float xh, float hz, float hr, float hh, float h) {
     const float z = pm_sigmoid(xz + hz);
     const float r = pm_sigmoid(xr + hr);

@@ -1,4 +1,4 @@
-// The latent-step engine of the four rollout units (racecar_imagine.hip, racecar_dream.hip, racecar_returns.hip,
+// The latent-step engine of the rollout units (racecar_imagine.hip, racecar_dream.hip, racecar_dream_grad.hip, racecar_returns.hip,
 // racecar_observe.hip): what a workgroup of racecar_policy_tiles.h needs to carry 32 latents through RSSM.img_step and the heads
 // that read them.  The latent lives in Z [32][233] = deter 200 | stoch 30 | action 2 behind the activation buffers X and Y.  A
 // unit keeps its call record, its row mapping and draw key, its schedule (which layers run at step t) and its output epilogues;
@@ -127,7 +127,7 @@ __device__ __forceinline__ void ro_dense_pair(const RoLayer &L, int lane, Pair &
 __device__ __forceinline__ float ro_sampled_stoch(float mean, float raw, float n) { return fmaf(pm_softplus(raw) + PM_STOCH_MIN_STD, n, mean); }
 
 // GRU on x = X[0, 200) and h = Z[0, 200), as rc_policy_kernel's: the new deter goes to Y[0, 200) because the other waves still
-// read the old one
+// read the old one.  (racecar_dream_grad.hip's dg_gru is a copy of this loop that also stores the gates: change both.)
 __device__ __forceinline__ void ro_gru(const RcPolicyDev &w, const float *X, const float *Z, float *Y, int wave, int lane) {
     const int cc = lane & 31, half = lane >> 5;
 #pragma unroll 1

@@ -1,14 +1,15 @@
 """Planning against the simulator's true dynamics (`BatchedRaceEnv.look_ahead`): a random-shooting
 baseline beside the learned agents, and an expert that sees further than follow-the-gap - and the same planners against the
 world model's dream (`BatchedRaceEnv.dream_ahead`, item 19: PlaNet-style random shooting and the cross-entropy method on the
-imagined return of a checkpoint with a reward head).
+imagined return of a checkpoint with a reward head; `dream_gradient_act` refines a few shooting candidates along the gradient
+of that return, `BatchedRaceEnv.dream_ahead_grad`, item 23).
 
     env.reset(mode="random", seed=0)
     for _ in range(steps):
         shooting_act(env, candidates=64, horizon=15)       # writes action_in
         env.step(None)
 
-`dream_shooting_act` and `dream_cem_act` take `shooting_act`'s place in that loop after `policy_act` has carried the latents to
+`dream_shooting_act`, `dream_cem_act` and `dream_gradient_act` take `shooting_act`'s place in that loop after `policy_act` has carried the latents to
 the current observation (on an env built with `remap_actions=True`: the dream's actions are raw, in [-1, 1], and what is written
 into `action_in` is raw too).
 
@@ -16,7 +17,7 @@ The candidates are generated in torch on the env's device; the look-ahead is one
 on [num_envs, candidates] - nothing here is a hot path of its own."""
 from __future__ import annotations
 
-from typing import Union
+from typing import Optional, Union
 
 import torch
 
@@ -142,4 +143,52 @@ def dream_cem_act(env, candidates: int = 64, horizon: int = 15, iterations: int 
         mean = elite.mean(dim=1, keepdim=True)
         std = elite.std(dim=1, unbiased=False, keepdim=True)
     action_in.copy_(mean[:, 0, 0].reshape(action_in.shape))
+    return action_in
+
+
+def dream_gradient_act(env, candidates: Union[int, torch.Tensor] = 8, horizon: int = 15, iterations: int = 10, step: float = 0.2, hold: int = 5,
+                       seed: int = 0, slots=None, discount: float = 0.99, info: Optional[dict] = None) -> torch.Tensor:
+    """Gradient-based planning in the dream: start from the candidates of `shooting_candidates` (or a tensor of explicit sequences
+    [num_envs, K, H, cars_per_env, 2]); `iterations` times, one `dream_ahead_grad` call (mode "mean") scores every sequence and
+    gives d return / d actions, and every sequence moves by `step` along its gradient normalised by its largest entry,
+    a <- clamp(a + step g / max|g|, -1, 1); one `dream_ahead` call scores the last iterate.  Per (car, candidate) the
+    best-scoring iterate seen is kept, so the result never scores below `dream_shooting_act` on the same candidates under the
+    same `discount`.  Writes the first action of the best iterate of the best candidate - the lowest index among equals - into
+    `action_in` for the cars in `slots` (None: every car) and returns `action_in`.  `info`, a dict, receives `return` [cars] of
+    what was chosen, `initial_return` [cars, K] of the candidates as given and `actions` [cars, H, 2], the chosen sequence."""
+    _needs_head(env, "dream_gradient_act")
+    n_it, step = int(iterations), float(step)
+    if n_it < 0 or not step > 0.0:
+        raise ValueError(f"iterations must be >= 0 and step > 0 (got {iterations}, {step})")
+    E, A = env.num_envs, env.cars_per_env
+    action_in = env.views["action_in"]
+    seq = candidates if torch.is_tensor(candidates) else shooting_candidates(env, candidates, horizon, hold, seed)
+    seq = seq.to(action_in.device, torch.float32).reshape(E, -1, seq.shape[2], A, 2)
+    acts = to_dream_actions(seq)                                                           # [E A, K, H, 2]
+    best_ret = best_acts = first_ret = None
+    for it in range(n_it + 1):
+        if it < n_it:
+            got = env.dream_ahead_grad(acts, slots=slots, discount=discount, outputs=("grad_actions", "return"))
+        else:
+            got = env.dream_ahead(acts, slots=slots, discount=discount, outputs=("return",))
+        ret = torch.nan_to_num(got["return"], nan=float("-inf"))
+        if best_ret is None:
+            first_ret, best_ret, best_acts = ret, ret.clone(), acts.clone()
+        else:
+            better = ret > best_ret
+            best_ret = torch.where(better, ret, best_ret)
+            best_acts = torch.where(better[:, :, None, None], acts, best_acts)
+        if it < n_it:
+            g = torch.nan_to_num(got["grad_actions"], nan=0.0, posinf=0.0, neginf=0.0)
+            scale = g.abs().amax(dim=(2, 3), keepdim=True).clamp_min(1e-30)
+            acts = (acts + step * (g / scale)).clamp_(-1.0, 1.0)
+    best = first_best(best_ret)
+    rows = torch.arange(E * A, device=acts.device)
+    chosen = best_acts[rows, best]                                                         # [E A, H, 2]
+    first = chosen[:, 0].reshape(E, A, 2)
+    flat = action_in.reshape(E, A, 2)
+    for a in (range(A) if slots is None else sorted({int(b) for b in slots})):
+        flat[:, a] = first[:, a]
+    if info is not None:
+        info.update({"return": best_ret[rows, best], "initial_return": first_ret, "actions": chosen})
     return action_in
