@@ -80,6 +80,12 @@ static void ps_dense(const float *x, int k_n, const float *w, int ld, int col0, 
     }
 }
 
+/* the dense chain alone over `rows` inputs x [rows][k_n] -> out [rows][n] (w [k_n][n], bias [n]): what tests/test_policy_edge_spec.py
+ * holds against exact rational arithmetic with one rounding per fmaf */
+void ps_dense_rows(int rows, int k_n, int n, const float *x, const float *w, const float *bias, float *out) {
+    for (int i = 0; i < rows; ++i) ps_dense(x + (size_t)i * k_n, k_n, w, n, 0, bias, n, out + (size_t)i * n);
+}
+
 /* one agent step for cars [0, n): scan [n][1080] metres, state [n][232] in place, fresh [n] or NULL, action [n][2] raw */
 void ps_act(const ps_weights *w, int n, const float *scan, float *state, const uint8_t *fresh, float *action) {
     for (int i = 0; i < n; ++i) {

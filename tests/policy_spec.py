@@ -70,6 +70,8 @@ def load():
     lib.ps_act.argtypes = [C.POINTER(_Weights), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ps_map.restype = None
     lib.ps_map.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    lib.ps_dense_rows.restype = None
+    lib.ps_dense_rows.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.ps_postprocess.restype = C.c_float
     lib.ps_postprocess.argtypes = [C.c_float, C.c_float, C.c_float]
     _lib = lib
@@ -82,6 +84,14 @@ def scalar_map(which, x):
     y = np.empty_like(x)
     load().ps_map({"exp": 0, "elu": 1, "sigmoid": 2, "tanh": 3}[which], x.size, x.ctypes.data, y.ctypes.data)
     return y
+
+
+def dense(x, w, bias):
+    """The spec's dense chain alone: x [rows, k] w [k, n] + bias [n], one fmaf chain per output, k ascending."""
+    x, w, bias = (np.ascontiguousarray(a, f32) for a in (x, w, bias))
+    out = np.empty((len(x), w.shape[1]), f32)
+    load().ps_dense_rows(len(x), w.shape[0], w.shape[1], x.ctypes.data, w.ctypes.data, bias.ctypes.data, out.ctypes.data)
+    return out
 
 
 class PolicySpec:

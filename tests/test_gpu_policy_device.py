@@ -69,8 +69,8 @@ def test_one_step_is_the_spec_bit_for_bit(name, remap):
         got_a, got_s = _device_step(env, scan, state, fresh)
         want_raw, want_s = spec_pol.act_packed(scan, state, fresh)
         want_a = want_raw if remap else spec_pol.postprocess(want_raw)
-        assert np.array_equal(got_s, want_s), (name, n, float(np.abs(got_s - want_s).max()))
-        assert np.array_equal(got_a, want_a), (name, n, float(np.abs(got_a - want_a).max()))
+        assert got_s.tobytes() == want_s.tobytes(), (name, n, float(np.abs(got_s - want_s).max()))
+        assert got_a.tobytes() == want_a.tobytes(), (name, n, float(np.abs(got_a - want_a).max()))
         assert np.abs(want_raw).max() <= 1.0 and np.abs(want_raw).max() > 0.01
         env.close()
 
@@ -90,7 +90,7 @@ def test_closed_loop_is_the_spec_on_the_c_oracle_step_for_step():
         assert np.array_equal(od["lidar"].reshape(n, -1), np.asarray(oo["lidar"]).reshape(n, -1)), f"scan differs at agent step {k}"
         ad = dev.env.policy_act().view(n, 2).cpu().numpy()
         ao, so = po.act(np.asarray(oo["lidar"]).reshape(n, -1), so, reset=np.asarray(oo["fresh"]).reshape(n) != 0)
-        assert np.array_equal(ad, ao), f"action differs at agent step {k}"
+        assert ad.tobytes() == ao.tobytes(), f"action differs at agent step {k}"
         od = dev._out(dev.env.step(None, repeat=4))
         oo = ora.step(ao, repeat=4)
         assert np.array_equal(od["pose"].reshape(n, 6), np.asarray(oo["pose"]).reshape(n, 6))
@@ -116,8 +116,8 @@ def _follow(env, spec_pol, steps, slots=None, check_rows=None):
         want_a, st_new = spec_pol.act_packed(scan, st, fresh)
         st[rows] = st_new[rows]
         got_s = env.policy_state.cpu().numpy()
-        assert np.array_equal(got_a[rows], want_a[rows]), f"action differs at agent step {k}"
-        assert np.array_equal(got_s[rows], st[rows]), f"state differs at agent step {k}"
+        assert got_a[rows].tobytes() == want_a[rows].tobytes(), f"action differs at agent step {k}"
+        assert got_s[rows].tobytes() == st[rows].tobytes(), f"state differs at agent step {k}"
         env.step(None, repeat=4)
     return n_fresh
 
@@ -160,7 +160,7 @@ def test_slot_mask_leaves_the_other_cars_alone(cars):
         want_a, st_new = spec_pol.act_packed(scan, st, fresh)
         st[slot != 0] = st_new[slot != 0]
         assert np.array_equal(got_a[slot == 0], np.tile(mine, (n_envs, 1))) and np.all(got_s[slot == 0] == 0.5)
-        assert np.array_equal(got_a[slot != 0], want_a[slot != 0]) and np.array_equal(got_s[slot != 0], st[slot != 0])
+        assert got_a[slot != 0].tobytes() == want_a[slot != 0].tobytes() and got_s[slot != 0].tobytes() == st[slot != 0].tobytes()
         env.step(None, repeat=4)
     env.close()
 
@@ -232,5 +232,5 @@ def test_the_agent_drives_65536_cars():
     print(f"65536 cars: {crashes} wall contacts in {n * steps} agent steps, mean speed {speed:.3f} m/s")
     assert crashes * 5000 <= n * steps and speed > 3.0, (crashes, speed)
     _, want = PolicySpec(weights("austria")).act_packed(scan, before, fresh)
-    assert np.array_equal(env.policy_state[pick].cpu().numpy(), want)
+    assert env.policy_state[pick].cpu().numpy().tobytes() == want.tobytes()
     env.close()

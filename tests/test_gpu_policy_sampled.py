@@ -44,8 +44,8 @@ def test_one_step_is_the_spec_bit_for_bit(name, remap):
             got_a, got_s = _device_step(env, scan, state, fresh)
             want_raw, want_s = spec_pol.act_packed(scan, state, fresh, clock.keys())
             want_a = want_raw if remap else spec_pol.postprocess(want_raw)
-            assert np.array_equal(got_s, want_s), (name, n, mode, float(np.abs(got_s - want_s).max()))
-            assert np.array_equal(got_a, want_a), (name, n, mode, float(np.abs(got_a - want_a).max()))
+            assert got_s.tobytes() == want_s.tobytes(), (name, n, mode, float(np.abs(got_s - want_s).max()))
+            assert got_a.tobytes() == want_a.tobytes(), (name, n, mode, float(np.abs(got_a - want_a).max()))
             assert np.abs(want_raw).max() <= 1.0 and np.abs(want_raw).max() > 0.01
         env.close()
 
@@ -74,7 +74,7 @@ def test_closed_loop_is_the_spec_on_the_c_oracle_step_for_step(mode, amount, sta
         fresh = np.asarray(oo["fresh"]).reshape(n) != 0
         resets += int(fresh.sum()) if k else 0
         ao, so = po.act(np.asarray(oo["lidar"]).reshape(n, -1), so, reset=fresh, keys=keys)
-        assert np.array_equal(ad, ao), f"action differs at agent step {k}"
+        assert ad.tobytes() == ao.tobytes(), f"action differs at agent step {k}"
         od = dev._out(dev.env.step(None, repeat=4))
         oo = ora.step(ao, repeat=4)
         assert np.array_equal(od["pose"].reshape(n, 6), np.asarray(oo["pose"]).reshape(n, 6))
@@ -107,8 +107,8 @@ def _follow(env, spec_pol, steps, clock, slots=None, check_rows=None):
         want_a, st_new = spec_pol.act_packed(scan, st, fresh, clock.keys())
         st[rows] = st_new[rows]
         got_s = env.policy_state.cpu().numpy()
-        assert np.array_equal(got_a[rows], want_a[rows]), f"action differs at agent step {k}"
-        assert np.array_equal(got_s[rows], st[rows]), f"state differs at agent step {k}"
+        assert got_a[rows].tobytes() == want_a[rows].tobytes(), f"action differs at agent step {k}"
+        assert got_s[rows].tobytes() == st[rows].tobytes(), f"state differs at agent step {k}"
         env.step(None, repeat=4)
     return n_fresh
 
@@ -236,7 +236,7 @@ def test_mode_switches_determinism_and_the_noise_amount():
     env.set_policy_sampling("mean")
     env.policy_state.zero_()
     got_a, got_s = _run(env, 6)
-    assert np.array_equal(got_a, want_a) and np.array_equal(got_s, want_s)
+    assert got_a.tobytes() == want_a.tobytes() and got_s.tobytes() == want_s.tobytes()
     env.set_policy_sampling("explore", seed=2)
     assert env.policy_sampling == dict(mode="explore", seed=2, expl_amount=pytest.approx(0.3))
     env.load_policy(weights("austria"))
@@ -263,7 +263,7 @@ def test_mode_switches_determinism_and_the_noise_amount():
     want, _, d = spec_pol.act_packed(scan, np.zeros((n, 232), np.float32), fresh, clock.keys(), detail=True)
     mu, sd = d["dist"][:, :2].astype(np.float64), d["dist"][:, 2:].astype(np.float64)
     assert np.allclose(want, np.tanh(mu + sd * d["normals"][:, 32:34]), atol=1e-5)
-    assert np.array_equal(env.policy_act().view(n, 2).cpu().numpy(), want)
+    assert env.policy_act().view(n, 2).cpu().numpy().tobytes() == want.tobytes()
     env.close()
 
 
