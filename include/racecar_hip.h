@@ -607,9 +607,27 @@ int rc_policy_returns(rc_env *env, const rc_policy_returns_args *args);
  * target NULL, rows outside [1, 2^31), a hyper-parameter negative or not finite, a beta outside [0, 1); read_critic: no critic
  * loaded, a wrong shape, pcont_* asked for without a pcont head.  Kernels: rc_policy_fit_rows_kernel, rc_policy_fit_wgrad_kernel,
  * rc_policy_fit_sums_kernel, rc_policy_fit_scale_kernel, rc_policy_fit_apply_kernel (and rc_policy_fit_transpose_kernel in begin),
- * timed together under RC_K_POLICY. */
+ * timed together under RC_K_POLICY.
+ *
+ * The reward head (RC_POLICY_FIT_REWARD; DESIGN.md §2 item 24, tests/policy_reward_fit_spec.c is the CPU restatement, the device
+ * equals it bit for bit): the same engine at two hidden layers, on the arrays rc_policy_load_heads loaded - DenseDecoder((), 2, 400),
+ * 230 -> 400 -> 400 -> 1, under the value head's Normal(o, 1) likelihood: loss and delta_o as "value" above, target = the recorded
+ * reward.  The reference trains this term inside its model loss under model_opt (dreamer/models.py:97-110, 135, 167-181), where its gradient also
+ * reaches the RSSM and the encoder; here the head's six arrays move and nothing else.  The gradient is [231][400] | [401][400] |
+ * [401][1] = 253 201 elements in the same fixed order, the rest (sum tree, skip, clip, Adam) is unchanged.  The new weights are
+ * written where rc_policy_imagine, rc_policy_observe, rc_policy_dream_ahead, rc_policy_returns and rc_policy_dream_grad read them
+ * (the last keeps transposed copies: its next call makes them again on the stream); the critic, the policy, the latents, the arena
+ * and every counter stay as they are.  Its optimizer is independent of the critic's two: rc_policy_load_heads, rc_policy_load and
+ * rc_policy_unload close it, rc_policy_load_critic does not (and rc_policy_load_heads leaves the critic's open).  begin without a
+ * loaded reward head is RC_ERR_INVALID.  Kernels: rc_policy_fit_reward_rows_kernel in place of rc_policy_fit_rows_kernel, the other
+ * four as above.
+ *   rc_policy_read_heads  copies the loaded reward head back into the caller's host arrays (data pointers to [rows, cols] float32 of
+ *                        the checkpoint's shapes, written despite the const): the inverse of rc_policy_load_heads' packing.
+ *                        Synchronises the stream.  RC_ERR_INVALID: wrong struct_size, no reward head loaded, an array missing or
+ *                        of a wrong shape. */
 #define RC_POLICY_FIT_VALUE 0
 #define RC_POLICY_FIT_PCONT 1
+#define RC_POLICY_FIT_REWARD 2
 typedef struct rc_policy_fit_config {
     uint32_t struct_size;          /* = sizeof(rc_policy_fit_config) */
     int32_t head;                  /* RC_POLICY_FIT_* */
@@ -621,7 +639,7 @@ typedef struct rc_policy_fit_args {
     const float *features;         /* device float32 [rows, 230] = stoch | deter */
     const float *target;           /* device float32 [rows] */
     const float *weight;           /* device float32 [rows], or NULL: all 1 */
-    float lr, clip;                /* the reference's value_lr 8e-5 and grad_clip 1.0 (dream.py:88); clip 0: none */
+    float lr, clip;                /* the reference's value_lr 8e-5 (the reward head: model_lr 6e-4) and grad_clip 1.0 (dream.py:85-88); clip 0: none */
     float beta1, beta2, epsilon;   /* TF's 0.9, 0.999, 1e-7 */
     float *status;                 /* device float32 [4] = loss, grad_norm, skipped, step; or NULL */
 } rc_policy_fit_args;
@@ -629,6 +647,7 @@ int rc_policy_fit_begin(rc_env *env, const rc_policy_fit_config *cfg);
 int rc_policy_fit_step(rc_env *env, const rc_policy_fit_args *args);
 int rc_policy_fit_end(rc_env *env, int32_t head);
 int rc_policy_read_critic(rc_env *env, rc_policy_critic *out);
+int rc_policy_read_heads(rc_env *env, rc_policy_heads *out);
 
 /* Recorded sequences: the posterior chain over N recorded windows of T scans and actions (DESIGN.md §2 item 17;
  * tests/policy_observe_spec.c is the CPU restatement, the device equals it bit for bit) - dreamer/models.py:325-336 RSSM.observe,

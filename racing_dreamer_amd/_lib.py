@@ -158,7 +158,9 @@ class RcPolicyReturnsArgs(C.Structure):
                 ("value_start", C.c_void_p), ("pcont_start", C.c_void_p)]
 
 
-FIT_HEADS = {"value": 0, "pcont": 1}                            # RC_POLICY_FIT_*
+FIT_HEADS = {"value": 0, "pcont": 1}                            # RC_POLICY_FIT_*: the critic's (critic_fit)
+FIT_REWARD = 2                                                  # RC_POLICY_FIT_REWARD: the reward head's own (reward_fit)
+HEAD_SHAPES = ((230, 400), (400,), (400, 400), (400,), (400, 1), (1,))      # of HEAD_KEYS
 CRITIC_SHAPES = ((230, 400), (400,), (400, 400), (400,), (400, 400), (400,), (400, 1), (1,))      # of VALUE_KEYS / PCONT_KEYS
 
 
@@ -374,6 +376,7 @@ SYMBOLS = {
     "rc_policy_fit_step": (C.c_int, [C.c_void_p, _P(RcPolicyFitArgs)]),
     "rc_policy_fit_end": (C.c_int, [C.c_void_p, C.c_int32]),
     "rc_policy_read_critic": (C.c_int, [C.c_void_p, _P(RcPolicyCritic)]),
+    "rc_policy_read_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
     "rc_policy_observe": (C.c_int, [C.c_void_p, _P(RcPolicyObserveArgs)]),
     "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
     "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),

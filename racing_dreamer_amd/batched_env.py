@@ -258,9 +258,9 @@ def _value_setup(env, features, slots, outputs):
 
 
 def _fit_setup(env, features, target, weight, head):
-    """critic_fit's tensors (shared by BatchedRaceEnv and MixedTrackEnv): contiguous float32 [N, 230], [N], [N] or None on the
+    """critic_fit's and reward_fit's (head None) tensors (shared by BatchedRaceEnv and MixedTrackEnv): contiguous float32 [N, 230], [N], [N] or None on the
     env's device, and the status block."""
-    if head not in L.FIT_HEADS:
+    if head is not None and head not in L.FIT_HEADS:
         raise ValueError(f"head must be one of {sorted(L.FIT_HEADS)}, got {head!r}")
     if features.shape[-1] != L.POLICY_FEATURE or features.numel() == 0:
         raise ValueError(f"features must be [..., {L.POLICY_FEATURE}] with at least one row, got {tuple(features.shape)}")
@@ -1027,7 +1027,7 @@ class BatchedRaceEnv:
         return {n[:-6]: got[n].reshape(lead) for n in names}
 
     def _fit(self, head, feat, tgt, wgt, status, hyper) -> int:
-        a = L.RcPolicyFitArgs(C.sizeof(L.RcPolicyFitArgs), L.FIT_HEADS[head], feat.shape[0], feat.data_ptr(), tgt.data_ptr(),
+        a = L.RcPolicyFitArgs(C.sizeof(L.RcPolicyFitArgs), L.FIT_HEADS.get(head, head), feat.shape[0], feat.data_ptr(), tgt.data_ptr(),
                               None if wgt is None else wgt.data_ptr(), hyper["lr"], hyper["clip"], hyper["beta1"], hyper["beta2"],
                               hyper["epsilon"], None if status is None else status.data_ptr())
         return self._lib.rc_policy_fit_step(self._h, C.byref(a))
@@ -1086,6 +1086,69 @@ class BatchedRaceEnv:
         finally:
             self._exit()
         return out
+
+    # ---- the reward head's own fit (rc_policy_fit_* with RC_POLICY_FIT_REWARD): not one of critic_fit's heads
+    def reward_fit_begin(self) -> None:
+        """Open the optimizer of the loaded reward head (`rc_policy_fit_begin`, RC_POLICY_FIT_REWARD): Adam moments zero, step 0.
+        Independent of the critic's optimizers; `load_reward_head`, `load_policy` and `unload_policy` close it."""
+        cfg = L.RcPolicyFitConfig(C.sizeof(L.RcPolicyFitConfig), L.FIT_REWARD)
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_fit_begin(self._h, C.byref(cfg)))
+        finally:
+            self._exit()
+
+    def reward_fit(self, features: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, lr: float = 6e-4,
+                   clip: float = 1.0, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-7) -> Dict[str, torch.Tensor]:
+        """One step of the reward head towards recorded rewards, on the device (`rc_policy_fit_step`, RC_POLICY_FIT_REWARD): the
+        head's forward and backward pass on `features` [..., 230] = stoch | deter (e.g. `policy_observe`'s) against `target` [...]
+        under `weight` [...] or None - loss = -mean(weight * Normal(head(features), 1).log_prob(target)) -, the global-norm clip
+        (`clip` 0: none) and Adam, as `critic_fit` does for the value head: no synchronisation, no host copy.  The defaults are
+        the reference's model_lr and grad_clip (dreamer/dream.py:85, 88) and TF's Adam.  Returns device scalars `loss`,
+        `grad_norm` (before the clip), `skipped`, `step`.  The fitted head is what `policy_imagine`, `policy_observe`,
+        `dream_ahead`, `policy_returns`, `dream_ahead_grad` and the planners read next; nothing else moves."""
+        feat, tgt, wgt, status = _fit_setup(self, features, target, weight, None)
+        hyper = dict(lr=lr, clip=clip, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        self._enter()
+        try:
+            L.check(self._fit(L.FIT_REWARD, feat, tgt, wgt, status, hyper))
+        finally:
+            self._exit()
+        return _fit_status(status)
+
+    def reward_fit_end(self) -> None:
+        """Free the reward optimizer's state (`rc_policy_fit_end`); the fitted head stays loaded."""
+        L.check(self._lib.rc_policy_fit_end(self._h, L.FIT_REWARD))
+
+    def reward_head_weights(self) -> Dict[str, np.ndarray]:
+        """The loaded reward head as NumPy arrays under `HEAD_KEYS`, as `load_reward_head` takes them (`rc_policy_read_heads`;
+        waits for the env's stream)."""
+        out = {k: np.empty(shape, np.float32) for k, shape in zip(L.HEAD_KEYS, L.HEAD_SHAPES)}
+        h = L.RcPolicyHeads()
+        h.struct_size = C.sizeof(L.RcPolicyHeads)
+        for k, a in out.items():
+            arr = getattr(h, k)
+            arr.data = a.ctypes.data
+            arr.rows, arr.cols = (1, a.shape[0]) if a.ndim == 1 else a.shape
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_read_heads(self._h, C.byref(h)))
+        finally:
+            self._exit()
+        return out
+
+    def load_reward_head(self, weights) -> None:
+        """Replace the reward head alone (`rc_policy_load_heads`): a mapping (or an .npz path) with `reward_h0_w` .. `reward_hout_b`.
+        The policy, the latents and the critic stay as they are; the reward optimizer is closed."""
+        heads = L.policy_heads(weights)
+        if heads is None:
+            raise KeyError("reward head weights lack the reward_* arrays")
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_load_heads(self._h, C.byref(heads[0])))
+        finally:
+            self._exit()
+        self._policy_has_head = True
 
     @property
     def policy_has_decoder(self) -> bool:
@@ -1880,6 +1943,35 @@ class MixedTrackEnv:
     def critic_weights(self) -> Dict[str, np.ndarray]:
         """The first block's critic (every block holds the same)."""
         return self.parts[0].critic_weights()
+
+    def reward_fit_begin(self) -> None:
+        """BatchedRaceEnv.reward_fit_begin on every block."""
+        for p in self.parts:
+            p.reward_fit_begin()
+
+    def reward_fit(self, features: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, lr: float = 6e-4,
+                   clip: float = 1.0, beta1: float = 0.9, beta2: float = 0.999, epsilon: float = 1e-7) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.reward_fit on every block with the same inputs: the step is deterministic, so the blocks' reward heads
+        stay byte-identical.  The status is the first block's."""
+        feat, tgt, wgt, status = _fit_setup(self, features, target, weight, None)
+        hyper = dict(lr=lr, clip=clip, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        self._fork_join(lambda p, blk: p._fit(L.FIT_REWARD, feat, tgt, wgt, status if p is self.parts[0] else None, hyper))
+        return _fit_status(status)
+
+    def reward_fit_end(self) -> None:
+        for p in self.parts:
+            p.reward_fit_end()
+
+    def reward_head_weights(self) -> Dict[str, np.ndarray]:
+        """The first block's reward head (every block holds the same)."""
+        return self.parts[0].reward_head_weights()
+
+    def load_reward_head(self, weights) -> None:
+        """The reward head on every block (BatchedRaceEnv.load_reward_head)."""
+        if isinstance(weights, (str, os.PathLike)):
+            weights = dict(np.load(weights))
+        for p in self.parts:
+            p.load_reward_head(weights)
 
     def look_ahead(self, actions: torch.Tensor, repeat: Optional[int] = None, outputs=("reward", "flags", "return", "length"),
                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:

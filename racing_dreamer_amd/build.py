@@ -122,6 +122,7 @@ CHECKED_KERNELS = (
     ("rc_policy_returns_kernel", None, False, "shipped"),       # (imagination with the critic's heads and the lambda-return behind it)
     ("rc_policy_returns_sampled_kernel", None, False, "shipped"),
     ("rc_policy_fit_rows_kernel", None, False, "shipped"),      # (the critic's fit: the head forward and backward on the same tiles)
+    ("rc_policy_fit_reward_rows_kernel", None, False, "shipped"),     # (the reward head's: the same body at two hidden layers)
     ("rc_policy_fit_wgrad_kernel", None, False, "shipped"),     # (its weight gradients: one accumulator tile per wave over all rows)
     ("rc_policy_observe_kernel", None, False, "shipped"),       # (recorded sequences: imagination's tiles and the agent's staged scan)
     ("rc_policy_observe_sampled_kernel", None, False, "shipped"),

@@ -406,9 +406,15 @@ int dream_grad_run(rc_env *env, RcDreamGradCall &c, int64_t chunk_rows) {
         {&RcDreamGradDev::rh0_t, U, FEAT, LDT, RC_POLICY_LD400, U, 0},
         {&RcDreamGradDev::rh1_t, U, U, RC_POLICY_LD400, RC_POLICY_LD400, U, 0},
     };
+    const float *src[7] = {env->pol.img1_w, env->pol.gru_k, env->pol.gru_r, env->pol_i.img2_w, env->pol_i.img3_w, env->pol_i.rh_w[0], env->pol_i.rh_w[1]};
+    auto transpose = [&](int i, float *dst) {
+        const TImage &im = table[i];
+        const unsigned blocks = (unsigned)(((size_t)im.k_n * im.dst_ld + PT - 1) / PT);
+        hipLaunchKernelGGL(rc_policy_dream_grad_transpose_kernel, dim3(blocks), dim3(PT), 0, env->stream, src[i], im.src_ld, im.group, im.group_ld,
+                           im.k_n, im.n, im.dst_ld, dst);
+    };
     if (!env->dgrad) {
         // the first call after the weights were loaded: the transposed images, built on the device
-        const float *src[7] = {env->pol.img1_w, env->pol.gru_k, env->pol.gru_r, env->pol_i.img2_w, env->pol_i.img3_w, env->pol_i.rh_w[0], env->pol_i.rh_w[1]};
         size_t at[7], total = 0;
         for (int i = 0; i < 7; ++i) {
             at[i] = total;
@@ -422,15 +428,17 @@ int dream_grad_run(rc_env *env, RcDreamGradCall &c, int64_t chunk_rows) {
         }
         env->dgrad = d;
         for (int i = 0; i < 7; ++i) {
-            const TImage &im = table[i];
             float *dst = d->images + at[i];
-            const unsigned blocks = (unsigned)(((size_t)im.k_n * im.dst_ld + PT - 1) / PT);
-            hipLaunchKernelGGL(rc_policy_dream_grad_transpose_kernel, dim3(blocks), dim3(PT), 0, env->stream, src[i], im.src_ld, im.group, im.group_ld,
-                               im.k_n, im.n, im.dst_ld, dst);
-            d->wt.*(im.dst) = dst;
+            transpose(i, dst);
+            d->wt.*(table[i].dst) = dst;
         }
         HIP_TRY(hipGetLastError());
+    } else if (env->dgrad_reward_stale) {
+        // rc_policy_fit_step moved the reward head since: its two images again, in place and in stream order behind that step
+        for (int i = 5; i < 7; ++i) transpose(i, const_cast<float *>(env->dgrad->wt.*(table[i].dst)));
+        HIP_TRY(hipGetLastError());
     }
+    env->dgrad_reward_stale = false;
     RcDreamGrad &d = *env->dgrad;
     const int64_t n_rows = c.d.n_rows, H = c.d.horizon;
     const size_t row_floats = (size_t)H * SW;

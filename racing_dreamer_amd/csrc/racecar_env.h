@@ -151,7 +151,7 @@ struct StagedTable {
 };
 
 struct P2p;                        // the peer-copy all-gather's state (racecar_gather.hip)
-struct RcFit;                      // the critic's optimizers (racecar_fit.hip)
+struct RcFit;                      // the critic's and the reward head's optimizers (racecar_fit.hip)
 struct RcDreamGrad;                // the dream's backward pass: transposed weight images and the activation stash (racecar_dream_grad.hip)
 
 struct rc_env {
@@ -208,8 +208,9 @@ struct rc_env {
     float *pol_ldec_mem = nullptr;     // rc_policy_load_lidar_decoder
     RcCriticDev pol_c{};               // rc_policy_returns: the value head and the pcont head (null = none loaded)
     float *pol_critic_mem = nullptr;   // rc_policy_load_critic
-    RcFit *fit = nullptr;              // rc_policy_fit_begin: the critic's optimizers and their scratch (racecar_fit.hip)
+    RcFit *fit = nullptr;              // rc_policy_fit_begin: the heads' optimizers and their scratch (racecar_fit.hip)
     RcDreamGrad *dgrad = nullptr;      // rc_policy_dream_grad: made at its first call, dropped with the weights it was made from
+    bool dgrad_reward_stale = false;   // a reward fit step moved the head under dgrad's two transposed images of it: the next call remakes them
     rc_policy_sampling pol_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};      // rc_policy_set_sampling
     float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
     float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)
@@ -234,6 +235,7 @@ struct rc_env {
 
 int drain_events(rc_env *env);      // folds the finished event pairs into the accumulators (racecar_abi.hip)
 int fit_release(rc_env *env);       // closes the critic's optimizers: whoever replaces or drops the critic (racecar_fit.hip)
+int fit_release_reward(rc_env *env);      // closes the reward head's optimizer: whoever replaces or drops the reward head
 int dream_grad_release(rc_env *env);      // drops the transposed images and the stash: whoever replaces or drops the prior or the reward head
 int dream_grad_run(rc_env *env, RcDreamGradCall &c, int64_t chunk_rows);      // racecar_dream_grad.hip: the chunks of one rc_policy_dream_grad
 

@@ -23,6 +23,10 @@
 //       counter, the running powers of the betas and the bias-corrected rate.
 //   rc_policy_fit_apply_kernel  g scale, Adam (TF's ResourceApplyAdam), the new weight into the forward image - the memory
 //       rc_policy_returns and the rest read - and into the transposed image.
+// The reward head (RC_POLICY_FIT_REWARD: the reference's DenseDecoder((), 2, 400) under the same Normal(o, 1); DESIGN.md §2 item 24,
+// tests/policy_reward_fit_spec.c) is the same engine at two hidden layers: the rows kernel's body without the third layer and without
+// the transposed product behind it (rc_policy_fit_reward_rows_kernel), the other four launches with a shorter table.  Its gradient is
+// [231][400] | [401][400] | [401][1] = 253 201 elements, its scratch [4][N][416] + 2 N, its weights rc_policy_load_heads' images.
 #include "racecar_env.h"
 #include "racecar_policy_math.h"
 #include "racecar_policy_tiles.h"
@@ -39,6 +43,10 @@ static_assert(kFitLds <= 160 * 1024, "X, Y, the feature tile and the output delt
 // the gradient, the moments: the head's eight arrays one behind the other, [K_l + 1][400] = kernel | bias per hidden layer, [401][1]
 constexpr int G1 = (FEAT + 1) * UNITS, G2 = G1 + (UNITS + 1) * UNITS, GO = G2 + (UNITS + 1) * UNITS, NG = GO + UNITS + 1;
 static_assert(NG == 413601, "230 x 400 + 400 + 2 (400 x 400 + 400) + 400 + 1");
+// a head of `depth` hidden layers: where its output layer's [401][1] lies in the gradient, and the gradient's length
+__host__ __device__ constexpr int fit_go(int depth) { return depth == 3 ? GO : G2; }
+__host__ __device__ constexpr int fit_ng(int depth) { return fit_go(depth) + UNITS + 1; }
+static_assert(fit_ng(3) == NG && fit_ng(2) == 253201, "the value and pcont heads; the reward head");
 constexpr int SUM_BLOCKS = 128, SUM_STRIDE = SUM_BLOCKS * PT;
 constexpr float HALF_LOG_2PI = 0.9189385332f;
 
@@ -53,8 +61,9 @@ struct FitCtl {                                // one per optimizer, on the devi
 };
 
 struct FitHeadDev {
-    float *w[3], *b[3], *wout, *bout;          // the forward images (RcCriticDev's memory): [230 | 400][416], [416]; [400][32], [32]
-    float *t1, *t2;                            // W1^T, W2^T [400][416], padding zero
+    float *w[3], *b[3], *wout, *bout;          // the forward images (RcCriticDev's memory; the reward head: RcImagineDev's, two hidden
+                                               // layers): [230 | 400][416], [416]; [400][32], [32]
+    float *t1, *t2;                            // W1^T, W2^T [400][416], padding zero (the reward head: W1^T alone)
 };
 
 struct FitRowsCall {
@@ -63,7 +72,7 @@ struct FitRowsCall {
     int64_t n;
     float inv_n;
     int32_t pcont;
-    float *act;                                // [6][N][416]: a1, a2, a3, delta1, delta2, delta3
+    float *act;                                // [6][N][416]: a1, a2, a3, delta1, delta2, delta3 (two hidden layers: [4][N][416])
     float *dout, *lterm;                       // [N] the output delta and the loss term
 };
 
@@ -128,15 +137,18 @@ __device__ __forceinline__ void fit_layer(const FitLayer &L, int wave, int lane,
     else fit_dense<3>(L, 32 * wave, lane, row0, n);
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(PT) void rc_policy_fit_rows_kernel(FitRowsCall c) {
+// The rows kernel's body for a head of DEPTH hidden layers, 3 or 2.  Two layers are three without the third layer's forward product
+// and without the transposed product that takes delta3 to delta2: the last hidden activation is then in Y, not in X.
+template <int DEPTH>
+__device__ __forceinline__ void fit_rows(const FitRowsCall &c) {
+    static_assert(DEPTH == 2 || DEPTH == 3, "the reward head; the value and pcont heads");
     extern __shared__ float fit_lds[];
     float *X = fit_lds, *Y = fit_lds + PM * XS, *Z = fit_lds + 2 * PM * XS, *dl = Z + PM * FS;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, cc = lane & 31, half = lane >> 5;
     const int64_t row0 = (int64_t)blockIdx.x * PM, n = c.n;
     const size_t plane = (size_t)n * LD;
-    float *a1 = c.act, *a2 = c.act + plane, *a3 = c.act + 2 * plane, *d1 = c.act + 3 * plane, *d2 = c.act + 4 * plane, *d3 = c.act + 5 * plane;
+    float *a1 = c.act, *a2 = c.act + plane, *d1 = c.act + DEPTH * plane, *d2 = c.act + (DEPTH + 1) * plane;
+    float *top = DEPTH == 3 ? X : Y, *dtop = c.act + (2 * DEPTH - 1) * plane;          // a_DEPTH's tile, delta_DEPTH's scratch
 
     for (int idx = tid; idx < PM * FS; idx += PT) {
         const int row = idx / FS, j = idx - row * FS;
@@ -148,14 +160,16 @@ __global__ __launch_bounds__(PT) void rc_policy_fit_rows_kernel(FitRowsCall c) {
     __syncthreads();
     fit_layer(FitLayer{X, UNITS, XS, c.h.w[1], c.h.b[1], Y, nullptr, a2, FK_FORWARD}, wave, lane, row0, n);
     __syncthreads();
-    fit_layer(FitLayer{Y, UNITS, XS, c.h.w[2], c.h.b[2], X, nullptr, a3, FK_FORWARD}, wave, lane, row0, n);
-    __syncthreads();
+    if constexpr (DEPTH == 3) {
+        fit_layer(FitLayer{Y, UNITS, XS, c.h.w[2], c.h.b[2], X, nullptr, c.act + 2 * plane, FK_FORWARD}, wave, lane, row0, n);
+        __syncthreads();
+    }
     // the one output column: lanes 0 and 32 of wave 0 hold it for 16 rows each; the output delta and the row's loss term
     if (wave == 0) {
         const int col[1] = {0};
         pm_f32x16 acc[1];
         pm_bias<1>(acc, c.h.bout, col, cc);
-        pm_gemm<1>(acc, X + cc * XS + half, UNITS / 2, c.h.wout + (size_t)half * RC_POLICY_LDSMALL + cc, RC_POLICY_LDSMALL, col);
+        pm_gemm<1>(acc, top + cc * XS + half, UNITS / 2, c.h.wout + (size_t)half * RC_POLICY_LDSMALL + cc, RC_POLICY_LDSMALL, col);
         if (cc == 0) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -186,26 +200,34 @@ __global__ __launch_bounds__(PT) void rc_policy_fit_rows_kernel(FitRowsCall c) {
         }
     }
     __syncthreads();
-    // delta3 in place of a3: a chain of one product from zero
+    // delta3 in place of a3 (two layers: delta2 in place of a2): a chain of one product from zero
     for (int idx = tid; idx < PM * UNITS; idx += PT) {
         const int row = idx / UNITS, j = idx - row * UNITS;
         const int64_t q = row0 + row;
-        const float v = fmaf(dl[row], c.h.wout[(size_t)j * RC_POLICY_LDSMALL], 0.0f) * fit_elu_grad(X[row * XS + j]);
-        X[row * XS + j] = v;
-        if (q < n) d3[(size_t)q * LD + j] = v;
+        const float v = fmaf(dl[row], c.h.wout[(size_t)j * RC_POLICY_LDSMALL], 0.0f) * fit_elu_grad(top[row * XS + j]);
+        top[row * XS + j] = v;
+        if (q < n) dtop[(size_t)q * LD + j] = v;
     }
     __syncthreads();
-    fit_layer(FitLayer{X, UNITS, XS, c.h.t2, nullptr, Y, nullptr, d2, FK_BACK_LDS}, wave, lane, row0, n);
-    __syncthreads();
+    if constexpr (DEPTH == 3) {
+        fit_layer(FitLayer{X, UNITS, XS, c.h.t2, nullptr, Y, nullptr, d2, FK_BACK_LDS}, wave, lane, row0, n);
+        __syncthreads();
+    }
     fit_layer(FitLayer{Y, UNITS, XS, c.h.t1, nullptr, nullptr, a1, d1, FK_BACK_GLOBAL}, wave, lane, row0, n);
 }
+
+}  // namespace
+
+__global__ __launch_bounds__(PT) void rc_policy_fit_rows_kernel(FitRowsCall c) { fit_rows<3>(c); }
+__global__ __launch_bounds__(PT) void rc_policy_fit_reward_rows_kernel(FitRowsCall c) { fit_rows<2>(c); }
 
 struct FitWgradCall {
     const float *a[4];                         // a_{l-1} [N][lda]: the features, a1, a2, a3
     const float *d[4];                         // delta_l [N][ldd]: delta1, delta2, delta3, the output delta
     int32_t lda[4], ldd[4], k[4], nc[4];       // K_l = 230, 400, 400, 400; the columns 400, 400, 400, 1
     int32_t tile0[4], nt[4], goff[4];          // the layer's first workgroup, its column tiles, its place in the gradient
-    float *g;                                  // [NG]
+                                               // (two hidden layers: three entries; the fourth's tile0 is the grid, no workgroup is its)
+    float *g;                                  // [fit_ng(depth)]
     int64_t n;
 };
 
@@ -265,11 +287,11 @@ __global__ __launch_bounds__(PT) void rc_policy_fit_wgrad_kernel(FitWgradCall c)
     }
 }
 
-__global__ __launch_bounds__(PT) void rc_policy_fit_sums_kernel(const float *g, const float *lterm, int64_t n, FitCtl *ctl) {
+__global__ __launch_bounds__(PT) void rc_policy_fit_sums_kernel(const float *g, int ng, const float *lterm, int64_t n, FitCtl *ctl) {
     __shared__ double sh[PT];
     const int tid = threadIdx.x, b = blockIdx.x;
     for (int which = 0; which < 2; ++which) {
-        const int64_t count = which == 0 ? (int64_t)NG : n;
+        const int64_t count = which == 0 ? (int64_t)ng : n;
         double s = 0.0;
         for (int64_t i = (int64_t)b * PT + tid; i < count; i += SUM_STRIDE) {
             const float x = which == 0 ? g[i] : lterm[i];
@@ -312,19 +334,20 @@ __global__ void rc_policy_fit_scale_kernel(FitCtl *ctl, int64_t n, float lr, flo
         for (int i = 0; i < 4; ++i) status[i] = ctl->status[i];
 }
 
-__global__ __launch_bounds__(PT) void rc_policy_fit_apply_kernel(FitHeadDev h, const float *g, float *m, float *v, const FitCtl *ctl, float beta1,
-                                                                 float beta2, float omb1, float omb2, float epsilon) {
+__global__ __launch_bounds__(PT) void rc_policy_fit_apply_kernel(FitHeadDev h, int depth, const float *g, float *m, float *v, const FitCtl *ctl,
+                                                                 float beta1, float beta2, float omb1, float omb2, float epsilon) {
     const int e = blockIdx.x * PT + threadIdx.x;
-    if (e >= NG || ctl->skipped) return;
+    const int go = fit_go(depth);
+    if (e >= go + UNITS + 1 || ctl->skipped) return;
     float *w, *wt = nullptr;
-    if (e < GO) {
+    if (e < go) {
         const int l = e < G1 ? 0 : (e < G2 ? 1 : 2);
         const int i = e - (l == 0 ? 0 : (l == 1 ? G1 : G2)), K = l == 0 ? FEAT : UNITS;
         const int k = i / UNITS, j = i - k * UNITS;
         w = k < K ? h.w[l] + (size_t)k * LD + j : h.b[l] + j;
         if (l > 0 && k < K) wt = (l == 1 ? h.t1 : h.t2) + (size_t)j * LD + k;
     } else {
-        const int k = e - GO;
+        const int k = e - go;
         w = k < UNITS ? h.wout + (size_t)k * RC_POLICY_LDSMALL : h.bout;
     }
     const float gs = g[e] * ctl->scale;
@@ -347,31 +370,46 @@ __global__ __launch_bounds__(PT) void rc_policy_fit_transpose_kernel(const float
 }
 
 // ---- the optimizers of a handle and the entry points (include/racecar_hip.h, rc_policy_fit_*)
+constexpr int kFitHeads = 3;                   // RC_POLICY_FIT_VALUE, _PCONT, _REWARD
+
 struct RcFit {
     struct Head {
-        float *mem = nullptr;                  // m [NG] | v [NG] | g [NG] | W1^T | W2^T
+        float *mem = nullptr;                  // m [ng] | v [ng] | g [ng] | W1^T | W2^T (the reward head: W1^T alone)
         FitCtl *ctl = nullptr;
-    } head[2];
-    float *scratch = nullptr;                  // [6][rows][416] | the output delta [rows] | the loss terms [rows]
-    int64_t scratch_rows = 0;
+    } head[kFitHeads];
+    float *scratch = nullptr;                  // [2 depth][rows][416] | the output delta [rows] | the loss terms [rows]: the heads share it
+    size_t scratch_floats = 0;
 };
 
 namespace {
 
-constexpr size_t kMoment = ((size_t)NG + 63) / 64 * 64, kImage = (size_t)UNITS * LD;
+constexpr size_t kImage = (size_t)UNITS * LD;
+
+constexpr int fit_depth(int head) { return head == RC_POLICY_FIT_REWARD ? 2 : 3; }
+constexpr size_t fit_moment(int depth) { return ((size_t)fit_ng(depth) + 63) / 64 * 64; }
 
 FitHeadDev fit_head(rc_env *env, int head) {
     const RcCriticDev &c = env->pol_c;
+    const RcImagineDev &r = env->pol_i;
     FitHeadDev h{};
-    for (int l = 0; l < 3; ++l) {
-        h.w[l] = const_cast<float *>(head ? c.ph_w[l] : c.vh_w[l]);
-        h.b[l] = const_cast<float *>(head ? c.ph_b[l] : c.vh_b[l]);
+    if (head == RC_POLICY_FIT_REWARD) {
+        for (int l = 0; l < 2; ++l) {
+            h.w[l] = const_cast<float *>(r.rh_w[l]);
+            h.b[l] = const_cast<float *>(r.rh_b[l]);
+        }
+        h.wout = const_cast<float *>(r.rout_w);
+        h.bout = const_cast<float *>(r.rout_b);
+    } else {
+        for (int l = 0; l < 3; ++l) {
+            h.w[l] = const_cast<float *>(head ? c.ph_w[l] : c.vh_w[l]);
+            h.b[l] = const_cast<float *>(head ? c.ph_b[l] : c.vh_b[l]);
+        }
+        h.wout = const_cast<float *>(head ? c.pout_w : c.vout_w);
+        h.bout = const_cast<float *>(head ? c.pout_b : c.vout_b);
     }
-    h.wout = const_cast<float *>(head ? c.pout_w : c.vout_w);
-    h.bout = const_cast<float *>(head ? c.pout_b : c.vout_b);
     if (env->fit && env->fit->head[head].mem) {
-        h.t1 = env->fit->head[head].mem + 3 * kMoment;
-        h.t2 = h.t1 + kImage;
+        h.t1 = env->fit->head[head].mem + 3 * fit_moment(fit_depth(head));
+        if (fit_depth(head) == 3) h.t2 = h.t1 + kImage;
     }
     return h;
 }
@@ -384,7 +422,7 @@ int fit_close(rc_env *env, int head) {
     (void)hipFree(o.mem);
     (void)hipFree(o.ctl);
     o = RcFit::Head{};
-    if (!env->fit->head[0].mem && !env->fit->head[1].mem) {
+    if (!env->fit->head[0].mem && !env->fit->head[1].mem && !env->fit->head[2].mem) {
         if (env->fit->scratch) (void)hipFree(env->fit->scratch);
         delete env->fit;
         env->fit = nullptr;
@@ -392,15 +430,19 @@ int fit_close(rc_env *env, int head) {
     return RC_OK;
 }
 
-const char *fit_head_name(int head) { return head == RC_POLICY_FIT_PCONT ? "pcont" : "value"; }
+const char *fit_head_name(int head) { return head == RC_POLICY_FIT_REWARD ? "reward" : (head == RC_POLICY_FIT_PCONT ? "pcont" : "value"); }
+bool fit_head_known(int head) { return head == RC_POLICY_FIT_VALUE || head == RC_POLICY_FIT_PCONT || head == RC_POLICY_FIT_REWARD; }
 
 }  // namespace
 
-// rc_policy_load_critic, rc_policy_load, rc_policy_unload and rc_destroy close the optimizers
+// rc_policy_load_critic, rc_policy_load, rc_policy_unload and rc_destroy close the critic's optimizers
 int fit_release(rc_env *env) {
-    const int rc = fit_close(env, 0);
-    return rc ? rc : fit_close(env, 1);
+    const int rc = fit_close(env, RC_POLICY_FIT_VALUE);
+    return rc ? rc : fit_close(env, RC_POLICY_FIT_PCONT);
 }
+
+// rc_policy_load_heads, rc_policy_load, rc_policy_unload and rc_destroy close the reward head's
+int fit_release_reward(rc_env *env) { return fit_close(env, RC_POLICY_FIT_REWARD); }
 
 extern "C" {
 
@@ -408,17 +450,19 @@ int rc_policy_fit_begin(rc_env *env, const rc_policy_fit_config *cfg) {
     if (!env || !cfg) return fail(RC_ERR_INVALID, "NULL argument");
     if (cfg->struct_size != sizeof(rc_policy_fit_config))
         return fail(RC_ERR_INVALID, "rc_policy_fit_config.struct_size %u != %zu", cfg->struct_size, sizeof(rc_policy_fit_config));
-    if (cfg->head != RC_POLICY_FIT_VALUE && cfg->head != RC_POLICY_FIT_PCONT) return fail(RC_ERR_INVALID, "rc_policy_fit_begin: unknown head %d", cfg->head);
-    const int head = cfg->head;
-    if (!(head ? env->pol_c.pout_w : env->pol_c.vout_w))
-        return fail(RC_ERR_INVALID, "rc_policy_fit_begin: no %s head is loaded (rc_policy_load_critic)", fit_head_name(head));
+    if (!fit_head_known(cfg->head)) return fail(RC_ERR_INVALID, "rc_policy_fit_begin: unknown head %d", cfg->head);
+    const int head = cfg->head, depth = fit_depth(head);
+    if (!fit_head(env, head).wout)
+        return fail(RC_ERR_INVALID, "rc_policy_fit_begin: no %s head is loaded (%s)", fit_head_name(head),
+                    head == RC_POLICY_FIT_REWARD ? "rc_policy_load_heads" : "rc_policy_load_critic");
     int rc = fit_close(env, head);
     if (rc) return rc;
     HIP_TRY(hipSetDevice(env->cfg.device));
     HIP_TRY(hipFuncSetAttribute((const void *)rc_policy_fit_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitLds));
+    HIP_TRY(hipFuncSetAttribute((const void *)rc_policy_fit_reward_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kFitLds));
     if (!env->fit) env->fit = new RcFit();
     RcFit::Head &o = env->fit->head[head];
-    const size_t floats = 3 * kMoment + 2 * kImage;
+    const size_t kMoment = fit_moment(depth), floats = 3 * kMoment + (size_t)(depth - 1) * kImage;
     hipError_t e = hipMalloc((void **)&o.mem, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void **)&o.ctl, sizeof(FitCtl));
     if (e != hipSuccess) {
@@ -434,7 +478,7 @@ int rc_policy_fit_begin(rc_env *env, const rc_policy_fit_config *cfg) {
     const FitHeadDev h = fit_head(env, head);
     const unsigned blocks = (unsigned)((kImage + PT - 1) / PT);
     hipLaunchKernelGGL(rc_policy_fit_transpose_kernel, dim3(blocks), dim3(PT), 0, env->stream, (const float *)h.w[1], h.t1);
-    hipLaunchKernelGGL(rc_policy_fit_transpose_kernel, dim3(blocks), dim3(PT), 0, env->stream, (const float *)h.w[2], h.t2);
+    if (depth == 3) hipLaunchKernelGGL(rc_policy_fit_transpose_kernel, dim3(blocks), dim3(PT), 0, env->stream, (const float *)h.w[2], h.t2);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(env->stream));             // (`init` goes out of scope)
     return RC_OK;
@@ -444,8 +488,8 @@ int rc_policy_fit_step(rc_env *env, const rc_policy_fit_args *a) {
     if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
     if (a->struct_size != sizeof(rc_policy_fit_args))
         return fail(RC_ERR_INVALID, "rc_policy_fit_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_fit_args));
-    if (a->head != RC_POLICY_FIT_VALUE && a->head != RC_POLICY_FIT_PCONT) return fail(RC_ERR_INVALID, "rc_policy_fit_step: unknown head %d", a->head);
-    const int head = a->head;
+    if (!fit_head_known(a->head)) return fail(RC_ERR_INVALID, "rc_policy_fit_step: unknown head %d", a->head);
+    const int head = a->head, depth = fit_depth(head), ng = fit_ng(depth);
     if (!env->fit || !env->fit->head[head].mem)
         return fail(RC_ERR_INVALID, "rc_policy_fit_step: no optimizer is open for the %s head (rc_policy_fit_begin)", fit_head_name(head));
     if (!a->features || !a->target) return fail(RC_ERR_INVALID, "rc_policy_fit_step: %s is NULL", !a->features ? "features" : "target");
@@ -460,17 +504,19 @@ int rc_policy_fit_step(rc_env *env, const rc_policy_fit_args *a) {
     HIP_TRY(hipSetDevice(env->cfg.device));
     RcFit &f = *env->fit;
     const int64_t n = a->rows;
-    if (n > f.scratch_rows) {
+    const size_t need = (size_t)n * (2 * depth * LD + 2);
+    if (need > f.scratch_floats) {
         if (f.scratch) {
             HIP_TRY(hipStreamSynchronize(env->stream));
             (void)hipFree(f.scratch);
             f.scratch = nullptr;
-            f.scratch_rows = 0;
+            f.scratch_floats = 0;
         }
-        HIP_TRY(hipMalloc((void **)&f.scratch, (size_t)n * (6 * LD + 2) * sizeof(float)));
-        f.scratch_rows = n;
+        HIP_TRY(hipMalloc((void **)&f.scratch, need * sizeof(float)));
+        f.scratch_floats = need;
     }
     RcFit::Head &o = f.head[head];
+    const size_t kMoment = fit_moment(depth);
     float *m = o.mem, *v = o.mem + kMoment, *g = o.mem + 2 * kMoment;
     const size_t plane = (size_t)n * LD;
     FitRowsCall r{};
@@ -480,42 +526,47 @@ int rc_policy_fit_step(rc_env *env, const rc_policy_fit_args *a) {
     r.inv_n = 1.0f / (float)n;
     r.pcont = head == RC_POLICY_FIT_PCONT;
     r.act = f.scratch;
-    r.dout = f.scratch + 6 * plane;
+    r.dout = f.scratch + 2 * depth * plane;
     r.lterm = r.dout + n;
     FitWgradCall w{};
-    const float *prev[4] = {a->features, r.act, r.act + plane, r.act + 2 * plane};
-    const float *delta[4] = {r.act + 3 * plane, r.act + 4 * plane, r.act + 5 * plane, r.dout};
     const int goff[4] = {0, G1, G2, GO};
     int tiles = 0;
-    for (int l = 0; l < 4; ++l) {
-        w.a[l] = prev[l]; w.d[l] = delta[l];
+    for (int l = 0; l <= depth; ++l) {          // layer l's input a_l (the features, a1 ..) and delta_{l+1} (.., the output delta)
+        const bool out = l == depth;
+        w.a[l] = l == 0 ? a->features : r.act + (size_t)(l - 1) * plane;
+        w.d[l] = out ? r.dout : r.act + (size_t)(depth + l) * plane;
         w.lda[l] = l == 0 ? FEAT : LD;
-        w.ldd[l] = l == 3 ? 1 : LD;
+        w.ldd[l] = out ? 1 : LD;
         w.k[l] = l == 0 ? FEAT : UNITS;
-        w.nc[l] = l == 3 ? 1 : UNITS;
+        w.nc[l] = out ? 1 : UNITS;
         w.tile0[l] = tiles;
         w.nt[l] = (w.nc[l] + 31) / 32;
         w.goff[l] = goff[l];
         tiles += (w.k[l] + 1 + 31) / 32 * w.nt[l];
     }
+    for (int l = depth + 1; l < 4; ++l) w.tile0[l] = tiles;
     w.g = g;
     w.n = n;
     KernelTimer t;
     int rc = t.begin(env, RC_K_POLICY, true);
     if (rc) return rc;
-    hipLaunchKernelGGL(rc_policy_fit_rows_kernel, dim3((unsigned)((n + PM - 1) / PM)), dim3(PT), (uint32_t)kFitLds, env->stream, r);
+    const dim3 row_blocks((unsigned)((n + PM - 1) / PM));
+    if (depth == 3) hipLaunchKernelGGL(rc_policy_fit_rows_kernel, row_blocks, dim3(PT), (uint32_t)kFitLds, env->stream, r);
+    else hipLaunchKernelGGL(rc_policy_fit_reward_rows_kernel, row_blocks, dim3(PT), (uint32_t)kFitLds, env->stream, r);
     hipLaunchKernelGGL(rc_policy_fit_wgrad_kernel, dim3((unsigned)tiles), dim3(PT), 0, env->stream, w);
-    hipLaunchKernelGGL(rc_policy_fit_sums_kernel, dim3(SUM_BLOCKS), dim3(PT), 0, env->stream, (const float *)g, (const float *)r.lterm, n, o.ctl);
+    hipLaunchKernelGGL(rc_policy_fit_sums_kernel, dim3(SUM_BLOCKS), dim3(PT), 0, env->stream, (const float *)g, ng, (const float *)r.lterm, n, o.ctl);
     hipLaunchKernelGGL(rc_policy_fit_scale_kernel, dim3(1), dim3(64), 0, env->stream, o.ctl, n, a->lr, a->clip, a->beta1, a->beta2, a->status);
-    hipLaunchKernelGGL(rc_policy_fit_apply_kernel, dim3((NG + PT - 1) / PT), dim3(PT), 0, env->stream, r.h, (const float *)g, m, v, (const FitCtl *)o.ctl,
-                       a->beta1, a->beta2, 1.0f - a->beta1, 1.0f - a->beta2, a->epsilon);
+    hipLaunchKernelGGL(rc_policy_fit_apply_kernel, dim3((ng + PT - 1) / PT), dim3(PT), 0, env->stream, r.h, depth, (const float *)g, m, v,
+                       (const FitCtl *)o.ctl, a->beta1, a->beta2, 1.0f - a->beta1, 1.0f - a->beta2, a->epsilon);
+    // rc_policy_dream_grad keeps transposed copies of the reward head's two hidden layers: its next call makes them again, on the stream
+    if (head == RC_POLICY_FIT_REWARD) env->dgrad_reward_stale = true;
     HIP_TRY(hipGetLastError());
     return t.end();
 }
 
 int rc_policy_fit_end(rc_env *env, int32_t head) {
     if (!env) return fail(RC_ERR_INVALID, "env is NULL");
-    if (head != RC_POLICY_FIT_VALUE && head != RC_POLICY_FIT_PCONT) return fail(RC_ERR_INVALID, "rc_policy_fit_end: unknown head %d", head);
+    if (!fit_head_known(head)) return fail(RC_ERR_INVALID, "rc_policy_fit_end: unknown head %d", head);
     return fit_close(env, head);
 }
 

@@ -426,9 +426,34 @@ void pol_point(const PolImage<W> (&table)[N], const W &w, rc_env *env, const flo
         if (table[i].ld) table[i].dst(*env) = (w.*(table[i].arr)).data ? mem + at[i] : nullptr;
 }
 
+// pol_pack's inverse for the images at `mem` on the device: the arrays of `w` that have a data pointer receive their [rows][cols],
+// the padding dropped (written despite the const).  Synchronises the stream.
+template <class W, size_t N>
+int pol_unpack(const PolImage<W> (&table)[N], const W &w, rc_env *env, const float *mem) {
+    size_t at[N], total = 0;
+    for (size_t i = 0; i < N; ++i) {                        // pol_pack's offsets: every image on a 64-float boundary
+        at[i] = total;
+        total += (table[i].floats() + 63) / 64 * 64;
+    }
+    std::vector<float> img(total);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(hipMemcpyAsync(img.data(), mem, total * sizeof(float), hipMemcpyDeviceToHost, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));
+    for (size_t i = 0; i < N; ++i) {
+        const PolImage<W> &im = table[i];
+        float *dst = const_cast<float *>((w.*(im.arr)).data);
+        if (!dst) continue;
+        for (int k = 0; k < im.rows; ++k)
+            for (int j = 0; j < im.cols; ++j) dst[(size_t)k * im.cols + j] = img[at[i] + (size_t)k * im.ld + j];
+    }
+    return RC_OK;
+}
+
 // the reward head's memory and pointers go (rc_policy_load_heads(NULL), a new rc_policy_load); the prior's layers stay
 int pol_drop_heads(rc_env *env) {
-    const int rc = dream_grad_release(env);      // (its transposed images were made from these weights)
+    int rc = dream_grad_release(env);            // (its transposed images were made from these weights)
+    if (rc) return rc;
+    rc = fit_release_reward(env);                // (the optimizer holds pointers into the head's memory)
     if (rc) return rc;
     if (env->pol_heads_mem) {
         HIP_TRY(hipSetDevice(env->cfg.device));
@@ -725,6 +750,8 @@ int rc_policy_load_heads(rc_env *env, const rc_policy_heads *h) {
     HIP_TRY(hipSetDevice(env->cfg.device));
     const int rc_grad = dream_grad_release(env);            // new weights: the transposed images are another head's
     if (rc_grad) return rc_grad;
+    const int rc_fit = fit_release_reward(env);             // and the moments another head's
+    if (rc_fit) return rc_fit;
     if (!env->pol_heads_mem) HIP_TRY(hipMalloc((void **)&env->pol_heads_mem, img.size() * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(env->pol_heads_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
     HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
@@ -892,24 +919,18 @@ int rc_policy_read_critic(rc_env *env, rc_policy_critic *out) {
     for (const PolImage<PC> &im : kCriticImages)
         if (im.optional && (out->*(im.arr)).data && !env->pol_c.pout_w)
             return fail(RC_ERR_INVALID, "rc_policy_read_critic: %s is asked for and no pcont head is loaded", im.name);
-    constexpr size_t n_img = sizeof(kCriticImages) / sizeof(kCriticImages[0]);
-    size_t at[n_img], total = 0;
-    for (size_t i = 0; i < n_img; ++i) {                    // pol_pack's offsets: every image on a 64-float boundary
-        at[i] = total;
-        total += (kCriticImages[i].floats() + 63) / 64 * 64;
-    }
-    std::vector<float> img(total);
-    HIP_TRY(hipSetDevice(env->cfg.device));
-    HIP_TRY(hipMemcpyAsync(img.data(), env->pol_critic_mem, total * sizeof(float), hipMemcpyDeviceToHost, env->stream));
-    HIP_TRY(hipStreamSynchronize(env->stream));
-    for (size_t i = 0; i < n_img; ++i) {
-        const PolImage<PC> &im = kCriticImages[i];
-        float *dst = const_cast<float *>((out->*(im.arr)).data);
-        if (!dst) continue;
-        for (int k = 0; k < im.rows; ++k)
-            for (int j = 0; j < im.cols; ++j) dst[(size_t)k * im.cols + j] = img[at[i] + (size_t)k * im.ld + j];
-    }
-    return RC_OK;
+    return pol_unpack(kCriticImages, *out, env, env->pol_critic_mem);
+}
+
+// The inverse of rc_policy_load_heads' packing, as rc_policy_read_critic is of the critic's
+int rc_policy_read_heads(rc_env *env, rc_policy_heads *out) {
+    if (!env || !out) return fail(RC_ERR_INVALID, "NULL argument");
+    if (out->struct_size != sizeof(rc_policy_heads))
+        return fail(RC_ERR_INVALID, "rc_policy_heads.struct_size %u != %zu", out->struct_size, sizeof(rc_policy_heads));
+    if (!env->pol_heads_mem || !env->pol_i.rout_w) return fail(RC_ERR_INVALID, "rc_policy_read_heads: no reward head is loaded (rc_policy_load_heads)");
+    const int rc = pol_check(kHeadImages, *out, "rc_policy_read_heads", "the reward head's");
+    if (rc) return rc;
+    return pol_unpack(kHeadImages, *out, env, env->pol_heads_mem);
 }
 
 int rc_policy_returns(rc_env *env, const rc_policy_returns_args *a) {

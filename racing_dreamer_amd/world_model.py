@@ -154,6 +154,21 @@ def pcont_learning_step(env, batch: Dict[str, torch.Tensor], discount: float = 0
     return env.critic_fit(feat, target, weight, head="pcont", **fit)
 
 
+def reward_learning_step(env, batch: Dict[str, torch.Tensor], seed: int = 0, **fit) -> Dict[str, torch.Tensor]:
+    """One step of the reward head ALONE on a replay batch, the world model frozen, `policy_observe`'s launch plus the
+    fit's five and no host copy: the head on the posterior features (`policy_observe(mode="sample", seed)` on `batch["lidar"]` and
+    `batch["action"]`) against `batch["reward"]` [B, T] under Normal(., 1) (dreamer/models.py:97-100), through `reward_fit`,
+    whose optimizer must be open (`reward_fit_begin`).  `fit` goes to `reward_fit` (weight, lr, clip, ...).  This is NOT the
+    reference's rule: there the reward likelihood is a term of the model loss under model_opt and its gradient also reaches the
+    RSSM and the encoder; here nothing but the head's six arrays moves.  Returns the fit's status (`loss`, `grad_norm`, `skipped`,
+    `step`) and `reward_loss` = `loss` = -`model_terms`' reward_loglik on these features, on the weights before the update."""
+    feat = env.policy_observe(batch["lidar"], batch["action"], mode="sample", seed=seed, outputs=("feature",))["feature"]
+    target = batch["reward"].to(feat.device, torch.float32).reshape(feat.shape[:-1])
+    status = env.reward_fit(feat, target, **fit)
+    status["reward_loss"] = status["loss"]
+    return status
+
+
 def imagined_vs_simulated(env, horizon: int = 15, mode: str = "mean", seed: int = 0, repeat=None) -> Dict[str, torch.Tensor]:
     """The world model's dream beside what the simulator would really do, without spending the run:
     `policy_imagine` from every car's latent under the actor's own actions, then `look_ahead` with one candidate per env - those

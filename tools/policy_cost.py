@@ -43,7 +43,10 @@ lambda-return in plain fp32 torch on features already in memory.
 1 024 envs x 14) and 35 000 rows (the reference's 2 500 starts x 14), beside the same iteration done the way tools/fit_critic.py --fit
 torch does it - torch autograd, clip_grad_norm_, Adam.step and the load_critic upload with the synchronisation it forces - with the
 condition: device step <= 1.0 x that, reported as met or missed; and, a record without a threshold, the same torch step without the
-upload.  All three are wall-clock times per iteration over a window of iterations that ends with a synchronisation.
+upload.  All three are wall-clock times per iteration over a window of iterations that ends with a synchronisation.  Then the reward
+head's step (reward_fit, the same engine at two hidden layers, 665 200 multiply-adds per row against 1 145 200) beside critic_fit of
+the same run, and - a record - the torch step on the reward head's layers (profiles/reward_fit_cost.json).  `--device-only` leaves
+the torch steps out and `--root DIR` imports the package from another checkout: the two halves of an A/B against a parent build.
 
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
 windows; the torch baseline is timed with stream events around a window of calls (its dozen launches per call included - that is
@@ -451,10 +454,13 @@ def measure_returns(n, args):
 
 
 MACS_FIT_ROW = (230 * 400 + 2 * 400 * 400 + 400) * 2 + 2 * 400 * 400 + 400      # forward + weight gradients + backward data: 1 145 200
+MACS_REWARD_FIT_ROW = (230 * 400 + 400 * 400 + 400) * 2 + 400 * 400 + 400       # the same at two hidden layers: 665 200 (x 0.58)
 
 
 def measure_fit(rows, args):
-    """Wall-clock time per iteration of critic_fit beside tools/fit_critic.py's torch step with and without its load_critic upload."""
+    """Wall-clock time per iteration of critic_fit beside tools/fit_critic.py's torch step with and without its load_critic upload;
+    then reward_fit (where the package has it) beside critic_fit and - a record - beside the torch step on the reward head's layers.
+    `--device-only` leaves the torch steps out: the figures an A/B of two builds needs."""
     import math
     import torch
     from racing_dreamer_amd import _lib as L
@@ -500,28 +506,57 @@ def measure_fit(rows, args):
             windows.append((time.perf_counter() - t0) * 1e3 / iters)
         return statistics.median(windows), [round(v, 4) for v in windows]
 
-    res = {"rows": rows}
-    with torch.cuda.stream(env.stream):
-        ms, windows = wall(lambda: torch_step(True), args.calls)
-        res["torch_step_with_load_critic_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
-        ms, windows = wall(lambda: torch_step(False), args.calls)
-        res["torch_step_without_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
-        env.load_critic(start)
-        env.critic_fit_begin("value")
-        ms, windows = wall(lambda: env.critic_fit(feat, target, weight), args.calls)
-        res["critic_fit"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows,
-                             "tflops": round(2 * MACS_FIT_ROW * rows / (ms * 1e-3) / 1e12, 2)}
+    def device(step, macs):
+        """{wall clock per iteration, its windows, TFLOP/s, the five launches' RC_K_POLICY time} of one fit step"""
+        ms, windows = wall(step, args.calls)
+        entry = {"ms_per_iteration": round(ms, 4), "windows_ms": windows, "tflops": round(2 * macs * rows / (ms * 1e-3) / 1e12, 2)}
         env.reset_kernel_times()
         env.set_profiling(True, kernels=[L.K_POLICY])
         for k in range(args.calls):
-            env.critic_fit(feat, target, weight)
+            step()
         env.sync()
         env.set_profiling(False)
-        res["critic_fit"]["device_ms_five_launches"] = round(env.kernel_times()["rc_policy_kernel"]["avg_ms"], 4)
+        entry["device_ms_five_launches"] = round(env.kernel_times()["rc_policy_kernel"]["avg_ms"], 4)
+        return entry
+
+    res = {"rows": rows}
+    with torch.cuda.stream(env.stream):
+        if not args.device_only:
+            ms, windows = wall(lambda: torch_step(True), args.calls)
+            res["torch_step_with_load_critic_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
+            ms, windows = wall(lambda: torch_step(False), args.calls)
+            res["torch_step_without_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
+        env.load_critic(start)
+        env.critic_fit_begin("value")
+        res["critic_fit"] = device(lambda: env.critic_fit(feat, target, weight), MACS_FIT_ROW)
         env.critic_fit_end("value")
-    base = res["torch_step_with_load_critic_upload"]["ms_per_iteration"]
-    res["critic_fit"].update(over_torch_with_upload=round(ms / base, 4), met=bool(ms <= base),
-                             over_torch_without_upload=round(ms / res["torch_step_without_upload"]["ms_per_iteration"], 4))
+        if hasattr(env, "reward_fit"):
+            env.reward_fit_begin()
+            res["reward_fit"] = device(lambda: env.reward_fit(feat, target, weight), MACS_REWARD_FIT_ROW)
+            env.reward_fit_end()
+            res["reward_fit"].update(macs_over_critic_fit=round(MACS_REWARD_FIT_ROW / MACS_FIT_ROW, 4),
+                                     over_critic_fit=round(res["reward_fit"]["ms_per_iteration"] / res["critic_fit"]["ms_per_iteration"], 4))
+            if not args.device_only:
+                head = {k: torch.from_numpy(np.array(weights[k])).to(env.device).requires_grad_(True) for k in L.HEAD_KEYS}
+                head_opt = torch.optim.Adam(list(head.values()), lr=6e-4)
+
+                def torch_reward_step():
+                    x = feat
+                    for i in range(2):
+                        x = torch.nn.functional.elu(torch.addmm(head[f"reward_h{i}_b"], x, head[f"reward_h{i}_w"]))
+                    reward = torch.addmm(head["reward_hout_b"], x, head["reward_hout_w"])[:, 0]
+                    loss = -(weight * (-0.5 * (reward - target) ** 2 - 0.5 * math.log(2.0 * math.pi))).mean()
+                    head_opt.zero_grad()
+                    loss.backward()
+                    torch.nn.utils.clip_grad_norm_(list(head.values()), 1.0)
+                    head_opt.step()
+                ms, windows = wall(torch_reward_step, args.calls)
+                res["torch_reward_step_without_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
+                res["reward_fit"]["over_torch_without_upload"] = round(res["reward_fit"]["ms_per_iteration"] / ms, 4)
+    if not args.device_only:
+        ms, base = res["critic_fit"]["ms_per_iteration"], res["torch_step_with_load_critic_upload"]["ms_per_iteration"]
+        res["critic_fit"].update(over_torch_with_upload=round(ms / base, 4), met=bool(ms <= base),
+                                 over_torch_without_upload=round(ms / res["torch_step_without_upload"]["ms_per_iteration"], 4))
     env.close()
     return res
 
@@ -838,17 +873,23 @@ def main():
     ap.add_argument("--observe", action="store_true", help="measure recorded sequences (profiles/policy_observe_cost.json)")
     ap.add_argument("--returns", action="store_true", help="measure the critic and the lambda-return (profiles/policy_returns_cost.json)")
     ap.add_argument("--fit", action="store_true", help="measure the critic's fit (profiles/policy_fit_cost.json)")
+    ap.add_argument("--device-only", action="store_true", help="--fit: the device steps alone, no torch baseline (an A/B of two builds)")
+    ap.add_argument("--root", default=None, help="import racing_dreamer_amd from this checkout instead (--fit --device-only: the other build of an A/B)")
     ap.add_argument("--horizon", type=int, default=15)
     args = ap.parse_args()
+    if args.root:
+        sys.path.insert(0, os.path.abspath(args.root))
     import torch
     if args.fit:
         sizes = args.envs if args.envs != [4096, 65536] else [14336, 35000]
-        out = {"tool": "tools/policy_cost.py --fit", "checkpoint": args.checkpoint, "critic": "critic.init_critic(0, pcont=False)",
+        out = {"tool": "tools/policy_cost.py --fit" + (" --device-only" if args.device_only else ""), "checkpoint": args.checkpoint,
+               "critic": "critic.init_critic(0, pcont=False)", "reward_head": "the checkpoint's",
                "device": torch.cuda.get_device_name(0), "iterations_per_window": args.calls, "windows": args.rounds,
-               "macs_per_row_forward_backward": MACS_FIT_ROW, "clock": "wall clock per iteration over a window that ends with a synchronisation",
+               "macs_per_row_forward_backward": MACS_FIT_ROW, "macs_per_row_forward_backward_reward": MACS_REWARD_FIT_ROW,
+               "clock": "wall clock per iteration over a window that ends with a synchronisation",
                "condition": "critic_fit ms_per_iteration <= 1.0 x torch_step_with_load_critic_upload ms_per_iteration of the same run, at every size",
                "sizes": [measure_fit(n, args) for n in sizes]}
-        out["condition_met"] = all(s["critic_fit"]["met"] for s in out["sizes"])
+        out["condition_met"] = None if args.device_only else all(s["critic_fit"]["met"] for s in out["sizes"])
         print(json.dumps(out))
         if args.out:
             with open(args.out, "w") as f:
