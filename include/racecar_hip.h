@@ -649,6 +649,67 @@ int rc_policy_fit_end(rc_env *env, int32_t head);
 int rc_policy_read_critic(rc_env *env, rc_policy_critic *out);
 int rc_policy_read_heads(rc_env *env, rc_policy_heads *out);
 
+/* Fitting the actor on the device: the actor's own backward pass and optimizer on the fit engine (RC_POLICY_FIT_ACTOR; DESIGN.md §2
+ * item 25, tests/policy_actor_fit_spec.c is the CPU restatement, the device equals it bit for bit).  The network is the reference's
+ * plain ActionDecoder(2, 4, 400, 'tanh_normal'), 230 -> 400 -> 400 -> 400 -> 400 -> 4, ELU, init_std 5, min_std 1e-4, mean_scale 5
+ * (dreamer/models.py:535-560); the optimizer is actor_opt's: lr 8e-5, clip 1.0 (dreamer/dream.py:87-88), dreamer/tools.py:421-455 as
+ * for the critic.  The closed-loop gradient through the dream (the reference's actor_loss) is NOT computed here: the caller supplies
+ * the gradient with respect to the actions, or target actions.  Per row q of N, with o[0..3] the output layer on features[q], e =
+ * eps[q] (NULL: the mode action, u = mu), w = weight[q] (NULL: 1):
+ *   mu_j = 5 tanh(o_j / 5);  sd_j = softplus(o_{2+j} + raw_init_std) + 1e-4;  u_j = fmaf(sd_j, e_j, mu_j);  act_j = tanh(u_j)
+ *   target  loss = (1/N) sum w 0.5 sum_j (act_j - target_j)^2        ga_j = w (act_j - target_j) / N
+ *   grad    loss = 0 (the caller owns it)                            ga_j = w grad_j
+ *   du_j = ga_j (1 - act_j^2);  delta o_j = du_j (1 - tanh(o_j / 5)^2);  delta o_{2+j} = du_j e_j sigmoid(o_{2+j} + raw_init_std)
+ * then back through the four hidden layers as the critic's fit does, and, when asked for, grad_features = delta1 W0^T.  The gradient
+ * is [231][400] | 3 x [401][400] | [401][4] = 575 204 elements in the critic's fixed order; sum tree, skip, clip and Adam are the
+ * critic's.  The new weights are written into every image of the actor that a kernel reads: rc_policy_act (all three modes),
+ * rc_policy_imagine and rc_policy_returns read the fitted actor at their next call, with no reload and no latent reset; the RSSM,
+ * the heads, the latents, the arena and every counter stay as they are.  Actions are raw, in [-1, 1]: RC_F_ACTION_IN's convention
+ * under remap_actions.
+ *   rc_policy_fit_begin / rc_policy_fit_end  with RC_POLICY_FIT_ACTOR open and free the optimizer.  rc_policy_load, rc_policy_unload,
+ *                        rc_policy_load_actor and rc_destroy close it.  A "normalized" actor (hnorm_* arrays: batch statistics in
+ *                        training) is refused.
+ *   rc_policy_actor_fit_step  one update, stream-ordered, no synchronisation; status as rc_policy_fit_step's.
+ *   rc_policy_actor_forward   the forward pass alone on given features: action, mean (mu), std (sd), each [rows, 2] or NULL.  With eps
+ *                        NULL the action is byte-identical to what rc_policy_act writes in mode mean for the same feature.
+ *   rc_policy_read_actor copies the actor's ten arrays back into the caller's host arrays (data pointers to [rows, cols] float32 of
+ *                        the checkpoint's shapes, written despite the const).  Synchronises the stream.
+ *   rc_policy_load_actor replaces the actor's ten arrays alone, in every image; closes the actor's optimizer and resets nothing else.
+ * RC_ERR_INVALID: wrong struct_size, no policy loaded, a normalized actor, no optimizer open (step), both or neither of target and
+ * grad, rows outside [1, 2^31), features NULL, no output asked for (forward), a hyper-parameter negative or not finite, a beta
+ * outside [0, 1), an array missing or of a wrong shape (read, load).  Kernels: rc_policy_fit_actor_rows_kernel in place of
+ * rc_policy_fit_rows_kernel, the other four as for the critic; rc_policy_actor_forward_kernel; timed under RC_K_POLICY. */
+#define RC_POLICY_FIT_ACTOR 3
+typedef struct rc_policy_actor_fit_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_actor_fit_args) */
+    int64_t rows;                  /* N in [1, 2^31) */
+    const float *features;         /* device float32 [rows, 230] = stoch | deter */
+    const float *eps;              /* device float32 [rows, 2], or NULL: the mode action */
+    const float *weight;           /* device float32 [rows], or NULL: all 1 */
+    const float *target;           /* device float32 [rows, 2] raw actions, or NULL ... */
+    const float *grad;             /* ... device float32 [rows, 2] the gradient with respect to the actions: exactly one of the two */
+    float *grad_features;          /* device float32 [rows, 230], or NULL */
+    float lr, clip;                /* the reference's actor_lr 8e-5 and grad_clip 1.0 (dreamer/dream.py:87-88); clip 0: none */
+    float beta1, beta2, epsilon;   /* TF's 0.9, 0.999, 1e-7 */
+    float *status;                 /* device float32 [4] = loss, grad_norm, skipped, step; or NULL */
+} rc_policy_actor_fit_args;
+typedef struct rc_policy_actor_forward_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_actor_forward_args) */
+    int64_t rows;                  /* in [1, 2^31) */
+    const float *features;         /* device float32 [rows, 230] */
+    const float *eps;              /* device float32 [rows, 2], or NULL */
+    float *action, *mean, *std;    /* device float32 [rows, 2] each; any may be NULL, not all */
+} rc_policy_actor_forward_args;
+typedef struct rc_policy_actor {   /* the ActionDecoder's arrays (dreamer/models.py:535-560), rc_policy_weights' of the same names */
+    uint32_t struct_size;          /* = sizeof(rc_policy_actor) */
+    rc_policy_array h0_w, h0_b, h1_w, h1_b, h2_w, h2_b, h3_w, h3_b;      /* [230, 400], [400]; 3 x ([400, 400], [400]) */
+    rc_policy_array hout_w, hout_b;                                      /* [400, 4], [4]: mean 0, mean 1, raw std 0, raw std 1 */
+} rc_policy_actor;
+int rc_policy_actor_fit_step(rc_env *env, const rc_policy_actor_fit_args *args);
+int rc_policy_actor_forward(rc_env *env, const rc_policy_actor_forward_args *args);
+int rc_policy_read_actor(rc_env *env, rc_policy_actor *out);
+int rc_policy_load_actor(rc_env *env, const rc_policy_actor *actor);
+
 /* Recorded sequences: the posterior chain over N recorded windows of T scans and actions (DESIGN.md §2 item 17;
  * tests/policy_observe_spec.c is the CPU restatement, the device equals it bit for bit) - dreamer/models.py:325-336 RSSM.observe,
  * the operation the reference runs on every replay batch: `post, prior = observe(embed, action)`, kl_divergence(post, prior) and the

@@ -176,6 +176,30 @@ class RcPolicyFitArgs(C.Structure):
                 ("epsilon", C.c_float), ("status", C.c_void_p)]
 
 
+FIT_ACTOR = 3                                                   # RC_POLICY_FIT_ACTOR: the actor's own (actor_fit)
+ACTOR_KEYS = ("h0_w", "h0_b", "h1_w", "h1_b", "h2_w", "h2_b", "h3_w", "h3_b", "hout_w", "hout_b")      # rc_policy_actor, of POLICY_KEYS
+ACTOR_SHAPES = ((230, 400), (400,), (400, 400), (400,), (400, 400), (400,), (400, 400), (400,), (400, 4), (4,))
+ACTOR_OUTPUTS = ("action", "mean", "std")                       # policy_action's
+
+
+class RcPolicyActorFitArgs(C.Structure):
+    """rc_policy_actor_fit_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rows", C.c_int64), ("features", C.c_void_p), ("eps", C.c_void_p), ("weight", C.c_void_p),
+                ("target", C.c_void_p), ("grad", C.c_void_p), ("grad_features", C.c_void_p), ("lr", C.c_float), ("clip", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float), ("status", C.c_void_p)]
+
+
+class RcPolicyActorForwardArgs(C.Structure):
+    """rc_policy_actor_forward_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("rows", C.c_int64), ("features", C.c_void_p), ("eps", C.c_void_p), ("action", C.c_void_p),
+                ("mean", C.c_void_p), ("std", C.c_void_p)]
+
+
+class RcPolicyActor(C.Structure):
+    """rc_policy_actor (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, RcPolicyArray) for k in ACTOR_KEYS]
+
+
 LOOK_AHEAD_MAX_HORIZON = 64
 LA_DONE, LA_TRUNCATED, LA_WALL, LA_OPPONENT, LA_WRONG_WAY = 1, 2, 4, 8, 16      # rc_look_ahead's flags
 # look_ahead's output names -> (rc_look_ahead_args field, torch dtype name, shape as a function of (E, K, H, A))
@@ -297,6 +321,16 @@ def policy_critic(weights):
     return h, _fill_arrays(h, weights, VALUE_KEYS + pcont)
 
 
+def policy_actor(weights):
+    """rc_policy_actor over a mapping that holds the actor's ten arrays `h0_w` .. `hout_b` (or an .npz path), as policy_heads."""
+    import numpy as np
+    if isinstance(weights, (str, os.PathLike)):
+        weights = np.load(weights)
+    a = RcPolicyActor()
+    a.struct_size = C.sizeof(RcPolicyActor)
+    return a, _fill_arrays(a, weights, ACTOR_KEYS)
+
+
 def policy_decoder(weights):
     """rc_policy_decoder over a mapping that holds the dec_* arrays of a LidarOccupancyDecoder (or an .npz path), as policy_heads;
     None if it holds none."""
@@ -377,6 +411,10 @@ SYMBOLS = {
     "rc_policy_fit_end": (C.c_int, [C.c_void_p, C.c_int32]),
     "rc_policy_read_critic": (C.c_int, [C.c_void_p, _P(RcPolicyCritic)]),
     "rc_policy_read_heads": (C.c_int, [C.c_void_p, _P(RcPolicyHeads)]),
+    "rc_policy_actor_fit_step": (C.c_int, [C.c_void_p, _P(RcPolicyActorFitArgs)]),
+    "rc_policy_actor_forward": (C.c_int, [C.c_void_p, _P(RcPolicyActorForwardArgs)]),
+    "rc_policy_read_actor": (C.c_int, [C.c_void_p, _P(RcPolicyActor)]),
+    "rc_policy_load_actor": (C.c_int, [C.c_void_p, _P(RcPolicyActor)]),
     "rc_policy_observe": (C.c_int, [C.c_void_p, _P(RcPolicyObserveArgs)]),
     "rc_policy_load_decoder": (C.c_int, [C.c_void_p, _P(RcPolicyDecoder)]),
     "rc_policy_decode": (C.c_int, [C.c_void_p, _P(RcPolicyDecodeArgs)]),

@@ -277,6 +277,36 @@ def _fit_status(status):
     return {"loss": status[0], "grad_norm": status[1], "skipped": status[2], "step": status[3]}
 
 
+def _actor_rows(env, features, pairs, rows):
+    """actor_fit's and policy_action's tensors (shared by BatchedRaceEnv and MixedTrackEnv): `features` as contiguous float32
+    [N, 230] on the env's device with its leading shape, each of `pairs` (name -> tensor or None) as [N, 2], each of `rows` as [N]."""
+    if features.shape[-1] != L.POLICY_FEATURE or features.numel() == 0:
+        raise ValueError(f"features must be [..., {L.POLICY_FEATURE}] with at least one row, got {tuple(features.shape)}")
+    lead = tuple(features.shape[:-1])
+    feat = features.to(env.device, torch.float32).reshape(-1, L.POLICY_FEATURE).contiguous()
+    n = feat.shape[0]
+    out = {}
+    for name, t in list(pairs.items()) + list(rows.items()):
+        width = 2 if name in pairs else 1
+        if t is None:
+            out[name] = None
+            continue
+        t = torch.as_tensor(t).to(env.device, torch.float32).reshape(-1).contiguous()
+        if t.numel() != n * width:
+            raise ValueError(f"features have {n} rows, {name} {t.numel()} elements, not {n * width}")
+        out[name] = t
+    return feat, lead, out
+
+
+def _actor_fit_setup(env, features, target, grad_actions, eps, weight, grad_features):
+    """actor_fit's tensors: (features [N, 230], the [N, 2] / [N] inputs by name, grad_features [N, 230] or None, its shape, status)."""
+    if (target is None) == (grad_actions is None):
+        raise ValueError("actor_fit takes exactly one of target and grad_actions")
+    feat, lead, t = _actor_rows(env, features, dict(target=target, grad=grad_actions, eps=eps), dict(weight=weight))
+    gfeat = torch.empty(feat.shape, dtype=torch.float32, device=env.device) if grad_features else None
+    return feat, t, gfeat, lead + (L.POLICY_FEATURE,), torch.empty(4, dtype=torch.float32, device=env.device)
+
+
 def _look_ahead_setup(env, actions, repeat, outputs, out):
     """look_ahead's arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
     rc_look_ahead_args field - env-major, one row per env -, the dict to return)."""
@@ -1150,6 +1180,107 @@ class BatchedRaceEnv:
             self._exit()
         self._policy_has_head = True
 
+    # ---- the actor's own fit (rc_policy_fit_begin / _end with RC_POLICY_FIT_ACTOR, rc_policy_actor_*)
+    def _actor_fit(self, feat, t, gfeat, status, hyper) -> int:
+        ptr = lambda x: None if x is None else x.data_ptr()
+        a = L.RcPolicyActorFitArgs(C.sizeof(L.RcPolicyActorFitArgs), feat.shape[0], feat.data_ptr(), ptr(t["eps"]), ptr(t["weight"]),
+                                   ptr(t["target"]), ptr(t["grad"]), ptr(gfeat), hyper["lr"], hyper["clip"], hyper["beta1"], hyper["beta2"],
+                                   hyper["epsilon"], ptr(status))
+        return self._lib.rc_policy_actor_fit_step(self._h, C.byref(a))
+
+    def actor_fit_begin(self) -> None:
+        """Open the optimizer of the loaded actor (`rc_policy_fit_begin`, RC_POLICY_FIT_ACTOR): Adam moments zero, step 0.
+        Independent of the other optimizers; `load_actor`, `load_policy` and `unload_policy` close it.  The plain actor only: a
+        checkpoint with `hnorm_*` arrays ("normalized") is refused."""
+        cfg = L.RcPolicyFitConfig(C.sizeof(L.RcPolicyFitConfig), L.FIT_ACTOR)
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_fit_begin(self._h, C.byref(cfg)))
+        finally:
+            self._exit()
+
+    def actor_fit(self, features: torch.Tensor, target: Optional[torch.Tensor] = None, grad_actions: Optional[torch.Tensor] = None,
+                  eps: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None, grad_features: bool = False,
+                  lr: float = 8e-5, clip: float = 1.0, beta1: float = 0.9, beta2: float = 0.999,
+                  epsilon: float = 1e-7) -> Dict[str, torch.Tensor]:
+        """One step of the actor's optimizer on the device (`rc_policy_actor_fit_step`; the reference's ActionDecoder,
+        dreamer/models.py:535-560, under actor_opt, dreamer/dream.py:87-88): the actor's forward pass on `features` [..., 230] =
+        stoch | deter, the action act = tanh(mean + std * eps) (`eps` [..., 2] standard normal draws, or None: the mode action),
+        then its backward pass from EITHER `target` [..., 2] raw actions in [-1, 1] - loss = mean(weight * 0.5 * |act - target|^2)
+        - OR `grad_actions` [..., 2], the gradient of a loss of the caller's with respect to act (times `weight`; the reported loss
+        is then 0); the global-norm clip (`clip` 0: none) and Adam, all in the env's stream: no synchronisation, no host copy.
+        The defaults are the reference's actor_lr and grad_clip and TF's Adam.  Returns device scalars `loss`, `grad_norm`
+        (before the clip), `skipped`, `step`, and with `grad_features` the gradient with respect to the features [..., 230]
+        (before the clip, of the same loss).  The fitted actor is what `policy_act` (every mode), `policy_imagine`,
+        `policy_returns` and `policy_action` read next; nothing else moves.  The closed-loop gradient through the dream is not
+        computed here."""
+        feat, t, gfeat, gshape, status = _actor_fit_setup(self, features, target, grad_actions, eps, weight, grad_features)
+        hyper = dict(lr=lr, clip=clip, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        self._enter()
+        try:
+            L.check(self._actor_fit(feat, t, gfeat, status, hyper))
+        finally:
+            self._exit()
+        out = _fit_status(status)
+        if gfeat is not None:
+            out["grad_features"] = gfeat.reshape(gshape)
+        return out
+
+    def actor_fit_end(self) -> None:
+        """Free the actor optimizer's state (`rc_policy_fit_end`); the fitted actor stays loaded."""
+        L.check(self._lib.rc_policy_fit_end(self._h, L.FIT_ACTOR))
+
+    def _actor_forward(self, feat, eps, tensors) -> int:
+        a = L.RcPolicyActorForwardArgs(C.sizeof(L.RcPolicyActorForwardArgs), feat.shape[0], feat.data_ptr(), None if eps is None else eps.data_ptr())
+        for name, t in tensors.items():
+            setattr(a, name, t.data_ptr())
+        return self._lib.rc_policy_actor_forward(self._h, C.byref(a))
+
+    def policy_action(self, features: torch.Tensor, eps: Optional[torch.Tensor] = None, outputs=("action",)) -> Dict[str, torch.Tensor]:
+        """The actor on given features (`rc_policy_actor_forward`, one launch): `features` float32 [..., 230] = stoch | deter,
+        e.g. `policy_state[:, :230]`; `eps` [..., 2] standard normal draws or None for the mode action, which is byte for byte
+        what `policy_act` writes in mode "mean" for the same feature.  `outputs` among "action" (raw, in [-1, 1]), "mean", "std"
+        (of the normal under the tanh); each comes back as a device float32 tensor [..., 2]."""
+        names = tuple(outputs)
+        unknown = [n for n in names if n not in L.ACTOR_OUTPUTS]
+        if unknown or not names:
+            raise ValueError(f"policy_action outputs must be among {sorted(L.ACTOR_OUTPUTS)}, got {list(names)}")
+        feat, lead, t = _actor_rows(self, features, dict(eps=eps), {})
+        tensors = {n: torch.empty((feat.shape[0], 2), dtype=torch.float32, device=self.device) for n in names}
+        self._enter()
+        try:
+            L.check(self._actor_forward(feat, t["eps"], tensors))
+        finally:
+            self._exit()
+        return {n: v.reshape(lead + (2,)) for n, v in tensors.items()}
+
+    def actor_weights(self) -> Dict[str, np.ndarray]:
+        """The loaded actor as NumPy arrays under `ACTOR_KEYS` (`h0_w` .. `hout_b`, the checkpoint's names), as `load_actor`
+        takes them (`rc_policy_read_actor`; waits for the env's stream)."""
+        out = {k: np.empty(shape, np.float32) for k, shape in zip(L.ACTOR_KEYS, L.ACTOR_SHAPES)}
+        h = L.RcPolicyActor()
+        h.struct_size = C.sizeof(L.RcPolicyActor)
+        for k, a in out.items():
+            arr = getattr(h, k)
+            arr.data = a.ctypes.data
+            arr.rows, arr.cols = (1, a.shape[0]) if a.ndim == 1 else a.shape
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_read_actor(self._h, C.byref(h)))
+        finally:
+            self._exit()
+        return out
+
+    def load_actor(self, weights) -> None:
+        """Replace the actor alone (`rc_policy_load_actor`): a mapping (or an .npz path) with `h0_w` .. `hout_b`.  The RSSM, the
+        heads, the critic and the latents stay as they are; the actor's optimizer is closed."""
+        actor = L.policy_actor(weights)
+        self._enter()
+        try:
+            L.check(self._lib.rc_policy_load_actor(self._h, C.byref(actor[0])))
+        finally:
+            self._exit()
+
     @property
     def policy_has_decoder(self) -> bool:
         """Whether the loaded checkpoint brought a LidarOccupancyDecoder (`dec_*` arrays): `policy_decode` needs one."""
@@ -1972,6 +2103,45 @@ class MixedTrackEnv:
             weights = dict(np.load(weights))
         for p in self.parts:
             p.load_reward_head(weights)
+
+    def actor_fit_begin(self) -> None:
+        """BatchedRaceEnv.actor_fit_begin on every block."""
+        for p in self.parts:
+            p.actor_fit_begin()
+
+    def actor_fit(self, features: torch.Tensor, target: Optional[torch.Tensor] = None, grad_actions: Optional[torch.Tensor] = None,
+                  eps: Optional[torch.Tensor] = None, weight: Optional[torch.Tensor] = None, grad_features: bool = False,
+                  lr: float = 8e-5, clip: float = 1.0, beta1: float = 0.9, beta2: float = 0.999,
+                  epsilon: float = 1e-7) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.actor_fit on every block with the same inputs: the step is deterministic, so the blocks' actors stay
+        byte-identical.  The status and `grad_features` are the first block's."""
+        feat, t, gfeat, gshape, status = _actor_fit_setup(self, features, target, grad_actions, eps, weight, grad_features)
+        hyper = dict(lr=lr, clip=clip, beta1=beta1, beta2=beta2, epsilon=epsilon)
+        first = self.parts[0]
+        self._fork_join(lambda p, blk: p._actor_fit(feat, t, gfeat if p is first else None, status if p is first else None, hyper))
+        out = _fit_status(status)
+        if gfeat is not None:
+            out["grad_features"] = gfeat.reshape(gshape)
+        return out
+
+    def actor_fit_end(self) -> None:
+        for p in self.parts:
+            p.actor_fit_end()
+
+    def policy_action(self, features: torch.Tensor, eps: Optional[torch.Tensor] = None, outputs=("action",)) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_action through the first block (every block holds the same actor)."""
+        return self.parts[0].policy_action(features, eps, outputs)
+
+    def actor_weights(self) -> Dict[str, np.ndarray]:
+        """The first block's actor (every block holds the same)."""
+        return self.parts[0].actor_weights()
+
+    def load_actor(self, weights) -> None:
+        """The actor on every block (BatchedRaceEnv.load_actor)."""
+        if isinstance(weights, (str, os.PathLike)):
+            weights = dict(np.load(weights))
+        for p in self.parts:
+            p.load_actor(weights)
 
     def look_ahead(self, actions: torch.Tensor, repeat: Optional[int] = None, outputs=("reward", "flags", "return", "length"),
                    out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:

@@ -151,7 +151,7 @@ struct StagedTable {
 };
 
 struct P2p;                        // the peer-copy all-gather's state (racecar_gather.hip)
-struct RcFit;                      // the critic's and the reward head's optimizers (racecar_fit.hip)
+struct RcFit;                      // the critic's, the reward head's and the actor's optimizers (racecar_fit.hip)
 struct RcDreamGrad;                // the dream's backward pass: transposed weight images and the activation stash (racecar_dream_grad.hip)
 
 struct rc_env {
@@ -236,6 +236,7 @@ struct rc_env {
 int drain_events(rc_env *env);      // folds the finished event pairs into the accumulators (racecar_abi.hip)
 int fit_release(rc_env *env);       // closes the critic's optimizers: whoever replaces or drops the critic (racecar_fit.hip)
 int fit_release_reward(rc_env *env);      // closes the reward head's optimizer: whoever replaces or drops the reward head
+int fit_release_actor(rc_env *env);       // closes the actor's optimizer: whoever replaces or drops the actor
 int dream_grad_release(rc_env *env);      // drops the transposed images and the stash: whoever replaces or drops the prior or the reward head
 int dream_grad_run(rc_env *env, RcDreamGradCall &c, int64_t chunk_rows);      // racecar_dream_grad.hip: the chunks of one rc_policy_dream_grad
 

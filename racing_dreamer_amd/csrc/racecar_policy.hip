@@ -601,6 +601,7 @@ int pol_launch(rc_env *env, hipError_t (*launch)(const Call &, hipEvent_t, hipEv
 
 // rc_policy_unload and rc_destroy; the caller has synchronised the stream
 void policy_release(rc_env *env) {
+    (void)fit_release_actor(env);        // (the optimizer holds pointers into the policy's memory)
     (void)pol_drop_heads(env);
     (void)pol_drop_decoder(env);
     (void)pol_drop_lidar_decoder(env);
@@ -648,6 +649,8 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(rck_decode_prepare());
     HIP_TRY(rck_decode_lidar_prepare());
     HIP_TRY(rck_returns_prepare());
+    rc = fit_release_actor(env);                            // new weights: the moments and the transposed images are another actor's
+    if (rc) return rc;
     rc = pol_drop_heads(env);
     if (rc) return rc;
     rc = pol_drop_decoder(env);
@@ -931,6 +934,83 @@ int rc_policy_read_heads(rc_env *env, rc_policy_heads *out) {
     const int rc = pol_check(kHeadImages, *out, "rc_policy_read_heads", "the reward head's");
     if (rc) return rc;
     return pol_unpack(kHeadImages, *out, env, env->pol_heads_mem);
+}
+
+// The actor's arrays inside rc_policy_load's image: rc_policy_actor's ten as an rc_policy_weights that holds them alone, so that
+// kPolImages' rows - the hidden layers' images, hout's mean image and its pair image - serve the actor's own entry points
+static rc_policy_weights pol_actor_as_weights(const rc_policy_actor &a) {
+    rc_policy_weights w{};
+    w.struct_size = (uint32_t)sizeof(rc_policy_weights);
+    w.h0_w = a.h0_w; w.h0_b = a.h0_b; w.h1_w = a.h1_w; w.h1_b = a.h1_b; w.h2_w = a.h2_w; w.h2_b = a.h2_b; w.h3_w = a.h3_w; w.h3_b = a.h3_b;
+    w.hout_w = a.hout_w; w.hout_b = a.hout_b;
+    return w;
+}
+
+// every one of the ten is there and has the checkpoint's shape
+static int pol_actor_check(const rc_policy_weights &w, const char *fn) {
+    for (const PolImage<PW> &im : kPolImages) {
+        if (std::strncmp(im.name, "h", 1) != 0 || !std::strncmp(im.name, "hnorm", 5)) continue;
+        const rc_policy_array &a = w.*(im.arr);
+        if (!a.data) return fail(RC_ERR_INVALID, "%s: %s is missing", fn, im.name);
+        if (a.rows != im.rows || a.cols != im.cols)
+            return fail(RC_ERR_INVALID, "%s: %s has shape [%d, %d], the actor's is [%d, %d]", fn, im.name, a.rows, a.cols, im.rows, im.cols);
+    }
+    return RC_OK;
+}
+
+// The inverse of rc_policy_load's packing for the actor's ten arrays, as rc_policy_fit's apply last left them: the hidden layers
+// from their images, hout's four columns from the pair image (the mean image holds two of them)
+int rc_policy_read_actor(rc_env *env, rc_policy_actor *out) {
+    if (!env || !out) return fail(RC_ERR_INVALID, "NULL argument");
+    if (out->struct_size != sizeof(rc_policy_actor))
+        return fail(RC_ERR_INVALID, "rc_policy_actor.struct_size %u != %zu", out->struct_size, sizeof(rc_policy_actor));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_read_actor: no policy loaded (rc_policy_load)");
+    const rc_policy_weights w = pol_actor_as_weights(*out);
+    const int rc = pol_actor_check(w, "rc_policy_read_actor");
+    if (rc) return rc;
+    constexpr size_t N = sizeof(kPolImages) / sizeof(kPolImages[0]);
+    size_t at[N], total = 0;
+    for (size_t i = 0; i < N; ++i) {                        // pol_pack's offsets: every image on a 64-float boundary
+        at[i] = total;
+        total += (kPolImages[i].floats() + 63) / 64 * 64;
+    }
+    std::vector<float> img(total);
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    HIP_TRY(hipMemcpyAsync(img.data(), env->pol_mem, total * sizeof(float), hipMemcpyDeviceToHost, env->stream));
+    HIP_TRY(hipStreamSynchronize(env->stream));
+    for (size_t i = 0; i < N; ++i) {
+        const PolImage<PW> &im = kPolImages[i];
+        float *dst = const_cast<float *>((w.*(im.arr)).data);
+        if (!dst || !im.ld || (im.gates == 1 && im.take < im.cols)) continue;          // (not the actor's; hout's mean image)
+        for (int k = 0; k < im.rows; ++k)
+            for (int g = 0; g < im.gates; ++g)
+                for (int j = 0; j < im.take; ++j) dst[(size_t)k * im.cols + g * im.group + j] = img[at[i] + ((size_t)k * im.gates + g) * im.ld + j];
+    }
+    return RC_OK;
+}
+
+int rc_policy_load_actor(rc_env *env, const rc_policy_actor *actor) {
+    if (!env || !actor) return fail(RC_ERR_INVALID, "NULL argument");
+    if (actor->struct_size != sizeof(rc_policy_actor))
+        return fail(RC_ERR_INVALID, "rc_policy_actor.struct_size %u != %zu", actor->struct_size, sizeof(rc_policy_actor));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_load_actor: no policy loaded (rc_policy_load)");
+    const rc_policy_weights w = pol_actor_as_weights(*actor);
+    int rc = pol_actor_check(w, "rc_policy_load_actor");
+    if (rc) return rc;
+    rc = fit_release_actor(env);                            // new weights: the moments and the transposed images are another actor's
+    if (rc) return rc;
+    constexpr size_t N = sizeof(kPolImages) / sizeof(kPolImages[0]);
+    std::vector<float> img;
+    size_t at[N];
+    pol_pack(kPolImages, w, img, at);                       // (the images of the arrays that are not given stay zero and are not copied)
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    for (size_t i = 0; i < N; ++i) {
+        const PolImage<PW> &im = kPolImages[i];
+        if (!(w.*(im.arr)).data || !im.ld) continue;
+        HIP_TRY(hipMemcpyAsync(env->pol_mem + at[i], img.data() + at[i], im.floats() * sizeof(float), hipMemcpyHostToDevice, env->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
+    return RC_OK;
 }
 
 int rc_policy_returns(rc_env *env, const rc_policy_returns_args *a) {

@@ -192,3 +192,47 @@ def dream_gradient_act(env, candidates: Union[int, torch.Tensor] = 8, horizon: i
     if info is not None:
         info.update({"return": best_ret[rows, best], "initial_return": first_ret, "actions": chosen})
     return action_in
+
+
+def distil_step(env, expert, slots=None, **fit) -> dict:
+    """One step of distilling a planner into the actor, on an env built with `remap_actions=True` whose
+    actor optimizer is open (`actor_fit_begin`): read every car's live feature from `policy_state` (as `policy_act` last left
+    it), ask `expert(env)` - one of the planners above, e.g. `lambda e: shooting_act(e, 64)`, or any callable that returns raw
+    actions shaped like `action_in` - for its action at the present state, put `action_in` back as it was, and take one
+    `actor_fit(features, target=the expert's actions)` step; `fit` is passed on to it (lr, clip, eps, ...).  `slots`: the car
+    slots whose rows are fitted (None: all).  Returns `actor_fit`'s status with `target` [rows, 2] and `features` [rows, 230]."""
+    E, A = env.num_envs, env.cars_per_env
+    action_in = env.views["action_in"]
+    kept = action_in.clone()
+    label = expert(env)
+    label = (action_in if label is None else label).to(action_in.device, torch.float32).reshape(E, A, 2).clone()
+    action_in.copy_(kept)
+    feat = env.policy_state[:, :230].reshape(E, A, 230)
+    if slots is not None:
+        pick = sorted({int(a) for a in slots})
+        feat, label = feat[:, pick], label[:, pick]
+    feat, label = feat.reshape(-1, 230).contiguous(), label.reshape(-1, 2).clamp(-1.0, 1.0).contiguous()
+    out = dict(env.actor_fit(feat, target=label, **fit))
+    out["target"], out["features"] = label, feat
+    return out
+
+
+def distil_actor(env, expert, iterations: int, act: str = "explore", seed: int = 0, expl_amount: Optional[float] = None,
+                 slots=None, **fit) -> torch.Tensor:
+    """DAgger on the device: `iterations` times the ACTOR drives - `policy_act` in mode `act` ("explore": its own draw plus
+    exploration noise, so that the visited latents spread; or "mean"), then `step` - and `distil_step` fits it to `expert`'s
+    action on every visited latent, before the step is taken.  The actor's optimizer must be open (`actor_fit_begin`); the
+    sampling mode is restored at the end.  Returns the per-iteration `loss` as a device tensor [iterations]."""
+    if act not in ("explore", "mean"):
+        raise ValueError(f"act must be 'explore' or 'mean', got {act!r}")
+    before = env.policy_sampling
+    env.set_policy_sampling(act, seed=seed, expl_amount=expl_amount)
+    losses = []
+    try:
+        for _ in range(int(iterations)):
+            env.policy_act(slots)
+            losses.append(distil_step(env, expert, slots=slots, **fit)["loss"])
+            env.step(None)
+    finally:
+        env.set_policy_sampling(before["mode"], seed=before["seed"], expl_amount=before["expl_amount"])
+    return torch.stack(losses) if losses else torch.zeros(0, device=env.views["action_in"].device)

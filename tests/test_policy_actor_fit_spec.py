@@ -1,0 +1,339 @@
+"""The specification of the actor's fit (tests/policy_actor_fit_spec.c) against NumPy restatements of the
+update - the plain ActionDecoder's tanh-normal action (dreamer/models.py:535-560), a loss on the action given as target actions or
+as the caller's gradient with respect to the actions, the reference's `Optimizer` (dreamer/tools.py:421-455): forward pass, analytic
+backward pass down to the features, global-norm clip and TF's Adam in float64, and the same in plain float32 (NumPy's own summation
+order) as the yardstick of what binary32 can give.  The starting weights are the austria checkpoint's own actor, the features recorded
+latents.  No GPU: the device is held to the spec bit for bit by tests/test_gpu_actor_fit.py."""
+import os
+
+import numpy as np
+import pytest
+
+from policy_actor_fit_spec import DEFAULTS, KEYS, N_GRAD, PolicyActorFitSpec
+from policy_spec import PolicySpec
+from test_golden_policy import weights
+from test_gpu_policy_device import _recorded_inputs
+
+N = 97
+CHECKPOINT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dreamer_policy_austria.npz")
+RAW_INIT_STD = float.fromhex("0x1.3f913cp+2")
+MODES = [(mode, with_eps) for mode in ("target", "grad") for with_eps in (True, False)]
+_cache = {}
+
+# spec_error <= R x float32_error per quantity, both against float64 (max |x - float64| over the array).  R = the ratio measured on
+# the CPU with these fixed inputs plus 25 %, because the measurement depends on the drawn rows (DESIGN.md §2 item 25 quotes the same
+# figures).  The arrays - each gradient array, grad_features, each weight array - are compared one by one in each of the four
+# combinations {target, grad} x {eps given, absent}, weighted rows, N = 97; R is the worst ratio over arrays and combinations:
+#   grad           x 1.33  (hout_b, four numbers; the arrays of 400 elements and more: x 0.93 - 1.22)
+#   grad_features  x 1.06
+#   weights        x 1.62  (hout_w, after one step)  and after three steps  x 1.54
+# loss and grad_norm are ONE number per combination, and the float32 restatement's single draw lands anywhere between its bound and
+# nothing (its grad_norm is off by 3.0e-9 in one combination, by 1.0e-6 in another), so for them both errors are pooled first: the
+# spec's worst over the combinations against the float32 restatement's worst:
+#   loss           x 1.36  (4.3e-8 against 3.2e-8; the two target combinations - in grad mode the loss is 0 on both sides)
+#   grad_norm      x 0.86  (9.0e-7 against 1.0e-6)
+MEASURED = {"grad": 1.33, "grad_features": 1.06, "weights": 1.62, "weights3": 1.54, "loss": 1.36, "grad_norm": 0.86}
+R = {k: 1.25 * v for k, v in MEASURED.items()}
+
+
+def _actor():
+    if "actor" not in _cache:
+        with np.load(CHECKPOINT) as z:
+            _cache["actor"] = {k: np.array(z[k], np.float32) for k in KEYS}
+    return _cache["actor"]
+
+
+def _rows(n=N):
+    """features [n, 230] of recorded latents; target actions, action gradients, standard normal draws [n, 2]; weights [n].  (The
+    trained checkpoint's standard deviations sit at their floor of 1e-4, so a full-size draw moves the action by about 1e-4 and
+    saturates nothing: test_at_most_a_quarter_of_the_rows_are_saturated.)"""
+    if "rows" not in _cache:
+        state = _recorded_inputs(263, seed=3)[1]
+        rng = np.random.default_rng(17)
+        _cache["rows"] = dict(feat=np.ascontiguousarray(state[:, :230]), target=rng.uniform(-1, 1, (263, 2)).astype(np.float32),
+                              grad=rng.normal(0, 0.01, (263, 2)).astype(np.float32), eps=rng.normal(0, 1, (263, 2)).astype(np.float32),
+                              weight=rng.uniform(0.2, 1.0, 263).astype(np.float32))
+    return {k: v[:n] for k, v in _cache["rows"].items()}
+
+
+def _inputs(mode, with_eps, n=N, weighted=True):
+    """The keyword arguments of a step in `mode` ("target" | "grad")."""
+    r = _rows(n)
+    kw = dict(eps=r["eps"] if with_eps else None, weight=r["weight"] if weighted else None)
+    kw["target" if mode == "target" else "grad_actions"] = r["target"] if mode == "target" else r["grad"]
+    return r["feat"], kw
+
+
+def _elu(x):
+    return np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
+
+
+def _forward(W, feat, eps, dt):
+    """The activations a[0..4], and a dict of the action's parts, in dtype dt."""
+    a = [feat.astype(dt)]
+    for l in range(4):
+        a.append(_elu(a[-1] @ W[f"h{l}_w"] + W[f"h{l}_b"]))
+    o = a[4] @ W["hout_w"] + W["hout_b"]
+    th = np.tanh(o[:, :2] / dt(5))
+    raw = o[:, 2:] + dt(RAW_INIT_STD)
+    sd = np.logaddexp(dt(0), raw) + dt(np.float32(1e-4))
+    mu = dt(5) * th
+    u = mu if eps is None else mu + sd * eps.astype(dt)
+    return a, dict(th=th, raw=raw, sd=sd, mu=mu, act=np.tanh(u))
+
+
+def _objective(W, feat, dt, target=None, grad_actions=None, eps=None, weight=None):
+    """What the step descends, in dtype dt: mean(w 0.5 |act - target|^2), or - the caller's gradient as a linear functional of the
+    action - sum(w grad . act), whose gradient with respect to the action is w grad."""
+    act = _forward(W, feat, eps, dt)[1]["act"]
+    w = np.ones(len(feat), dt) if weight is None else weight.astype(dt)
+    if target is not None:
+        return (w * dt(0.5) * ((act - target.astype(dt)) ** 2).sum(1)).mean(dtype=dt)
+    return (w[:, None] * grad_actions.astype(dt) * act).sum(dtype=dt)
+
+
+def _gradient(W, feat, dt, target=None, grad_actions=None, eps=None, weight=None):
+    """The analytic gradient in dtype dt: (loss as the step reports it, the ten arrays by name, grad_features)."""
+    a, f = _forward(W, feat, eps, dt)
+    w = np.ones(len(feat), dt) if weight is None else weight.astype(dt)
+    if target is not None:
+        diff = f["act"] - target.astype(dt)
+        ga = w[:, None] * diff / dt(len(feat))
+        loss = (w * dt(0.5) * (diff ** 2).sum(1)).mean(dtype=dt)
+    else:
+        ga, loss = w[:, None] * grad_actions.astype(dt), dt(0)
+    du = ga * (1 - f["act"] ** 2)
+    d_std = np.zeros_like(du) if eps is None else du * eps.astype(dt) / (1 + np.exp(-f["raw"]))
+    delta = np.concatenate([du * (1 - f["th"] ** 2), d_std], axis=1)
+    g = {"hout_w": a[4].T @ delta, "hout_b": delta.sum(0)}
+    delta = (delta @ W["hout_w"].T) * np.where(a[4] > 0, 1, a[4] + 1)
+    for l in (3, 2, 1, 0):
+        g[f"h{l}_w"], g[f"h{l}_b"] = a[l].T @ delta, delta.sum(0)
+        delta = delta @ W[f"h{l}_w"].T
+        if l:
+            delta = delta * np.where(a[l] > 0, 1, a[l] + 1)
+    return loss, {k: g[k].astype(dt) for k in KEYS}, delta.astype(dt)
+
+
+class Restatement:
+    """The update in dtype dt: clip_by_global_norm, then TF's ResourceApplyAdam."""
+
+    def __init__(self, actor, dt):
+        self.W = {k: np.asarray(actor[k]).astype(dt) for k in KEYS}
+        self.dt, self.t = dt, 0
+        self.m = {k: np.zeros_like(a) for k, a in self.W.items()}
+        self.v = {k: np.zeros_like(a) for k, a in self.W.items()}
+
+    def step(self, feat, **kw):
+        dt = self.dt
+        hp = {k: dt(np.float32(v)) for k, v in DEFAULTS.items()}
+        loss, g, gfeat = _gradient(self.W, feat, dt, **kw)
+        norm = np.sqrt(sum((a.astype(dt) ** 2).sum(dtype=dt) for a in g.values()))
+        out = dict(loss=loss, grad_norm=norm, grad=g, grad_features=gfeat)
+        scale = hp["clip"] / max(norm, hp["clip"])
+        self.t += 1
+        c1, c2 = 1 - hp["beta1"] ** self.t, 1 - hp["beta2"] ** self.t
+        for k in KEYS:
+            gk = g[k] * scale
+            self.m[k] = hp["beta1"] * self.m[k] + (1 - hp["beta1"]) * gk
+            self.v[k] = hp["beta2"] * self.v[k] + (1 - hp["beta2"]) * gk * gk
+            self.W[k] = self.W[k] - hp["lr"] * np.sqrt(c2) / c1 * self.m[k] / (np.sqrt(self.v[k]) + hp["epsilon"])
+        return out
+
+
+def _err(a, b):
+    return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))))
+
+
+def _ratios(mode, with_eps, steps=1):
+    """{quantity: (spec error, float32 error)} against float64 after `steps` steps at N = 97."""
+    key = (mode, with_eps, steps)
+    if key not in _cache:
+        feat, kw = _inputs(mode, with_eps)
+        spec, r64, r32 = PolicyActorFitSpec(_actor()), Restatement(_actor(), np.float64), Restatement(_actor(), np.float32)
+        for _ in range(steps):
+            s, d, f = spec.step(feat, **kw), r64.step(feat, **kw), r32.step(feat, **kw)
+        out = {"loss": (_err(s["loss"], d["loss"]), _err(f["loss"], d["loss"])),
+               "grad_norm": (_err(s["grad_norm"], d["grad_norm"]), _err(f["grad_norm"], d["grad_norm"])),
+               "grad_features": (_err(s["grad_features"], d["grad_features"]), _err(f["grad_features"], d["grad_features"]))}
+        for k in KEYS:
+            out["grad/" + k] = (_err(s["grad"][k], d["grad"][k]), _err(f["grad"][k], d["grad"][k]))
+            out["weights/" + k] = (_err(spec.arrays[k], r64.W[k]), _err(r32.W[k], r64.W[k]))
+        _cache[key] = out
+    return _cache[key]
+
+
+def test_the_gradient_has_575204_elements():
+    """[231][400] | 3 x [401][400] | [401][4], and the arrays of a step's gradient have the actor's shapes."""
+    spec = PolicyActorFitSpec(_actor())
+    assert spec.n_grad == N_GRAD == 231 * 400 + 3 * 401 * 400 + 401 * 4 == 575204
+    feat, kw = _inputs("target", True, 5)
+    got = spec.step(feat, **kw)
+    assert got["grad_flat"].shape == (575204,) and got["grad_features"].shape == (5, 230)
+    assert {k: a.shape for k, a in got["grad"].items()} == {k: a.shape for k, a in spec.arrays.items()}
+
+
+@pytest.mark.parametrize("mode,with_eps", MODES)
+def test_the_analytic_gradient_is_the_slope_of_the_objective(mode, with_eps):
+    """Independent of the formulas: at N = 5, central differences of the float64 objective with respect to 12 randomly chosen weights
+    of each array, and to 40 feature elements, equal the float64 analytic gradients (weights and grad_features).  This guards the
+    restatement the spec is measured against, in both loss modes, with and without eps."""
+    feat, kw = _inputs(mode, with_eps, 5)
+    W = {k: np.asarray(_actor()[k], np.float64) for k in KEYS}
+    x = feat.astype(np.float64)
+    _, g, gfeat = _gradient(W, x, np.float64, **kw)
+    rng = np.random.default_rng(4)
+    h = 1e-6
+
+    def slope(flat, i):
+        keep = flat[i]
+        flat[i] = keep + h
+        up = _objective(W, x, np.float64, **kw)
+        flat[i] = keep - h
+        dn = _objective(W, x, np.float64, **kw)
+        flat[i] = keep
+        return (up - dn) / (2 * h)
+    # the difference quotient's own noise: the objective, at most 1 in magnitude here, carries a rounding error of a few units of
+    # 2.2e-16, which the division by 2 h magnifies: 16 x 2.2e-16 / h = 3.5e-9, five orders below the largest gradient entries
+    assert abs(_objective(W, x, np.float64, **kw)) <= 1.0
+    noise = 16 * np.finfo(np.float64).eps / h
+    assert max(float(np.max(np.abs(a))) for a in g.values()) > 1e4 * noise and float(np.max(np.abs(gfeat))) > 1e4 * noise
+    for k in KEYS:
+        flat = W[k].reshape(-1)
+        for i in rng.choice(flat.size, min(12, flat.size), replace=False):
+            want = g[k].reshape(-1)[i]
+            assert abs(slope(flat, i) - want) <= 1e-6 * abs(want) + noise, (k, int(i), slope(flat, i), want)
+    flat = x.reshape(-1)
+    for i in rng.choice(flat.size, 40, replace=False):
+        want = gfeat.reshape(-1)[i]
+        assert abs(slope(flat, i) - want) <= 1e-6 * abs(want) + noise, ("features", int(i), slope(flat, i), want)
+
+
+@pytest.mark.parametrize("mode,with_eps", MODES)
+def test_one_step_is_as_close_to_float64_as_float32_can_be(mode, with_eps):
+    """Every gradient array, grad_features and the updated weights of one spec step at N = 97 on the austria checkpoint's actor and
+    recorded latents against the float64 restatement, each within R x the error of the plain float32 restatement.  R = measured
+    ratio + 25 % (above): grad 1.25 x 1.33, grad_features 1.25 x 1.06, weights 1.25 x 1.62."""
+    for k, (spec_err, f32_err) in _ratios(mode, with_eps).items():
+        print(f"actor {mode} eps={with_eps} {k}: spec {spec_err:.3e} float32 {f32_err:.3e} ratio {spec_err / max(f32_err, 1e-300):.2f}")
+        if k in ("loss", "grad_norm"):
+            continue
+        assert f32_err > 0 or spec_err == 0, k
+        assert spec_err <= R[k.split("/")[0]] * f32_err, (k, spec_err, f32_err)
+
+
+def test_loss_and_norm_are_as_close_to_float64_as_float32_can_be():
+    """The two single numbers of a step: the spec's worst error over the four combinations within R x the float32 restatement's
+    worst (R = 1.25 x 1.36 for the loss, 1.25 x 0.86 for the norm; above, why they are pooled).  In grad mode the reported loss
+    is a zero."""
+    for k in ("loss", "grad_norm"):
+        spec_err = max(_ratios(mode, e)[k][0] for mode, e in MODES)
+        f32_err = max(_ratios(mode, e)[k][1] for mode, e in MODES)
+        print(f"actor {k}: spec {spec_err:.3e} float32 {f32_err:.3e} ratio {spec_err / f32_err:.2f}")
+        assert spec_err <= R[k] * f32_err, (k, spec_err, f32_err)
+    for with_eps in (True, False):
+        assert _ratios("grad", with_eps)["loss"] == (0.0, 0.0)
+
+
+def test_the_moments_carry_over_three_steps():
+    """Three consecutive steps (the carried moments, the bias correction at t = 1, 2, 3) against the float64 restatement of TF's
+    formula, within R["weights3"] x the float32 restatement's error; the step count is 3."""
+    for mode, with_eps in (("target", True), ("grad", False)):
+        for k, (spec_err, f32_err) in _ratios(mode, with_eps, steps=3).items():
+            if k.startswith("weights/"):
+                print(f"actor {mode} {k} after 3 steps: spec {spec_err:.3e} float32 {f32_err:.3e} ratio {spec_err / max(f32_err, 1e-300):.2f}")
+                assert spec_err <= R["weights3"] * f32_err, (k, spec_err, f32_err)
+    spec = PolicyActorFitSpec(_actor())
+    feat, kw = _inputs("target", True)
+    first = spec.step(feat, **kw)
+    assert np.any(spec.m != 0) and np.array_equal(spec.m, np.float32(1.0 - np.float32(0.9)) * first["grad_flat"])
+    spec.step(feat, **kw)
+    assert spec.step(feat, **kw)["step"] == 3 and spec.step_count == 3
+
+
+def test_without_eps_the_forward_is_the_agents_mean_action():
+    """eps absent: the spec's action on the features of recorded latents equals policy_spec.c's ps_act action - what policy_act
+    writes in mode mean - byte for byte; and mean, std are those the sampled agent computes from the same outputs."""
+    scan, state, fresh = _recorded_inputs(40, seed=5)
+    action, after = PolicySpec(weights("austria")).act_packed(scan, state, fresh)
+    spec = PolicyActorFitSpec(_actor())
+    got = spec.forward(after[:, :230])
+    assert got["action"].tobytes() == np.ascontiguousarray(after[:, 230:232]).tobytes()
+    assert got["action"].tobytes() == np.ascontiguousarray(action, np.float32).reshape(-1, 2).tobytes()
+    assert np.array_equal(np.tanh(got["mean"].astype(np.float64)).astype(np.float32), got["action"]) or \
+        _err(np.tanh(got["mean"].astype(np.float64)), got["action"]) < 1e-6
+    assert np.all(got["std"] >= np.float32(1e-4)) and np.all(got["std"] < 1.0)
+    drawn = spec.forward(after[:, :230], eps=_rows(40)["eps"])
+    assert drawn["mean"].tobytes() == got["mean"].tobytes() and drawn["action"].tobytes() != got["action"].tobytes()
+
+
+def test_at_most_a_quarter_of_the_rows_are_saturated():
+    """The rows the device is compared on (tests/test_gpu_actor_fit.py draws these same rows): a row is saturated when 1 - act^2 or
+    1 - tanh(o_j / 5)^2 is zero in binary32 for either j, so that it carries no gradient.  At most a quarter are, with and without
+    eps - and not none of the rest is trivial: the gradient is not zero."""
+    spec = PolicyActorFitSpec(_actor())
+    for with_eps in (True, False):
+        r = _rows(263)
+        fwd = spec.forward(r["feat"], r["eps"] if with_eps else None)
+        out = PolicyActorFitSpec(_actor()).step(r["feat"], target=r["target"], eps=r["eps"] if with_eps else None)["out"]
+        th = np.tanh(out[:, :2].astype(np.float64) / 5).astype(np.float32)
+        dead = np.any(np.float32(1) - fwd["action"] * fwd["action"] == 0, axis=1) | np.any(np.float32(1) - th * th == 0, axis=1)
+        print(f"saturated rows (eps={with_eps}): {int(dead.sum())} of 263")
+        assert dead.mean() <= 0.25
+
+
+def test_a_saturated_row_contributes_exactly_zero():
+    """(a) A draw that pushes tanh(u) to +-1: in grad mode (no 1 / N) the step on 96 rows plus that row, appended, has the gradient
+    of the 96 rows bit for bit - the row's contribution to every element is +0 - and its grad_features row is all +0.  (b) Output
+    biases that push tanh(o_j / 5) to +-1 with eps absent: every element of the gradient is +0, the norm is 0, the step counts and
+    no weight moves."""
+    r = _rows(97)
+    eps = r["eps"].copy()
+    eps[96] = (1e6, -1e6)                                  # (std is about 1e-4: u = mu +- 100)
+    whole = PolicyActorFitSpec(_actor()).step(r["feat"], grad_actions=r["grad"], eps=eps, weight=r["weight"])
+    part = PolicyActorFitSpec(_actor()).step(r["feat"][:96], grad_actions=r["grad"][:96], eps=eps[:96], weight=r["weight"][:96])
+    assert whole["grad_flat"].tobytes() == part["grad_flat"].tobytes() and part["grad_norm"] > 0
+    assert whole["grad_features"][96].tobytes() == np.zeros(230, np.float32).tobytes()
+    assert whole["grad_features"][:96].tobytes() == part["grad_features"].tobytes()
+    shifted = dict(_actor())
+    shifted["hout_b"] = shifted["hout_b"] + np.array([1000.0, -1000.0, 0.0, 0.0], np.float32)
+    spec = PolicyActorFitSpec(shifted)
+    got = spec.step(r["feat"], target=r["target"], weight=r["weight"])
+    assert np.all(np.abs(got["out"][:, :2]) > 46)
+    assert got["grad_flat"].tobytes() == np.zeros(N_GRAD, np.float32).tobytes()
+    assert got["grad_norm"] == 0 and got["skipped"] == 0 and got["step"] == 1 and got["loss"] > 0
+    assert all(spec.arrays[k].tobytes() == shifted[k].tobytes() for k in KEYS)
+
+
+def test_a_nan_target_skips_the_step():
+    """One NaN target (and one NaN action gradient): skipped = 1, and weights, moments and the step count are byte for byte what
+    they were - after a good step, so that the moments are not zero."""
+    feat, kw = _inputs("target", True)
+    spec = PolicyActorFitSpec(_actor())
+    assert spec.step(feat, **kw)["skipped"] == 0 and spec.step_count == 1
+
+    def held():
+        return {k: a.tobytes() for k, a in spec.arrays.items()}, spec.m.tobytes(), spec.v.tobytes(), spec.opt.b1pow, spec.opt.b2pow
+    before = held()
+    bad = kw["target"].copy()
+    bad[13, 1] = np.nan
+    got = spec.step(feat, **{**kw, "target": bad})
+    assert got["skipped"] == 1 and got["step"] == 1 and spec.step_count == 1 and not np.isfinite(got["grad_norm"])
+    assert before == held()
+    _, kg = _inputs("grad", True)
+    badg = kg["grad_actions"].copy()
+    badg[5, 0] = np.nan
+    assert spec.step(feat, **{**kg, "grad_actions": badg})["skipped"] == 1 and before == held()
+    assert spec.step(feat, **kw)["step"] == 2
+
+
+def test_ten_steps_lower_the_loss():
+    """Ten target-mode steps on 97 fixed rows at lr = 1e-3: the loss after the tenth is below the first, and the mode actions have
+    moved towards the targets."""
+    feat, kw = _inputs("target", False, weighted=False)
+    spec = PolicyActorFitSpec(_actor())
+    losses = [spec.step(feat, lr=1e-3, **kw)["loss"] for _ in range(10)]
+    print("actor loss over ten steps:", [float(x) for x in losses])
+    assert losses[-1] < losses[0] and all(np.isfinite(losses))
+    gap0 = np.abs(PolicyActorFitSpec(_actor()).forward(feat)["action"] - kw["target"]).mean()
+    assert np.abs(spec.forward(feat)["action"] - kw["target"]).mean() < gap0

@@ -45,7 +45,11 @@ torch does it - torch autograd, clip_grad_norm_, Adam.step and the load_critic u
 condition: device step <= 1.0 x that, reported as met or missed; and, a record without a threshold, the same torch step without the
 upload.  All three are wall-clock times per iteration over a window of iterations that ends with a synchronisation.  Then the reward
 head's step (reward_fit, the same engine at two hidden layers, 665 200 multiply-adds per row against 1 145 200) beside critic_fit of
-the same run, and - a record - the torch step on the reward head's layers (profiles/reward_fit_cost.json).  `--device-only` leaves
+the same run, and - a record - the torch step on the reward head's layers (profiles/reward_fit_cost.json).  Then the actor's step
+(actor_fit, the engine at four hidden layers: 1 630 404 multiply-adds per row against the value step's 1 146 401, both with the bias
+rows) beside critic_fit of the same run under the condition actor_fit <= 1.422 x critic_fit x 1.05, and - records - the step with
+grad_features, the forward alone (policy_action) and a plain fp32 torch step on the actor's layers
+(profiles/actor_fit_cost.json).  `--device-only` leaves
 the torch steps out and `--root DIR` imports the package from another checkout: the two halves of an A/B against a parent build.
 
 One process.  Device times are RC_K_POLICY events (the dispatch's own start / stop timestamps) after a warm-up, the median over
@@ -455,6 +459,11 @@ def measure_returns(n, args):
 
 MACS_FIT_ROW = (230 * 400 + 2 * 400 * 400 + 400) * 2 + 2 * 400 * 400 + 400      # forward + weight gradients + backward data: 1 145 200
 MACS_REWARD_FIT_ROW = (230 * 400 + 400 * 400 + 400) * 2 + 400 * 400 + 400       # the same at two hidden layers: 665 200 (x 0.58)
+# the actor's step beside the value head's, counted with the bias rows: forward + backward data + weight gradient
+MACS_VALUE_STEP_ROW = 412400 + 320400 + 413601
+MACS_ACTOR_STEP_ROW = 573600 + 481600 + 575204                                  # x 1.422
+MACS_ACTOR_GRAD_FEATURES_ROW = 230 * 400                                        # delta1 W0^T: + 92 000
+ACTOR_SPREAD_ALLOWANCE = 1.05                                                   # policy_returns' condition used the same margin
 
 
 def measure_fit(rows, args):
@@ -553,6 +562,37 @@ def measure_fit(rows, args):
                 ms, windows = wall(torch_reward_step, args.calls)
                 res["torch_reward_step_without_upload"] = {"ms_per_iteration": round(ms, 4), "windows_ms": windows}
                 res["reward_fit"]["over_torch_without_upload"] = round(res["reward_fit"]["ms_per_iteration"] / ms, 4)
+        if hasattr(env, "actor_fit"):
+            # the actor's step (the engine at four hidden layers) beside critic_fit of the same run: target mode, no grad_features;
+            # then - records - the step with grad_features, the forward alone and a plain fp32 torch step on the same layers
+            actions = (torch.rand((rows, 2), generator=gen) * 2.0 - 1.0).to(env.device)
+            env.actor_fit_begin()
+            res["actor_fit"] = device(lambda: env.actor_fit(feat, target=actions), MACS_ACTOR_STEP_ROW)
+            res["actor_fit_grad_features"] = device(lambda: env.actor_fit(feat, target=actions, grad_features=True),
+                                                    MACS_ACTOR_STEP_ROW + MACS_ACTOR_GRAD_FEATURES_ROW)
+            env.actor_fit_end()
+            res["actor_forward"] = device(lambda: env.policy_action(feat), 573600)
+            ratio = MACS_ACTOR_STEP_ROW / MACS_VALUE_STEP_ROW
+            ms, base = res["actor_fit"]["ms_per_iteration"], res["critic_fit"]["ms_per_iteration"]
+            res["actor_fit"].update(macs_over_critic_fit=round(ratio, 4), over_critic_fit=round(ms / base, 4),
+                                    bound_ms=round(ratio * base * ACTOR_SPREAD_ALLOWANCE, 4), met=bool(ms <= ratio * base * ACTOR_SPREAD_ALLOWANCE))
+            if not args.device_only:
+                actor = {k: torch.from_numpy(np.array(weights[k])).to(env.device).requires_grad_(True) for k in L.ACTOR_KEYS}
+                actor_opt = torch.optim.Adam(list(actor.values()), lr=8e-5)
+
+                def torch_actor_step():
+                    x = feat
+                    for i in range(4):
+                        x = torch.nn.functional.elu(torch.addmm(actor[f"h{i}_b"], x, actor[f"h{i}_w"]))
+                    out = torch.addmm(actor["hout_b"], x, actor["hout_w"])
+                    loss = (0.5 * ((torch.tanh(5.0 * torch.tanh(out[:, :2] / 5.0)) - actions) ** 2).sum(1)).mean()
+                    actor_opt.zero_grad()
+                    loss.backward()
+                    torch.nn.utils.clip_grad_norm_(list(actor.values()), 1.0)
+                    actor_opt.step()
+                ms_t, windows = wall(torch_actor_step, args.calls)
+                res["torch_actor_step_without_upload"] = {"ms_per_iteration": round(ms_t, 4), "windows_ms": windows}
+                res["actor_fit"]["over_torch_without_upload"] = round(ms / ms_t, 4)
     if not args.device_only:
         ms, base = res["critic_fit"]["ms_per_iteration"], res["torch_step_with_load_critic_upload"]["ms_per_iteration"]
         res["critic_fit"].update(over_torch_with_upload=round(ms / base, 4), met=bool(ms <= base),
@@ -890,6 +930,11 @@ def main():
                "condition": "critic_fit ms_per_iteration <= 1.0 x torch_step_with_load_critic_upload ms_per_iteration of the same run, at every size",
                "sizes": [measure_fit(n, args) for n in sizes]}
         out["condition_met"] = None if args.device_only else all(s["critic_fit"]["met"] for s in out["sizes"])
+        if all("actor_fit" in s for s in out["sizes"]):
+            out["macs_per_row_value_step"], out["macs_per_row_actor_step"] = MACS_VALUE_STEP_ROW, MACS_ACTOR_STEP_ROW
+            out["actor_condition"] = ("actor_fit ms_per_iteration <= (macs_per_row_actor_step / macs_per_row_value_step = 1.422) x critic_fit "
+                                      f"ms_per_iteration of the same run x {ACTOR_SPREAD_ALLOWANCE}, at every size")
+            out["actor_condition_met"] = all(s["actor_fit"]["met"] for s in out["sizes"])
         print(json.dumps(out))
         if args.out:
             with open(args.out, "w") as f:
