@@ -5,7 +5,9 @@ tests/test_gpu_policy_edges.py runs the device beside it.  Recipes only multiply
 subnormals) or assign special values.
 
 Units: act (modes mean / deploy / explore), imagine, observe, dream, dream_grad, returns (modes mean / sample), value, fit (heads
-value / pcont), decode (with its log-likelihood), decode_lidar (with its log-likelihood).  `cases(unit)` names a unit's cases,
+value / pcont), decode (with its log-likelihood), decode_lidar (with its log-likelihood), reward_fit (the fit engine at two hidden
+layers), actor_fit (at four; modes target / grad, eps and weights given), action (the actor's forward alone; modes mean - no eps - and
+draw).  `cases(unit)` names a unit's cases,
 `make(unit, case)` builds one, `spec(unit, call, mode)` is the spec's answer as {output: float32 array}."""
 import functools
 from fractions import Fraction
@@ -16,7 +18,9 @@ f32 = np.float32
 N, ROW = 33, 17                                # one workgroup and one row; the poisoned row
 UNITS = {"act": ("mean", "deploy", "explore"), "imagine": ("mean", "sample"), "observe": ("mean", "sample"), "dream": ("mean", "sample"),
          "dream_grad": ("mean", "sample"), "returns": ("mean", "sample"), "value": ("mean",), "fit": ("value", "pcont"),
-         "decode": ("mean",), "decode_lidar": ("mean",)}
+         "decode": ("mean",), "decode_lidar": ("mean",), "reward_fit": ("reward",), "actor_fit": ("target", "grad"), "action": ("mean", "draw")}
+FIT_UNITS = ("fit", "reward_fit", "actor_fit")     # the units that take optimizer steps: status, weights, moments
+PRIVATE = ("m", "v", "out", "grad_hout_w", "grad_hout_b")      # what the spec's answer holds for the guards alone: the device does not offer it
 SEED = 77
 
 
@@ -205,10 +209,13 @@ def _base():
     from test_golden_policy import weights
     from test_gpu_dream_ahead import _actions, _latents
     from test_gpu_policy_device import _recorded_inputs
+    from test_policy_actor_fit_spec import _rows as _actor_rows
     from test_policy_fit_spec import _rows
+    from test_policy_reward_fit_spec import _rows as _reward_rows
     scan, state, fresh = _recorded_inputs(2 * N, seed=3)
     feat, targets, weight = _rows(64)
-    return dict(policy=_arrays(weights("austria")), occ=_arrays(weights("treitlstrasse_occupancy")), critic=_arrays(init_critic(5)),
+    return dict(reward_rows=_reward_rows(64), actor_rows=_actor_rows(64),
+                policy=_arrays(weights("austria")), occ=_arrays(weights("treitlstrasse_occupancy")), critic=_arrays(init_critic(5)),
                 ldec=_arrays(init_lidar_decoder(11, -3.0)), scan=scan, state=state, fresh=fresh, latents=_latents(64), actions=_actions(64, 2, 4),
                 feat=feat, targets=targets, weight=weight,
                 image=(np.random.default_rng(5).integers(0, 2, (N, 64, 64))).astype(np.uint8),
@@ -355,17 +362,28 @@ def _inputs(unit, rows=N, horizon=2):
         return dict(features=b["feat"][:rows].copy(), target=b["image"][:rows].copy())
     if unit == "decode_lidar":
         return dict(features=b["feat"][:rows].copy(), target=b["scan"][:rows].copy())
+    if unit == "reward_fit":                       # (the rows of tests/test_policy_reward_fit_spec.py)
+        feat, target, weight = b["reward_rows"]
+        return dict(features=feat[:rows].copy(), target={"reward": target[:rows].copy()}, weight=weight[:rows].copy(), steps=1, hyper={})
+    if unit in ("actor_fit", "action"):            # (the rows of tests/test_policy_actor_fit_spec.py)
+        r = b["actor_rows"]
+        if unit == "action":
+            return dict(features=r["feat"][:rows].copy(), eps=r["eps"][:rows].copy())
+        return dict(features=r["feat"][:rows].copy(), target=r["target"][:rows].copy(), grad_actions=r["grad"][:rows].copy(), eps=r["eps"][:rows].copy(),
+                    weight=r["weight"][:rows].copy(), steps=1, hyper={})
     raise KeyError(unit)
 
 
 LATENT = {"act": "state", "imagine": "state", "observe": "state", "dream": "state", "dream_grad": "state", "returns": "state", "value": "features",
-          "fit": "features", "decode": "features", "decode_lidar": "features"}
+          "fit": "features", "decode": "features", "decode_lidar": "features", "reward_fit": "features", "actor_fit": "features", "action": "features"}
 FIRST = {"act": ("policy", "img1"), "imagine": ("policy", "img1"), "observe": ("policy", "img1"), "dream": ("policy", "img1"),
          "dream_grad": ("policy", "img1"), "returns": ("critic", "value_h0"), "value": ("critic", "value_h0"), "fit": ("critic", "value_h0"),
-         "decode": ("policy", "dec_h1"), "decode_lidar": ("ldec", "ldec_dense1")}
+         "decode": ("policy", "dec_h1"), "decode_lidar": ("ldec", "ldec_dense1"), "reward_fit": ("policy", "reward_h0"),
+         "actor_fit": ("policy", "h0"), "action": ("policy", "h0")}
 OUTPUT_LAYERS = {"act": ("policy", (ACTOR_OUT,)), "imagine": ("policy", (REWARD_OUT, ACTOR_OUT)), "observe": ("policy", (REWARD_OUT,)),
                  "dream": ("policy", (REWARD_OUT,)), "dream_grad": ("policy", (REWARD_OUT,)), "decode": ("policy", (OCC_OUT,)),
-                 "decode_lidar": ("ldec", (LDEC_OUT,))}
+                 "decode_lidar": ("ldec", (LDEC_OUT,)), "reward_fit": ("policy", (REWARD_OUT,)), "actor_fit": ("policy", (ACTOR_OUT,)),
+                 "action": ("policy", (ACTOR_OUT,))}
 
 
 def _weights(unit, **edits):
@@ -381,6 +399,15 @@ def _weights(unit, **edits):
 
 def cases(unit):
     """The names of a unit's cases (the table in tests/test_gpu_policy_edges.py says why the others do not apply)."""
+    if unit == "reward_fit":                       # the fit unit's, but E2: the likelihood is Normal
+        return ["A-zero-layer", "A-negzero-inputs", "B1", "B2", "B3", "B4", "B4-one-row", "C1", "C2", "D3", "D4-target+inf", "D4-target-inf",
+                "D4-weight0", "D4-weight-1", "D4-weight-inf", "F"]
+    if unit == "actor_fit":
+        return ["A-zero-layer", "A-negzero-inputs", "A-no-eps", "B1", "B2", "B1g", "B2g", "B3", "B4", "B4-one-row", "C1", "C2", "D3",
+                "D4-target+inf", "D4-target-inf", "D4-weight0+inf-target", "D4-weight-1", "D4-weight-inf", "D5-eps+inf", "D5-eps-inf", "D5-eps-nan",
+                "D6-grad-inf", "E2+", "E2-", "E4+", "E4-", "E5-on-target", "F"]
+    if unit == "action":
+        return ["A-zero-layer", "A-negzero-inputs", "B1", "B2", "B4", "D3", "D5-eps+inf", "D5-eps-inf", "D5-eps-nan", "E2+", "E2-", "E4+", "E4-"]
     names = ["A-zero-layer", "A-negzero-inputs", "B1", "B2", "D3"]
     if unit in ("value", "fit", "decode", "decode_lidar"):
         names.append("B4")
@@ -407,7 +434,123 @@ def cases(unit):
     return names
 
 
+def _stale_first(unit):
+    """Case F's first call for the heads that came after the critic: on ANOTHER head of the same handle, 64 rows, features x 2^127 and
+    NaN targets (the fit unit's poison) - an actor step before a reward step, a value-head step before an actor step."""
+    big = _inputs("actor_fit" if unit == "reward_fit" else "fit", 64)
+    big["features"] = scaled(big["features"], 127)
+    if unit == "reward_fit":
+        big["target"] = np.full((64, 2), np.nan, f32)
+    else:
+        big["target"] = {h: np.full(64, np.nan, f32) for h in big["target"]}
+    return Call(rows=64, **big)
+
+
+def _flat_negzeros(a, step=5):
+    """A copy with every `step`-th element -0.0, counted over the flattened array."""
+    out = np.array(a, f32)
+    out.reshape(-1)[::step] = f32(-0.0)
+    return out
+
+
+def _hout_b(lo, hi, v):
+    return {"hout_b": lambda a: a.__setitem__(slice(lo, hi), v)}
+
+
+def _make_actor(unit, case):
+    """The cases of actor_fit and action: the actor is the checkpoint's own (Call.policy's h0_w .. hout_b)."""
+    kw = _inputs(unit)
+    fit = unit == "actor_fit"
+    expect, guard = EXPECT.get((unit, case), {}), GUARDS.get((unit, case))
+    if case == "A-zero-layer":
+        return Call(policy=policy(assign={"h0_w": 0.0, "h0_b": -0.0}), expect=expect, guard=guard, **kw)
+    if case == "A-negzero-inputs":
+        keys = ("features", "target", "grad_actions", "eps") if fit else ("features", "eps")
+        clean = {k: kw[k].copy() for k in keys}
+        kw["features"] = negzeros(kw["features"])
+        for k in keys[1:]:
+            kw[k] = _flat_negzeros(kw[k])
+        plus = {k: np.where(negzero(kw[k]), f32(0.0), kw[k]) for k in keys}
+        return Call(guard=_guard_resolved(unit, clean, plus), **kw)
+    if case == "A-no-eps":
+        kw["eps"] = None
+        return Call(guard=guard, **kw)
+    if case in ("B1", "B2"):
+        return Call(policy=policy(scale=_both((ACTOR_OUT,), -135 if case == "B1" else -120)), expect=expect, **kw)
+    if case in ("B1g", "B2g"):
+        kw["grad_actions"] = scaled(kw["grad_actions"], -135 if case == "B1g" else -120)
+        return Call(expect=expect, **kw)
+    if case == "B3":
+        kw.update(steps=3, hyper=dict(epsilon=float(2.0 ** -80)), weight=scaled(kw["weight"], -60))
+        return Call(expect=expect, **kw)
+    if case in ("B4", "B4-one-row"):
+        rows = 1 if case == "B4-one-row" else N
+        kw = _inputs(unit, rows)
+        kw["features"] = scaled(kw["features"], -130)
+        return Call(policy=policy(assign={"h0_b": 0.0}), expect=expect, guard=guard, rows=rows, **kw)
+    if case == "C1":
+        # grad: the caller's gradient x 2^100 - every delta and every gradient element is 2^100 times the ordinary one, finite, and its
+        # square overflows.  target: targets x 2^100 do the same through act - target (and take the loss to +inf)
+        kw["grad_actions"], kw["target"] = scaled(kw["grad_actions"], 100), scaled(kw["target"], 100)
+        return Call(expect=expect, **kw)
+    if case == "C2":
+        return Call(policy=policy(scale={"h1_w": 100, "h2_w": 100}), expect=expect, guard=guard, **kw)
+    if case == "D3":
+        clean = Call(**kw)
+        bad = dict(kw, features=poisoned(kw["features"]))
+        return Call(clean=clean, expect=expect, guard=guard or (lambda out, call, mode: _guard_poison(out, call, mode, unit)), **bad)
+    if case.startswith("D4"):
+        what = case[3:]
+        if what.startswith("target"):
+            kw["target"][ROW] = np.inf if what == "target+inf" else -np.inf
+        elif what == "weight0+inf-target":         # (grad mode takes no target: there the row's action gradient is infinite)
+            kw["weight"][ROW], kw["target"][ROW], kw["grad_actions"][ROW] = 0.0, np.inf, np.inf
+        else:
+            clean = kw["weight"].copy()
+            kw["weight"][ROW] = {"weight-1": -1.0, "weight-inf": np.inf}[what]
+            guard = None if expect else _guard_differs(unit, dict(weight=clean))
+        return Call(expect=expect, guard=guard, **kw)
+    if case.startswith("D5"):
+        clean = Call(**kw)
+        kw["eps"] = kw["eps"].copy()
+        kw["eps"][ROW] = {"eps+inf": np.inf, "eps-inf": -np.inf, "eps-nan": np.nan}[case[3:]]
+        return Call(clean=None if fit else clean, expect=expect, guard=_guard_eps(unit, clean), **kw)
+    if case == "D6-grad-inf":
+        kw["grad_actions"][ROW, 1] = np.inf
+        return Call(expect=expect, **kw)
+    if case in ("E2+", "E2-"):
+        return Call(policy=policy(assign=_hout_b(2, 4, 100.0 if case == "E2+" else -100.0)), expect=expect, guard=guard, **kw)
+    if case in ("E4+", "E4-"):                     # |o| = 1000: tanh(o / 5) is +-1 exactly (beyond |x| = 9.1)
+        return Call(policy=policy(assign=_hout_b(0, 2, 1000.0 if case == "E4+" else -1000.0)), expect=expect, guard=guard, **kw)
+    if case == "E5-on-target":
+        from policy_actor_fit_spec import PolicyActorFitSpec
+        kw["target"] = PolicyActorFitSpec(_base()["policy"]).forward(kw["features"], kw["eps"])["action"]
+        return Call(guard=guard, **kw)
+    if case == "F":
+        return Call(guard=_guard_stale_heads(unit), first=_stale_first(unit), **kw)
+    raise KeyError((unit, case))
+
+
 def make(unit, case):
+    """One case of a unit as a Call.  Case F of the fit units and the scratch the four heads share - [2 depth][rows][416] | the output
+    delta [rows][nout] | the loss terms [rows], planes at multiples of rows x 416 floats, so the plane offsets depend on the depth AND
+    the row count of the call:
+      fit (depth 3 after depth 3, the note at its branch below): the 33-row call's six planes [0, 82 368) overlie the 64-row call's a1,
+        a2, a3 and the head of delta1.
+      reward_fit (depth 2, 33 rows, after an actor step of 64 rows): the actor's eight planes of 26 624 floats are a1 .. a4 [0, 106 496),
+        delta1 .. delta4 [106 496, 212 992), then its output deltas [64][4] and loss terms to 213 312.  The reward call's four planes of
+        13 728 floats [0, 54 912), its output deltas [54 912, 54 945) and its loss terms [54 945, 54 978) overlie the actor's a1, a2 and
+        the head of a3 - +inf and expm1(-86) from the overflowed layers - and are rewritten in full but for the padding columns; all of the
+        actor's NaN delta planes lie past the reward call's end, where a row or plane index that ran over would read.
+      actor_fit (depth 4, 33 rows, after a value-head step of 64 rows): the value head's six planes are a1, a2, a3 [0, 79 872) and
+        delta1, delta2, delta3 [79 872, 159 744), then its output deltas and loss terms to 159 872.  The actor's eight planes [0, 109 824)
+        overlie a1, a2, a3, delta1 and the head of delta2: its own delta planes (from 54 912) start inside the value head's a3, its
+        output deltas [109 824, 109 956) and loss terms [109 956, 109 989) lie in the value head's NaN delta2.  Stale past its end: the
+        rest of delta2, delta3, the output deltas.
+    The scratch is not reallocated by the smaller call (it needs fewer floats: 54 978 < 213 312, 109 989 < 159 872) and both heads'
+    optimizers stay open, so it is not freed in between."""
+    if unit in ("actor_fit", "action"):
+        return _make_actor(unit, case)
     kw = _inputs(unit)
     lat = LATENT[unit]
     if case == "A-zero-layer":
@@ -450,6 +593,13 @@ def make(unit, case):
     if case == "B3":
         kw.update(steps=3, hyper=dict(epsilon=float(2.0 ** -80)), weight=scaled(kw["weight"], -60))
         return Call(expect=EXPECT.get((unit, case), {}), **kw)
+    if case == "C1" and unit == "reward_fit":
+        # the last hidden layer x 2^40: a2, the output and its delta are 2^40 times the trained ones, the output layer's gradient a2^T delta
+        # 2^80 times: finite, and every square overflows
+        return Call(policy=policy(scale={"reward_h1_w": 40}), expect=EXPECT.get((unit, case), {}), **kw)
+    if case == "C2" and unit == "reward_fit":
+        # both hidden layers x 2^100: a1 is 2^100 times the trained one, a2 +inf wherever its sum is positive, the output inf - inf
+        return Call(policy=policy(scale={"reward_h0_w": 100, "reward_h1_w": 100}), expect=EXPECT.get((unit, case), {}), **kw)
     if case == "C1":
         return Call(critic=critic(scale={"value_h1_w": 40, "pcont_h1_w": 40}), expect=EXPECT.get((unit, case), {}), **kw)
     if case == "C2":
@@ -488,7 +638,7 @@ def make(unit, case):
         zero = clean.copy()
         zero[ROW] = 0.0
         return Call(guard=_guard_resolved(unit, dict(scan=clean), dict(scan=zero)), **kw)
-    if case == "D3" and unit == "fit":
+    if case == "D3" and unit in ("fit", "reward_fit"):
         kw[lat] = poisoned(kw[lat])
         return Call(expect=EXPECT.get((unit, case), {}), **kw)
     if case == "D3":
@@ -530,6 +680,8 @@ def make(unit, case):
         if case == "E3-far":
             far(p["obs2_b"])
         return Call(policy=p, expect=EXPECT.get((unit, case), {}), guard=GUARDS.get((unit, case)), **kw)
+    if case == "F" and unit == "reward_fit":       # (the docstring above: an actor step of 64 rows before it)
+        return Call(guard=_guard_stale_heads(unit), first=_stale_first(unit), **kw)
     if case == "F":
         # a 64-row call that leaves non-finite values in everything the handle keeps, then the clean 33-row call on the same handle
         big = _inputs(unit, 64, horizon=4 if unit == "dream_grad" else 2)
@@ -655,7 +807,146 @@ def _guard_kl_same(out, call, mode):
     assert np.all(np.abs(out["kl"]) < 1e-5)
 
 
-GUARDS = {("returns", "A-zero-layer"): _guard_rows_identical, ("value", "A-zero-layer"): _guard_rows_identical,
+def _forward(call, eps="given"):
+    """The actor's forward under the call's weights: on its eps, or on another (None: the mode action)."""
+    from policy_actor_fit_spec import PolicyActorFitSpec
+    return PolicyActorFitSpec(call.policy).forward(call.kw["features"], call.kw["eps"] if isinstance(eps, str) else eps)
+
+
+def _loaded(unit, call):
+    """The arrays the unit's optimizer owns, as the call loads them."""
+    from policy_actor_fit_spec import KEYS as ACTOR_KEYS
+    from policy_reward_fit_spec import KEYS as REWARD_KEYS
+    if unit == "fit":
+        return dict(call.critic)
+    return {k: call.policy[k] for k in (REWARD_KEYS if unit == "reward_fit" else ACTOR_KEYS)}
+
+
+def _guard_step_taken(unit):
+    """A zero first layer: a1 = ELU(-0) = +0 for every row, the next bias takes over - a step is taken, its norm an ordinary number.
+    The first kernel starts from zero, so after Adam's first step each element is -lr g / (|g| + epsilon): within lr of zero, and
+    not all zero."""
+    def guard(out, call, mode):
+        from policy_actor_fit_spec import DEFAULTS as ACTOR
+        from policy_reward_fit_spec import DEFAULTS as REWARD
+        lr = (REWARD if unit == "reward_fit" else ACTOR)["lr"]
+        w = out[FIRST[unit][1] + "_w"]
+        assert out["step"] == 1 and out["skipped"] == 0 and 1e-3 < out["grad_norm"] < 1e3, (out["step"], out["grad_norm"])
+        assert np.all(np.abs(w) <= 1.01 * lr) and int((w != 0).sum()) >= w.size // 2, (float(np.abs(w).max()), int((w != 0).sum()))
+    return guard
+
+
+def _guard_no_eps(out, call, mode):
+    """eps absent: d_std is never computed - the raw-std columns of the output layer's gradient are +0 by bit pattern, and so are
+    their moments after the step; the mean columns' are not."""
+    gw, gb = out["grad_hout_w"], out["grad_hout_b"]
+    m, v = (out[k][-401 * 4:].reshape(401, 4) for k in ("m", "v"))
+    assert not bits(gw[:, 2:]).any() and not bits(gb[2:]).any() and not bits(m[:, 2:]).any() and not bits(v[:, 2:]).any()
+    assert out["step"] == 1 and np.all(gw[:, :2] != 0) and np.all(m[:, :2] != 0)
+
+
+def _guard_forward_finite(out, call, mode):
+    """Hidden layers that overflow: the action, the mean and the standard deviation are still numbers (an ELU takes a NaN and -inf to
+    expm1(-86), tanh takes +-inf and NaN to +-1)."""
+    fwd = _forward(call)
+    assert all(np.isfinite(a).all() for a in fwd.values()) and out["skipped"] == 1
+
+
+def _guard_actor_poison(out, call, mode):
+    """A NaN feature row: the norm is NaN through feat^T delta1 and the step is skipped, but the row's own grad_features are 230 zeros -
+    the ELU takes the NaN to expm1(-86) = -1 in every unit of a1 and elu'(a1) = a1 + 1 = 0 - and the other rows' are the clean twin's."""
+    clean = spec("actor_fit", call.clean, mode)
+    assert np.isnan(out["grad_norm"]) and out["skipped"] == 1 and clean["skipped"] == 0
+    assert np.all(out["grad_features"][ROW] == 0) and np.all(clean["grad_features"][ROW] != 0)
+    assert same(np.delete(out["grad_features"], ROW, axis=0), np.delete(clean["grad_features"], ROW, axis=0))
+
+
+def _guard_eps(unit, clean):
+    """An infinite or NaN draw in row ROW: u = fmaf(sd, eps, mu) is +-inf or NaN and tanh makes the action +-1 exactly (a NaN: the
+    clamped end, under the NaN's sign).  The forward shows that and nothing else; the fit has du = ga 0 = 0 and d_std = (0 eps) sigma =
+    NaN, so the norm is NaN and the step skipped, under a finite loss - which for +-inf is not the clean one."""
+    def guard(out, call, mode):
+        base = spec(unit, clean, mode)
+        if unit == "action":
+            assert np.all(np.abs(out["action"][ROW]) == 1.0) and not same(out["action"][ROW], base["action"][ROW])
+            assert same(out["mean"], base["mean"]) and same(out["std"], base["std"])
+            assert same(np.delete(out["action"], ROW, axis=0), np.delete(base["action"], ROW, axis=0))
+            return
+        assert np.all(np.abs(_forward(call)["action"][ROW]) == 1.0)
+        assert np.isnan(out["grad_norm"]) and out["skipped"] == 1 and base["skipped"] == 0 and np.isfinite(out["loss"])
+        if mode == "target" and not np.isnan(call.kw["eps"][ROW]).any():
+            assert not same(out["loss"], base["loss"])
+    return guard
+
+
+def _guard_actor_fit_std(unit, sign):
+    def guard(out, call, mode):
+        fwd = out if unit == "action" else _forward(call)
+        if sign > 0:       # the trained raw outputs lie in [-77, -14] on these rows: sd = softplus(100 + 4.99 + o) is 28 .. 91, and
+            #                tanh(mu + sd n), |mu| <= 5, is +-1 exactly beyond |u| = 9.1: for every |n| > 0.5
+            assert np.all(fwd["std"] > 20.0)
+            if call.kw["eps"] is not None and mode != "mean":
+                assert int((np.abs(fwd["action"]) == 1.0).sum()) >= fwd["action"].size // 2
+        else:              # sd = exp(-86) + 1e-4 = 1e-4 exactly: softplus has saturated, a bias of -200 gives the same bytes
+            lower = Call(policy=_edit(call.policy, assign=_hout_b(2, 4, -200.0)), **call.kw)
+            low = spec(unit, lower, mode) if unit == "action" else _forward(lower)
+            assert np.all(fwd["std"] == f32(1e-4)) and all(same(fwd[k], low[k]) for k in ("action", "mean", "std"))
+            assert not same(fwd["std"], (spec(unit, Call(**call.kw), mode) if unit == "action" else _forward(Call(**call.kw)))["std"])
+        if unit == "actor_fit":
+            assert out["skipped"] == 0 and out["step"] == 1
+    return guard
+
+
+def _guard_actor_mean_saturated(unit):
+    def guard(out, call, mode):
+        if unit == "action":                       # 5 tanh(+-200) = +-5 exactly
+            assert np.all(np.abs(out["mean"]) == 5.0)
+            return
+        # d_mean = du (1 - th th) = du 0 for every row: the mean columns of the output layer's gradient are zeros, the raw-std columns
+        # (eps is given) are not, and a step is taken
+        assert np.all(np.abs(out["out"][:, :2]) > 46.0)
+        assert not np.any(out["grad_hout_w"][:, :2]) and not np.any(out["grad_hout_b"][:2]) and np.all(out["grad_hout_b"][2:] != 0)
+        assert out["skipped"] == 0 and out["step"] == 1 and out["grad_norm"] > 0
+    return guard
+
+
+def _guard_on_target(out, call, mode):
+    """The targets are the actions themselves: every act - target is +0, the loss a zero (minus the mean of -0 terms summed from +0:
+    its sign is compared with the device's), the gradient and its norm +0; the step counts and moves no weight."""
+    assert not bits(out["grad_norm"]).any() and out["loss"] == 0 and out["skipped"] == 0 and out["step"] == 1
+    assert not np.any(out["grad_features"]) and not bits(out["m"]).any() and not bits(out["v"]).any()
+    assert all(same(out[k], a) for k, a in _loaded("actor_fit", call).items())
+
+
+def _guard_stale_heads(unit):
+    """Case F behind another head: the first call's spec answer - the actor's step before a reward step, the value head's before an
+    actor step - is skipped on a non-finite norm and its first layer overflows to +inf in at least 2000 of the 25 600 pre-activations;
+    the second call's answer is finite throughout."""
+    def guard(out, call, mode):
+        fk = call.kw["first"].kw
+        with np.errstate(all="ignore"):
+            if unit == "reward_fit":
+                from policy_actor_fit_spec import PolicyActorFitSpec
+                got = PolicyActorFitSpec(call.policy).step(fk["features"], target=fk["target"], eps=fk["eps"], weight=fk["weight"])
+                pre = fk["features"] @ call.policy["h0_w"] + call.policy["h0_b"]
+            else:
+                from policy_fit_spec import PolicyFitSpec
+                got = PolicyFitSpec(call.critic, "value").step(fk["features"], fk["target"]["value"], fk["weight"])
+                pre = fk["features"] @ call.critic["value_h0_w"] + call.critic["value_h0_b"]
+        assert got["skipped"] == 1 and not np.isfinite(got["grad_norm"])
+        assert int(np.isposinf(pre).sum()) >= 2000, int(np.isposinf(pre).sum())
+        assert all(np.isfinite(a).all() for a in out.values())
+    return guard
+
+
+GUARDS = {("reward_fit", "A-zero-layer"): _guard_step_taken("reward_fit"), ("actor_fit", "A-zero-layer"): _guard_step_taken("actor_fit"),
+          ("actor_fit", "A-no-eps"): _guard_no_eps, ("actor_fit", "C2"): _guard_forward_finite, ("actor_fit", "D3"): _guard_actor_poison,
+          ("actor_fit", "E2+"): _guard_actor_fit_std("actor_fit", 1), ("actor_fit", "E2-"): _guard_actor_fit_std("actor_fit", -1),
+          ("action", "E2+"): _guard_actor_fit_std("action", 1), ("action", "E2-"): _guard_actor_fit_std("action", -1),
+          ("actor_fit", "E4+"): _guard_actor_mean_saturated("actor_fit"), ("actor_fit", "E4-"): _guard_actor_mean_saturated("actor_fit"),
+          ("action", "E4+"): _guard_actor_mean_saturated("action"), ("action", "E4-"): _guard_actor_mean_saturated("action"),
+          ("actor_fit", "E5-on-target"): _guard_on_target, ("action", "B4"): _guard_rows_identical, ("action", "A-zero-layer"): _guard_rows_identical,
+          ("returns", "A-zero-layer"): _guard_rows_identical, ("value", "A-zero-layer"): _guard_rows_identical,
           ("decode", "A-zero-layer"): _guard_rows_identical, ("decode_lidar", "A-zero-layer"): _guard_rows_identical,
           ("fit", "A-zero-layer"): _guard_fit_zero_layer, ("decode", "B4"): _guard_rows_identical,
           ("act", "E2+"): _guard_actor_std(1), ("act", "E2-"): _guard_actor_std(-1),
@@ -668,7 +959,10 @@ GUARDS = {("returns", "A-zero-layer"): _guard_rows_identical, ("value", "A-zero-
 NOT_APPLICABLE = {("act", "E2+", "mean"), ("act", "E2-", "mean"), ("fit", "E2+", "value"), ("fit", "E2-", "value"), ("fit", "C1", "pcont"),
                   ("act", "B1", "deploy"), ("act", "B1", "explore"), ("act", "B2", "deploy"), ("act", "B2", "explore"), ("dream", "B2"),
                   ("act", "A-zero-layer"), ("imagine", "A-zero-layer"), ("observe", "A-zero-layer"), ("dream", "A-zero-layer"),
-                  ("dream_grad", "A-zero-layer")}
+                  ("dream_grad", "A-zero-layer"),
+                  ("actor_fit", "B1g", "target"), ("actor_fit", "B2g", "target"), ("actor_fit", "D6-grad-inf", "target"),
+                  ("actor_fit", "D4-target+inf", "grad"), ("actor_fit", "D4-target-inf", "grad"), ("actor_fit", "E5-on-target", "grad"),
+                  ("action", "D5-eps+inf", "mean"), ("action", "D5-eps-inf", "mean"), ("action", "D5-eps-nan", "mean")}
 
 
 def _guard_grad_at_the_clamp(grad, actions):
@@ -768,6 +1062,27 @@ def spec(unit, call, mode):
         out = {k: np.array(a, f32) for k, a in fit.weights().items()}
         out.update(loss=f32(got["loss"]), grad_norm=f32(got["grad_norm"]), skipped=f32(got["skipped"]), step=f32(got["step"]), m=fit.m.copy(), v=fit.v.copy())
         return out
+    if unit == "reward_fit":                       # (case F's first call is the actor's and skipped: it moves nothing of the reward head's)
+        from policy_reward_fit_spec import PolicyRewardFitSpec
+        fit = PolicyRewardFitSpec(call.policy)
+        for _ in range(kw["steps"]):
+            got = fit.step(kw["features"], kw["target"]["reward"], kw["weight"], **kw["hyper"])
+        out = {k: np.array(a, f32) for k, a in fit.weights().items()}
+        out.update(loss=f32(got["loss"]), grad_norm=f32(got["grad_norm"]), skipped=f32(got["skipped"]), step=f32(got["step"]), m=fit.m.copy(), v=fit.v.copy())
+        return out
+    if unit == "actor_fit":                        # (case F's first call is the value head's)
+        from policy_actor_fit_spec import PolicyActorFitSpec
+        fit = PolicyActorFitSpec(call.policy)
+        given = {("target" if mode == "target" else "grad_actions"): kw["target" if mode == "target" else "grad_actions"]}
+        for _ in range(kw["steps"]):
+            got = fit.step(kw["features"], eps=kw["eps"], weight=kw["weight"], **given, **kw["hyper"])
+        out = {k: np.array(a, f32) for k, a in fit.weights().items()}
+        out.update(loss=f32(got["loss"]), grad_norm=f32(got["grad_norm"]), skipped=f32(got["skipped"]), step=f32(got["step"]), m=fit.m.copy(), v=fit.v.copy(),
+                   grad_features=got["grad_features"], out=got["out"], grad_hout_w=got["grad"]["hout_w"], grad_hout_b=got["grad"]["hout_b"])
+        return out
+    if unit == "action":
+        from policy_actor_fit_spec import PolicyActorFitSpec
+        return PolicyActorFitSpec(call.policy).forward(kw["features"], kw["eps"] if mode == "draw" else None)
     if unit == "decode":
         import policy_decode_loglik_spec as pdl
         from policy_decode_spec import PolicyDecodeSpec
@@ -861,3 +1176,47 @@ EXPECT.update({("act", "C3-inf"): {m: _ROLL("state", 1) for m in UNITS["act"]},
                ("dream", "C3-inf"): {m: _ROLL("final_feature", 2) for m in UNITS["dream"]},
                ("dream_grad", "C3-inf"): {m: [("grad_actions", "nan", 23), ("grad_state", "nan", 1840)] for m in UNITS["dream_grad"]},
                ("returns", "C3-inf"): {m: _ROLL("features", 2) for m in UNITS["returns"]}})
+# the fit engine's other heads and the actor's forward: as above, from the spec on the CPU at 33 rows; where a case runs in two modes a
+# floor is the smaller of the two counts ("zero" counts +0 by bit pattern: a norm, a skipped flag, every second moment)
+_NAN_NORM = [("grad_norm", "nan", 1)]
+_BOTH = lambda entries: {"target": list(entries), "grad": list(entries)}
+EXPECT.update({
+    ("reward_fit", "B1"): {"reward": [("m", "sub", 155057)]},
+    ("reward_fit", "B2"): {"reward": [("m", "sub", 252782)]},
+    ("reward_fit", "B3"): {"reward": [("v", "sub", 234749)]},
+    ("reward_fit", "B4"): {"reward": [("m", "sub", 236051)]},
+    ("reward_fit", "B4-one-row"): {"reward": [("m", "sub", 236291)]},
+    ("reward_fit", "C1"): {"reward": [("grad_norm", "inf", 1)]},
+    ("reward_fit", "C2"): {"reward": [("loss", "nan", 1)] + _NAN_NORM},
+    ("reward_fit", "D3"): {"reward": _NAN_NORM},
+    ("reward_fit", "D4-target+inf"): {"reward": [("loss", "inf", 1)] + _NAN_NORM},
+    ("reward_fit", "D4-target-inf"): {"reward": [("loss", "inf", 1)] + _NAN_NORM},
+    ("reward_fit", "D4-weight-inf"): {"reward": [("loss", "inf", 1)] + _NAN_NORM},
+    ("actor_fit", "B1"): _BOTH([("m", "sub", 332060), ("grad_features", "sub", 1494), ("grad_features", "negzero", 35)]),
+    ("actor_fit", "B2"): _BOTH([("m", "sub", 567853), ("grad_features", "sub", 6595)]),
+    ("actor_fit", "B1g"): {"grad": [("grad_norm", "zero", 1), ("skipped", "zero", 1), ("v", "zero", 575204), ("m", "sub", 107024),
+                                    ("grad_features", "sub", 694), ("grad_features", "negzero", 59)]},
+    ("actor_fit", "B2g"): {"grad": [("grad_norm", "zero", 1), ("skipped", "zero", 1), ("v", "zero", 575204), ("m", "sub", 563787),
+                                    ("grad_features", "sub", 6347), ("grad_features", "negzero", 10)]},
+    ("actor_fit", "B3"): _BOTH([("v", "sub", 37609)]),
+    ("actor_fit", "B4"): _BOTH([("m", "sub", 251190)]),
+    ("actor_fit", "B4-one-row"): _BOTH([("m", "sub", 210470)]),
+    ("actor_fit", "C1"): {"target": [("loss", "inf", 1), ("grad_norm", "inf", 1)], "grad": [("grad_norm", "inf", 1)]},
+    ("actor_fit", "C2"): _BOTH(_NAN_NORM),
+    ("actor_fit", "D3"): _BOTH(_NAN_NORM),
+    ("actor_fit", "D4-target+inf"): {"target": [("loss", "inf", 1), ("grad_features", "nan", 230)] + _NAN_NORM},
+    ("actor_fit", "D4-target-inf"): {"target": [("loss", "inf", 1), ("grad_features", "nan", 230)] + _NAN_NORM},
+    ("actor_fit", "D4-weight0+inf-target"): {"target": [("loss", "nan", 1), ("grad_features", "nan", 230)] + _NAN_NORM,
+                                             "grad": [("grad_features", "nan", 230)] + _NAN_NORM},
+    ("actor_fit", "D4-weight-inf"): {"target": [("loss", "inf", 1), ("grad_features", "nan", 230)] + _NAN_NORM,
+                                     "grad": [("grad_features", "nan", 230)] + _NAN_NORM},
+    ("actor_fit", "D5-eps+inf"): _BOTH([("grad_features", "nan", 230)] + _NAN_NORM),
+    ("actor_fit", "D5-eps-inf"): _BOTH([("grad_features", "nan", 230)] + _NAN_NORM),
+    ("actor_fit", "D5-eps-nan"): _BOTH([("grad_features", "nan", 230)] + _NAN_NORM),
+    ("actor_fit", "D6-grad-inf"): {"grad": [("grad_features", "nan", 230)] + _NAN_NORM},
+    ("actor_fit", "E2+"): _BOTH([("v", "sub", 286)]),
+    ("actor_fit", "E2-"): _BOTH([("m", "sub", 802)]),
+    ("actor_fit", "E4+"): _BOTH([("v", "sub", 27333)]),
+    ("actor_fit", "E4-"): _BOTH([("v", "sub", 30223)]),
+    ("action", "B1"): {"mean": [("action", "sub", 66), ("mean", "sub", 66)], "draw": [("mean", "sub", 66)]},
+    ("action", "B2"): {"mean": [("action", "sub", 1), ("mean", "sub", 1)], "draw": [("mean", "sub", 1)]}})

@@ -206,7 +206,7 @@ def test_a_fit_changes_nothing_else():
 
 
 def test_neutral_and_edge_rows():
-    """Rows of weight zero contribute nothing, whatever their targets; a NaN target or action gradient skips the step and changes no
+    """Rows of weight zero contribute nothing, whatever their finite targets (0 inf is NaN: tests/test_gpu_policy_edges.py); a NaN target or action gradient skips the step and changes no
     weight; a fully saturated batch (draws that push tanh to +-1) gives norm 0 and leaves the weights as they are."""
     feat, kw = _inputs("target", True, 97)
     env = _env()

@@ -88,6 +88,32 @@ def test_three_steps_are_the_specs_three_steps():
     env.close()
 
 
+@pytest.mark.gpu_slow          # (the spec's step on 32 769 rows takes 13 s on the CPU, the device's milliseconds: `pytest -m gpu_slow`)
+def test_the_loss_sum_takes_a_second_term_per_lane():
+    """rc_policy_fit_sums_kernel adds the N loss terms by lanes 32 768 apart (128 workgroups of 256): up to N = 32 768 every lane
+    has at most one term, at N = 32 769 lane 0 of workgroup 0 takes a second one - the loop's second pass over the loss terms, which
+    no other test reaches.  One reward-head step at that N: the recorded latents tiled, each row scaled by its own factor in
+    [0.5, 1.5], fresh targets and weights; the last row's target is 40, so its loss term (0.5 w (o - 40)^2, several hundred among
+    terms below 10) moves the mean by one part in a hundred and not by a few ulps.  loss, grad_norm, step and the six arrays equal
+    the spec - whose sum is pfs_tree, the same tree on the host - byte for byte."""
+    n = 32 * 1024 + 1
+    feat, _, _ = _rows(263)
+    rng = np.random.default_rng(23)
+    big = np.ascontiguousarray(feat[np.arange(n) % 263] * rng.uniform(0.5, 1.5, (n, 1)).astype(np.float32))
+    target, weight = rng.normal(0.1, 0.5, n).astype(np.float32), rng.uniform(0.2, 1.0, n).astype(np.float32)
+    target[-1] = 40.0
+    spec = PolicyRewardFitSpec(_head())
+    want = spec.step(big, target, weight)
+    assert want["step"] == 1 and want["skipped"] == 0 and want["loss"] > 0.63
+    env = _env(critic=False)
+    env.reward_fit_begin()
+    got = _fit(env, big, target, weight)
+    print(n, got)
+    _same_status(got, want, n)
+    _same_weights(env, spec, n)
+    env.close()
+
+
 def _readers(env, scan, rec, acts):
     """Every call that reads the reward head, on the env's live latents (and a recorded window)."""
     import torch

@@ -37,6 +37,23 @@ def test_every_unit_has_its_cases():
         assert call.expect.get(mode) or call.guard, p.id
 
 
+@pytest.mark.parametrize("unit", ["reward_fit", "actor_fit", "action"])
+def test_a_guard_fails_on_the_unedited_call(unit):
+    """The other half of a guard, for the fit engine's later units: on the spec's answer to the unit's UNEDITED inputs and weights -
+    an ordinary answer - every case's guard fails.  (Case F keeps a first call, but a clean one of the same 64 rows.)"""
+    for case in pe.cases(unit):
+        for mode in pe.UNITS[unit]:
+            if not pe.applies(unit, case, mode):
+                continue
+            call, kw = pe.make(unit, case), pe._inputs(unit)
+            if case == "F":
+                kw["first"] = pe.Call(rows=64, **pe._inputs("actor_fit" if unit == "reward_fit" else "fit", 64))
+            plain = pe.Call(expect=call.expect, guard=call.guard, clean=call.clean, **kw)
+            with pytest.raises(AssertionError):
+                pe.check_guard(unit, case, plain, pe.spec(unit, plain, mode), mode)
+                print("passes on the unedited call:", unit, case, mode)
+
+
 def test_the_comparison_rule():
     nan2 = np.array([0x7fc00000, 0xffc00001], np.uint32).view(f32)
     assert pe.same(nan2, nan2[::-1].copy())                                                  # a NaN's sign and payload are not compared
