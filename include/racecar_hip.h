@@ -578,6 +578,62 @@ typedef struct rc_policy_returns_args {
  * rc_policy_returns_sampled_kernel, timed under RC_K_POLICY. */
 int rc_policy_returns(rc_env *env, const rc_policy_returns_args *args);
 
+/* The actor loss's gradient through the dream: the joint between rc_policy_returns, rc_policy_dream_grad and
+ * rc_policy_actor_fit_step (the reference's actor_loss, dreamer/models.py:113-128; DESIGN.md §2 item 26;
+ * tests/policy_returns_grad_spec.c is the CPU restatement, the device equals it bit for bit).  The forward is rc_policy_returns'
+ * rollout - both modes, live latents or state_in, closed loop or under actions_in, the same draws and keys - and every forward output
+ * it offers comes out byte for byte as rc_policy_returns gives it.  The objective of a row is
+ *   J = sum over t < H - 1 of (scale * weight[t]) * returns[t]
+ * with weight a constant (the reference's stop_gradient(cumprod)) and returns differentiated through reward, value and pcont (p is
+ * the constant `discount`, without a gradient, where no pcont head is loaded); with scale = -1 / (rows * (H - 1)) the sum of J over
+ * the rows is the reference's actor_loss.  The backward pass carries J's cotangent through the three heads and the prior step
+ * (RSSM.img_step) for t = H - 1 .. 0, with respect to their inputs only.  The actor is NOT differentiated: the reference feeds it
+ * stop_gradient(feat) (models.py:218-219), so its weights see the loss only through the action that enters img_step at each step -
+ * what leaves here is that cotangent, with the actor's input and draw, as the rows rc_policy_actor_fit_step(grad_actions) takes.
+ * Outputs, each optional, at least one of grad_actions and grad_state:
+ *   grad_actions   [rows, H, 2]    dJ / d a_t, a_t the action that enters step t; under actions_in it is with respect to the raw
+ *                                  action: exactly +0 where it lies outside [-1, 1] (bounds inclusive, as rc_policy_dream_grad)
+ *   actor_features [rows, H, 230]  the feature the actor read for a_t: the start feature at t = 0, features[t - 1] after (stoch | deter)
+ *   eps            [rows, H, 2]    the two normals of a_t's draw (block 8, words 0-1); mode SAMPLE in closed loop only
+ *   grad_state     [rows, 230]     dJ / d (stoch | deter) of the start
+ * A reward head and a value head must be loaded.  The activations of the forward are kept in a scratch the handle owns (4 648
+ * floats per row and step, at most 1 GiB, grown on demand, released with the weights); the rows are cut into chunks of chunk_rows
+ * (0: as many as the scratch's limit holds), one launch per chunk - the results do not depend on the chunking, the grid or the
+ * shard.  No atomics and no reduction across rows.  A pure function of its inputs otherwise, as rc_policy_returns. */
+typedef struct rc_policy_returns_grad_args {
+    uint32_t struct_size;          /* = sizeof(rc_policy_returns_grad_args) */
+    int32_t horizon;               /* H in [2, RC_POLICY_IMAGINE_MAX_HORIZON] */
+    int32_t mode;                  /* RC_POLICY_IMAGINE_* */
+    uint32_t slot_mask;            /* live latents: bit a = slot a, as rc_policy_act's; with state_in: 0 */
+    float lambda_;                 /* in [0, 1] */
+    float discount;                /* in [0, 1]: the constant pcont when no pcont head is loaded */
+    float scale;                   /* finite; the actor loss: -1 / (rows * (H - 1)) */
+    uint32_t reserved;             /* 0 */
+    uint64_t seed;
+    int64_t starts;                /* with state_in: its rows, in [1, 2^31); live latents: 0 */
+    uint64_t row_offset;           /* with state_in: the id of row 0 (mode SAMPLE) */
+    int64_t chunk_rows;            /* rows per launch, rounded up to a multiple of 32; 0: derived from the scratch's limit */
+    const float *state_in;         /* device float32 [starts, 232], or NULL: the live latents */
+    const float *actions_in;       /* device float32 [rows, H, 2] raw (clamped), or NULL: the actor's own actions */
+    float *reward, *value, *pcont; /* device float32 [rows, H], or NULL: as rc_policy_returns' */
+    float *returns, *weight;       /* device float32 [rows, H - 1], or NULL */
+    float *actions;                /* device float32 [rows, H, 2], or NULL */
+    float *features;               /* device float32 [rows, H, 230], or NULL */
+    float *reward_start, *value_start, *pcont_start;      /* device float32 [rows], or NULL */
+    float *grad_actions;           /* device float32 [rows, H, 2], or NULL */
+    float *actor_features;         /* device float32 [rows, H, 230], or NULL */
+    float *eps;                    /* device float32 [rows, H, 2], or NULL */
+    float *grad_state;             /* device float32 [rows, 230], or NULL */
+} rc_policy_returns_grad_args;
+/* rc_policy_returns_grad: one launch per chunk on the handle's stream.  RC_ERR_INVALID: wrong struct_size, no policy loaded, the
+ * policy loaded without img2 / img3, no reward head, no value head, pcont_start without a pcont head, horizon outside [2, 64],
+ * unknown mode, lambda_ or discount not finite or outside [0, 1], scale not finite, chunk_rows < 0, neither grad_actions nor
+ * grad_state asked for, eps in mode MEAN or together with actions_in, state_in together with a non-zero mask or starts outside
+ * [1, 2^31), starts != 0 with state_in NULL, live latents with an empty mask or bits beyond cars_per_env; nothing is launched on a
+ * refusal.  Kernels: rc_policy_returns_grad_kernel, rc_policy_returns_grad_sampled_kernel (and, at the first call after a head was
+ * loaded or fitted, rc_policy_dream_grad_transpose_kernel for its transposed images), timed under RC_K_POLICY. */
+int rc_policy_returns_grad(rc_env *env, const rc_policy_returns_grad_args *args);
+
 /* Fitting the critic on the device: the reference's value update (dreamer/models.py:129-137: value_loss = -mean(weight *
  * value(feat).log_prob(stop_gradient(returns))) under value_opt, which owns the value head's eight arrays alone; dreamer/tools.py:421-455
  * `Optimizer`: clip_by_global_norm, then Adam) - one MLP's forward pass, backward pass, global-norm clip and Adam on tensors that

@@ -158,6 +158,23 @@ class RcPolicyReturnsArgs(C.Structure):
                 ("value_start", C.c_void_p), ("pcont_start", C.c_void_p)]
 
 
+# policy_returns_grad's output names: policy_returns' and the four of the backward pass
+RETURNS_GRAD_OUTPUTS = dict(RETURNS_OUTPUTS, grad_actions=("grad_actions", lambda H: (H, 2)),
+                            actor_features=("actor_features", lambda H: (H, POLICY_FEATURE)), eps=("eps", lambda H: (H, 2)),
+                            grad_state=("grad_state", lambda H: (POLICY_FEATURE,)))
+
+
+class RcPolicyReturnsGradArgs(C.Structure):
+    """rc_policy_returns_grad_args (include/racecar_hip.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("horizon", C.c_int32), ("mode", C.c_int32), ("slot_mask", C.c_uint32), ("lambda_", C.c_float),
+                ("discount", C.c_float), ("scale", C.c_float), ("reserved", C.c_uint32), ("seed", C.c_uint64), ("starts", C.c_int64),
+                ("row_offset", C.c_uint64), ("chunk_rows", C.c_int64), ("state_in", C.c_void_p), ("actions_in", C.c_void_p),
+                ("reward", C.c_void_p), ("value", C.c_void_p), ("pcont", C.c_void_p), ("returns", C.c_void_p), ("weight", C.c_void_p),
+                ("actions", C.c_void_p), ("features", C.c_void_p), ("reward_start", C.c_void_p), ("value_start", C.c_void_p),
+                ("pcont_start", C.c_void_p), ("grad_actions", C.c_void_p), ("actor_features", C.c_void_p), ("eps", C.c_void_p),
+                ("grad_state", C.c_void_p)]
+
+
 FIT_HEADS = {"value": 0, "pcont": 1}                            # RC_POLICY_FIT_*: the critic's (critic_fit)
 FIT_REWARD = 2                                                  # RC_POLICY_FIT_REWARD: the reward head's own (reward_fit)
 HEAD_SHAPES = ((230, 400), (400,), (400, 400), (400,), (400, 1), (1,))      # of HEAD_KEYS
@@ -406,6 +423,7 @@ SYMBOLS = {
     "rc_policy_dream_grad": (C.c_int, [C.c_void_p, _P(RcPolicyDreamGradArgs)]),
     "rc_policy_load_critic": (C.c_int, [C.c_void_p, _P(RcPolicyCritic)]),
     "rc_policy_returns": (C.c_int, [C.c_void_p, _P(RcPolicyReturnsArgs)]),
+    "rc_policy_returns_grad": (C.c_int, [C.c_void_p, _P(RcPolicyReturnsGradArgs)]),
     "rc_policy_fit_begin": (C.c_int, [C.c_void_p, _P(RcPolicyFitConfig)]),
     "rc_policy_fit_step": (C.c_int, [C.c_void_p, _P(RcPolicyFitArgs)]),
     "rc_policy_fit_end": (C.c_int, [C.c_void_p, C.c_int32]),

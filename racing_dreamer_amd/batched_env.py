@@ -199,12 +199,14 @@ def _chunk_rows(chunk_rows) -> int:
     return n
 
 
-def _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, row_offset, slots, outputs, out):
-    """policy_returns' arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv): (scalar args, the tensors by
-    rc_policy_returns_args field - one row per start -, the dict to return).  What only the library can tell (no policy, a missing
-    head, slots with a state, a horizon too short for the outputs) is left to it, which names it."""
+def _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, row_offset, slots, outputs, out, table=None, what="policy_returns"):
+    """policy_returns' arguments and tensors (shared by BatchedRaceEnv and MixedTrackEnv, and by policy_returns_grad with its own
+    `table` of outputs): (scalar args, the tensors by rc_policy_returns_args field - one row per start -, the dict to return).  What
+    only the library can tell (no policy, a missing head, slots with a state, a horizon too short for the outputs) is left to it,
+    which names it."""
+    table = L.RETURNS_OUTPUTS if table is None else table
     if mode not in L.IMAGINE_MODES:
-        raise ValueError(f"policy_returns mode must be one of {sorted(L.IMAGINE_MODES)}, got {mode!r}")
+        raise ValueError(f"{what} mode must be one of {sorted(L.IMAGINE_MODES)}, got {mode!r}")
     H, S = int(horizon), env.n_cars
     if not 0 <= H <= L.IMAGINE_MAX_HORIZON:
         raise ValueError(f"horizon must be in [0, {L.IMAGINE_MAX_HORIZON}], got {horizon}")
@@ -216,11 +218,11 @@ def _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, 
     if not 0.0 <= lambda_ <= 1.0 or not 0.0 <= discount <= 1.0:
         raise ValueError(f"lambda_ and discount must be in [0, 1], got {lambda_} and {discount}")
     names = tuple(outputs)
-    unknown = [n for n in names if n not in L.RETURNS_OUTPUTS]
+    unknown = [n for n in names if n not in table]
     if unknown:
-        raise ValueError(f"policy_returns outputs must be among {sorted(L.RETURNS_OUTPUTS)}, got {unknown}")
+        raise ValueError(f"{what} outputs must be among {sorted(table)}, got {unknown}")
     tensors, result = {"state_in": None, "actions_in": None}, {}
-    tensors.update({field: None for field, _ in L.RETURNS_OUTPUTS.values()})
+    tensors.update({field: None for field, _ in table.values()})
     if actions is not None and H > 0:
         tensors["actions_in"] = actions.to(env.device, torch.float32).reshape(S, H, 2).contiguous()
     if state is not None:
@@ -229,7 +231,7 @@ def _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, 
     else:
         mask = (1 << env.cars_per_env) - 1 if slots is None else sum({1 << int(b) for b in slots})
     for name in names:
-        field, tail = L.RETURNS_OUTPUTS[name]
+        field, tail = table[name]
         shape = (S,) + tuple(max(d, 0) for d in tail(H))
         t = None if out is None else out.get(name)
         if t is None:
@@ -239,6 +241,19 @@ def _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, 
         tensors[field] = result[name] = t
     args = dict(horizon=H, mode=L.IMAGINE_MODES[mode], mask=mask, lambda_=lambda_, discount=discount, seed=int(seed) & (2 ** 64 - 1),
                 starts=S, row_offset=int(row_offset) & (2 ** 64 - 1), live=state is None)
+    return args, tensors, result
+
+
+def _returns_grad_setup(env, horizon, mode, seed, lambda_, discount, scale, actions, state, row_offset, slots, outputs, out, chunk_rows):
+    """policy_returns_grad's arguments and tensors, as `_returns_setup`'s, with the scale (None: float32(-1 / (rows (H - 1))), rows
+    = the starts of the call: `state`'s rows, or the cars of `slots`) and the chunk."""
+    args, tensors, result = _returns_setup(env, horizon, mode, seed, lambda_, discount, actions, state, row_offset, slots, outputs, out,
+                                           L.RETURNS_GRAD_OUTPUTS, "policy_returns_grad")
+    if args["horizon"] < 2:
+        raise ValueError(f"horizon must be in [2, {L.IMAGINE_MAX_HORIZON}], got {horizon}")
+    rows = args["starts"] if state is not None else env.num_envs * bin(args["mask"]).count("1")
+    args["scale"] = float(np.float32(-1.0 / (max(rows, 1) * (args["horizon"] - 1)))) if scale is None else float(np.float32(scale))
+    args["chunk_rows"] = _chunk_rows(chunk_rows)
     return args, tensors, result
 
 
@@ -1044,6 +1059,38 @@ class BatchedRaceEnv:
         self._enter()
         try:
             L.check(self._returns(args, tensors, 0, self.n_cars))
+        finally:
+            self._exit()                 # a refused call still orders torch's stream after the env's
+        return result
+
+    def _returns_grad(self, args: dict, tensors: dict, lo: int, hi: int) -> int:
+        """rc_policy_returns_grad on this handle: rows as `_returns` takes them."""
+        a = L.RcPolicyReturnsGradArgs(C.sizeof(L.RcPolicyReturnsGradArgs), args["horizon"], args["mode"], args["mask"], args["lambda_"],
+                                      args["discount"], args["scale"], 0, args["seed"], args["starts"] if not args["live"] else 0,
+                                      args["row_offset"], args["chunk_rows"])
+        for field, t in tensors.items():
+            setattr(a, field, None if t is None else (t[lo:hi] if args["live"] else t).data_ptr())
+        return self._lib.rc_policy_returns_grad(self._h, C.byref(a))
+
+    def policy_returns_grad(self, horizon: int = 15, mode: str = "sample", seed: int = 0, lambda_: float = 0.95, discount: float = 0.99,
+                            scale: Optional[float] = None, actions: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                            row_offset: int = 0, slots=None, outputs=("grad_actions", "actor_features", "eps"),
+                            out: Optional[Dict[str, torch.Tensor]] = None, chunk_rows: int = 0) -> Dict[str, torch.Tensor]:
+        """The gradient of the reference's actor loss through the dream (`rc_policy_returns_grad`; dreamer/models.py:113-128):
+        `policy_returns`' rollout with the same arguments, draws and bytes, then the backward pass of J = sum_t (scale weight[t])
+        returns[t] per row - weight a constant, returns differentiated through the reward, value and pcont heads and the prior step.
+        `scale` None is float32(-1 / (rows (H - 1))): the sum of J over the rows is then the reference's actor_loss.  The actor is
+        not differentiated (the reference feeds it stop_gradient(feat)); `outputs` are the rows `actor_fit(grad_actions=...)` takes:
+        `grad_actions` [S, H, 2] (dJ / d a_t; under `actions` exactly +0 where the raw action lies outside [-1, 1]), `actor_features`
+        [S, H, 230] (what the actor read for a_t), `eps` [S, H, 2] (its draw's normals: mode "sample", closed loop), and `grad_state`
+        [S, 230]; every output of `policy_returns` may be asked for beside them and is byte for byte what it returns.  At least one
+        of `grad_actions` and `grad_state`; H >= 2; a reward head and a value head must be loaded.  `chunk_rows` as
+        `dream_ahead_grad`'s.  Nothing else changes: not the agent's state, not `action_in`, not a weight."""
+        args, tensors, result = _returns_grad_setup(self, horizon, mode, seed, lambda_, discount, scale, actions, state, row_offset, slots,
+                                                    outputs, out, chunk_rows)
+        self._enter()
+        try:
+            L.check(self._returns_grad(args, tensors, 0, self.n_cars))
         finally:
             self._exit()                 # a refused call still orders torch's stream after the env's
         return result
@@ -2044,6 +2091,21 @@ class MixedTrackEnv:
             self._ordered(lambda: self.parts[0]._returns(args, tensors, 0, 0))
         else:
             self._fork_join(lambda p, blk: p._returns(args, tensors, blk[0] * k, blk[1] * k))
+        return result
+
+    def policy_returns_grad(self, horizon: int = 15, mode: str = "sample", seed: int = 0, lambda_: float = 0.95, discount: float = 0.99,
+                            scale: Optional[float] = None, actions: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None,
+                            row_offset: int = 0, slots=None, outputs=("grad_actions", "actor_features", "eps"),
+                            out: Optional[Dict[str, torch.Tensor]] = None, chunk_rows: int = 0) -> Dict[str, torch.Tensor]:
+        """BatchedRaceEnv.policy_returns_grad over all blocks, forwarded the way `policy_returns` is (the default `scale` counts the
+        rows of all blocks)."""
+        args, tensors, result = _returns_grad_setup(self, horizon, mode, seed, lambda_, discount, scale, actions, state, row_offset, slots,
+                                                    outputs, out, chunk_rows)
+        k = self.cars_per_env
+        if state is not None:
+            self._ordered(lambda: self.parts[0]._returns_grad(args, tensors, 0, 0))
+        else:
+            self._fork_join(lambda p, blk: p._returns_grad(args, tensors, blk[0] * k, blk[1] * k))
         return result
 
     def policy_value(self, features: Optional[torch.Tensor] = None, slots=None, outputs=("value",)) -> Dict[str, torch.Tensor]:

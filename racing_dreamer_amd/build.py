@@ -12,8 +12,8 @@ LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libracecar_hip.so")
 # one unit per subsystem ("where things live"); SCAN_SOURCE holds the scan kernels that verify_scan_assembly reads
 SCAN_SOURCE = "racecar_kernels.hip"
-SOURCES = [SCAN_SOURCE, "racecar_tracks.hip", "racecar_agents.hip", "racecar_gather.hip", "racecar_abi.hip", "racecar_policy.hip", "racecar_imagine.hip", "racecar_dream.hip", "racecar_dream_grad.hip", "racecar_returns.hip", "racecar_fit.hip", "racecar_observe.hip", "racecar_decode.hip", "racecar_decode_lidar.hip", "racecar_episode.hip", "racecar_lookahead.hip"]
-HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_env.h", "racecar_car.h", "racecar_step.h", "racecar_substep.inc", "racecar_spec.h", "racecar_scan.h", "racecar_beam_pairs.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", "racecar_policy_tiles.h", "racecar_rollout.h", "racecar_episode.h", os.path.join("..", "..", "include", "racecar_hip.h")]
+SOURCES = [SCAN_SOURCE, "racecar_tracks.hip", "racecar_agents.hip", "racecar_gather.hip", "racecar_abi.hip", "racecar_policy.hip", "racecar_imagine.hip", "racecar_dream.hip", "racecar_dream_grad.hip", "racecar_returns.hip", "racecar_returns_grad.hip", "racecar_fit.hip", "racecar_observe.hip", "racecar_decode.hip", "racecar_decode_lidar.hip", "racecar_episode.hip", "racecar_lookahead.hip"]
+HEADERS = ["racecar_device.h", "racecar_internal.h", "racecar_env.h", "racecar_car.h", "racecar_step.h", "racecar_substep.inc", "racecar_spec.h", "racecar_scan.h", "racecar_beam_pairs.h", "racecar_patch_exact.h", "racecar_policy.h", "racecar_policy_math.h", "racecar_policy_tiles.h", "racecar_rollout.h", "racecar_dream_grad.h", "racecar_episode.h", os.path.join("..", "..", "include", "racecar_hip.h")]
 # The lab library: scan variants 0-6 and the instrumented build of the scan (racecar_lab.hip).  NOT part of the shipped
 # library; built by build_lab() - which tools/ and the variant tests call - and loaded by libracecar_hip.so on first use.
 LAB_PATH = os.path.join(LIB_DIR, "libracecar_lab.so")
@@ -121,6 +121,8 @@ CHECKED_KERNELS = (
     ("rc_policy_dream_grad_sampled_kernel", None, False, "shipped"),
     ("rc_policy_returns_kernel", None, False, "shipped"),       # (imagination with the critic's heads and the lambda-return behind it)
     ("rc_policy_returns_sampled_kernel", None, False, "shipped"),
+    ("rc_policy_returns_grad_kernel", None, False, "shipped"),  # (the actor loss's backward pass: item 20's forward, then three heads' and the prior's transposed products)
+    ("rc_policy_returns_grad_sampled_kernel", None, False, "shipped"),
     ("rc_policy_fit_rows_kernel", None, False, "shipped"),      # (the critic's fit: the head forward and backward on the same tiles)
     ("rc_policy_fit_reward_rows_kernel", None, False, "shipped"),     # (the reward head's: the same body at two hidden layers)
     ("rc_policy_fit_wgrad_kernel", None, False, "shipped"),     # (its weight gradients: one accumulator tile per wave over all rows)

@@ -14,102 +14,20 @@
 //             chain from zero over a transposed weight image (RcDreamGradDev), the normals of `sample` mode are drawn again from
 //             the step's key.  Nine barriers per step.
 // The host cuts the rows into chunks against the handle's stash (dream_grad_run): a row's numbers depend on nothing but the row.
-#include "racecar_env.h"
-#include "racecar_rollout.h"
-
-#define RC_DREAM_GRAD_STASH 2240
+// The record's layout and the transposed-product helpers are racecar_dream_grad.h's, shared with racecar_returns_grad.hip.
+#include "racecar_dream_grad.h"
 
 namespace {
 
-constexpr int SW = RC_DREAM_GRAD_STASH, LDT = RC_POLICY_LDT;
-enum { S_X1 = 0, S_Z = 200, S_R = 400, S_C = 600, S_HH = 800, S_H = 1000, S_X2 = 1200, S_RAW = 1400, S_A1 = 1440, S_A2 = 1840 };
+constexpr int SW = RC_DREAM_GRAD_STASH;
 constexpr int MAX_H = RC_POLICY_IMAGINE_MAX_HORIZON;
 // behind X, Y, Z: per row the output row s K + k and the state row of its start (int64, -1 past the end) and the return; the
 // forward's weight sequence w_t; sampled: the draw's key and a step's normals
 constexpr size_t kLdsBytes = RO_LDS_XYZ + PM * (2 * sizeof(int64_t) + sizeof(float)) + MAX_H * sizeof(float);
 constexpr size_t kLdsBytesSampled = kLdsBytes + RO_LDS_DRAWS;
 static_assert(kLdsBytesSampled <= 160 * 1024, "X, Y, Z, the rows' records, the weight sequence, the key and the normals");
-static_assert(2 * RC_POLICY_DETER <= XS && RC_POLICY_LD400 <= XS, "X and Y hold two 200-unit cotangents side by side");
 
 enum { DK_REWARD = RO_OUT };
-
-__device__ __forceinline__ float dg_elu_grad(float a) { return a > 0.0f ? 1.0f : a + 1.0f; }
-
-// n columns of the 32 rows of an LDS buffer into the rows' stash at `dst` (row 0's; rows `stride` apart)
-__device__ __forceinline__ void dg_keep(const float *src, int ss, int n, float *dst, size_t stride, int tid) {
-    for (int idx = tid; idx < PM * n; idx += PT) {
-        const int row = idx / n, j = idx - row * n;
-        dst[row * stride + j] = src[row * ss + j];
-    }
-}
-
-// ro_gru with the gates kept: z, r, the candidate and the recurrent candidate column hh go to the stash of step t
-__device__ __forceinline__ void dg_gru(const RcPolicyDev &w, const float *X, const float *Z, float *Y, float *st, size_t stride, int wave, int lane) {
-    const int cc = lane & 31, half = lane >> 5;
-#pragma unroll 1
-    for (int jt = wave; jt < RC_POLICY_LD200 / 32; jt += 4) {
-        const int col[3] = {32 * jt, RC_POLICY_LD200 + 32 * jt, 2 * RC_POLICY_LD200 + 32 * jt};
-        pm_f32x16 mx[3], mh[3];
-        pm_bias<3>(mx, w.gru_b, col, cc);
-        pm_gemm<3>(mx, X + cc * XS + half, RC_POLICY_DETER / 2, w.gru_k + (size_t)half * RC_POLICY_LDGRU + cc, RC_POLICY_LDGRU, col);
-        pm_bias<3>(mh, w.gru_b + RC_POLICY_LDGRU, col, cc);
-        pm_gemm<3>(mh, Z + cc * ZS + half, RC_POLICY_DETER / 2, w.gru_r + (size_t)half * RC_POLICY_LDGRU + cc, RC_POLICY_LDGRU, col);
-        const int j = 32 * jt + cc;
-        if (j < RC_POLICY_DETER) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = pm_row(r, half);
-                // pm_gru, its gates named
-                const float z = pm_sigmoid(mx[0][r] + mh[0][r]);
-                const float rg = pm_sigmoid(mx[1][r] + mh[1][r]);
-                const float hh = mh[2][r];
-                const float cand = pm_tanh(mx[2][r] + rg * hh);
-                Y[row * XS + j] = z * Z[row * ZS + j] + (1.0f - z) * cand;
-                float *s = st + row * stride + j;
-                s[S_Z] = z;
-                s[S_R] = rg;
-                s[S_C] = cand;
-                s[S_HH] = hh;
-            }
-        }
-    }
-}
-
-// One wave's 32-column tiles col0, col0 + 128, ... of a transposed product: a chain from zero, k ascending over the input's one
-// or two parts (rows `as` apart); epi(row, j, v) for the columns j < n
-template <int TN, class Epi>
-__device__ __forceinline__ void dg_dense(const float *a, int k, const float *a2, int k2, int as, const float *w, int ld, int n, int col0, int lane,
-                                         Epi &&epi) {
-    const int cc = lane & 31, half = lane >> 5;
-    int col[TN];
-#pragma unroll
-    for (int i = 0; i < TN; ++i) col[i] = col0 + 128 * i;
-    pm_f32x16 acc[TN];
-#pragma unroll
-    for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
-    pm_gemm<TN>(acc, a + cc * as + half, k / 2, w + (size_t)half * ld + cc, ld, col);
-    if (k2) pm_gemm<TN>(acc, a2 + cc * as + half, k2 / 2, w + (size_t)(k + half) * ld + cc, ld, col);
-#pragma unroll
-    for (int i = 0; i < TN; ++i) {
-        const int j = col[i] + cc;
-        if (j >= n) continue;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) epi(pm_row(r, half), j, acc[i][r]);
-    }
-}
-
-// the ladder over a 400-unit image (13 tiles: 4, 3, 3, 3) and over a 256-column image (8 tiles: 2 each)
-template <class Epi>
-__device__ __forceinline__ void dg_layer400(const float *a, int k, const float *w, int wave, int lane, Epi &&epi) {
-    if (wave == 0) dg_dense<4>(a, k, nullptr, 0, XS, w, RC_POLICY_LD400, RC_POLICY_UNITS, 0, lane, epi);
-    else dg_dense<3>(a, k, nullptr, 0, XS, w, RC_POLICY_LD400, RC_POLICY_UNITS, 32 * wave, lane, epi);
-}
-template <class Epi>
-__device__ __forceinline__ void dg_layer256(const float *a, int k, const float *a2, int k2, const float *w, int n, int wave, int lane, Epi &&epi) {
-    dg_dense<2>(a, k, a2, k2, XS, w, LDT, n, 32 * wave, lane, epi);
-}
 
 template <bool SAMPLED>
 __device__ __forceinline__ void dg_dream_grad(const RcDreamGradCall &g) {
@@ -364,6 +282,11 @@ __global__ __launch_bounds__(PT) void rc_policy_dream_grad_transpose_kernel(cons
     t[idx] = i < n ? w[(size_t)i * src_ld + g * group_ld + (k - g * group)] : 0.0f;
 }
 
+void rck_dream_grad_transpose(const float *w, int src_ld, int group, int group_ld, int k_n, int n, int dst_ld, float *t, hipStream_t s) {
+    const unsigned blocks = (unsigned)(((size_t)k_n * dst_ld + PT - 1) / PT);
+    hipLaunchKernelGGL(rc_policy_dream_grad_transpose_kernel, dim3(blocks), dim3(PT), 0, s, w, src_ld, group, group_ld, k_n, n, dst_ld, t);
+}
+
 hipError_t rck_dream_grad_prepare() {
     return ro_prepare(rc_policy_dream_grad_kernel, rc_policy_dream_grad_sampled_kernel, kLdsBytes, kLdsBytesSampled);
 }
@@ -409,9 +332,7 @@ int dream_grad_run(rc_env *env, RcDreamGradCall &c, int64_t chunk_rows) {
     const float *src[7] = {env->pol.img1_w, env->pol.gru_k, env->pol.gru_r, env->pol_i.img2_w, env->pol_i.img3_w, env->pol_i.rh_w[0], env->pol_i.rh_w[1]};
     auto transpose = [&](int i, float *dst) {
         const TImage &im = table[i];
-        const unsigned blocks = (unsigned)(((size_t)im.k_n * im.dst_ld + PT - 1) / PT);
-        hipLaunchKernelGGL(rc_policy_dream_grad_transpose_kernel, dim3(blocks), dim3(PT), 0, env->stream, src[i], im.src_ld, im.group, im.group_ld,
-                           im.k_n, im.n, im.dst_ld, dst);
+        rck_dream_grad_transpose(src[i], im.src_ld, im.group, im.group_ld, im.k_n, im.n, im.dst_ld, dst, env->stream);
     };
     if (!env->dgrad) {
         // the first call after the weights were loaded: the transposed images, built on the device

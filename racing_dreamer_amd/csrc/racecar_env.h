@@ -153,6 +153,7 @@ struct StagedTable {
 struct P2p;                        // the peer-copy all-gather's state (racecar_gather.hip)
 struct RcFit;                      // the critic's, the reward head's and the actor's optimizers (racecar_fit.hip)
 struct RcDreamGrad;                // the dream's backward pass: transposed weight images and the activation stash (racecar_dream_grad.hip)
+struct RcReturnsGrad;              // the actor loss's backward pass: the same for the prior and the three heads (racecar_returns_grad.hip)
 
 struct rc_env {
     rc_config cfg{};
@@ -211,6 +212,8 @@ struct rc_env {
     RcFit *fit = nullptr;              // rc_policy_fit_begin: the heads' optimizers and their scratch (racecar_fit.hip)
     RcDreamGrad *dgrad = nullptr;      // rc_policy_dream_grad: made at its first call, dropped with the weights it was made from
     bool dgrad_reward_stale = false;   // a reward fit step moved the head under dgrad's two transposed images of it: the next call remakes them
+    RcReturnsGrad *rgrad = nullptr;    // rc_policy_returns_grad: made at its first call, dropped with the weights it was made from
+    uint32_t rgrad_stale = 0;          // RC_RGRAD_* bits: a fit step moved that head under rgrad's transposed images of it
     rc_policy_sampling pol_sampling{(uint32_t)sizeof(rc_policy_sampling), RC_POLICY_MODE_MEAN, 0u, 0.0f};      // rc_policy_set_sampling
     float *ftg_prev = nullptr;         // rc_follow_the_gap_reference: previous heading per car (NaN = none), allocated on first use
     float *vp_mem = nullptr;           // RcParams::vparams, [n_cars][RC_VP_COUNT] (nominal values while randomization is off)
@@ -239,6 +242,9 @@ int fit_release_reward(rc_env *env);      // closes the reward head's optimizer:
 int fit_release_actor(rc_env *env);       // closes the actor's optimizer: whoever replaces or drops the actor
 int dream_grad_release(rc_env *env);      // drops the transposed images and the stash: whoever replaces or drops the prior or the reward head
 int dream_grad_run(rc_env *env, RcDreamGradCall &c, int64_t chunk_rows);      // racecar_dream_grad.hip: the chunks of one rc_policy_dream_grad
+enum { RC_RGRAD_REWARD = 1u, RC_RGRAD_VALUE = 2u, RC_RGRAD_PCONT = 4u };
+int returns_grad_release(rc_env *env);    // drops the transposed images and the stash: whoever replaces or drops the prior, the reward head or the critic
+int returns_grad_run(rc_env *env, RcReturnsGradCall &c, int64_t chunk_rows);  // racecar_returns_grad.hip: the chunks of one rc_policy_returns_grad
 
 // Times what lies between begin() and end() under accumulator `kernel`.  One launch: the launch itself carries the two timestamps
 // (rck_set_launch_events).  `bracket`: the pair is recorded on the stream around whatever is queued in between (the episode log's

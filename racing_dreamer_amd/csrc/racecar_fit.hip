@@ -693,6 +693,8 @@ int fit_run(rc_env *env, int head, int64_t n, FitRowsCall r, const FitHyper &hp,
                        (const FitCtl *)o.ctl, hp.beta1, hp.beta2, 1.0f - hp.beta1, 1.0f - hp.beta2, hp.epsilon);
     // rc_policy_dream_grad keeps transposed copies of the reward head's two hidden layers: its next call makes them again, on the stream
     if (head == RC_POLICY_FIT_REWARD) env->dgrad_reward_stale = true;
+    // rc_policy_returns_grad keeps such copies of every head it carries a cotangent through (not of the actor)
+    env->rgrad_stale |= head == RC_POLICY_FIT_REWARD ? RC_RGRAD_REWARD : (head == RC_POLICY_FIT_VALUE ? RC_RGRAD_VALUE : (head == RC_POLICY_FIT_PCONT ? RC_RGRAD_PCONT : 0u));
     HIP_TRY(hipGetLastError());
     return t.end();
 }

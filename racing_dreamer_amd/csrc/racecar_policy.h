@@ -148,6 +148,23 @@ struct RcReturnsCall {
     float *reward_start, *value_start, *pcont_start;      // [rows]
 };
 
+// The actor loss's gradient through the dream (racecar_returns_grad.hip): rc_policy_dream_grad's transposed
+// images and the critic's, in the same two shapes ([400][256] for a first layer's 230 columns, [400][416] for a hidden layer)
+struct RcReturnsGradDev {
+    RcDreamGradDev p;                        // the prior's five and the reward head's two
+    const float *vh_t[3];                    // value head: [400][256], 2 x [400][416]
+    const float *ph_t[3];                    // pcont head, the same shapes; null = none loaded
+};
+
+struct RcReturnsGradCall {
+    RcReturnsCall r;                         // the forward's record; r.n_rows: the END of this launch's rows
+    RcReturnsGradDev wt;
+    int64_t row_begin;                       // the first row of this launch (a multiple of 32): workgroup b owns rows row_begin + 32 b ..
+    float *stash;                            // [rows of the launch rounded up to 32][H][RC_RETURNS_GRAD_STASH]
+    float scale;
+    float *grad_actions, *actor_features, *eps, *grad_state;      // [rows][H][2], [rows][H][230], [rows][H][2], [rows][230]; any may be null
+};
+
 // Recorded sequences (racecar_observe.hip): rows are windows [T] of scans and actions, not cars of the env
 struct RcObserveCall {
     RcPolicyDev w;
@@ -229,6 +246,7 @@ hipError_t rck_launch_imagine(const RcImagineCall &c, hipEvent_t start, hipEvent
 hipError_t rck_dream_prepare();
 hipError_t rck_launch_dream(const RcDreamCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                    // c.sample: which kernel
 hipError_t rck_dream_grad_prepare();
+hipError_t rck_returns_grad_prepare();
 hipError_t rck_observe_prepare();
 hipError_t rck_launch_observe(const RcObserveCall &c, hipEvent_t start, hipEvent_t stop, hipStream_t s);                // c.sample: which kernel
 hipError_t rck_returns_prepare();

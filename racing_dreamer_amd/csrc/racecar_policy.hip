@@ -453,6 +453,8 @@ int pol_unpack(const PolImage<W> (&table)[N], const W &w, rc_env *env, const flo
 int pol_drop_heads(rc_env *env) {
     int rc = dream_grad_release(env);            // (its transposed images were made from these weights)
     if (rc) return rc;
+    rc = returns_grad_release(env);              // (and rc_policy_returns_grad's)
+    if (rc) return rc;
     rc = fit_release_reward(env);                // (the optimizer holds pointers into the head's memory)
     if (rc) return rc;
     if (env->pol_heads_mem) {
@@ -518,7 +520,9 @@ void pol_pack_lidar_decoder(const rc_policy_lidar_decoder &d, std::vector<float>
 
 // the critic's memory and pointers go (rc_policy_load_critic(NULL), a new rc_policy_load)
 int pol_drop_critic(rc_env *env) {
-    const int rc = fit_release(env);     // (an optimizer holds pointers into the critic's memory)
+    int rc = fit_release(env);           // (an optimizer holds pointers into the critic's memory)
+    if (rc) return rc;
+    rc = returns_grad_release(env);      // (rc_policy_returns_grad's transposed images were made from these weights)
     if (rc) return rc;
     if (env->pol_critic_mem) {
         HIP_TRY(hipSetDevice(env->cfg.device));
@@ -645,6 +649,7 @@ int rc_policy_load(rc_env *env, const rc_policy_weights *w) {
     HIP_TRY(rck_imagine_prepare());
     HIP_TRY(rck_dream_prepare());
     HIP_TRY(rck_dream_grad_prepare());
+    HIP_TRY(rck_returns_grad_prepare());
     HIP_TRY(rck_observe_prepare());
     HIP_TRY(rck_decode_prepare());
     HIP_TRY(rck_decode_lidar_prepare());
@@ -753,6 +758,8 @@ int rc_policy_load_heads(rc_env *env, const rc_policy_heads *h) {
     HIP_TRY(hipSetDevice(env->cfg.device));
     const int rc_grad = dream_grad_release(env);            // new weights: the transposed images are another head's
     if (rc_grad) return rc_grad;
+    const int rc_rgrad = returns_grad_release(env);         // (rc_policy_returns_grad's as well)
+    if (rc_rgrad) return rc_rgrad;
     const int rc_fit = fit_release_reward(env);             // and the moments another head's
     if (rc_fit) return rc_fit;
     if (!env->pol_heads_mem) HIP_TRY(hipMalloc((void **)&env->pol_heads_mem, img.size() * sizeof(float)));
@@ -904,6 +911,8 @@ int rc_policy_load_critic(rc_env *env, const rc_policy_critic *h) {
     HIP_TRY(hipSetDevice(env->cfg.device));
     const int rc_fit = fit_release(env);                    // new weights: the moments and the transposed images are another critic's
     if (rc_fit) return rc_fit;
+    const int rc_rgrad = returns_grad_release(env);         // and so are rc_policy_returns_grad's
+    if (rc_rgrad) return rc_rgrad;
     if (!env->pol_critic_mem) HIP_TRY(hipMalloc((void **)&env->pol_critic_mem, img.size() * sizeof(float)));
     HIP_TRY(hipMemcpyAsync(env->pol_critic_mem, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice, env->stream));
     HIP_TRY(hipStreamSynchronize(env->stream));             // (the staging vector goes out of scope)
@@ -1065,6 +1074,63 @@ int rc_policy_returns(rc_env *env, const rc_policy_returns_args *a) {
     c.actions = a->actions; c.features = a->features;
     c.reward_start = a->reward_start; c.value_start = a->value_start; c.pcont_start = a->pcont_start;
     return pol_launch(env, rck_launch_returns, c);
+}
+
+int rc_policy_returns_grad(rc_env *env, const rc_policy_returns_grad_args *a) {
+    if (!env || !a) return fail(RC_ERR_INVALID, "NULL argument");
+    if (a->struct_size != sizeof(rc_policy_returns_grad_args))
+        return fail(RC_ERR_INVALID, "rc_policy_returns_grad_args.struct_size %u != %zu", a->struct_size, sizeof(rc_policy_returns_grad_args));
+    if (!env->pol_mem) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: no policy loaded (rc_policy_load)");
+    if (!env->pol_i.img3_w) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: the policy was loaded without the prior's layers img2 / img3");
+    if (!env->pol_i.rout_w) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: no reward head is loaded (rc_policy_load_heads)");
+    if (!env->pol_c.vout_w) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: no value head is loaded (rc_policy_load_critic)");
+    if (a->pcont_start && !env->pol_c.pout_w)
+        return fail(RC_ERR_INVALID, "rc_policy_returns_grad: pcont_start is asked for and no pcont head is loaded (rc_policy_load_critic)");
+    if (a->horizon < 2 || a->horizon > RC_POLICY_IMAGINE_MAX_HORIZON)
+        return fail(RC_ERR_INVALID, "rc_policy_returns_grad: horizon %d is outside [2, %d]", a->horizon, RC_POLICY_IMAGINE_MAX_HORIZON);
+    if (a->mode != RC_POLICY_IMAGINE_MEAN && a->mode != RC_POLICY_IMAGINE_SAMPLE) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: unknown mode %d", a->mode);
+    if (!(a->lambda_ >= 0.0f && a->lambda_ <= 1.0f))
+        return fail(RC_ERR_INVALID, "rc_policy_returns_grad: lambda_ %g is not a number in [0, 1]", (double)a->lambda_);
+    if (!(a->discount >= 0.0f && a->discount <= 1.0f))
+        return fail(RC_ERR_INVALID, "rc_policy_returns_grad: discount %g is not a number in [0, 1]", (double)a->discount);
+    if (!std::isfinite(a->scale)) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: scale %g is not finite", (double)a->scale);
+    if (a->chunk_rows < 0) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: chunk_rows %lld is below 0", (long long)a->chunk_rows);
+    if (!a->grad_actions && !a->grad_state) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: no gradient output asked for (grad_actions, grad_state)");
+    if (a->eps && a->mode != RC_POLICY_IMAGINE_SAMPLE)
+        return fail(RC_ERR_INVALID, "rc_policy_returns_grad: eps is asked for in mode MEAN, which draws no action");
+    if (a->eps && a->actions_in) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: eps is asked for under actions_in (open loop), which draws no action");
+    RcReturnsGradCall c{};
+    if (a->state_in) {
+        if (a->slot_mask) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: a slot mask (0x%x) goes with the live latents, not with a given state_in", a->slot_mask);
+        if (a->starts < 1 || a->starts > (int64_t)INT32_MAX)
+            return fail(RC_ERR_INVALID, "rc_policy_returns_grad: starts %lld is outside [1, 2^31)", (long long)a->starts);
+        c.r.n_rows = a->starts;
+        c.r.state = a->state_in;
+        c.r.row_offset = a->row_offset;
+    } else {
+        if (a->starts) return fail(RC_ERR_INVALID, "rc_policy_returns_grad: starts %lld is given and state_in is NULL", (long long)a->starts);
+        const int rc = pol_rows(env, a->slot_mask, a->seed, "rc_policy_returns_grad", &c.r.rows);
+        if (rc) return rc;
+        c.r.n_rows = c.r.rows.n_active;
+        c.r.state = env->pol_state;
+        c.r.live = 1;
+    }
+    HIP_TRY(hipSetDevice(env->cfg.device));
+    c.r.w = env->pol;
+    c.r.ws = env->pol_s;
+    c.r.wi = env->pol_i;
+    c.r.wc = env->pol_c;
+    c.r.horizon = a->horizon;
+    c.r.sample = a->mode == RC_POLICY_IMAGINE_SAMPLE;
+    c.r.seed_lo = seed_lo(a->seed); c.r.seed_hi = seed_hi(a->seed);
+    c.r.lambda = a->lambda_; c.r.discount = a->discount;
+    c.r.actions_in = a->actions_in;
+    c.r.reward = a->reward; c.r.value = a->value; c.r.pcont = a->pcont; c.r.returns = a->returns; c.r.weight = a->weight;
+    c.r.actions = a->actions; c.r.features = a->features;
+    c.r.reward_start = a->reward_start; c.r.value_start = a->value_start; c.r.pcont_start = a->pcont_start;
+    c.scale = a->scale;
+    c.grad_actions = a->grad_actions; c.actor_features = a->actor_features; c.eps = a->eps; c.grad_state = a->grad_state;
+    return returns_grad_run(env, c, a->chunk_rows);
 }
 
 int rc_policy_observe(rc_env *env, const rc_policy_observe_args *a) {

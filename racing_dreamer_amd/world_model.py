@@ -139,6 +139,54 @@ def value_learning_step(env, batch: Dict[str, torch.Tensor], horizon: int = 15, 
     return status
 
 
+def _dream_with_gradient(env, batch, horizon, lambda_, discount, seed, extra=()):
+    """`value_learning_step`'s starts - `policy_observe(mode="sample")`, each window's last step dropped when a pcont head is loaded -
+    and ONE `policy_returns_grad(mode="sample")` from them under the actor: the rows `actor_fit` takes, `returns` and `weight`, and
+    `extra`.  `actor_loss` = -mean(weight * returns) of the same launch, summed in float64."""
+    feat = env.policy_observe(batch["lidar"], batch["action"], mode="sample", seed=seed, outputs=("feature",))["feature"]
+    if env.policy_has_pcont_head:
+        feat = feat[..., :-1, :]
+    state = torch.nn.functional.pad(feat.reshape(-1, feat.shape[-1]), (0, 2))
+    out = env.policy_returns_grad(horizon, "sample", seed=seed, lambda_=lambda_, discount=discount, state=state,
+                                  outputs=("grad_actions", "actor_features", "eps", "returns", "weight") + tuple(extra))
+    out["actor_loss"] = -(out["weight"].double() * out["returns"].double()).mean()
+    return out
+
+
+def _actor_step(env, out, fit):
+    return env.actor_fit(out["actor_features"].reshape(-1, out["actor_features"].shape[-1]), grad_actions=out["grad_actions"].reshape(-1, 2),
+                         eps=out["eps"].reshape(-1, 2), **fit)
+
+
+def actor_learning_step(env, batch: Dict[str, torch.Tensor], horizon: int = 15, lambda_: float = 0.95, discount: float = 0.99,
+                        seed: int = 0, **fit) -> Dict[str, torch.Tensor]:
+    """The reference's actor update on a replay batch (dreamer/models.py:113-128 under actor_opt), no host
+    copy: `policy_observe(mode="sample")`, each window's last step dropped when a pcont head is loaded, as `value_learning_step`;
+    one `policy_returns_grad` (scale -1 / (rows (H - 1)): the gradient of actor_loss = -mean(weight * returns) with respect to
+    every imagined action, weight held constant and the actor's input detached, as the reference's tape has them); then
+    `actor_fit(actor_features, grad_actions=..., eps=...)` on the actor's optimizer, which must be open (`actor_fit_begin`) - the
+    actor's own backward pass, the global-norm clip and Adam.  `fit` goes to `actor_fit` (lr, clip, ...).  Returns the fit's status
+    (`loss` = 0 in grad mode, `grad_norm`, `skipped`, `step`) and `actor_loss`, on the weights before the update."""
+    out = _dream_with_gradient(env, batch, horizon, lambda_, discount, seed)
+    status = _actor_step(env, out, fit)
+    status["actor_loss"] = out["actor_loss"]
+    return status
+
+
+def behaviour_learning_step(env, batch: Dict[str, torch.Tensor], horizon: int = 15, lambda_: float = 0.95, discount: float = 0.99,
+                            seed: int = 0, actor_fit=None, value_fit=None) -> Dict[str, torch.Tensor]:
+    """The reference's pair of behaviour updates from ONE dream (dreamer/models.py:113-137): `actor_learning_step`'s rollout also
+    returns the imagined features; the actor's step is taken from its rows and the value head's from `critic_fit(features[:, :-1],
+    returns, weight)`.  Both gradients are of the weights before either update, as the reference's two tapes are: the rollout's
+    outputs are on the device before `actor_fit` runs, and the value step reads nothing the actor's step writes.  Both optimizers
+    must be open (`actor_fit_begin`, `critic_fit_begin("value")`); `actor_fit` and `value_fit` are dicts of their hyper-parameters.
+    Returns `actor` and `value` (the two status dicts), `actor_loss` and `value_loss` (= value["loss"])."""
+    out = _dream_with_gradient(env, batch, horizon, lambda_, discount, seed, extra=("features",))
+    actor = _actor_step(env, out, dict(actor_fit or {}))
+    value = env.critic_fit(out["features"][:, :-1], out["returns"], out["weight"], head="value", **dict(value_fit or {}))
+    return dict(actor=actor, value=value, actor_loss=out["actor_loss"], value_loss=value["loss"])
+
+
 def pcont_learning_step(env, batch: Dict[str, torch.Tensor], discount: float = 0.99, seed: int = 0, **fit) -> Dict[str, torch.Tensor]:
     """One step of the pcont head ALONE on a replay batch, the world model frozen: the head on the posterior features
     (`policy_observe(mode="sample")`) against the soft targets `discount * batch["discount"]` [B, T] (dreamer/models.py:101-105),

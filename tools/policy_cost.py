@@ -37,6 +37,16 @@ time per step <= 1.734 x that call's (the ratio of the nominal multiply-adds) x 
 alone (1.367), `sample`, policy_value on 65 536 x 230 features, and - a record, not a condition - the three heads and a Python
 lambda-return in plain fp32 torch on features already in memory.
 
+    python tools/policy_cost.py --returns-grad [--out profiles/policy_returns_grad_cost.json]
+
+`--returns-grad`: the actor loss's gradient through the dream (rc_policy_returns_grad) at 2 450 starts (the reference's batch of 50 x 50
+with a pcont head) and at 65 536 starts, H = 15, `sample`, outputs grad_actions + actor_features + eps, both heads of a synthetic
+critic - alternated, window by window, with policy_returns(outputs = returns, weight) on the same cars in the same run, with the
+condition: time per call <= that call's x 1.706 (forward + backward multiply-adds over forward multiply-adds: the actor runs forward
+only, the prior and the three heads both ways) x 1.05 + the stash's bytes (4 648 floats per row and step, written once and read once)
+at the bandwidth of a device-to-device copy measured in that run, reported as met or missed at each size.  Records without a
+threshold: world_model.behaviour_learning_step's wall time per step on a 50 x 50 batch, and the call with every forward output.
+
     python tools/policy_cost.py --fit [--out profiles/policy_fit_cost.json]
 
 `--fit`: one step of the critic's fit (rc_policy_fit_step: forward, backward, clip, Adam on the value head) at 14 336 rows (tools/fit_critic.py's
@@ -453,6 +463,103 @@ def measure_returns(n, args):
             e1.synchronize()
             windows.append(e0.elapsed_time(e1) / max(1, args.calls // 4))
         res["torch_fp32_heads_and_recursion_ms_per_call"] = round(statistics.median(windows), 4)
+    env.close()
+    return res
+
+
+# rc_policy_returns_grad beside rc_policy_returns, per row and step, mode sample, both heads: the forward as it is counted above (with
+# the actor's two std columns), the backward = the transposed products of the prior and of the three heads; the actor has none
+MACS_RGRAD_FORWARD = MACS_RETURNS_BASE + 400 * 2 + 2 * MACS_CRITIC_HEAD                        # 1 949 200
+MACS_RGRAD_BACKWARD = ((400 * 400 + 400 * 230 + 400) + 2 * MACS_CRITIC_HEAD                   # reward; value, pcont
+                       + 60 * 200 + 200 * 200 + 2 * 600 * 200 + 200 * 32)                     # img3, img2, gru_k, gru_r, img1: 1 375 600
+RGRAD_STASH_FLOATS = 4648
+
+
+def measure_returns_grad(n, args):
+    """Per-call device time (RC_K_POLICY) of rc_policy_returns_grad at H = args.horizon, mode sample, alternated window by window with
+    rc_policy_returns(returns, weight) on the same cars; the copy bandwidth of the same run; behaviour_learning_step's wall time."""
+    import torch
+    from racing_dreamer_amd import _lib as L
+    from racing_dreamer_amd.batched_env import BatchedRaceEnv
+    from racing_dreamer_amd.critic import init_critic
+    weights = np.load(os.path.join(ROOT, "tests", "golden", f"dreamer_policy_{args.checkpoint}.npz"))
+    env = BatchedRaceEnv(args.track, n, 1, auto_reset=True, remap_actions=True)
+    env.load_policy(weights)
+    env.load_critic(init_critic(0))
+    h = args.horizon
+    res = {"starts": n, "horizon": h}
+
+    def window(call):
+        env.reset_kernel_times()
+        env.set_profiling(True, kernels=[L.K_POLICY])
+        for k in range(args.calls):
+            call()
+        env.sync()
+        env.set_profiling(False)
+        return env.kernel_times()["rc_policy_kernel"]["avg_ms"]
+
+    with torch.cuda.stream(env.stream):
+        env.reset(mode="random", seed=1)
+        for k in range(args.settle):
+            env.policy_act()
+            env.step(None, repeat=4)
+        env.sync()
+        fwd = {k: torch.empty((n, h - 1), device=env.device) for k in ("returns", "weight")}
+        bwd = dict(grad_actions=torch.empty((n, h, 2), device=env.device), actor_features=torch.empty((n, h, 230), device=env.device),
+                   eps=torch.empty((n, h, 2), device=env.device))
+        calls = {"returns": lambda: env.policy_returns(h, "sample", seed=1, outputs=tuple(fwd), out=fwd),
+                 "returns_grad": lambda: env.policy_returns_grad(h, "sample", seed=1, outputs=tuple(bwd), out=bwd)}
+        for call in calls.values():
+            for k in range(3):
+                call()
+        windows = {k: [] for k in calls}
+        for r in range(args.rounds):                     # alternated: a drift of the clocks falls on both
+            for k, call in calls.items():
+                windows[k].append(window(call))
+        # the bandwidth of a device-to-device copy of about the stash's size (at most 1 GiB), bytes copied per second
+        stash_bytes = n * h * RGRAD_STASH_FLOATS * 4
+        src = torch.empty(min(stash_bytes, 1 << 30) // 4, device=env.device)
+        dst = torch.empty_like(src)
+        copies = []
+        for r in range(args.rounds + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            dst.copy_(src)
+            e1.record()
+            e1.synchronize()
+            copies.append(src.numel() * 4 / (e0.elapsed_time(e1) * 1e-3))
+        copy_bw = statistics.median(copies[1:])
+        del src, dst
+        base, ms = statistics.median(windows["returns"]), statistics.median(windows["returns_grad"])
+        ratio = (MACS_RGRAD_FORWARD + MACS_RGRAD_BACKWARD) / MACS_RGRAD_FORWARD
+        stash_ms = stash_bytes / copy_bw * 1e3
+        limit = base * ratio * 1.05 + stash_ms
+        res["policy_returns_sample_returns_weight"] = {"ms_per_call": round(base, 4), "windows_ms": [round(v, 4) for v in windows["returns"]]}
+        res["policy_returns_grad"] = {"ms_per_call": round(ms, 4), "windows_ms": [round(v, 4) for v in windows["returns_grad"]],
+                                      "over_policy_returns": round(ms / base, 4), "macs_ratio": round(ratio, 4),
+                                      "tflops": round(2 * (MACS_RGRAD_FORWARD + MACS_RGRAD_BACKWARD) * n * h / (ms * 1e-3) / 1e12, 2),
+                                      "stash_bytes": stash_bytes, "copy_bytes_per_s": round(copy_bw), "stash_allowance_ms": round(stash_ms, 4),
+                                      "target_ms_per_call": round(limit, 4), "met": bool(ms <= limit), "over_target": round(ms / limit, 4)}
+        every = tuple(L.RETURNS_GRAD_OUTPUTS)
+        env.policy_returns_grad(h, "sample", seed=1, outputs=every)
+        res["policy_returns_grad_every_output_ms_per_call"] = round(window(lambda: env.policy_returns_grad(h, "sample", seed=1, outputs=every)), 4)
+        # ---- a record: the reference's pair of updates from one dream, wall clock per step over a window that ends with a synchronisation
+        if n <= 4096:
+            rng = np.random.default_rng(0)
+            batch = dict(lidar=torch.from_numpy(rng.uniform(0.2, 12.0, (50, 50, 1080)).astype(np.float32)).to(env.device),
+                         action=torch.from_numpy(rng.uniform(-1, 1, (50, 50, 2)).astype(np.float32)).to(env.device))
+            from racing_dreamer_amd.world_model import behaviour_learning_step
+            env.actor_fit_begin()
+            env.critic_fit_begin("value")
+            for k in range(2):
+                behaviour_learning_step(env, batch, horizon=h, seed=k)
+            env.sync()
+            steps = max(2, args.calls // 4)
+            t0 = time.perf_counter()
+            for k in range(steps):
+                behaviour_learning_step(env, batch, horizon=h, seed=2 + k)
+            env.sync()
+            res["behaviour_learning_step_50x50_wall_ms_per_step"] = round((time.perf_counter() - t0) / steps * 1e3, 3)
     env.close()
     return res
 
@@ -912,6 +1019,7 @@ def main():
     ap.add_argument("--decode-lidar", action="store_true", help="measure the LiDAR distance decoder (profiles/policy_decode_lidar_cost.json)")
     ap.add_argument("--observe", action="store_true", help="measure recorded sequences (profiles/policy_observe_cost.json)")
     ap.add_argument("--returns", action="store_true", help="measure the critic and the lambda-return (profiles/policy_returns_cost.json)")
+    ap.add_argument("--returns-grad", action="store_true", help="measure the actor loss's gradient through the dream (profiles/policy_returns_grad_cost.json)")
     ap.add_argument("--fit", action="store_true", help="measure the critic's fit (profiles/policy_fit_cost.json)")
     ap.add_argument("--device-only", action="store_true", help="--fit: the device steps alone, no torch baseline (an A/B of two builds)")
     ap.add_argument("--root", default=None, help="import racing_dreamer_amd from this checkout instead (--fit --device-only: the other build of an A/B)")
@@ -935,6 +1043,21 @@ def main():
             out["actor_condition"] = ("actor_fit ms_per_iteration <= (macs_per_row_actor_step / macs_per_row_value_step = 1.422) x critic_fit "
                                       f"ms_per_iteration of the same run x {ACTOR_SPREAD_ALLOWANCE}, at every size")
             out["actor_condition_met"] = all(s["actor_fit"]["met"] for s in out["sizes"])
+        print(json.dumps(out))
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
+    if args.returns_grad:
+        sizes = args.envs if args.envs != [4096, 65536] else [2450, 65536]
+        out = {"tool": "tools/policy_cost.py --returns-grad", "track": args.track, "checkpoint": args.checkpoint, "critic": "critic.init_critic(0)",
+               "device": torch.cuda.get_device_name(0), "calls_per_window": args.calls, "windows": args.rounds, "settle_agent_steps": args.settle,
+               "mode": "sample", "macs_per_step_forward": MACS_RGRAD_FORWARD, "macs_per_step_backward": MACS_RGRAD_BACKWARD,
+               "stash_floats_per_row_and_step": RGRAD_STASH_FLOATS, "spread_allowance": 1.05,
+               "condition": "policy_returns_grad ms_per_call <= policy_returns(returns, weight) ms_per_call of the same run x macs_ratio x 1.05 "
+                            "+ stash_bytes / copy_bytes_per_s of the same run, at every size",
+               "sizes": [measure_returns_grad(n, args) for n in sizes]}
+        out["condition_met"] = all(s["policy_returns_grad"]["met"] for s in out["sizes"])
         print(json.dumps(out))
         if args.out:
             with open(args.out, "w") as f:
