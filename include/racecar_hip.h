@@ -637,7 +637,7 @@ int rc_policy_returns_grad(rc_env *env, const rc_policy_returns_grad_args *args)
 /* Fitting the critic on the device: the reference's value update (dreamer/models.py:129-137: value_loss = -mean(weight *
  * value(feat).log_prob(stop_gradient(returns))) under value_opt, which owns the value head's eight arrays alone; dreamer/tools.py:421-455
  * `Optimizer`: clip_by_global_norm, then Adam) - one MLP's forward pass, backward pass, global-norm clip and Adam on tensors that
- * rc_policy_returns leaves on the device (tests/policy_fit_spec.c is the CPU restatement, the device equals it
+ * rc_policy_returns leaves on the device (tests/policy_fit_spec.c is the CPU restatement of the whole fit engine, the device equals it
  * bit for bit).  The pcont head is the same network under a Bernoulli likelihood with soft targets (models.py:101-105).  With o the
  * head's output on features[i], t = target[i], w = weight[i] (1 where weight is NULL), N = rows:
  *   value   loss = -(1/N) sum w (-(o - t)^2 / 2 - log(2 pi) / 2)                       delta_o = w (o - t) / N
@@ -665,7 +665,7 @@ int rc_policy_returns_grad(rc_env *env, const rc_policy_returns_grad_args *args)
  * rc_policy_fit_sums_kernel, rc_policy_fit_scale_kernel, rc_policy_fit_apply_kernel (and rc_policy_fit_transpose_kernel in begin),
  * timed together under RC_K_POLICY.
  *
- * The reward head (RC_POLICY_FIT_REWARD; DESIGN.md §2 item 24, tests/policy_reward_fit_spec.c is the CPU restatement, the device
+ * The reward head (RC_POLICY_FIT_REWARD; DESIGN.md §2 item 24, tests/policy_fit_spec.c at depth 2 is the CPU restatement, the device
  * equals it bit for bit): the same engine at two hidden layers, on the arrays rc_policy_load_heads loaded - DenseDecoder((), 2, 400),
  * 230 -> 400 -> 400 -> 1, under the value head's Normal(o, 1) likelihood: loss and delta_o as "value" above, target = the recorded
  * reward.  The reference trains this term inside its model loss under model_opt (dreamer/models.py:97-110, 135, 167-181), where its gradient also
@@ -706,7 +706,7 @@ int rc_policy_read_critic(rc_env *env, rc_policy_critic *out);
 int rc_policy_read_heads(rc_env *env, rc_policy_heads *out);
 
 /* Fitting the actor on the device: the actor's own backward pass and optimizer on the fit engine (RC_POLICY_FIT_ACTOR; DESIGN.md §2
- * item 25, tests/policy_actor_fit_spec.c is the CPU restatement, the device equals it bit for bit).  The network is the reference's
+ * item 25, tests/policy_actor_fit_spec.c - the actor's rule on policy_fit_spec.c's engine - is the CPU restatement, the device equals it bit for bit).  The network is the reference's
  * plain ActionDecoder(2, 4, 400, 'tanh_normal'), 230 -> 400 -> 400 -> 400 -> 400 -> 4, ELU, init_std 5, min_std 1e-4, mean_scale 5
  * (dreamer/models.py:535-560); the optimizer is actor_opt's: lr 8e-5, clip 1.0 (dreamer/dream.py:87-88), dreamer/tools.py:421-455 as
  * for the critic.  The closed-loop gradient through the dream (the reference's actor_loss) is NOT computed here: the caller supplies

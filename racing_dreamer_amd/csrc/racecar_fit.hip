@@ -2,7 +2,7 @@
 // stop_gradient(returns))), value_opt on the value head's eight arrays alone; dreamer/tools.py:421-455 `Optimizer`: global-norm clip,
 // then Adam) on the device, for the value head and - the same network with a Bernoulli output - the pcont head: one MLP's forward
 // pass, backward pass, clip and Adam on tensors rc_policy_returns leaves on the device, in the binary32 arithmetic of DESIGN.md §2
-// item 21 (tests/policy_fit_spec.c is the CPU restatement; the device equals it bit for bit).  Five launches on the handle's
+// item 21 (tests/policy_fit_spec.c is the CPU restatement, one engine as here; the device equals it bit for bit).  Five launches on the handle's
 // stream, no host round trip and no synchronisation in a step:
 //   rc_policy_fit_rows_kernel   one workgroup of four waves per 32 rows, rc_policy_returns_kernel's geometry.  Forward through
 //       the head, a1, a2, a3 kept (X, Y [32][417] in LDS and a global scratch [N][416] each); the output delta and the row's loss
@@ -24,11 +24,11 @@
 //   rc_policy_fit_apply_kernel  g scale, Adam (TF's ResourceApplyAdam), the new weight into the forward image - the memory
 //       rc_policy_returns and the rest read - and into the transposed image.
 // The reward head (RC_POLICY_FIT_REWARD: the reference's DenseDecoder((), 2, 400) under the same Normal(o, 1); DESIGN.md §2 item 24,
-// tests/policy_reward_fit_spec.c) is the same engine at two hidden layers: the rows kernel's body without the third layer and without
+// tests/policy_fit_spec.c at depth 2) is the same engine at two hidden layers: the rows kernel's body without the third layer and without
 // the transposed product behind it (rc_policy_fit_reward_rows_kernel), the other four launches with a shorter table.  Its gradient is
 // [231][400] | [401][400] | [401][1] = 253 201 elements, its scratch [4][N][416] + 2 N, its weights rc_policy_load_heads' images.
 // The actor (RC_POLICY_FIT_ACTOR, rc_policy_actor_fit_step: the reference's ActionDecoder(2, 4, 400, 'tanh_normal'),
-// dreamer/models.py:535-560, under actor_opt, dreamer/dream.py:87-88; DESIGN.md §2 item 25, tests/policy_actor_fit_spec.c) is the
+// dreamer/models.py:535-560, under actor_opt, dreamer/dream.py:87-88; DESIGN.md §2 item 25, tests/policy_actor_fit_spec.c's rule on that engine) is the
 // engine at four hidden layers with a four-column output stage (rc_policy_fit_actor_rows_kernel): the output layer is read from the
 // sampled modes' pair image [400][64] (mean columns 0, 1, raw std columns 32, 33), the tanh-normal action and its delta with respect
 // to the four outputs take the place of the likelihood, the gradient with respect to the ACTIONS comes from the caller or from

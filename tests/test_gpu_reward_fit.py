@@ -1,4 +1,4 @@
-"""rc_policy_fit_* with RC_POLICY_FIT_REWARD / reward_fit against its binary32 specification (tests/policy_reward_fit_spec.c), bit for
+"""rc_policy_fit_* with RC_POLICY_FIT_REWARD / reward_fit against its binary32 specification (tests/policy_fit_spec.c at two hidden layers), bit for
 bit: with and without weights, row counts that reach every path of the kernels; consecutive steps; that every reader of the reward
 head - the dream's backward pass with its transposed images among them - sees the fitted weights; purity; zero weights; a NaN
 target; MixedTrackEnv; world_model.reward_learning_step; the refusals; the round trip through reward_head_weights and

@@ -9,6 +9,8 @@ import os
 import numpy as np
 import pytest
 
+import fit_restatement
+from fit_restatement import _elu, _err
 from policy_actor_fit_spec import DEFAULTS, KEYS, N_GRAD, PolicyActorFitSpec
 from policy_spec import PolicySpec
 from test_golden_policy import weights
@@ -64,10 +66,6 @@ def _inputs(mode, with_eps, n=N, weighted=True):
     return r["feat"], kw
 
 
-def _elu(x):
-    return np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
-
-
 def _forward(W, feat, eps, dt):
     """The activations a[0..4], and a dict of the action's parts, in dtype dt."""
     a = [feat.astype(dt)]
@@ -115,34 +113,14 @@ def _gradient(W, feat, dt, target=None, grad_actions=None, eps=None, weight=None
     return loss, {k: g[k].astype(dt) for k in KEYS}, delta.astype(dt)
 
 
-class Restatement:
-    """The update in dtype dt: clip_by_global_norm, then TF's ResourceApplyAdam."""
+class Restatement(fit_restatement.Restatement):
+    """fit_restatement.Restatement over the actor, TF's Adam under the DEFAULTS; a step's rows are keyword arguments."""
 
     def __init__(self, actor, dt):
-        self.W = {k: np.asarray(actor[k]).astype(dt) for k in KEYS}
-        self.dt, self.t = dt, 0
-        self.m = {k: np.zeros_like(a) for k, a in self.W.items()}
-        self.v = {k: np.zeros_like(a) for k, a in self.W.items()}
+        super().__init__({k: actor[k] for k in KEYS}, DEFAULTS, lambda W, feat, kw: _gradient(W, feat, dt, **kw), dt)
 
     def step(self, feat, **kw):
-        dt = self.dt
-        hp = {k: dt(np.float32(v)) for k, v in DEFAULTS.items()}
-        loss, g, gfeat = _gradient(self.W, feat, dt, **kw)
-        norm = np.sqrt(sum((a.astype(dt) ** 2).sum(dtype=dt) for a in g.values()))
-        out = dict(loss=loss, grad_norm=norm, grad=g, grad_features=gfeat)
-        scale = hp["clip"] / max(norm, hp["clip"])
-        self.t += 1
-        c1, c2 = 1 - hp["beta1"] ** self.t, 1 - hp["beta2"] ** self.t
-        for k in KEYS:
-            gk = g[k] * scale
-            self.m[k] = hp["beta1"] * self.m[k] + (1 - hp["beta1"]) * gk
-            self.v[k] = hp["beta2"] * self.v[k] + (1 - hp["beta2"]) * gk * gk
-            self.W[k] = self.W[k] - hp["lr"] * np.sqrt(c2) / c1 * self.m[k] / (np.sqrt(self.v[k]) + hp["epsilon"])
-        return out
-
-
-def _err(a, b):
-    return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))))
+        return super().step(feat, kw)
 
 
 def _ratios(mode, with_eps, steps=1):

@@ -5,6 +5,8 @@ No GPU: the device is held to the spec bit for bit by tests/test_gpu_policy_fit.
 import numpy as np
 import pytest
 
+import fit_restatement
+from fit_restatement import _elu, _err
 from policy_fit_spec import DEFAULTS, LAYERS, PolicyFitSpec, tree_sum
 from test_gpu_policy_device import _recorded_inputs
 
@@ -44,10 +46,6 @@ def _rows(n=N):
     return feat[:n], {"value": value_t[:n], "pcont": pcont_t[:n]}, weight[:n]
 
 
-def _elu(x):
-    return np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
-
-
 def _softplus(x):
     return np.maximum(x, 0) + np.log1p(np.exp(-np.abs(x)))
 
@@ -81,40 +79,10 @@ def _gradient(W, feat, target, weight, head, dt):
     return loss, {k: g[k].astype(dt) for k in LAYERS}
 
 
-class Restatement:
-    """The update in dtype dt: clip_by_global_norm, then Adam - TF's ResourceApplyAdam, or (torch=True) torch.optim.Adam's
-    placement of epsilon."""
-
-    def __init__(self, critic, head, dt, torch=False):
-        self.W = {k: np.asarray(critic[f"{head}_{k}"]).astype(dt) for k in LAYERS}
-        self.head, self.dt, self.torch, self.t = head, dt, torch, 0
-        self.m = {k: np.zeros_like(a) for k, a in self.W.items()}
-        self.v = {k: np.zeros_like(a) for k, a in self.W.items()}
-
-    def step(self, feat, target, weight=None, **hyper):
-        dt = self.dt
-        hp = {k: dt(np.float32(v)) for k, v in {**DEFAULTS, **hyper}.items()}
-        loss, g = _gradient(self.W, feat, target, weight, self.head, dt)
-        norm = np.sqrt(sum((a.astype(dt) ** 2).sum(dtype=dt) for a in g.values()))
-        out = dict(loss=loss, grad_norm=norm, grad=g, skipped=int(not np.isfinite(norm)))
-        if out["skipped"]:
-            return out
-        scale = hp["clip"] / max(norm, hp["clip"]) if hp["clip"] > 0 else dt(1)
-        self.t += 1
-        c1, c2 = 1 - hp["beta1"] ** self.t, 1 - hp["beta2"] ** self.t
-        for k in LAYERS:
-            gk = g[k] * scale
-            self.m[k] = hp["beta1"] * self.m[k] + (1 - hp["beta1"]) * gk
-            self.v[k] = hp["beta2"] * self.v[k] + (1 - hp["beta2"]) * gk * gk
-            if self.torch:
-                self.W[k] = self.W[k] - hp["lr"] / c1 * self.m[k] / (np.sqrt(self.v[k]) / np.sqrt(c2) + hp["epsilon"])
-            else:
-                self.W[k] = self.W[k] - hp["lr"] * np.sqrt(c2) / c1 * self.m[k] / (np.sqrt(self.v[k]) + hp["epsilon"])
-        return out
-
-
-def _err(a, b):
-    return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))))
+def Restatement(critic, head, dt, torch=False):
+    """fit_restatement.Restatement over one head of the critic."""
+    return fit_restatement.Restatement({k: critic[f"{head}_{k}"] for k in LAYERS}, DEFAULTS,
+                                       lambda W, feat, target, weight=None: _gradient(W, feat, target, weight, head, dt), dt, torch)
 
 
 def _ratios(head, steps=1):

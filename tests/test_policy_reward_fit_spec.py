@@ -1,4 +1,4 @@
-"""The specification of the reward head's fit (tests/policy_reward_fit_spec.c) against NumPy restatements of
+"""The specification of the reward head's fit (tests/policy_fit_spec.c at two hidden layers) against NumPy restatements of
 the update - the head's Normal(o, 1) likelihood of the recorded reward (dreamer/models.py:97-100), the reference's `Optimizer`
 (dreamer/tools.py:421-455): the forward pass, the analytic backward pass, the global-norm clip and TF's Adam in float64, and the
 same in plain float32 (NumPy's own summation order) as the yardstick of what binary32 can give.  The starting weights are the
@@ -8,6 +8,8 @@ import os
 
 import numpy as np
 
+import fit_restatement
+from fit_restatement import _elu, _err
 from policy_reward_fit_spec import DEFAULTS, KEYS, LAYERS, N_GRAD, PolicyRewardFitSpec
 from test_gpu_policy_device import _recorded_inputs
 
@@ -45,10 +47,6 @@ def _rows(n=N):
     return feat[:n], target[:n], weight[:n]
 
 
-def _elu(x):
-    return np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
-
-
 def _loss(W, feat, target, weight, dt):
     """(loss, the activations, the output) in dtype dt."""
     a = [feat.astype(dt)]
@@ -74,40 +72,10 @@ def _gradient(W, feat, target, weight, dt):
     return loss, {k: g[k].astype(dt) for k in LAYERS}
 
 
-class Restatement:
-    """The update in dtype dt: clip_by_global_norm, then Adam - TF's ResourceApplyAdam, or (torch=True) torch.optim.Adam's
-    placement of epsilon."""
-
-    def __init__(self, head, dt, torch=False):
-        self.W = {k: np.asarray(head[f"reward_{k}"]).astype(dt) for k in LAYERS}
-        self.dt, self.torch, self.t = dt, torch, 0
-        self.m = {k: np.zeros_like(a) for k, a in self.W.items()}
-        self.v = {k: np.zeros_like(a) for k, a in self.W.items()}
-
-    def step(self, feat, target, weight=None, **hyper):
-        dt = self.dt
-        hp = {k: dt(np.float32(v)) for k, v in {**DEFAULTS, **hyper}.items()}
-        loss, g = _gradient(self.W, feat, target, weight, dt)
-        norm = np.sqrt(sum((a.astype(dt) ** 2).sum(dtype=dt) for a in g.values()))
-        out = dict(loss=loss, grad_norm=norm, grad=g, skipped=int(not np.isfinite(norm)))
-        if out["skipped"]:
-            return out
-        scale = hp["clip"] / max(norm, hp["clip"]) if hp["clip"] > 0 else dt(1)
-        self.t += 1
-        c1, c2 = 1 - hp["beta1"] ** self.t, 1 - hp["beta2"] ** self.t
-        for k in LAYERS:
-            gk = g[k] * scale
-            self.m[k] = hp["beta1"] * self.m[k] + (1 - hp["beta1"]) * gk
-            self.v[k] = hp["beta2"] * self.v[k] + (1 - hp["beta2"]) * gk * gk
-            if self.torch:
-                self.W[k] = self.W[k] - hp["lr"] / c1 * self.m[k] / (np.sqrt(self.v[k]) / np.sqrt(c2) + hp["epsilon"])
-            else:
-                self.W[k] = self.W[k] - hp["lr"] * np.sqrt(c2) / c1 * self.m[k] / (np.sqrt(self.v[k]) + hp["epsilon"])
-        return out
-
-
-def _err(a, b):
-    return float(np.max(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64))))
+def Restatement(head, dt, torch=False):
+    """fit_restatement.Restatement over the reward head."""
+    return fit_restatement.Restatement({k: head[f"reward_{k}"] for k in LAYERS}, DEFAULTS,
+                                       lambda W, feat, target, weight=None: _gradient(W, feat, target, weight, dt), dt, torch)
 
 
 def _ratios(steps=1):
